@@ -8,7 +8,7 @@ A step = one complete render through the C ABI: wavefront path tracing of every 
 replay, and the film's copy-back to the host (SURVEY §8d: t_render "incl. final film copy-back";
 integrator.cpp:43-78 is the reference's timer scope).  Inputs (scene, BVH, tables) are resident in HBM
 before the timed region.  N = 1: the step is msk_gpu_render; the same K steps with the film left in HBM
-(msk_gpu_render_device) ride along as `value_film_in_hbm`.
+(msk_gpu_render_device) ride along as `value_film_in_hbm` under `--full`.
 
 N > 1: one process per GPU.  Under torch.distributed.run (WORLD_SIZE set) this process is one rank; from
 a bare shell (`python bench.py --gpus 8`) this process only spawns the N ranks — before anything touches
@@ -25,6 +25,13 @@ rendezvous.  Rank 0 prints ONE JSON line.
 
 `--dry-run` exercises the launch / rendezvous / reduce / timing plumbing without a GPU (gloo backend, a
 host tensor as the film, no render): what tests/test_bench_launch.py runs on CPU.
+
+A plain run sets up, warms up, times the K steps and prints the line (its `roofline` is computed from the timed steps' own
+statistics and the committed profiles).  `--full` adds everything that takes runs of its own: the same K steps with the film
+left in HBM, the HBM stream yardstick, L2 against the CPU path, the CPU baselines and configs 3 / 4 / 5 (N = 1), or the
+sharded configs 4 / 5 (N > 1).  `--dump-outputs DIR` writes the film of the last timed step (rank 0's, reduced when N > 1) as
+DIR/film.npy: float32 [H, W, 5] weighted sums {X, Y, Z, A, W}, the array msk_gpu_render hands its caller; the inputs (scene,
+seed) are fixed, so two builds can be compared output for output (`--balance` re-splits by measured speed and is the exception).
 """
 import argparse
 import importlib
@@ -56,11 +63,11 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--spp", type=int, default=SPP_PER_GPU, help="spp per GPU (default: the BASELINE config)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines and the L2 comparisons with the CPU path")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the config 3 / 4 / 5 class renders that N = 1 adds under `other_configs`, and the sharded config 4 / 5 runs of N > 1")
-    ap.add_argument("--c4-spp", type=int, default=4096, help="N > 1: total spp of the config-4 run that follows the headline (rehearsals use less)")
-    ap.add_argument("--c5-spp", type=int, default=1024, help="N > 1: total spp of the config-5-class run that follows the headline")
+                    help="--full: skip the config 3 / 4 / 5 class renders that N = 1 adds under `other_configs`, and the sharded config 4 / 5 runs of N > 1")
+    ap.add_argument("--c4-spp", type=int, default=4096, help="N > 1, --full: total spp of the config-4 run that follows the headline (rehearsals use less)")
+    ap.add_argument("--c5-spp", type=int, default=1024, help="N > 1, --full: total spp of the config-5-class run that follows the headline")
     ap.add_argument("--shard", choices=("samples", "tiles"), default="samples",
                     help="N > 1: which axis the ranks split (misaki-render_amd/multigpu.py); both end in one film reduce")
     ap.add_argument("--balance", action="store_true",
@@ -73,7 +80,7 @@ def parse_args():
     ap.add_argument("--dry-run", action="store_true", help="no GPU: launch, rendezvous (gloo), reduce and timing only")
     ap.add_argument("--rccl-world1", action="store_true",
                     help="N = 1 through the N > 1 step: a process group of ONE rank over RCCL (nccl), msk_gpu_render_device + the film "
-                         "reduce + rank 0's pinned copy-back, and the sharded config 4 / 5 runs — everything of the multi-GPU step but a "
+                         "reduce + rank 0's pinned copy-back, and (--full) the sharded config 4 / 5 runs — everything of the multi-GPU step but a "
                          "peer, on a one-GPU box; the line says \"rccl_world1\": true")
     ap.add_argument("--sync-reduce", action="store_true",
                     help="N > 1: every step waits for its own film reduce and copy-back before the next render starts (rounds 1-5); default: "
@@ -84,7 +91,20 @@ def parse_args():
                     help="N > 1 ranks (or --in-process members) that ALL render on cuda:0, the ranks reducing over gloo through host "
                          "copies of the film: the whole multi-GPU path but the RCCL call / the peer reads, on a one-GPU box "
                          "(tests/test_bench_launch.py); its line says \"rehearsal\": true and is not a measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything that takes runs of its own: the film-in-HBM steps, the HBM stream yardstick, "
+                         "L2 vs the CPU path, CPU baselines, configs 3 / 4 / 5 (N = 1) or the sharded configs 4 / 5 (N > 1); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the film of the last timed step as DIR/film.npy (float32 [H, W, 5], rank 0)")
     return ap.parse_args()
+
+
+def dump_outputs(directory, film):
+    """The timed path's result of its last step, as the caller of that path receives it: the film of weighted sums
+    {X, Y, Z, A, W} (5 MB at 512 x 512), float32."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "film.npy"), np.ascontiguousarray(np.asarray(film, dtype=np.float32)))
 
 
 def build_id():
@@ -780,6 +800,9 @@ def main():
     ru0, th0 = resource.getrusage(resource.RUSAGE_SELF), _thread_cpu()
     own["render_s"] = 0.0
     dt, stats = timed(step, args.steps)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's film on rank 0's host: the pipeline's newest slot, else the film the step copied back into
+        dump_outputs(args.dump_outputs, film.numpy() if args.dry_run else pipe.last_host_film().numpy() if pipe is not None else host_film)
     # N > 1: every rank's own render time per step (the renders alone, no reduce, no waiting): the spread between the node's GPUs —
     # an equal split waits for the slowest — apart from what the reduce and rank 0's copy-back cost
     rank_render_ms = None
@@ -800,7 +823,7 @@ def main():
 
     # N > 1: the sharded config 4 / 5 runs — every rank takes part; rank 0 first puts the headline on stderr (below)
     sharded = {}
-    run_sharded = (world > 1 or multi) and not args.no_other_configs
+    run_sharded = (world > 1 or multi) and args.full and not args.no_other_configs
     if run_sharded and (rank != 0 or args.dry_run):
         sharded = sharded_configs(args, abi, hm, mg, ctx, dist, rank, world, rehearsal, fence)
     if rank == 0 and args.dry_run:
@@ -814,8 +837,8 @@ def main():
                                      "balanced": balance is not None, "reduce": "pipelined: two films in flight" if pipe is not None else "per step", **sharded}, "balance": balance}),
               flush=True)
     elif not args.dry_run:
-        # the same K steps with the film left in HBM (every rank takes part: the steps hold collectives)
-        dt_hbm, _ = timed(step_hbm, args.steps) if world == 1 else (None, None)       # (N = 1, also through --rccl-world1)
+        # --full: the same K steps with the film left in HBM (every rank takes part: the steps hold collectives)
+        dt_hbm, _ = timed(step_hbm, args.steps) if world == 1 and args.full else (None, None)       # (N = 1, also through --rccl-world1)
     if rank == 0 and not args.dry_run:
         import numpy as np
         n_gpus = max(world, members)
@@ -849,14 +872,15 @@ def main():
         if dt_hbm is not None:
             out["ms_per_step_film_in_hbm"] = round(dt_hbm / args.steps * 1e3, 3)
             out["value_film_in_hbm"] = round(samples_step * args.steps / dt_hbm / 1e6, 2)
-        if n_gpus == 1 and not rehearsal:
+        if n_gpus == 1 and not rehearsal and args.full:
             out["roofline"]["stream_yardstick"] = stream_yardstick(out["roofline"])
-        # the measured headline is safe on stderr before anything slower or riskier runs (CPU baselines, other configs)
-        print("bench.py headline (extras follow on stdout): " + json.dumps(out), file=sys.stderr, flush=True)
+        if args.full:
+            # the measured headline is safe on stderr before anything slower or riskier runs (CPU baselines, other configs)
+            print("bench.py headline (extras follow on stdout): " + json.dumps(out), file=sys.stderr, flush=True)
         if run_sharded:
             sharded = sharded_configs(args, abi, hm, mg, ctx, dist, rank, world, rehearsal, fence)
         compact = {}                    # scalars that ride in `config`: the driver's parser keeps `config`, `roofline` and `cpu_baseline`
-        if not args.no_cpu_baseline and n_gpus == 1:
+        if args.full and not args.no_cpu_baseline and n_gpus == 1:
             try:
                 out["l2_vs_cpu"] = l2_vs_cpu(abi, hm, flat, host_film, prm)
                 compact["l2_max"] = out["l2_vs_cpu"]["max"]
@@ -877,7 +901,7 @@ def main():
                                                    "sample": l2["cpu"], "host_cpus": os.cpu_count()}
         else:
             out["cpu_baseline"] = None
-        if n_gpus == 1 and not args.no_other_configs and not multi:
+        if args.full and n_gpus == 1 and not args.no_other_configs and not multi:
             out["other_configs"] = other_configs(abi, hm, ctx, skip_cpu=args.no_cpu_baseline)
             for e in out["other_configs"]:
                 if "value" in e:

@@ -103,7 +103,17 @@ def main():
                            "res-64 sRGB table the reference's rgb2spec_opt wrote in this container (platform libm); table_sha256 "
                            "is that file's hash", "table_sha256": sha, "table_bytes": os.path.getsize(f"{ROOT}/oracle/_ref/srgb.coeff"),
                "rows": sweep}, open(f"{HERE}/rgb2spec_sweep.json", "w"), indent=0)
-    print("wrote fixtures:", len(cie), len(d65), len(out), len(sweep))
+
+    # the 500 colours tests/test_oracle_kat.py draws (RandomState(3)), as the compiled reference fetch answers them
+    rows = []
+    for rgb in np.random.RandomState(3).uniform(0.001, 1, (500, 3)).astype(np.float32):
+        a, o = (C.c_float * 3)(*[float(v) for v in rgb]), (C.c_float * 3)()
+        lib.rgb2spec_fetch(model, a, o)
+        rows.append([f32_hex(float(v)) for v in rgb] + [f32_hex(o[i]) for i in range(3)])
+    json.dump({"_comment": "rgb (3 x float32 hex, numpy RandomState(3).uniform(0.001, 1, (500, 3))) -> coefficients (3 x float32 hex) "
+                           "from the reference's compiled rgb2spec_fetch on the table of rgb2spec_sweep.json's table_sha256",
+               "rows": rows}, open(f"{HERE}/rgb2spec_random500.json", "w"), indent=0)
+    print("wrote fixtures:", len(cie), len(d65), len(out), len(sweep), len(rows))
 
 
 if __name__ == "__main__":

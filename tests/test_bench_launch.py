@@ -32,7 +32,7 @@ def _env():
 
 
 def test_bare_shell_gpus_2_spawns_two_ranks():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "2", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=300, env=_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -47,7 +47,7 @@ def test_bare_shell_gpus_2_spawns_two_ranks():
     assert (c["c4_shard"], c["c4_spp"], c["c5_shard"], c["c5_spp"]) == ("tiles", 4096, "samples", 1024)
     assert c["c4_reduce_ok"] and c["c5_reduce_ok"] and c["c4_ms"] > 0 and c["c5_ms"] > 0
     assert "1920x1080" in c["c4_workload"] and "1024x1024" in c["c5_workload"]
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "1", "--warmup", "0", "--no-other-configs"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "1", "--warmup", "0", "--full", "--no-other-configs"],
                        capture_output=True, text=True, timeout=300, env=_env(), cwd=ROOT)
     assert r.returncode == 0 and not any(k.startswith(("c4_", "c5_")) for k in _last_json(r.stdout)["config"]), r.stderr[-2000:]
     # the default N > 1 step keeps two films in flight (multigpu.ReducePipeline); --sync-reduce is rounds 1-5's step
@@ -64,15 +64,30 @@ def test_bare_shell_gpus_2_spawns_two_ranks():
 def test_a_rank_that_cannot_set_a_sharded_config_up_does_not_hang_the_others():
     """sharded_configs: every rank learns before the first collective of a config whether every rank is ready; a rank that failed
     (out of memory on its GPU, say) makes all of them skip that config — the line carries c4_error, config 5 still runs, exit code 0."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "1", "--warmup", "0"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "1", "--warmup", "0", "--full"],
                        capture_output=True, text=True, timeout=300, env=dict(_env(), MSK_BENCH_TEST_FAIL_CONFIG="1:c4"), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     c = _last_json(r.stdout)["config"]
     assert "another rank" in c["c4_error"] and "c4_ms" not in c and c["c5_reduce_ok"] and _scalar_config({"config": c})
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "1", "--warmup", "0"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "1", "--warmup", "0", "--full"],
                        capture_output=True, text=True, timeout=300, env=dict(_env(), MSK_BENCH_TEST_FAIL_CONFIG="0:c5"), cwd=ROOT)
     c = _last_json(r.stdout)["config"]
     assert r.returncode == 0 and "test: rank 0" in c["c5_error"] and c["c4_reduce_ok"]
+
+
+def test_plain_run_is_the_headline_only_and_dumps_its_film(tmp_path):
+    """Without --full the line is the headline alone (no sharded config 4 / 5 runs behind it); --steps is the number of timed
+    steps; --dump-outputs writes the last timed step's film as rank 0 holds it: here the sum of two ranks' films of ones."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=300, env=_env(), cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["reduce_ok"] and _scalar_config(d)
+    assert not any(k.startswith(("c4_", "c5_")) for k in d["config"])
+    assert sorted(os.listdir(tmp_path / "out")) == ["film.npy"]
+    import numpy as np
+    film = np.load(tmp_path / "out" / "film.npy")
+    assert film.dtype == np.float32 and film.shape == (8, 8, 5) and (film == 2.0).all()
 
 
 def test_under_torch_distributed_run():
@@ -159,7 +174,7 @@ def test_two_ranks_rehearsed_on_one_gpu():
     assert _scalar_config(d1) and d1["config"]["shard"] == "none"
     # the sharded config 4 / 5 runs behind the headline (reduced sample counts: two ranks share this one GPU and its memory)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu", "--spp", "8", "--steps", "1", "--warmup", "1",
-                        "--no-cpu-baseline", "--c4-spp", "16", "--c5-spp", "8"], capture_output=True, text=True, timeout=900, env=_env(), cwd=ROOT)
+                        "--full", "--no-cpu-baseline", "--c4-spp", "16", "--c5-spp", "8"], capture_output=True, text=True, timeout=900, env=_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     c = _last_json(r.stdout)["config"]
     assert c["c4_film_finite"] and c["c5_film_finite"] and c["c4_msamples_per_s"] > 0 and c["c5_msamples_per_s"] > 0 and "c4_error" not in c
@@ -182,6 +197,27 @@ def test_in_process_group_rehearsed_on_one_gpu():
                         capture_output=True, text=True, timeout=600, env=_env(), cwd=ROOT)
     d1 = _last_json(r1.stdout)
     assert abs(d["film_weight_sum"] - d1["film_weight_sum"]) <= 1e-5 * abs(d1["film_weight_sum"])
+
+
+@pytest.mark.gpu
+def test_dumped_film_is_the_timed_paths_film(tmp_path, gpu_ctx, abi, hostmirror):
+    """A plain N = 1 run: the headline line without the --full extras, and --dump-outputs writes the film msk_gpu_render returned
+    in the last timed step — the same bits a caller gets from one render of the bench scene with the bench's parameters."""
+    import numpy as np
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--spp", "8", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, env=_env(), cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert d["unit"] == "Msamples/s" and d["config"]["samples_per_step"] == 512 * 512 * 8 and _scalar_config(d)
+    assert "other_configs" not in d and "l2_vs_cpu" not in d and "value_film_in_hbm" not in d and "stream_yardstick" not in d["roofline"]
+    film = np.load(out / "film.npy")
+    assert film.dtype == np.float32 and film.shape == (512, 512, 5)
+    scene = abi.Scene(gpu_ctx, hostmirror.cbox_scene(512, 512))
+    want, _ = scene.render(abi.render_params(spp=8, seed=0))
+    scene.close()
+    assert np.array_equal(film.view(np.uint32), want.view(np.uint32))
 
 
 def test_build_id_ignores_comments_and_white_space():

@@ -9,8 +9,8 @@ SPP=${1:-512}
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out
 rm -rf $OUT/prof_kt $OUT/prof_kt1 $OUT/prof_fetch $OUT/prof_write $OUT/prof_sq $OUT/prof_sq2
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/prof_kt -o kt -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-other-configs > $OUT/prof_kt.json 2> $OUT/prof_kt.log
-MSK_STREAMS=1 rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/prof_kt1 -o kt1 -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-other-configs > $OUT/prof_kt1.json 2> $OUT/prof_kt1.log
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/prof_kt -o kt -- python3 bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-other-configs > $OUT/prof_kt.json 2> $OUT/prof_kt.log
+MSK_STREAMS=1 rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/prof_kt1 -o kt1 -- python3 bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-other-configs > $OUT/prof_kt1.json 2> $OUT/prof_kt1.log
 export MSK_STREAMS=1
 rocprofv3 --output-format csv --kernel-trace --pmc FETCH_SIZE -d $OUT/prof_fetch -o fetch -- python3 tools/prof_run.py $SPP > $OUT/prof_fetch.log 2>&1
 rocprofv3 --output-format csv --kernel-trace --pmc WRITE_SIZE -d $OUT/prof_write -o write -- python3 tools/prof_run.py $SPP > $OUT/prof_write.log 2>&1
