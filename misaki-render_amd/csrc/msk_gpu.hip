@@ -1196,14 +1196,25 @@ static int run_wavefront(msk_scene *sc, hipStream_t stream, const msk_render_par
     return MSK_OK;
 }
 
+// samples per pixel this call renders: s = sample_first + k * sample_stride < spp.  64-bit: spp - first + stride - 1 wraps in
+// 32 bits (spp 0xFFFFFFFF, stride 4095 owns 1048833 samples; a 32-bit sum would give 0 and render nothing)
+static unsigned long long owned_spp(const msk_render_params *p) {
+    const unsigned long long ss = p->sample_stride ? p->sample_stride : 1;
+    return p->sample_first < p->spp ? ((unsigned long long) p->spp - p->sample_first + ss - 1) / ss : 0;
+}
+
 static int check_params(msk_ctx *ctx, const msk_render_params *p, int block_min) {
     if (!p) return fail(ctx, MSK_ERR_INVALID_ARG, "render params are NULL");
     if (p->rng_mode != MSK_RNG_COUNTER && p->rng_mode != MSK_RNG_PCG_BLOCK)
         return fail(ctx, MSK_ERR_INVALID_ARG, "rng_mode %d is neither MSK_RNG_COUNTER nor MSK_RNG_PCG_BLOCK", p->rng_mode);
     if (p->spp == 0) return fail(ctx, MSK_ERR_INVALID_ARG, "spp must be > 0");
-    if (p->spp > (1u << MSK_DEPTH_SHIFT))
-        return fail(ctx, MSK_ERR_UNSUPPORTED, "spp %u: at most %u samples per pixel and call (the path state holds 20 bits of sample index); "
-                    "shard the samples with sample_first / sample_stride", p->spp, 1u << MSK_DEPTH_SHIFT);
+    // the path state holds the OWNED sample index (PathState::id: s_own | depth << 20); the RNG key takes the global one,
+    // first + s_own * stride, in full 32 bits.  So the limit is on the samples this call owns, not on spp.  (MSK_RNG_PCG_BLOCK
+    // cannot shard samples — below — so there the two are the same.)
+    if (owned_spp(p) > (1ull << MSK_DEPTH_SHIFT))
+        return fail(ctx, MSK_ERR_UNSUPPORTED, "spp %u, sample_first %u, sample_stride %u: %llu samples per pixel in this call, at most %u "
+                    "(the path state holds 20 bits of sample index); shard the samples with sample_first / sample_stride",
+                    p->spp, p->sample_first, p->sample_stride, owned_spp(p), 1u << MSK_DEPTH_SHIFT);
     if (p->rr_depth <= 0) return fail(ctx, MSK_ERR_INVALID_ARG, "\"rr_depth\" must be set to a value greater than zero!");
     if (p->max_depth < 0 && p->max_depth != -1)
         return fail(ctx, MSK_ERR_INVALID_ARG, "\"max_depth\" must be set to -1 (infinite) or a value >= 0");
@@ -1225,11 +1236,6 @@ static int check_params(msk_ctx *ctx, const msk_render_params *p, int block_min)
         return fail(ctx, MSK_ERR_UNSUPPORTED, "MSK_RNG_PCG_BLOCK: the samples of a block share one sequential PCG32 stream and cannot be sharded "
                     "(sample_first %u, sample_stride %u); shard the blocks with block_first / block_stride", p->sample_first, p->sample_stride);
     return MSK_OK;
-}
-
-static uint32_t owned_spp(const msk_render_params *p) {
-    const uint32_t ss = p->sample_stride ? p->sample_stride : 1;
-    return p->sample_first < p->spp ? (p->spp - p->sample_first + ss - 1) / ss : 0;
 }
 
 // Short rays (LDS-resident scene): many small regions, one chunk loop per wave: 8192 x 512 = 4 M path slots (0.6 GB of state;
@@ -1346,7 +1352,7 @@ static int render_impl(msk_scene *sc, const msk_render_params *prm, float *d_fil
     int nbx, nby;
     std::vector<HostBlock> all = spiral_blocks(W, H, bs, &nbx, &nby);
     const uint32_t bstride = prm->block_stride ? prm->block_stride : 1;
-    const uint32_t spp_owned = owned_spp(prm);
+    const uint32_t spp_owned = (uint32_t) owned_spp(prm);            // <= 2^20 (check_params)
     std::vector<int32_t> block_of((size_t) nbx * nby, -1);
     std::vector<uint32_t> spiral_id((size_t) nbx * nby, 0);
     std::vector<BlockInfo> owned;
@@ -1651,6 +1657,11 @@ extern "C" int msk_gpu_sample_pixels(msk_scene *scene, const msk_render_params *
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = check_params(ctx, prm, 1);
     if (rc) return rc;
+    // every sample 0 .. spp-1 of a listed pixel is rendered (the selectors are ignored below): all of them count against the
+    // path state's 20 bits of sample index
+    if (prm->spp > (1u << MSK_DEPTH_SHIFT))
+        return fail(ctx, MSK_ERR_UNSUPPORTED, "msk_gpu_sample_pixels: spp %u, at most %u (every sample of a pixel is rendered)",
+                    prm->spp, 1u << MSK_DEPTH_SHIFT);
     if (prm->rng_mode != MSK_RNG_COUNTER)
         return fail(ctx, MSK_ERR_UNSUPPORTED, "msk_gpu_sample_pixels: rng_mode %d (a pixel's samples are only addressable with the counter RNG: "
                     "a per-block PCG32 stream is sequential by construction)", prm->rng_mode);

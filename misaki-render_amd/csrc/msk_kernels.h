@@ -39,7 +39,7 @@ namespace msk {
 #define MSK_PRIM_ID 0x03ffffffu
 #define MSK_CLASS_SHIFT 27
 #define MSK_N_CLASSES 4
-#define MSK_DEPTH_SHIFT 20                 /* id.y: 20 bits of sample index (msk_gpu_render rejects more than 2^20 samples per pixel and pass), */
+#define MSK_DEPTH_SHIFT 20                 /* id.y: 20 bits of owned sample index (msk_gpu_render rejects more than 2^20 owned samples per pixel and call), */
 #define MSK_SI_MASK 0xfffffu               /* 12 bits of depth: a path that reaches bounce 4094 is cut (Russian roulette makes that a 1e-89 event) */
 #define MSK_MAX_DEPTH 4094u
 

@@ -1483,6 +1483,14 @@ void msk_oracle_block_put(const msk_film_desc *film, int off_x, int off_y, int s
     for (int i = 0; i < n; ++i) b.put(V2{pos2[2 * i], pos2[2 * i + 1]}, val5 + 5 * i);
     std::memcpy(out, b.data.data(), b.data.size() * sizeof(float));
 }
+// the same puts into a bordered block that already holds earlier ones (inout): one block's sample list fed in pieces
+void msk_oracle_block_put_acc(const msk_film_desc *film, int off_x, int off_y, int size_x, int size_y, int n,
+                              const float *pos2, const float *val5, float *inout) {
+    ImageBlock b; b.off_x = off_x; b.off_y = off_y; b.init(size_x, size_y, film, true);
+    std::memcpy(b.data.data(), inout, b.data.size() * sizeof(float));
+    for (int i = 0; i < n; ++i) b.put(V2{pos2[2 * i], pos2[2 * i + 1]}, val5 + 5 * i);
+    std::memcpy(inout, b.data.data(), b.data.size() * sizeof(float));
+}
 void msk_oracle_mesh_tables(void *s, uint32_t mesh, float *area, float *cdf, int max_cdf) {
     const Scene &sc = *(Scene *) s;
     *area = sc.mesh_area[mesh];

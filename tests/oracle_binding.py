@@ -40,6 +40,8 @@ class Oracle:
         lib.msk_oracle_spiral_blocks.restype = C.c_int
         lib.msk_oracle_block_put.argtypes = [C.POINTER(abi.FilmDesc), C.c_int, C.c_int, C.c_int, C.c_int,
                                              C.c_int, vp, vp, vp]
+        lib.msk_oracle_block_put_acc.argtypes = [C.POINTER(abi.FilmDesc), C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 C.c_int, vp, vp, vp]
         lib.msk_oracle_rgb2spec_fetch.argtypes = [C.c_int, vp, vp, vp, vp]
         lib.msk_oracle_det_math2.argtypes = [C.c_float, vp]
         lib.msk_oracle_bsdf_eval.argtypes = [C.POINTER(abi.BsdfDesc), C.c_int, C.c_int, vp, vp, vp, vp, vp]
@@ -218,6 +220,48 @@ class OracleScene:
         rc = self.orc.lib.msk_oracle_sample_pixels(self.h, C.byref(params), n, _p(pixels), _p(xyz), _p(pos))
         assert rc == 0
         return xyz, pos
+
+    def film_pixels(self, params, pixels, threads=16):
+        """float32[n, 5]: the film's {X,Y,Z,A,W} at the whole-film pixels `pixels` ((x, y) pairs), bit for bit what render()
+        puts there, from only the samples that can reach them — for sample counts at which a render of every block a pixel
+        touches is out of reach.  render() sums the bordered blocks in spiral order into a zeroed film (film_put); a block's
+        entry at F is the float32 sum of ImageBlock::put over the block's pixels in raster order, each pixel's samples in order.
+        A sample of source pixel s lies in [s, s + 1] and the filter reaches radius <= border + 1/2 from it, so only the
+        block's pixels within border + 1 of F can add to F: those are fed, in the same order, and the rest left out."""
+        assert params.rng_mode == self.abi.MSK_RNG_COUNTER and params.sample_first == 0 and params.sample_stride in (0, 1)
+        from concurrent.futures import ThreadPoolExecutor
+        fd = self.flat.desc.film
+        border = int(np.ceil(np.float32(fd.filter_radius) - np.float32(0.5)))       # rfilter.cpp:22
+        reach, spp = border + 1, params.spp
+        px = np.asarray(pixels, np.int64).reshape(-1, 2)
+        out = np.zeros((len(px), 5), np.float32)
+        bstride = params.block_stride or 1
+        chunk = max(threads, (1 << 22) // spp)                    # source pixels per block_put_acc call (bounds the memory)
+        with ThreadPoolExecutor(max(1, threads)) as pool:         # sample_pixels is single-threaded; ctypes drops the GIL
+            for bid, (ox, oy, sx, sy) in enumerate(self.orc.spiral_blocks(fd.width, fd.height, params.block_size)):
+                if bid % bstride != params.block_first:
+                    continue
+                hit = np.nonzero((px[:, 0] >= ox - border) & (px[:, 0] < ox + sx + border) &
+                                 (px[:, 1] >= oy - border) & (px[:, 1] < oy + sy + border))[0]
+                if not len(hit):
+                    continue
+                ys, xs = np.mgrid[oy:oy + sy, ox:ox + sx]
+                near = np.zeros((sy, sx), bool)
+                for f in hit:
+                    near |= (np.abs(xs - px[f, 0]) <= reach) & (np.abs(ys - px[f, 1]) <= reach)
+                src = np.stack([xs[near], ys[near]], -1).astype(np.int32)         # raster order within the block
+                buf = np.zeros((sy + 2 * border, sx + 2 * border, 5), np.float32)
+                for c0 in range(0, len(src), chunk):
+                    parts = list(pool.map(lambda p: self.sample_pixels(params, p[None]), src[c0:c0 + chunk]))
+                    xyz = np.concatenate([x.reshape(-1, 3) for x, _ in parts])
+                    pos = np.ascontiguousarray(np.concatenate([p.reshape(-1, 2) for _, p in parts]))
+                    val = np.ones((len(xyz), 5), np.float32)
+                    val[:, :3] = xyz                                  # integrator.cpp:119-123: {X, Y, Z, 1, 1}
+                    self.orc.lib.msk_oracle_block_put_acc(C.byref(fd), int(ox), int(oy), int(sx), int(sy), len(pos), _p(pos),
+                                                          _p(val), _p(buf))
+                for f in hit:
+                    out[f] += buf[px[f, 1] - oy + border, px[f, 0] - ox + border]       # film_put (oracle.cpp: render)
+        return out
 
     def trace_closest(self, rays):
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)

@@ -372,6 +372,40 @@ def test_error_behaviour(scene256, gpu_ctx, abi, hostmirror, golden_lookup):
         g.sample_pixels(abi.render_params(spp=1), np.array([[300, 2]], np.int32))
 
 
+def test_spp_limit_counts_the_owned_samples(gpu_ctx, abi, hostmirror, oracle, golden_lookup):
+    """The path state holds 20 bits of OWNED sample index (msk_kernels.h: MSK_DEPTH_SHIFT); the RNG key takes the global index
+    in 32 bits.  So a call may own at most 2^20 samples per pixel, whatever spp is: a shard of a render above 2^20 spp runs."""
+    g, o = abi.Scene(gpu_ctx, cbox(hostmirror, golden_lookup, 64, 64)), None
+    px = np.array([[3, 4]], np.int32)
+    try:
+        for kw in (dict(spp=(1 << 20) + 1), dict(spp=(1 << 21) + 2, sample_stride=2),      # 2^20 + 1 owned
+                   dict(spp=0xFFFFFFFF, sample_stride=4095)):     # 1,048,833 owned (a 32-bit owned count wraps to 0)
+            with pytest.raises(abi.MskError) as e:
+                g.render(abi.render_params(seed=1, **kw))
+            assert e.value.code == abi.MSK_ERR_UNSUPPORTED and "sample_stride" in str(e.value), kw
+        with pytest.raises(abi.MskError) as e:                      # sample_pixels renders all spp samples of a pixel
+            g.sample_pixels(abi.render_params(spp=1 << 21, sample_stride=2), px)
+        assert e.value.code == abi.MSK_ERR_UNSUPPORTED
+        # 64 owned samples with global indices 2^20 .. 2^20 + 63: bit-exact vs the oracle with the same selectors
+        crop = hostmirror.cbox_scene(64, 64, coeff_lookup=golden_lookup, crop=(10, 12, 40, 36))
+        gc, o = abi.Scene(gpu_ctx, crop), oracle.scene(crop)
+        prm = abi.render_params(spp=(1 << 20) + 64, seed=1, sample_first=1 << 20)
+        film, st = gc.render(prm)
+        ref, rst = o.render(prm, threads=16)
+        gc.close()
+        assert st.samples == rst.samples == 64 * 64 * 64
+        assert np.array_equal(film.view(np.uint32), ref.view(np.uint32))
+        # half of 2^21: exactly the 20-bit field, on a crop inside one block (one block rendered)
+        one = abi.Scene(gpu_ctx, hostmirror.cbox_scene(128, 128, coeff_lookup=golden_lookup, crop=(48, 48, 2, 2)))
+        film, st = one.render(abi.render_params(spp=1 << 21, seed=1, sample_first=1, sample_stride=2))
+        one.close()
+        assert st.samples == 32 * 32 * (1 << 20) and st.invalid_samples == 0 and (film[..., 4] > 0).all()
+    finally:
+        g.close()
+        if o is not None:
+            o.close()
+
+
 def test_two_members_behind_one_context(abi, hostmirror, oracle, golden_lookup):
     """msk_gpu_init(ids, n = 2) — rehearsed on the one GPU of the box with ids = {0, 0}: two member contexts, each renders the
     sample indices s = k (mod 2), the films are summed on the first device by k_film_sum.  The union of the shards is the
