@@ -56,6 +56,7 @@ extern "C" {
 #define MSK_BSDF_DIFFUSE        0  /* "diffuse"        bsdfs/diffuse.cpp:73          */
 #define MSK_BSDF_ROUGHCONDUCTOR 1  /* "roughconductor" bsdfs/roughconductor.cpp:139 (GGX only) */
 #define MSK_BSDF_ROUGHDIELECTRIC 2 /* "roughdielectric" bsdfs/roughdielectric.cpp:209 (GGX only) */
+#define MSK_BSDF_DIELECTRIC     3  /* "dielectric"     bsdfs/dielectric.cpp:105 (smooth interface: two delta lobes) */
 #define MSK_EMITTER_AREA       0   /* "area"     emitters/area.cpp:61          */
 #define MSK_TEXTURE_CHECKERBOARD 1 /* "checkerboard" textures/checkerboard.cpp:52 */
 
@@ -135,6 +136,12 @@ typedef struct msk_spectrum_desc {
  * MSK_BSDF_ROUGHDIELECTRIC (bsdfs/roughdielectric.cpp:14-55): GGX microfacet dielectric with reflection and
  * transmission lobes; ior_eta = int_ior / ext_ior, ior_inv_eta = ext_ior / int_ior, alpha_*, sample_visible,
  * specular_reflectance / specular_transmittance.
+ * MSK_BSDF_DIELECTRIC (bsdfs/dielectric.cpp:13-72): smooth dielectric interface, a delta reflection and a delta
+ * transmission lobe chosen by the Fresnel reflectance (render/fresnel.h:37-63); ior_eta / ior_inv_eta and
+ * specular_reflectance / specular_transmittance as for MSK_BSDF_ROUGHDIELECTRIC (the reference's defaults: int_ior 1.49,
+ * ext_ior 1.00028); alpha_* and sample_visible are ignored.  eval and pdf are zero: no next-event sample is taken at such a
+ * hit (path.cpp:56) and the emitter the sampled ray reaches counts with MIS weight 1 (path.cpp:104-106).  back_bsdf must be
+ * -1 (twosided.cpp:33-35: no transmission under "twosided").
  * back_bsdf implements the "twosided" adapter (bsdfs/twosided.cpp:38-101): the BSDF evaluated with
  * flipped wi/wo when cos(theta_i) < 0; the entry's own index for twosided(A), -1 for a one-sided BSDF.
  * reflectance_texture: 0 = the diffuse reflectance is the constant `reflectance`; k > 0 = it is

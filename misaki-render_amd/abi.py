@@ -16,6 +16,7 @@ MSK_REGULAR_MAX = 95
 MSK_OK = 0
 MSK_ERR_INVALID_ARG, MSK_ERR_NO_DEVICE, MSK_ERR_HIP, MSK_ERR_OOM, MSK_ERR_UNSUPPORTED = -1, -2, -3, -4, -5
 MSK_BSDF_DIFFUSE, MSK_BSDF_ROUGHCONDUCTOR, MSK_BSDF_ROUGHDIELECTRIC = 0, 1, 2
+MSK_BSDF_DIELECTRIC = 3       # "dielectric" (bsdfs/dielectric.cpp): smooth interface, two delta lobes
 MSK_EMITTER_AREA, MSK_EMITTER_CONSTANT = 0, 1
 MSK_TEXTURE_CHECKERBOARD = 1
 MSK_EMITTER_AREA = 0

@@ -110,6 +110,7 @@ struct msk_scene {
     DeviceScene dev;
     DevBuf nodes, nodes4, nodes4q, nodes8, tris, tris3, tri_bounds, tri_verts, tri_frames, tri_normals, tri_uvs, mesh_info, bsdfs, emitters, emitter_d65, emitter_grid, spectra, cdf, cie;
     bool lds_scene = false, lds_tables = false, all_diffuse = true;
+    bool has_dielectric = false;       // the scene holds a smooth `dielectric`: the instantiations with its delta lobes run (k_shade_gen_d, ...)
     bool has_regular = false;          // the scene holds tabulated spectra (ABI v7): the shading instantiations that evaluate them run
     int trace_mode = 0;                // 0 binary tree in LDS, 1 binary tree in HBM/L2, 2 4-wide tree in HBM/L2, 4 8-wide quantised tree in HBM/L2,
                                        // 5 4-wide tree with quantised boxes in HBM/L2 (64-byte nodes; the default for trees in HBM)
@@ -374,18 +375,21 @@ extern "C" int msk_gpu_scene_create(msk_ctx *ctx, const msk_scene_desc *d, msk_s
         o[4] = td.color1[0]; o[5] = td.color1[1]; o[6] = td.color1[2]; o[7] = td.to_uv[5];
         o[8] = td.to_uv[0]; o[9] = td.to_uv[1]; o[10] = td.to_uv[3]; o[11] = td.to_uv[4];
     }
-    bool all_diffuse = true;
+    bool all_diffuse = true, any_dielectric = false;
     for (uint32_t b = 0; b < d->n_bsdfs; ++b) {
         const msk_bsdf_desc &bd = d->bsdfs[b];
-        if (bd.type != MSK_BSDF_DIFFUSE && bd.type != MSK_BSDF_ROUGHCONDUCTOR && bd.type != MSK_BSDF_ROUGHDIELECTRIC)
+        if (bd.type != MSK_BSDF_DIFFUSE && bd.type != MSK_BSDF_ROUGHCONDUCTOR && bd.type != MSK_BSDF_ROUGHDIELECTRIC && bd.type != MSK_BSDF_DIELECTRIC)
             return fail(ctx, MSK_ERR_UNSUPPORTED,
-                        "bsdf %u: type %d is not supported by this back end (diffuse, roughconductor, roughdielectric)", b, bd.type);
+                        "bsdf %u: type %d is not supported by this back end (diffuse, roughconductor, roughdielectric, dielectric)", b, bd.type);
         if (bd.back_bsdf >= (int32_t) d->n_bsdfs || bd.back_bsdf < -1)
             return fail(ctx, MSK_ERR_INVALID_ARG, "bsdf %u: back_bsdf %d out of range", b, bd.back_bsdf);
         if (bd.type != MSK_BSDF_DIFFUSE && !(bd.alpha_u >= 0.f && bd.alpha_v >= 0.f))
             return fail(ctx, MSK_ERR_INVALID_ARG, "bsdf %u: negative roughness", b);
-        if (bd.type == MSK_BSDF_ROUGHDIELECTRIC && !(bd.ior_eta > 0.f && bd.ior_inv_eta > 0.f))
+        if ((bd.type == MSK_BSDF_ROUGHDIELECTRIC || bd.type == MSK_BSDF_DIELECTRIC) && !(bd.ior_eta > 0.f && bd.ior_inv_eta > 0.f))
             return fail(ctx, MSK_ERR_INVALID_ARG, "bsdf %u: the relative index of refraction must be positive", b);
+        if (bd.type == MSK_BSDF_DIELECTRIC && bd.back_bsdf >= 0)                                         // twosided.cpp:33-35
+            return fail(ctx, MSK_ERR_INVALID_ARG, "bsdf %u: Only materials without a transmission component can be nested!", b);
+        if (bd.type == MSK_BSDF_DIELECTRIC) any_dielectric = true;
         if (bd.reflectance_texture > d->n_textures)
             return fail(ctx, MSK_ERR_INVALID_ARG, "bsdf %u: reflectance_texture %u out of range", b, bd.reflectance_texture);
         if (bd.type == MSK_BSDF_DIFFUSE && !bd.reflectance_regular && !(bd.reflectance_scale >= 0.f && bd.reflectance_scale < INFINITY))
@@ -501,13 +505,13 @@ extern "C" int msk_gpu_scene_create(msk_ctx *ctx, const msk_scene_desc *d, msk_s
             std::memcpy(&w, &bvh.tris[k * 16 + 3], 4);
             std::memcpy(&mesh, &tv[(size_t) w * 12 + 3], 4);
             const int32_t b = mesh_info[(size_t) mesh * 4];
-            const uint32_t cls = (b >= 0 && (uint32_t) b < d->n_bsdfs) ? (uint32_t) d->bsdfs[b].type : 0u;      // MSK_BSDF_* = 0, 1, 2
+            const uint32_t cls = (b >= 0 && (uint32_t) b < d->n_bsdfs) ? (uint32_t) d->bsdfs[b].type : 0u;      // MSK_BSDF_* = 0, 1, 2, 3
             w |= (cls & (MSK_N_CLASSES - 1u)) << MSK_CLASS_SHIFT;
             std::memcpy(&bvh.tris[k * 16 + 3], &w, 4);
         }
 
     msk_scene *s = new msk_scene();
-    s->ctx = ctx; s->n_tris = d->n_faces; s->bvh_depth = bvh.max_depth; s->all_diffuse = all_diffuse; s->has_regular = any_regular;
+    s->ctx = ctx; s->n_tris = d->n_faces; s->bvh_depth = bvh.max_depth; s->all_diffuse = all_diffuse; s->has_regular = any_regular; s->has_dielectric = any_dielectric;
     std::vector<float> cie(d->cie1931_xyz, d->cie1931_xyz + 3 * MSK_CIE_SAMPLES);
     hipError_t e = hipSuccess;
     auto up = [&](DevBuf &b, const std::vector<float> &v) { if (e == hipSuccess) e = b.upload(v); };
@@ -1013,10 +1017,12 @@ static int run_wavefront(msk_scene *sc, hipStream_t stream, const msk_render_par
             // (not timed: msk_stats::ms_shade / ms_trace stay the sums of k_shade_gen / k_trace launches)
             hipEvent_t a = nullptr, b = nullptr;
             if (fused_h) {
-                if (diffuse_only) hipExtLaunchKernelGGL((k_wavefront_h<true>), dim3(grid), dim3(MSK_BLOCK), fused_lds, stream_h, a, b, 0, sc->dev, sb.st, pp, fused_iters, fused_queue_f4, fused_trace_f4);
+                if (sc->has_dielectric) hipExtLaunchKernelGGL(k_wavefront_h_d, dim3(grid), dim3(MSK_BLOCK), fused_lds, stream_h, a, b, 0, sc->dev, sb.st, pp, fused_iters, fused_queue_f4, fused_trace_f4);
+                else if (diffuse_only) hipExtLaunchKernelGGL((k_wavefront_h<true>), dim3(grid), dim3(MSK_BLOCK), fused_lds, stream_h, a, b, 0, sc->dev, sb.st, pp, fused_iters, fused_queue_f4, fused_trace_f4);
                 else if (sc->has_regular) hipExtLaunchKernelGGL((k_wavefront_h<false, true>), dim3(grid), dim3(MSK_BLOCK), fused_lds, stream_h, a, b, 0, sc->dev, sb.st, pp, fused_iters, fused_queue_f4, fused_trace_f4);
                 else hipExtLaunchKernelGGL((k_wavefront_h<false>), dim3(grid), dim3(MSK_BLOCK), fused_lds, stream_h, a, b, 0, sc->dev, sb.st, pp, fused_iters, fused_queue_f4, fused_trace_f4);
             }
+            else if (sc->has_dielectric) hipExtLaunchKernelGGL(k_wavefront_d, dim3(grid), dim3(MSK_BLOCK), fused_lds, stream_h, a, b, 0, sc->dev, sb.st, pp, fused_iters, fused_queue_f4, fused_trace_f4);
             else if (diffuse_only) hipExtLaunchKernelGGL((k_wavefront<true>), dim3(grid), dim3(MSK_BLOCK), fused_lds, stream_h, a, b, 0, sc->dev, sb.st, pp, fused_iters, fused_queue_f4, fused_trace_f4);
             else if (sc->has_regular) hipExtLaunchKernelGGL((k_wavefront<false, true>), dim3(grid), dim3(MSK_BLOCK), fused_lds, stream_h, a, b, 0, sc->dev, sb.st, pp, fused_iters, fused_queue_f4, fused_trace_f4);
             else hipExtLaunchKernelGGL((k_wavefront<false>), dim3(grid), dim3(MSK_BLOCK), fused_lds, stream_h, a, b, 0, sc->dev, sb.st, pp, fused_iters, fused_queue_f4, fused_trace_f4);
@@ -1028,7 +1034,11 @@ static int run_wavefront(msk_scene *sc, hipStream_t stream, const msk_render_par
                 if (timed) { a = p.ev.get(); b = p.ev.get(); c = p.ev.get(); d = p.ev.get(); }
                 const bool have_ev = a && b && c && d;
 #define MSK_SHADE(...) hipExtLaunchKernelGGL((k_shade_gen<__VA_ARGS__>), dim3(grid), dim3(MSK_BLOCK), shade_lds + shade_pad_lds, stream_h, a, b, 0, sc->dev, sb.st, pp)
-                if (sc->lds_tables) { if (diffuse_only) MSK_SHADE(true, true); else if (sc->has_regular) MSK_SHADE(true, false, true); else MSK_SHADE(true, false); }
+                if (sc->has_dielectric) {          // (never diffuse_only: such a scene is not all_diffuse)
+                    if (sc->lds_tables) hipExtLaunchKernelGGL((k_shade_gen_d<true>), dim3(grid), dim3(MSK_BLOCK), shade_lds + shade_pad_lds, stream_h, a, b, 0, sc->dev, sb.st, pp);
+                    else hipExtLaunchKernelGGL((k_shade_gen_d<false>), dim3(grid), dim3(MSK_BLOCK), shade_lds + shade_pad_lds, stream_h, a, b, 0, sc->dev, sb.st, pp);
+                }
+                else if (sc->lds_tables) { if (diffuse_only) MSK_SHADE(true, true); else if (sc->has_regular) MSK_SHADE(true, false, true); else MSK_SHADE(true, false); }
                 else { if (diffuse_only) MSK_SHADE(false, true); else if (sc->has_regular) MSK_SHADE(false, false, true); else MSK_SHADE(false, false); }
 #undef MSK_SHADE
                 if (dump_path && p.it == dump_iter && p.first == 0) dump_rays(p);      // (measurements only: MSK_DUMP_RAYS)
@@ -1310,7 +1320,8 @@ static int render_serial(msk_scene *sc, const msk_render_params *prm, float *d_f
         sp.blocks = ws.blocks.as<BlockInfo>(); sp.n_blocks = (uint32_t) owned.size();
         sp.block_buf = ws.block_buf.as<float>(); sp.buf_stride = buf_stride;
         sp.stack_ovf = ovf.as<uint32_t>(); sp.counters = counters.as<unsigned long long>(); sp.per_wave = per_wave ? 1u : 0u;
-        hipLaunchKernelGGL(k_path_serial, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
+        if (sc->has_dielectric) hipLaunchKernelGGL(k_path_serial_d, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
+        else hipLaunchKernelGGL(k_path_serial, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
     }
     FilmOut fo;
     fo.film = d_film; fo.stride = 5;

@@ -34,7 +34,7 @@ namespace msk {
 #define MSK_NO_PRIM 0xffffffffu
 // The prim word of a triangle record / hit record: bits 0..25 the scene-global triangle index (msk_gpu_scene_create rejects
 // scenes of 2^26 triangles and more), bits 27..28 the MATERIAL CLASS of the triangle's BSDF (0 diffuse, 1 rough conductor,
-// 2 rough dielectric; a miss reads 3), written into the leaf records at scene creation so that the traversal kernels deliver
+// 2 rough dielectric, 3 smooth dielectric; a miss reads 3 too and shares the last place of the sort with it), written into the leaf records at scene creation so that the traversal kernels deliver
 // it with the hit for free.  k_shade_gen sorts a region's paths by it (material-sorted shading, shade_region).
 #define MSK_PRIM_ID 0x03ffffffu
 #define MSK_CLASS_SHIFT 27
@@ -105,7 +105,9 @@ struct PathState {
     float4 *sh;         // shadow d.xyz, tmax                                        } written / read only for the slots
     float4 *contrib;    // NEE contribution added when the shadow ray is unoccluded  } c < ns of a region (RegionView)
     float4 *hit;        // t,u,v,prim
-    float2 *aux;        // {eta (path.cpp:29), pdf_emitter_direct of the last NEE record (path.cpp:103-106 on an environment hit)}
+    float2 *aux;        // {eta (path.cpp:29), pdf_emitter_direct of the last NEE record (path.cpp:103-106 on an environment hit)}.
+                        // eta > 0; its SIGN BIT set = the bounce that made ray_d sampled a delta lobe (a smooth `dielectric`): the
+                        // emitter pdf of the next hit's MIS weight is then 0 (path.cpp:104-106).  Scenes with such a BSDF only.
 };
 
 // Per-region bookkeeping, one record per wave-region, touched only by its owner wave: no atomics
@@ -1388,8 +1390,13 @@ struct SceneTables {
 // records of the table form, emitters' tables on their own grids).  Scenes without any — every BASELINE config — run the
 // instantiations that do not carry those branches (measured: 3.2 % of the config-3-class render, 1.4 % of the config-5-class one).
 struct SceneTablesR : SceneTables {};
-template <class TB> struct tb_traits { static constexpr bool regular = false; };
-template <> struct tb_traits<SceneTablesR> { static constexpr bool regular = true; };
+// ... and the tables of a scene that holds a smooth `dielectric` (MSK_BSDF_DIELECTRIC): the delta lobes, the guard around next-event
+// estimation and the delta mark of the path state are compiled only into the instantiations that carry this type, which such
+// scenes alone run.  It carries the table forms of tabulated spectra always (as k_path_serial does): one set of instantiations.
+struct SceneTablesD : SceneTablesR {};
+template <class TB> struct tb_traits { static constexpr bool regular = false, dielectric = false; };
+template <> struct tb_traits<SceneTablesR> { static constexpr bool regular = true, dielectric = false; };
+template <> struct tb_traits<SceneTablesD> { static constexpr bool regular = true, dielectric = true; };
 MSK_DEV uint32_t tables_lds_float4s(const DeviceScene &sc) {
     return sc.n_tris * 6 + sc.n_meshes + sc.n_bsdf_f4 + sc.n_emitters * 3 + (sc.n_emitters * 95 + 3) / 4 + (sc.cdf_len + 3) / 4 + 72 + (sc.n_spectra + 3) / 4;
 }
@@ -1623,6 +1630,28 @@ MSK_DEV spec roughdielectric_sample(const TB &tb, const BsdfRec &b, f3 wi, float
     return weight;
 }
 
+// bsdfs/dielectric.cpp:26-72 sample (both delta components enabled, TransportMode::Radiance): the lobe is chosen by the x of the
+// 2D sample, not by sample1; *eta_out = bs.eta.  fresnel.h:12-14,22-27: reflect(wi), refract(wi, cos_theta_t, eta_ti).
+template <class TB>
+MSK_DEV spec dielectric_sample(const TB &tb, const BsdfRec &b, f3 wi, f2 sample, spec wl, f3 *wo, float *pdf, float *eta_out, bool *ok) {
+    float r_i, cos_t, eta_it, eta_ti;
+    fresnel_dielectric(wi.z, b.ior.x, &r_i, &cos_t, &eta_it, &eta_ti);
+    const float t_i = 1.f - r_i;
+    const bool selected_r = sample.x <= r_i;
+    *ok = true;
+    *pdf = selected_r ? r_i : t_i;
+    *eta_out = selected_r ? 1.f : eta_it;
+    if (selected_r) {
+        *wo = mk3(-wi.x, -wi.y, wi.z);
+        return spectrum_eval(tb, b.spec, wl);
+    }
+    *wo = mk3(-eta_ti * wi.x, -eta_ti * wi.y, cos_t);
+    return spectrum_eval(tb, b.trans, wl) * eta_ti * eta_ti;
+}
+// BSDFFlags::Smooth (path.cpp:56): every lobe but the delta ones of `dielectric` takes a next-event sample
+template <class TB>
+MSK_DEV bool bsdf_is_delta(const BsdfRec &b) { return tb_traits<TB>::dielectric && __float_as_int(b.a.x) == MSK_BSDF_DIELECTRIC; }
+
 // eval + pdf with wi on the front side (roughconductor.cpp:82-117 / diffuse.cpp:35-57)
 // `refl` = the diffuse reflectance spectrum at wl, evaluated once per bounce by the caller (used by eval and by sample)
 template <bool DIFFUSE_ONLY, class TB>
@@ -1637,6 +1666,7 @@ MSK_DEV void bsdf_eval_pdf(const TB &tb, const BsdfRec &b, f3 wi, f3 wo, spec wl
         return;
     }
     if (__float_as_int(b.a.x) == MSK_BSDF_ROUGHDIELECTRIC) { roughdielectric_eval_pdf(tb, b, wi, wo, wl, val, pdf); return; }
+    if (tb_traits<TB>::dielectric && __float_as_int(b.a.x) == MSK_BSDF_DIELECTRIC) return;      // dielectric.cpp:74-82: zero
     const float au = clamp_alpha(b.b.y), av = clamp_alpha(b.b.z);
     if (cos_i > 0.f && cos_o > 0.f) {
         const f3 H = normalized(wo + wi);
@@ -1665,6 +1695,8 @@ MSK_DEV spec bsdf_sample(const TB &tb, const BsdfRec &b, f3 wi, float sample1, f
     *wo = mk3(0.f, 0.f, 0.f); *pdf = 0.f; *ok = false; *eta_out = 1.f;
     if (!DIFFUSE_ONLY && __float_as_int(b.a.x) == MSK_BSDF_ROUGHDIELECTRIC)
         return roughdielectric_sample(tb, b, wi, sample1, sample, wl, wo, pdf, eta_out, ok);
+    if (!DIFFUSE_ONLY && tb_traits<TB>::dielectric && __float_as_int(b.a.x) == MSK_BSDF_DIELECTRIC)
+        return dielectric_sample(tb, b, wi, sample, wl, wo, pdf, eta_out, ok);
     const float cos_i = wi.z;
     if (cos_i <= 0.f) return splat(0.f);
     *ok = true;
@@ -1948,6 +1980,10 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
         hit.w = __uint_as_float(__float_as_uint(hit.w) & MSK_PRIM_ID);
         float bs_pdf = -rd4.w;                                             // meaningful for depth > 1 (PathState::ray_d)
         float eta = cur.aux.x, nee_pdf = cur.aux.y;                        // carried only by the general variant
+        // the sign of eta (> 0) says that the bounce which made this ray sampled a delta lobe (BSDFFlags::Delta, path.cpp:104-106)
+        const bool delta_in = tb_traits<TB>::dielectric && cur.aux.x < 0.f;
+        if (tb_traits<TB>::dielectric) eta = fabsf(eta);
+        bool delta_out = false;
         uint32_t depth = id.y >> MSK_DEPTH_SHIFT;
         const uint32_t s_own = id.y & MSK_SI_MASK;
         const f3 rd = mk3(rd4.x, rd4.y, rd4.z);
@@ -1967,7 +2003,7 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
                 if (depth == 1) {
                     if (!pp.hide_emitters && pp.max_depth != 0) res = res + thr * emitter_radiance(tb, sc.env_emitter, wl);   // path.cpp:33
                 }
-                else res = res + thr * emitter_radiance(tb, sc.env_emitter, wl) * mis_weight(bs_pdf, nee_pdf);
+                else res = res + thr * emitter_radiance(tb, sc.env_emitter, wl) * mis_weight(bs_pdf, delta_in ? 0.f : nee_pdf);
             }
             alive = false;
         }
@@ -2000,6 +2036,7 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
                     const float dp = fabsf(dot(rd, si.sh.n));
                     pdf *= (dp != 0.f) ? (si.t * si.t) / dp : 0.f;
                     if (n_em != 1) pdf = pdf * (1.f / n_em);
+                    if (delta_in) pdf = 0.f;
                     res = res + thr * value * mis_weight(bs_pdf, pdf);
                 }
                 // ---- Russian roulette (path.cpp:116-122)
@@ -2027,8 +2064,9 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
                     if (tex) { c = checkerboard_coeffs(tb, tex, hit); scale = 1.f; }
                     refl = spectrum_eval(tb, make_float4(c.x, c.y, c.z, scale), wl);      // (scale -1: a `regular` reflectance)
                 }
-                // ---- next-event estimation (path.cpp:56-67, scene.cpp:68-103)
-                if (n_em > 0) {
+                // ---- next-event estimation (path.cpp:56-67, scene.cpp:68-103): not at a BSDF without a smooth lobe
+                delta_out = bsdf_is_delta<TB>(bs);
+                if (n_em > 0 && !delta_out) {
                     f2 u = counter_pair(key, pb + 0);
                     uint32_t e = 0;
                     float light_sel_pdf = 1.f;
@@ -2172,7 +2210,7 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
             st4<1>(st.wl + o, to4(wl)); st4<1>(st.thr + o, to4(thr)); st4<1>(st.res + o, to4(res));
             st4<4>(st.ray_o + o, new_o); st4<4>(st.ray_d + o, new_d);
             if (has_shadow) { st4<4>(st.sh + o, new_sh); st4<1>(st.contrib + o, to4(contrib)); }
-            if (!DIFFUSE_ONLY) st.aux[o] = make_float2(eta, nee_pdf);
+            if (!DIFFUSE_ONLY) st.aux[o] = make_float2(delta_out ? -eta : eta, nee_pdf);
         }
         cur_s += (uint32_t) __popcll(m_s); cur_n += (uint32_t) __popcll(m_n);
     }
@@ -2263,10 +2301,14 @@ MSK_DEV DoneQueue done_queue(float4 *base) {
     return dq;
 }
 
-template <bool LDS_TABLES, bool DIFFUSE_ONLY, bool REGULAR = false>
+// the table type of an instantiation: plain, with tabulated spectra, with the smooth dielectric (which includes them)
+template <bool REGULAR, bool DIELECTRIC>
+using tables_of = typename std::conditional<DIELECTRIC, SceneTablesD, typename std::conditional<REGULAR, SceneTablesR, SceneTables>::type>::type;
+
+template <bool LDS_TABLES, bool DIFFUSE_ONLY, bool REGULAR = false, bool DIELECTRIC = false>
 MSK_DEV void shade_gen_body(const DeviceScene &sc, const PathState &st, const PassParams &pp) {
     extern __shared__ float4 lds_dyn[];
-    typename std::conditional<REGULAR, SceneTablesR, SceneTables>::type tb;
+    tables_of<REGULAR, DIELECTRIC> tb;
     static_cast<SceneTables &>(tb) = stage_tables<LDS_TABLES>(sc, lds_dyn);
     const uint32_t lwave = (blockIdx.x * MSK_BLOCK + threadIdx.x) / MSK_WAVE;
     const uint32_t queue_f4 = LDS_TABLES ? tables_lds_float4s(sc) : small_tables_float4s(sc);   // after the staged tables
@@ -2300,6 +2342,11 @@ k_shade_gen<false, false, true>(DeviceScene sc, PathState st, PassParams pp) { s
 template <>
 __global__ void __launch_bounds__(MSK_BLOCK) __attribute__((amdgpu_waves_per_eu(MSK_SHADE_GEN_WAVES)))
 k_shade_gen<true, false, true>(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<true, false, true>(sc, st, pp); }
+// ... and the two that scenes with a smooth `dielectric` run, and only they (SceneTablesD): kernels of their own, so that every
+// other scene launches the kernels above, unchanged
+template <bool LDS_TABLES>
+__global__ void __launch_bounds__(MSK_BLOCK) __attribute__((amdgpu_waves_per_eu(MSK_SHADE_GEN_WAVES)))
+k_shade_gen_d(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_TABLES, false, true, true>(sc, st, pp); }
 // The diffuse-only variants fit four waves per SIMD (128 VGPRs, no scratch); left alone, the allocator spends 24 more registers
 // on the explicit fp64 fma chains of det_sincos and lands at three.
 #ifndef MSK_NO_SHADE4
@@ -2318,51 +2365,64 @@ k_shade_gen<true, true>(DeviceScene sc, PathState st, PassParams pp) { shade_gen
 // left (or `max_iters` sweeps have run: a bounded launch, the host relaunches while work remains).  Tables, tree and
 // triangles are staged once per block instead of once per launch.  Same arithmetic as k_shade_gen / k_trace<0>: same records.
 // ------------------------------------------------------------------------------------------
+// The kernel body is written once, as a macro over the table type TB and DIFFUSE_ONLY, and stamped into k_wavefront and into
+// k_wavefront_d: the instantiations every scene without a `dielectric` runs then compile from the token stream they always had.
+#define MSK_WAVEFRONT_BODY \
+    extern __shared__ float4 lds_dyn[];                                                                                                                            \
+    /* LDS: [tables][done queues][traversal stacks][tree + triangles]; offsets in float4 from the host's plan */                                                   \
+    TB tb;                                                                                                                                                         \
+    static_cast<SceneTables &>(tb) = stage_tables<true>(sc, lds_dyn);                                                                                              \
+    const DoneQueue dq = done_queue(lds_dyn + queue_f4);                                                                                                           \
+    uint32_t *stack_base = (uint32_t *) (lds_dyn + trace_f4);                                                                                                      \
+    float4 *scene_lds = lds_dyn + trace_f4 + (sc.stack_entries * MSK_BLOCK) / 4;                                                                                   \
+    const TraceLds g = stage_scene(sc, scene_lds, true, false);                                                                                                    \
+    const LaneStack<false> stack{stack_base + threadIdx.x, nullptr, (int) sc.stack_entries, 0};                                                                    \
+    const uint32_t lwave = (blockIdx.x * MSK_BLOCK + threadIdx.x) / MSK_WAVE;                                                                                      \
+    const uint32_t lane = threadIdx.x & (MSK_WAVE - 1);                                                                                                            \
+    if (lwave >= pp.region_count) return;                                                                                                                          \
+    const uint32_t wave = pp.region_first + lwave;                                                                                                                 \
+    for (uint32_t it = 0; it < max_iters; ++it) {                                                                                                                  \
+        const RegionView rv = shade_region<DIFFUSE_ONLY>(sc, tb, dq, SortScratch{nullptr, nullptr}, st, pp, wave, lane);   /* (the thin end of a pass: no sort) */ \
+        /* the rays this wave has just written are read back by the same wave (other lanes): program order through the */                                          \
+        /* CU's own L1 after the stores have drained */                                                                                                            \
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");                                                                                                     \
+        if (rv.n == 0) break;   /* no live path, and regeneration found no sample to start */                                                                      \
+        if (MSK_THIN_RAYS_LDS && rv.n + rv.ns <= MSK_WAVE) trace_thin<0>(sc, st, g, rv, stack, lane, 4);   /* one ray per lane (see trace_thin) */                 \
+        else                                                                                                                                                       \
+        for (uint32_t c = lane; c < rv.n; c += MSK_WAVE) {                                                                                                         \
+            const uint32_t i = rv.slot(c);                                                                                                                         \
+            const float4 ro = st.ray_o[i];                                                                                                                         \
+            float4 rd = st.ray_d[i];                                                                                                                               \
+            const bool has_shadow = c < rv.ns;                                                                                                                     \
+            rd.w = slot_tmax(rd.w);                                                                                                                                \
+            const f3 o = mk3(ro.x, ro.y, ro.z);                                                                                                                    \
+            float bt, bu, bv; uint32_t bp;                                                                                                                         \
+            uint32_t unocc = 0;                                                                                                                                    \
+            if (has_shadow) {                                                                                                                                      \
+                const float4 s = st.sh[i];                                                                                                                         \
+                const bool occ = traverse_scene<0, true>(sc, g, o, mk3(s.x, s.y, s.z), ro.w, s.w, stack, &bt, &bu, &bv, &bp);                                      \
+                unocc = occ ? 0u : MSK_HIT_UNOCCLUDED;                                                                                                             \
+            }                                                                                                                                                      \
+            traverse_scene<0, false>(sc, g, o, mk3(rd.x, rd.y, rd.z), ro.w, rd.w, stack, &bt, &bu, &bv, &bp);                                                      \
+            const bool valid = (bp != MSK_NO_PRIM) && (bt != rd.w);   /* scene.cpp:234 tfar != maxt */                                                             \
+            st.hit[i] = make_float4(valid ? bt : MSK_INF_F, bu, bv, __uint_as_float((valid ? bp : MSK_PRIM_MASK) | unocc));                                        \
+        }                                                                                                                                                          \
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");                                                                                                     \
+    }
 template <bool DIFFUSE_ONLY, bool REGULAR = false>
 __global__ void __launch_bounds__(MSK_BLOCK)
 k_wavefront(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
-    extern __shared__ float4 lds_dyn[];
-    // LDS: [tables][done queues][traversal stacks][tree + triangles]; offsets in float4 from the host's plan
-    typename std::conditional<REGULAR, SceneTablesR, SceneTables>::type tb;
-    static_cast<SceneTables &>(tb) = stage_tables<true>(sc, lds_dyn);
-    const DoneQueue dq = done_queue(lds_dyn + queue_f4);
-    uint32_t *stack_base = (uint32_t *) (lds_dyn + trace_f4);
-    float4 *scene_lds = lds_dyn + trace_f4 + (sc.stack_entries * MSK_BLOCK) / 4;
-    const TraceLds g = stage_scene(sc, scene_lds, true, false);
-    const LaneStack<false> stack{stack_base + threadIdx.x, nullptr, (int) sc.stack_entries, 0};
-    const uint32_t lwave = (blockIdx.x * MSK_BLOCK + threadIdx.x) / MSK_WAVE;
-    const uint32_t lane = threadIdx.x & (MSK_WAVE - 1);
-    if (lwave >= pp.region_count) return;
-    const uint32_t wave = pp.region_first + lwave;
-    for (uint32_t it = 0; it < max_iters; ++it) {
-        const RegionView rv = shade_region<DIFFUSE_ONLY>(sc, tb, dq, SortScratch{nullptr, nullptr}, st, pp, wave, lane);   // (the thin end of a pass: no sort)
-        // the rays this wave has just written are read back by the same wave (other lanes): program order through the
-        // CU's own L1 after the stores have drained
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        if (rv.n == 0) break;                                  // no live path, and regeneration found no sample to start
-        if (MSK_THIN_RAYS_LDS && rv.n + rv.ns <= MSK_WAVE) trace_thin<0>(sc, st, g, rv, stack, lane, 4);      // one ray per lane (see trace_thin)
-        else
-        for (uint32_t c = lane; c < rv.n; c += MSK_WAVE) {
-            const uint32_t i = rv.slot(c);
-            const float4 ro = st.ray_o[i];
-            float4 rd = st.ray_d[i];
-            const bool has_shadow = c < rv.ns;
-            rd.w = slot_tmax(rd.w);
-            const f3 o = mk3(ro.x, ro.y, ro.z);
-            float bt, bu, bv; uint32_t bp;
-            uint32_t unocc = 0;
-            if (has_shadow) {
-                const float4 s = st.sh[i];
-                const bool occ = traverse_scene<0, true>(sc, g, o, mk3(s.x, s.y, s.z), ro.w, s.w, stack, &bt, &bu, &bv, &bp);
-                unocc = occ ? 0u : MSK_HIT_UNOCCLUDED;
-            }
-            traverse_scene<0, false>(sc, g, o, mk3(rd.x, rd.y, rd.z), ro.w, rd.w, stack, &bt, &bu, &bv, &bp);
-            const bool valid = (bp != MSK_NO_PRIM) && (bt != rd.w);           // scene.cpp:234 tfar != maxt
-            st.hit[i] = make_float4(valid ? bt : MSK_INF_F, bu, bv, __uint_as_float((valid ? bp : MSK_PRIM_MASK) | unocc));
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    }
+    typedef typename std::conditional<REGULAR, SceneTablesR, SceneTables>::type TB;
+    MSK_WAVEFRONT_BODY
 }
+// the one scenes with a smooth `dielectric` run (see k_shade_gen_d)
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_wavefront_d(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
+    typedef SceneTablesD TB;
+    constexpr bool DIFFUSE_ONLY = false;
+    MSK_WAVEFRONT_BODY
+}
+#undef MSK_WAVEFRONT_BODY
 
 // k_wavefront_h (round 6): the same device-side loop for scenes whose TREE STAYS IN HBM / L2 (trace mode 6: the 4-wide tree with
 // half-float boxes) — for the thin end of a pass.  Measured on the mesh configs (profiles/r06_tail_*.txt): once every sample has
@@ -2372,49 +2432,60 @@ k_wavefront(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uin
 // own region until it is empty.  Tables: the small ones in LDS as in k_shade_gen<false, *>; rays: whole chunks through
 // traverse4h (k_trace<6>'s walk — the arithmetic of k_trace_r<6>'s lanes, so the same hits; lane replacement has nothing to
 // replace with when a region holds a chunk or two).
+#define MSK_WAVEFRONT_H_BODY \
+    extern __shared__ float4 lds_dyn[];                                                                                                         \
+    /* LDS: [small tables][done queues][traversal stacks + four words per lane of node4h_step]; offsets in float4 from the host's plan */       \
+    TB tb;                                                                                                                                      \
+    static_cast<SceneTables &>(tb) = stage_tables<false>(sc, lds_dyn);                                                                          \
+    const DoneQueue dq = done_queue(lds_dyn + queue_f4);                                                                                        \
+    uint32_t *stack_base = (uint32_t *) (lds_dyn + trace_f4);                                                                                   \
+    const TraceLds g = stage_scene(sc, nullptr, false, false);                                                                                  \
+    const LaneStack<true> stack{stack_base + threadIdx.x, pp.stack_ovf + (size_t) blockIdx.x * MSK_BLOCK + threadIdx.x, (int) sc.stack_entries, \
+                                (size_t) gridDim.x * MSK_BLOCK, stack_base + sc.stack_entries * MSK_BLOCK + threadIdx.x * 4};                   \
+    const uint32_t lwave = (blockIdx.x * MSK_BLOCK + threadIdx.x) / MSK_WAVE;                                                                   \
+    const uint32_t lane = threadIdx.x & (MSK_WAVE - 1);                                                                                         \
+    if (lwave >= pp.region_count) return;                                                                                                       \
+    const uint32_t wave = pp.region_first + lwave;                                                                                              \
+    for (uint32_t it = 0; it < max_iters; ++it) {                                                                                               \
+        const RegionView rv = shade_region<DIFFUSE_ONLY>(sc, tb, dq, SortScratch{nullptr, nullptr}, st, pp, wave, lane);                        \
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   /* the rays just written are read back by this wave's other lanes */           \
+        if (rv.n == 0) break;                                                                                                                   \
+        if (MSK_THIN_RAYS && rv.n + rv.ns <= MSK_WAVE) trace_thin<6>(sc, st, g, rv, stack, lane, 3);                                            \
+        else                                                                                                                                    \
+        for (uint32_t c = lane; c < rv.n; c += MSK_WAVE) {                                                                                      \
+            const uint32_t i = rv.slot(c);                                                                                                      \
+            const float4 ro = st.ray_o[i];                                                                                                      \
+            float4 rd = st.ray_d[i];                                                                                                            \
+            const bool has_shadow = c < rv.ns;                                                                                                  \
+            rd.w = slot_tmax(rd.w);                                                                                                             \
+            const f3 o = mk3(ro.x, ro.y, ro.z);                                                                                                 \
+            float bt, bu, bv; uint32_t bp;                                                                                                      \
+            uint32_t unocc = 0;                                                                                                                 \
+            if (has_shadow) {                                                                                                                   \
+                const float4 s = st.sh[i];                                                                                                      \
+                const bool occ = traverse_scene<6, true>(sc, g, o, mk3(s.x, s.y, s.z), ro.w, s.w, stack, &bt, &bu, &bv, &bp);                   \
+                unocc = occ ? 0u : MSK_HIT_UNOCCLUDED;                                                                                          \
+            }                                                                                                                                   \
+            traverse_scene<6, false>(sc, g, o, mk3(rd.x, rd.y, rd.z), ro.w, rd.w, stack, &bt, &bu, &bv, &bp);                                   \
+            const bool valid = (bp != MSK_NO_PRIM) && (bt != rd.w);   /* scene.cpp:234 tfar != maxt */                                          \
+            st.hit[i] = make_float4(valid ? bt : MSK_INF_F, bu, bv, __uint_as_float((valid ? bp : MSK_PRIM_MASK) | unocc));                     \
+        }                                                                                                                                       \
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");                                                                                  \
+    }
 template <bool DIFFUSE_ONLY, bool REGULAR = false>
 __global__ void __launch_bounds__(MSK_BLOCK)
 k_wavefront_h(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
-    extern __shared__ float4 lds_dyn[];
-    // LDS: [small tables][done queues][traversal stacks + four words per lane of node4h_step]; offsets in float4 from the host's plan
-    typename std::conditional<REGULAR, SceneTablesR, SceneTables>::type tb;
-    static_cast<SceneTables &>(tb) = stage_tables<false>(sc, lds_dyn);
-    const DoneQueue dq = done_queue(lds_dyn + queue_f4);
-    uint32_t *stack_base = (uint32_t *) (lds_dyn + trace_f4);
-    const TraceLds g = stage_scene(sc, nullptr, false, false);
-    const LaneStack<true> stack{stack_base + threadIdx.x, pp.stack_ovf + (size_t) blockIdx.x * MSK_BLOCK + threadIdx.x, (int) sc.stack_entries,
-                                (size_t) gridDim.x * MSK_BLOCK, stack_base + sc.stack_entries * MSK_BLOCK + threadIdx.x * 4};
-    const uint32_t lwave = (blockIdx.x * MSK_BLOCK + threadIdx.x) / MSK_WAVE;
-    const uint32_t lane = threadIdx.x & (MSK_WAVE - 1);
-    if (lwave >= pp.region_count) return;
-    const uint32_t wave = pp.region_first + lwave;
-    for (uint32_t it = 0; it < max_iters; ++it) {
-        const RegionView rv = shade_region<DIFFUSE_ONLY>(sc, tb, dq, SortScratch{nullptr, nullptr}, st, pp, wave, lane);
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");    // the rays just written are read back by this wave's other lanes
-        if (rv.n == 0) break;
-        if (MSK_THIN_RAYS && rv.n + rv.ns <= MSK_WAVE) trace_thin<6>(sc, st, g, rv, stack, lane, 3);
-        else
-        for (uint32_t c = lane; c < rv.n; c += MSK_WAVE) {
-            const uint32_t i = rv.slot(c);
-            const float4 ro = st.ray_o[i];
-            float4 rd = st.ray_d[i];
-            const bool has_shadow = c < rv.ns;
-            rd.w = slot_tmax(rd.w);
-            const f3 o = mk3(ro.x, ro.y, ro.z);
-            float bt, bu, bv; uint32_t bp;
-            uint32_t unocc = 0;
-            if (has_shadow) {
-                const float4 s = st.sh[i];
-                const bool occ = traverse_scene<6, true>(sc, g, o, mk3(s.x, s.y, s.z), ro.w, s.w, stack, &bt, &bu, &bv, &bp);
-                unocc = occ ? 0u : MSK_HIT_UNOCCLUDED;
-            }
-            traverse_scene<6, false>(sc, g, o, mk3(rd.x, rd.y, rd.z), ro.w, rd.w, stack, &bt, &bu, &bv, &bp);
-            const bool valid = (bp != MSK_NO_PRIM) && (bt != rd.w);           // scene.cpp:234 tfar != maxt
-            st.hit[i] = make_float4(valid ? bt : MSK_INF_F, bu, bv, __uint_as_float((valid ? bp : MSK_PRIM_MASK) | unocc));
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    }
+    typedef typename std::conditional<REGULAR, SceneTablesR, SceneTables>::type TB;
+    MSK_WAVEFRONT_H_BODY
 }
+// the one scenes with a smooth `dielectric` run (see k_shade_gen_d)
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_wavefront_h_d(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
+    typedef SceneTablesD TB;
+    constexpr bool DIFFUSE_ONLY = false;
+    MSK_WAVEFRONT_H_BODY
+}
+#undef MSK_WAVEFRONT_H_BODY
 
 // AOVIntegrator::sample's primary-hit channels (aov.cpp:89-122): runs after k_trace, picks the slots whose camera ray
 // has just been traced (depth 1) and writes their record groups.  A miss writes zeros.

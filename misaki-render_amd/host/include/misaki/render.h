@@ -129,6 +129,7 @@ public:
     // `textures`: the scene's table of surface-varying textures; a BSDF that uses one appends it (msk_bsdf_desc::reflectance_texture)
     virtual bool flatten(msk_bsdf_desc &out, FlatTables &tables) const { (void) out; (void) tables; return false; }
     virtual const BSDF *nested(int side) const { (void) side; return nullptr; }   // twosided: the BSDF of side 0 / 1
+    virtual bool has_transmission() const { return false; }                        // BSDFFlags::Transmission, as far as twosided.cpp:33-35 asks
     std::string id() const override { return m_id; }
     MSK_DECLARE_CLASS()
 protected:

@@ -558,6 +558,33 @@ private:
 MSK_IMPLEMENT_CLASS(RoughDielectric, BSDF)
 MSK_REGISTER_INSTANCE(RoughDielectric, "roughdielectric")
 
+// bsdfs/dielectric.cpp:13-24: the smooth interface.  eta = int_ior / ext_ior in fp32; the device takes it from there
+// (Fresnel term, lobe choice, refraction: msk_kernels.h dielectric_sample).
+class SmoothDielectric final : public BSDF {
+public:
+    SmoothDielectric(const Properties &props) : BSDF(props) {
+        const float int_ior = props.float_("int_ior", 1.49f), ext_ior = props.float_("ext_ior", 1.00028f);
+        m_eta = int_ior / ext_ior; m_inv_eta = ext_ior / int_ior;
+        m_specular_reflectance = props.texture("specular_reflectance", 1.f);
+        m_specular_transmittance = props.texture("specular_transmittance", 1.f);
+    }
+    bool has_transmission() const override { return true; }
+    bool flatten(msk_bsdf_desc &out, FlatTables &tables) const override {
+        Texture::Flat r, t;
+        if (!m_specular_reflectance->flatten(r) || !m_specular_transmittance->flatten(t) || r.uses_d65 || t.uses_d65) return false;
+        init_bsdf_desc(out);
+        out.type = MSK_BSDF_DIELECTRIC;
+        out.ior_eta = m_eta; out.ior_inv_eta = m_inv_eta;
+        return tables.put(out.specular_reflectance, r) && tables.put(out.specular_transmittance, t);
+    }
+    MSK_DECLARE_CLASS()
+private:
+    ref<Texture> m_specular_reflectance, m_specular_transmittance;
+    float m_eta, m_inv_eta;
+};
+MSK_IMPLEMENT_CLASS(SmoothDielectric, BSDF)
+MSK_REGISTER_INSTANCE(SmoothDielectric, "dielectric")
+
 // bsdfs/twosided.cpp:12-36
 class TwoSidedBRDF final : public BSDF {
 public:
@@ -569,6 +596,8 @@ public:
         else if (bsdfs.size() > 2) Throw("At most two nested BSDFs can be specified!");
         if (!m_brdf[0]) Throw("A nested one-sided material is required!");
         if (!m_brdf[1]) m_brdf[1] = m_brdf[0];
+        // twosided.cpp:33-35 (BSDFFlags::Transmission of either side; `roughdielectric` keeps passing as it did)
+        if (m_brdf[0]->has_transmission() || m_brdf[1]->has_transmission()) Throw("Only materials without a transmission component can be nested!");
     }
     const BSDF *nested(int i) const override { return m_brdf[i].get(); }
     bool flatten(msk_bsdf_desc &out, FlatTables &tables) const override { return m_brdf[0]->flatten(out, tables); }   // front side; flatten_scene adds the back

@@ -177,7 +177,9 @@ class MeshSpec:
     def __init__(self, name, faces, reflectance, radiance=None, translate=(0, 0, 0), normals=None, bsdf=None, texcoords=None):
         """bsdf: None = <bsdf type="diffuse"> with `reflectance`; or a dict for a rough conductor
         {"type": "roughconductor", "alpha": a | ("alpha_u","alpha_v"), "eta": rgb, "k": rgb,
-         "specular_reflectance": rgb (default 1), "sample_visible": bool, "twosided": bool}, a rough dielectric, or
+         "specular_reflectance": rgb (default 1), "sample_visible": bool, "twosided": bool}, a rough dielectric,
+        {"type": "dielectric", "int_ior": 1.49, "ext_ior": 1.00028, "specular_reflectance": rgb | c, "specular_transmittance": rgb | c}
+        (the smooth interface; a scalar c = the `uniform` spectrum <spectrum value="c"/>), or
         {"type": "diffuse", "twosided": bool, "texture": {"type": "checkerboard", "color0": rgb, "color1": rgb,
          "scale": (sx, sy) | "matrix": 16 floats (the to_uv 4x4, row-major)}} (texture absent = `reflectance`).
         texcoords: None, or per face a tuple of (u, v) per corner as written in the OBJ `vt` lines (the loader stores 1 - v)."""
@@ -246,19 +248,22 @@ def _bsdf_xml(m, v3):
             inner = ['<bsdf type="twosided">'] + ['    ' + b for b in inner] + ['</bsdf>']
         return ['        ' + b for b in inner]
     body = []
-    a = spec.get("alpha", 0.1)
-    if np.isscalar(a):
-        body.append('<float name="alpha" value="%r"/>' % float(a))
-    else:
-        body += ['<float name="alpha_u" value="%r"/>' % float(a[0]), '<float name="alpha_v" value="%r"/>' % float(a[1])]
-    body.append('<string name="distribution" value="ggx"/>')
-    if spec.get("sample_visible"):
-        body.append('<boolean name="sample_visible" value="true"/>')
+    if spec["type"] != "dielectric":          # (bsdfs/dielectric.cpp reads no microfacet parameters)
+        a = spec.get("alpha", 0.1)
+        if np.isscalar(a):
+            body.append('<float name="alpha" value="%r"/>' % float(a))
+        else:
+            body += ['<float name="alpha_u" value="%r"/>' % float(a[0]), '<float name="alpha_v" value="%r"/>' % float(a[1])]
+        body.append('<string name="distribution" value="ggx"/>')
+        if spec.get("sample_visible"):
+            body.append('<boolean name="sample_visible" value="true"/>')
     keys = {"roughconductor": ("eta", "k", "specular_reflectance"),
-            "roughdielectric": ("specular_reflectance", "specular_transmittance")}[spec["type"]]
+            "roughdielectric": ("specular_reflectance", "specular_transmittance"),
+            "dielectric": ("specular_reflectance", "specular_transmittance")}[spec["type"]]
     for k in keys:
         if k in spec:
             body.append('<spectrum name="%s" value="%s"/>' % (k, spec[k].text) if isinstance(spec[k], Regular) else
+                        '<spectrum name="%s" value="%.9g"/>' % (k, float(spec[k])) if np.isscalar(spec[k]) else
                         '<rgb name="%s" value="%s"/>' % (k, v3(spec[k])))
     for k in ("int_ior", "ext_ior"):
         if k in spec:
@@ -438,6 +443,8 @@ def spectrum_desc(rgb, fetch, pool=None):
     A Regular: the tabulated form (its index in the scene's pool)."""
     if isinstance(rgb, Regular):
         return abi.SpectrumDesc((C.c_float * 3)(0.0, 0.0, 0.0), 1.0, pool.add(rgb))
+    if np.isscalar(rgb):                    # <spectrum value="c"/>: the `uniform` plugin (spectra/uniform.cpp:16-27)
+        return abi.SpectrumDesc((C.c_float * 3)(0.0, 0.0, float("inf")), float(np.float32(rgb)))
     rgb = np.asarray(rgb, np.float32)
     if rgb.max() <= 1.0:
         return abi.SpectrumDesc((C.c_float * 3)(*fetch(tuple(float(x) for x in rgb))), 1.0)
@@ -496,6 +503,15 @@ def _bsdf_desc(m, fetch, index, textures=None, pool=None):
         b.alpha_u, b.alpha_v = (a, a) if np.isscalar(a) else a
         b.sample_visible = int(bool(spec.get("sample_visible", False)))
         int_ior, ext_ior = np.float32(spec.get("int_ior", 1.5046)), np.float32(spec.get("ext_ior", 1.00028))
+        b.ior_eta, b.ior_inv_eta = float(int_ior / ext_ior), float(ext_ior / int_ior)
+        b.specular_reflectance = spectrum_desc(spec.get("specular_reflectance", (1.0, 1.0, 1.0)), fetch, pool)
+        b.specular_transmittance = spectrum_desc(spec.get("specular_transmittance", (1.0, 1.0, 1.0)), fetch, pool)
+    elif spec["type"] == "dielectric":
+        # bsdfs/dielectric.cpp:14-20: m_eta = int_ior / ext_ior in fp32, defaults 1.49 / 1.00028; no microfacet parameters
+        if spec.get("twosided"):
+            raise ValueError("Only materials without a transmission component can be nested!")      # twosided.cpp:33-35
+        b.type = abi.MSK_BSDF_DIELECTRIC
+        int_ior, ext_ior = np.float32(spec.get("int_ior", 1.49)), np.float32(spec.get("ext_ior", 1.00028))
         b.ior_eta, b.ior_inv_eta = float(int_ior / ext_ior), float(ext_ior / int_ior)
         b.specular_reflectance = spectrum_desc(spec.get("specular_reflectance", (1.0, 1.0, 1.0)), fetch, pool)
         b.specular_transmittance = spectrum_desc(spec.get("specular_transmittance", (1.0, 1.0, 1.0)), fetch, pool)
