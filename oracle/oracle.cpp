@@ -64,6 +64,11 @@
  *            weight (path.cpp:90-95,103-108).  These paths are pinned by closed-form
  *            properties (tests/test_rough_*.py, tests/test_environment.py), not by
  *            reference outputs: "parity unpinned" applies to them.
+ *            The smooth `dielectric` (bsdfs/dielectric.cpp) is in the same position: left out of
+ *            the reference's build (src/librender/CMakeLists.txt:63), its tints read through
+ *            eval_3.  Restated as written with the same repair (the tints are spectra at the
+ *            path's wavelengths); pinned by float64 (tests/test_dielectric_parity.py: Fresnel
+ *            term, Snell's law, where a refracted ray lands), not by reference outputs.
  *   D10      ray/triangle acceptance = the Moeller-Trumbore test above AND "the hit point
  *            o + t d lies in the triangle's own bounding box (grown by 0.5e-5 of the scene's
  *            scale = max(diagonal, largest |coordinate|))": see intersect_triangle().  Found by the randomised parity sweep
@@ -690,7 +695,9 @@ static float mis_weight(float pdf_a, float pdf_b) {
 // ===========================================================================
 // BSDFs: a11 diffuse (bsdfs/diffuse.cpp:18-57); §8(f)1 rough conductor
 // (bsdfs/roughconductor.cpp:52-120, render/microfacet.h:11-44,145-175,
-// render/fresnel.h:65-88) and the twosided adapter (bsdfs/twosided.cpp:38-101).
+// render/fresnel.h:65-88) and the twosided adapter (bsdfs/twosided.cpp:38-101); the
+// rough dielectric (bsdfs/roughdielectric.cpp:57-190) and the smooth one
+// (bsdfs/dielectric.cpp:26-82, render/fresnel.h:12-14,22-27,37-63).
 //
 // The rough conductor has NO runnable reference (not compiled, written
 // against Color3/eval_3, default distribution Beckmann is unimplemented).  This
@@ -699,7 +706,8 @@ static float mis_weight(float pdf_a, float pdf_b) {
 // spectra evaluated at the path's four wavelengths (value = scale * S(coeff, l)).
 // ===========================================================================
 struct BSDFSampleRec { V3 wo; float pdf, eta; uint32_t sampled_type; };   // render/bsdf.h:60-80
-enum : uint32_t { kDiffuseReflection = 1u, kGlossyReflection = 2u, kGlossyTransmission = 4u };
+enum : uint32_t { kDiffuseReflection = 1u, kGlossyReflection = 2u, kGlossyTransmission = 4u, kDeltaReflection = 8u, kDeltaTransmission = 16u,
+                  kDelta = kDeltaReflection | kDeltaTransmission };   // BSDFFlags::Delta: what path.cpp:104 asks of sampled_type
 
 static S4 spectrum_eval(const Scene &sc, const msk_spectrum_desc &sp, S4 wl) {
     if (sp.regular) return regular_eval(sc.regular[sp.regular - 1], wl);          // RegularSpectrum::eval (regular.cpp:148)
@@ -837,6 +845,22 @@ static S4 roughdielectric_sample(const Scene &sc, const msk_bsdf_desc &b, V3 wi,
     bs->pdf *= std::fabs(dwh_dwo);
     return weight;
 }
+// bsdfs/dielectric.cpp:26-72 sample (both delta components enabled, TransportMode::Radiance).  The lobe is chosen by the x of the
+// 2D sample (:37), sample1 is drawn by the caller and unused; reflect(wi) / refract(wi, cos_theta_t, eta_ti) are fresnel.h:12-14,22-27.
+static S4 dielectric_sample(const Scene &sc, const msk_bsdf_desc &b, V3 wi, V2 sample, S4 wl, BSDFSampleRec *bs) {
+    float r_i, cos_theta_t, eta_it, eta_ti;
+    fresnel_dielectric(wi.z, b.ior_eta, &r_i, &cos_theta_t, &eta_it, &eta_ti);          // :31-32
+    const float t_i = 1.f - r_i;
+    const bool selected_r = sample.x <= r_i;                                             // :37
+    bs->pdf = selected_r ? r_i : t_i;                                                    // :38
+    bs->sampled_type = selected_r ? kDeltaReflection : kDeltaTransmission;               // :48-49
+    bs->wo = selected_r ? mk3(-wi.x, -wi.y, wi.z) : mk3(-eta_ti * wi.x, -eta_ti * wi.y, cos_theta_t);   // :50-51
+    bs->eta = selected_r ? 1.f : eta_it;                                                 // :52
+    if (selected_r) return spectrum_eval(sc, b.specular_reflectance, wl);               // :55-56,61,65-66
+    return spectrum_eval(sc, b.specular_transmittance, wl) * eta_ti * eta_ti;           // :57-58,61,67-70
+}
+// BSDFFlags::Smooth of bsdf->flags() (path.cpp:56): every BSDF here but `dielectric`, whose two components are delta (dielectric.cpp:21-23)
+static bool bsdf_has_smooth_lobe(const msk_bsdf_desc &b) { return b.type != MSK_BSDF_DIELECTRIC; }
 
 // textures/checkerboard.cpp:24-33: which of the two colours the texture shows at uv.  The 3x3 product of
 // Transform3f::transform_affine_point (core/transform.h:41-48) is Eigen's coefficient-based one: each row is
@@ -872,6 +896,7 @@ static void bsdf_eval_pdf(const Scene &sc, const msk_bsdf_desc &b, Reflectance r
         return;
     }
     if (b.type == MSK_BSDF_ROUGHDIELECTRIC) { roughdielectric_eval_pdf(sc, b, wi, wo, wl, val, pdf); return; }
+    if (b.type == MSK_BSDF_DIELECTRIC) return;                         // dielectric.cpp:74-82: eval and pdf are zero
     const float au = clamp_alpha(b.alpha_u), av = clamp_alpha(b.alpha_v);
     // roughconductor.cpp:82-98 eval
     if (cos_i > 0.f && cos_o > 0.f) {
@@ -894,6 +919,7 @@ static void bsdf_eval_pdf(const Scene &sc, const msk_bsdf_desc &b, Reflectance r
 static S4 bsdf_sample(const Scene &sc, const msk_bsdf_desc &b, Reflectance refl, V3 wi, float sample1, V2 sample, S4 wl, BSDFSampleRec *bs) {
     bs->wo = mk3(0, 0, 0); bs->pdf = 0.f; bs->eta = 1.f; bs->sampled_type = 0;       // render/bsdf.h:75-77
     if (b.type == MSK_BSDF_ROUGHDIELECTRIC) return roughdielectric_sample(sc, b, wi, sample1, sample, wl, bs);
+    if (b.type == MSK_BSDF_DIELECTRIC) return dielectric_sample(sc, b, wi, sample, wl, bs);
     float cos_i = wi.z;
     if (cos_i <= 0.f) return s4(0.f);
     if (b.type == MSK_BSDF_DIFFUSE) {                                  // diffuse.cpp:18-33
@@ -949,9 +975,10 @@ static S4 path_sample(const Scene &sc, Sampler &sampler, Ray ray, S4 wl, const m
         if (depth >= max_depth && max_depth > 0) break;
         const uint32_t base = 3 + 3 * (uint32_t) (depth - 1);
         const msk_bsdf_desc &bsdf = sc.bsdfs[sc.meshes[si.mesh].bsdf_id];
-        // ---- direct illumination (path.cpp:56-67); diffuse has a Smooth lobe
+        // ---- direct illumination (path.cpp:56-67): only for a BSDF with a Smooth lobe.  Without one the sample is not drawn
+        // (MSK_RNG_PCG_BLOCK: no next2d(); MSK_RNG_COUNTER: the pair base + 0 stays unused) and `ds` stays default-constructed
         DirectSample ds; ds.pdf = 0; ds.emitter = -1;
-        {
+        if (bsdf_has_smooth_lobe(bsdf)) {
             V2 u; sampler.pair(base + 0, &u.x, &u.y);
             S4 emitter_val;
             ds = sample_emitter_direct(sc, si, u, wl, &emitter_val, &cnt.shadow_rays);
@@ -1011,7 +1038,8 @@ static S4 path_sample(const Scene &sc, Sampler &sampler, Ray ray, S4 wl, const m
                         throughput.v[0], throughput.v[1], throughput.v[2], throughput.v[3], (int) si_bsdf.valid(), si_bsdf.t, (int) hit_emitter);
         eta *= bs_eta;
         if (hit_emitter) {
-            float emitter_pdf = pdf_emitter_direct(sc, ds);        // diffuse lobe is not Delta
+            // path.cpp:104-106: a delta lobe has no emitter pdf (and after one `ds` may hold no emitter at all)
+            float emitter_pdf = !(sampled_type & kDelta) ? pdf_emitter_direct(sc, ds) : 0.f;
             result = result + throughput * value * mis_weight(bs_pdf, emitter_pdf);
         }
         si = si_bsdf;

@@ -2,7 +2,7 @@
 
 Written from the reference's render/fresnel.h:37-63 (the Fresnel term as the plugin computes it), bsdfs/dielectric.cpp:26-72
 (lobe choice and weights) and integrators/path.cpp:116-122 (Russian roulette), and from the textbook forms of the same
-quantities.  It shares no arithmetic with csrc/, oracle/ or hostmirror.
+quantities (the refracted direction: Snell's law in vector form).  It shares no arithmetic with csrc/, oracle/ or hostmirror.
 """
 import numpy as np
 
@@ -58,6 +58,34 @@ def transmittance_textbook(theta_i, n1, n2):
     ts = 2.0 * n1 * ci / (n1 * ci + n2 * ct)
     tp = 2.0 * n1 * ci / (n2 * ci + n1 * ct)
     return np.where(tir, 0.0, (n2 * ct) / (n1 * ci) * 0.5 * (ts * ts + tp * tp))
+
+
+def refract(d, n, eta):
+    """Snell's law in float64, in vector form, knowing nothing of local frames.  d: unit directions of travel [..., 3]; n: the unit
+    normal of the interface, pointing to the OUTSIDE (where the index is 1; the inside has `eta`).  With c = -d . n (> 0: the ray
+    arrives from outside) and eta_ti = n_incident / n_transmitted, the refracted direction is
+    t = eta_ti d + (eta_ti c' - sqrt(1 - eta_ti^2 (1 - c'^2))) n', with n' the normal on the ray's own side and c' = |c|
+    -> (t [..., 3], tir [...] = total internal reflection: t is then the mirrored direction d + 2 c' n')"""
+    d, n = np.asarray(d, np.float64), np.asarray(n, np.float64)
+    c = -(d @ n)
+    outside = c >= 0.0
+    eta_ti = np.where(outside, 1.0 / float(eta), float(eta))
+    ns = np.where(outside[..., None], n, -n)
+    ca = np.abs(c)
+    ct2 = 1.0 - eta_ti * eta_ti * (1.0 - ca * ca)
+    tir = ct2 <= 0.0
+    ct = np.sqrt(np.maximum(ct2, 0.0))
+    t = eta_ti[..., None] * d + (eta_ti * ca - ct)[..., None] * ns
+    return np.where(tir[..., None], d + 2.0 * ca[..., None] * ns, t), tir
+
+
+def refract_local(wi, eta):
+    """The same in the BSDF's local frame (normal = +z, wi pointing AWAY from the surface, as the plugin sees it): Snell's law
+    sin_t = eta_ti sin_i in the plane of incidence, on the other side -> (wo [..., 3], cos_t (signed), eta_it, eta_ti, tir)"""
+    wi = np.asarray(wi, np.float64)
+    t, tir = refract(-wi, np.array([0.0, 0.0, 1.0]), eta)
+    outside = wi[..., 2] >= 0.0
+    return t, t[..., 2], np.where(outside, float(eta), 1.0 / float(eta)), np.where(outside, 1.0 / float(eta), float(eta)), tir
 
 
 def critical_angle(eta):

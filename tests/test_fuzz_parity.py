@@ -27,6 +27,33 @@ def test_random_scenes_are_valid_oracle_inputs(oracle, abi):
         b, _ = sc.render(abi.render_params(spp=2, seed=s), threads=3)
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32)) and np.isfinite(a[..., 4]).all() and a[..., 4].min() > 0
         sc.close()
+    # with the smooth `dielectric` on some meshes (glass=True): valid inputs as well, at least one glass BSDF per scene, and the
+    # scene without the option is unchanged by its existence (the choice is drawn from a generator of its own)
+    for s in (9001, 9005, 9006, 9007):
+        flat = fz.random_scene(np.random.RandomState(s), glass=True, seed=s)
+        plain, again = fz.random_scene(np.random.RandomState(s)), fz.random_scene(np.random.RandomState(s), glass=False, seed=s)
+        d = flat.desc
+        assert any(d.bsdfs[i].type == abi.MSK_BSDF_DIELECTRIC for i in range(d.n_bsdfs))
+        assert not any(plain.desc.bsdfs[i].type == abi.MSK_BSDF_DIELECTRIC for i in range(plain.desc.n_bsdfs))
+        assert np.array_equal(flat.vertices.view(np.uint32), plain.vertices.view(np.uint32)) and np.array_equal(flat.faces, plain.faces)
+        assert np.array_equal(again.vertices.view(np.uint32), plain.vertices.view(np.uint32))
+        assert all(bytes(again.desc.bsdfs[i]) == bytes(plain.desc.bsdfs[i]) for i in range(plain.desc.n_bsdfs))
+        sc = oracle.scene(flat)
+        a, st = sc.render(abi.render_params(spp=2, seed=s), threads=2)
+        b, _ = sc.render(abi.render_params(spp=2, seed=s), threads=3)
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)) and np.isfinite(a).all() and a[..., 4].min() > 0 and st.invalid_samples == 0
+        sc.close()
+
+
+def test_the_seeds_of_the_regression_sweeps_still_make_their_scenes():
+    """The scenes of the seeds the GPU sweeps below use (5000-5060, 7000-7007, 20657), as digests recorded before the generator
+    learnt the glass option (tests/golden/fuzz_scene_digests.json): an option added to random_scene must not move them."""
+    import json
+    fz = _fuzz()
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "fuzz_scene_digests.json")))
+    assert sorted(int(k) for k in want) == list(range(5000, 5061)) + list(range(7000, 7008)) + [20657]
+    moved = [int(k) for k, v in want.items() if fz.scene_digest(fz.random_scene(np.random.RandomState(int(k)))) != v]
+    assert moved == []
 
 
 def test_hit_acceptance_does_not_depend_on_the_tree(oracle):
@@ -71,6 +98,18 @@ def test_gpu_equals_oracle_on_random_scenes_with_many_samples(gpu_ctx, oracle):
     """The same random scenes at 400 spp: enough samples (>= 1024 regions) for the wavefront loop to run as four loops on
     four streams with every material, emitter and shard kind the generator makes."""
     assert _fuzz().sweep(gpu_ctx, oracle, list(range(7000, 7008)), verbose=False, spp=400) == []
+
+
+@pytest.mark.gpu
+def test_gpu_equals_oracle_on_random_scenes_with_glass(gpu_ctx, oracle):
+    """The sweep with some meshes of every scene turned into the smooth `dielectric` (either side dense, tinted, some of them
+    emitters), next to whatever else the generator makes"""
+    assert _fuzz().sweep(gpu_ctx, oracle, list(range(9000, 9040)), glass=True) == []
+
+
+@pytest.mark.gpu
+def test_gpu_equals_oracle_on_random_scenes_with_glass_and_many_samples(gpu_ctx, oracle):
+    assert _fuzz().sweep(gpu_ctx, oracle, list(range(9100, 9104)), verbose=False, spp=400, glass=True) == []
 
 
 def _fuzz_rays():

@@ -1,6 +1,7 @@
 """The smooth `dielectric` BSDF (bsdfs/dielectric.cpp): glass.
 
-The CPU oracle does not render it, so there is no bit-for-bit twin.  What pins it instead:
+The CPU oracle renders it too (oracle.cpp: dielectric_sample), and tests/test_dielectric_parity.py compares the device with that
+twin bit for bit, and the twin with float64 through the helpers of this module.  What this module pins needs no twin:
 
   * identities that need no oracle.  Behind one interface in a constant environment a sample's value is the environment's
     times ONE of two exactly known factors (the reflection weight or the transmission weight eta_ti^2), so the ratio of a

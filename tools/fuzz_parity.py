@@ -1,6 +1,7 @@
 """Randomised parity sweep: random triangle soups (including slivers and near-degenerate triangles), random BSDFs of
 every type, one to three area emitters, optional environment, random integrator properties — the GPU film must equal
-the oracle's bit for bit on every one.  usage: fuzz_parity.py n_scenes [first_seed [spp]]"""
+the oracle's bit for bit on every one.  usage: fuzz_parity.py n_scenes [first_seed [spp [glass]]]  (glass: any fourth argument
+turns some meshes of every scene into smooth `dielectric`)"""
 import importlib, sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import numpy as np
@@ -8,7 +9,10 @@ abi = importlib.import_module("misaki-render_amd.abi"); hm = importlib.import_mo
 import oracle_binding
 
 
-def random_scene(rng):
+def random_scene(rng, glass=False, seed=0):
+    """glass=True turns some meshes into the smooth `dielectric` (emitters included: glass that emits); what becomes glass is drawn
+    from a generator of its own, made from `seed`, so that `rng` is consumed exactly as without it: a seed's scene with
+    glass=False is the scene it always was, and with glass=True it is that scene with some BSDFs exchanged."""
     meshes = []
     n_mesh = rng.randint(3, 9)
     n_light = rng.randint(1, 4)
@@ -109,6 +113,30 @@ def random_scene(rng):
                 m.radiance = table(0.01, 0.4)
         if env is not None and trng.randint(0, 2):
             env["radiance"] = table(0.001, 0.02)
+    if glass:
+        grng = np.random.RandomState((int(seed) * 2654435761 + 0x61a55) % (2 ** 32))
+        def tint():
+            k = grng.randint(0, 5)
+            if k == 0:
+                return float(grng.uniform(0.2, 1.0))                                   # `uniform`
+            if k == 1:
+                return hm.Regular(360.0, 830.0, grng.uniform(0.2, 1.0, int(grng.choice([2, 7, 31]))).astype(np.float32))
+            if k == 2:
+                return tuple(float(x) for x in grng.uniform(0.05, 1.0, 3))             # rgb
+            return (1.0, 1.0, 1.0)
+        n_glass = 0
+        for k, m in enumerate(meshes):
+            # every third mesh on average, and at least one per scene (the last one, if none was drawn before it)
+            if grng.randint(0, 3) and not (n_glass == 0 and k == len(meshes) - 1):
+                continue
+            n_glass += 1
+            ior = float(grng.uniform(1.05, 2.6))
+            inside_dense = bool(grng.randint(0, 2))                                   # either side dense
+            m.bsdf = {"type": "dielectric", "int_ior": ior if inside_dense else float(grng.choice([1.0, 1.33])),
+                      "ext_ior": float(grng.choice([1.0, 1.33])) if inside_dense else ior,
+                      "specular_reflectance": tint(), "specular_transmittance": tint()}
+            if isinstance(m.reflectance, hm.Regular) or np.isscalar(m.reflectance):
+                m.reflectance = (0.5, 0.5, 0.5)                                        # (unused by the BSDF)
     flat = hm.flatten(meshes, fw, fh, env=env, camera=camera, filter_stddev=stddev, crop=crop)
     # vertex normals (perturbed face normals) and texture coordinates on some meshes: mesh.cpp:68-96
     verts, faces = flat.vertices, flat.faces
@@ -132,6 +160,20 @@ def random_scene(rng):
     return flat
 
 
+def scene_digest(flat):
+    """sha256 over everything a flattened scene hands to the back ends (the arrays' contents, not their addresses)"""
+    import hashlib
+    d = flat.desc
+    h = hashlib.sha256()
+    h.update(flat.vertices.tobytes()); h.update(flat.faces.tobytes())
+    for arr, n in ((d.meshes, d.n_meshes), (d.bsdfs, d.n_bsdfs), (d.emitters, d.n_emitters), (d.textures, d.n_textures), (d.regular_spectra, d.n_regular_spectra)):
+        for i in range(n):
+            h.update(bytes(arr[i]))
+    h.update(np.ctypeslib.as_array(d.regular_values, (max(1, d.n_regular_values),))[:d.n_regular_values].tobytes())
+    h.update(bytes(d.camera)); h.update(bytes(d.film))
+    return h.hexdigest()
+
+
 def random_params(rng):
     kw = dict(spp=int(rng.choice([1, 4, 4, 7])), seed=int(rng.randint(0, 1000)), rr_depth=int(rng.choice([1, 2, 5])),
               max_depth=int(rng.choice([-1, -1, 1, 3, 6])), hide_emitters=int(rng.randint(0, 2)), block_size=int(rng.choice([8, 16, 32])))
@@ -146,11 +188,11 @@ def random_params(rng):
     return kw
 
 
-def sweep(ctx, orc, seeds, verbose=True, spp=None):
+def sweep(ctx, orc, seeds, verbose=True, spp=None, glass=False):
     bad = []
     for s in seeds:
         rng = np.random.RandomState(s)
-        flat = random_scene(rng)
+        flat = random_scene(rng, glass=glass, seed=s)
         kw = random_params(rng)
         if spp:
             kw["spp"] = spp
@@ -177,6 +219,6 @@ if __name__ == "__main__":
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 50
     seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     spp = int(sys.argv[3]) if len(sys.argv) > 3 else None        # optional: samples per pixel for every scene
-    bad = sweep(abi.Context(0), oracle_binding.load(), range(seed0, seed0 + n), spp=spp)
+    bad = sweep(abi.Context(0), oracle_binding.load(), range(seed0, seed0 + n), spp=spp or None, glass=len(sys.argv) > 4)
     print("fuzz: %d scenes, %d with a film different from the oracle's" % (n, len(bad)))
     sys.exit(1 if bad else 0)
