@@ -241,6 +241,24 @@ static inline Built build(const float *pos, uint32_t n, float tri_pad) {
     return out;
 }
 
+// The bounds a camera ray must meet to be worth a slot of the path pool (msk_kernels.h: shade_region's regeneration): the union
+// of the two child boxes the ROOT of the binary tree tests, from the floats as the tree stores them — padded, and before any wide
+// collapse or fp16 / byte rounding, which only grow boxes.  The conservative slab test is monotonic in the box, so a ray that
+// fails it on this union fails it on both children: the binary traversal would have left the root with no hit.
+// `on` is false where there is no such pair of boxes: no triangles, or a tree that is a single leaf.
+struct CullBounds { bool on = false; float lo[3] = {0.f, 0.f, 0.f}, hi[3] = {0.f, 0.f, 0.f}; };
+static inline CullBounds cull_bounds(const std::vector<float> &nodes, uint32_t root_ref, uint32_t n_tris) {
+    CullBounds c;
+    if (n_tris == 0 || (root_ref & 0x80000000u) || ((size_t) root_ref + 1) * 16 > nodes.size()) return c;
+    const float *n = &nodes[(size_t) root_ref * 16];
+    for (int a = 0; a < 3; ++a) {
+        c.lo[a] = std::min(n[2 * a], n[2 * a + 1]);
+        c.hi[a] = std::max(n[6 + 2 * a], n[6 + 2 * a + 1]);
+    }
+    c.on = true;
+    return c;
+}
+
 // Collapses the binary tree into 4-wide nodes: a node's two children are replaced by their own children, largest
 // surface area first, until four slots are filled or only leaves remain.
 struct Collapser {

@@ -118,6 +118,8 @@ struct msk_scene {
     int bvh_depth = 0;
     uint32_t n_tris = 0;
     size_t tree_bytes = 0;             // node array the traversal walks
+    bool cull_ok = false;              // dev.cull_lo / cull_hi hold the root's bounds and a camera ray that misses them is a record of
+                                       // zeros: triangles, a tree with an inner root, no environment emitter (PassParams::cull)
 };
 
 static int ctx_sync(msk_ctx *ctx, hipStream_t stream, const char *what, double limit_scale = 1.0);     // (below: every wait of a render is timed)
@@ -582,6 +584,13 @@ extern "C" int msk_gpu_scene_create(msk_ctx *ctx, const msk_scene_desc *d, msk_s
         ds.env_radius = std::max(MSK_RAY_EPS_F, radius * (1.f + MSK_RAY_EPS_F));
         s->all_diffuse = false;             // the environment terms live in the general shading variant
     }
+    // the bounds a camera ray must meet (msk_bvh.h: cull_bounds): the binary tree's root, host- or device-built, before any collapse.
+    // With an environment emitter a ray that leaves the scene carries radiance: nothing is culled
+    {
+        const mskbvh::CullBounds cb = mskbvh::cull_bounds(bvh.nodes, bvh.root_ref, d->n_faces);
+        for (int k = 0; k < 3; ++k) { ds.cull_lo[k] = cb.lo[k]; ds.cull_hi[k] = cb.hi[k]; }
+        s->cull_ok = cb.on && env_emitter < 0;
+    }
     // LDS plan of k_trace: per-lane stack + (when it fits) the whole BVH
     const size_t stack_bytes = (size_t) ds.stack_entries * MSK_BLOCK * 4;
     const size_t scene_bytes = (size_t) ds.n_nodes * 64 + (size_t) ds.n_tris * 96;
@@ -904,6 +913,10 @@ static int run_wavefront(msk_scene *sc, hipStream_t stream, const msk_render_par
     for (uint32_t g = 0; g < MSK_MAX_AOV_GROUPS; ++g) pp0.aov_rec[g] = aov && g < aov->n_groups ? aov->rec[g] : nullptr;
     pp0.packed = packed ? 1u : 0u;
     pp0.stack_ovf = nullptr;
+    // camera samples that miss the scene's bounds are finished where they are made (shade_region's regeneration) — unless a miss
+    // is more than a record of zeros: an "aov" render's record groups and nested RGB record are written per sample by other code.
+    // MSK_CAMERA_CULL=0 (read per call): off
+    pp0.cull = (sc->cull_ok && !aov_rgb && !(aov && aov->n_groups) && env_u32("MSK_CAMERA_CULL", 1) != 0) ? 1u : 0u;
     // (MSK_FORCE_GENERAL_SHADE=1, measurements only: an all-diffuse scene through the general variant — what a per-class diffuse
     // instantiation could save a mixed scene's diffuse chunks)
     const bool force_general = env_u32("MSK_FORCE_GENERAL_SHADE", 0) != 0;
@@ -952,7 +965,7 @@ static int run_wavefront(msk_scene *sc, hipStream_t stream, const msk_render_par
     // this was built: 49.3 against 55.0 ms for the bench step.  WHO drives the loops is a separate choice (MSK_HOST_THREADS below).
     struct Part {
         uint32_t first = 0, count = 0; hipStream_t stream = nullptr; Ctrl *d_ctrl = nullptr, *h_ctrl = nullptr; EventPool ev{nullptr}; uint32_t *stack_ovf = nullptr;
-        msk_stats st; int rc = MSK_OK; unsigned long long expected = 0; std::string err; bool lost = false;
+        msk_stats st; int rc = MSK_OK; unsigned long long expected = 0, culled = 0; std::string err; bool lost = false;
         // the loop's state between two sync groups
         PassParams pp; uint32_t grid = 0, it = 0, gi = 0, parity = 0, last_iters = 0; bool fused_now = false, done = false; size_t ev_mark = 0;
         // Two alternating sets of events: a group's timestamps are read (hipEventElapsedTime is a host call of a few
@@ -1067,6 +1080,7 @@ static int run_wavefront(msk_scene *sc, hipStream_t stream, const msk_render_par
             p.ev.next = p.ev_mark;                            // every timestamp has been read: the events are free again
             p.st.samples = h.samples_done; p.st.segments = h.segments; p.st.shadow_rays = h.shadow_rays;
             p.st.invalid_samples = h.invalid;
+            p.culled = h.culled;
             p.st.iterations = p.it;
             p.done = true;
             if (h.samples_done != p.expected)
@@ -1196,10 +1210,13 @@ static int run_wavefront(msk_scene *sc, hipStream_t stream, const msk_render_par
             //            + 48 B/shadow ray (contrib in; sh, contrib out) + 20 B/sample (its record)
             //   traversal 48 B/segment (ray_o, ray_d in; hit out) + per shadow ray: sh in, and ray_o again where the shadow rays are a
             //            second queue of the launch (k_trace_q / k_trace: 32 B; k_trace_r walks both rays of a slot together: 16 B)
+            //   a CULLED sample (round 9; counted in samples and in segments) moves its 20-byte record and nothing else: it never
+            //            holds a slot — 112 B less of shading (176 - 64; 128 with the general variant's aux) and 48 B less of traversal than the terms above give it
             const unsigned long long seg = hf.st.segments, smp = hf.st.samples, shd = hf.st.shadow_rays;
             const bool lane_refill = sc->trace_mode != 0 && sc->trace_mode != 3 && (getenv("MSK_TRACE_REFILL") ? atoi(getenv("MSK_TRACE_REFILL")) != 0 : true);
-            stats->bytes_shade += seg * (176ull + (diffuse_only ? 0ull : 16ull)) + shd * 48ull + smp * 20ull - std::min(smp * 64ull, seg * 176ull);
-            stats->bytes_trace += seg * 48ull + shd * (lane_refill ? 16ull : 32ull);
+            const unsigned long long cul = hf.culled;
+            stats->bytes_shade += seg * (176ull + (diffuse_only ? 0ull : 16ull)) + shd * 48ull + smp * 20ull - std::min(smp * 64ull, seg * 176ull) - cul * (112ull + (diffuse_only ? 0ull : 16ull));
+            stats->bytes_trace += seg * 48ull + shd * (lane_refill ? 16ull : 32ull) - cul * 48ull;
         }
     }
     (void) ev_trace; (void) ev_shade;

@@ -91,6 +91,9 @@ struct DeviceScene {
     float lut[33];
     int32_t env_emitter;        // index of the constant environment emitter in `emitters`, or -1 (scene.cpp:35-41)
     float env_radius;           // ConstantBackgroundEmitter::m_bsphere.radius after set_scene (constant.cpp:21-28)
+    float cull_lo[3], cull_hi[3];   // union of the two child boxes of the binary tree's root (msk_bvh.h: cull_bounds): a camera ray that
+                                // fails the slab test on it hits nothing — its sample is finished where it is made
+                                // (shade_region's regeneration, PassParams::cull)
 };
 
 struct PathState {
@@ -125,8 +128,10 @@ struct RegionCtl {
     uint32_t n_new;                               // the last n_new live slots are camera samples the last sweep started: their throughput is 1
                                                   // and their radiance 0 by definition — neither written nor read
     uint32_t invalid;                             // records ImageBlock::put would have warned about (imageblock.cpp:57-81; msk_stats::invalid_samples)
-    uint32_t pad[2];
+    unsigned long long culled;                    // camera samples finished where they were made (PassParams::cull): each is also one of
+                                                  // samples_done and one of segments (its camera ray), as the oracle counts a miss
 };
+static_assert(sizeof(RegionCtl) == 64, "one record per 64-byte half line");
 // A region is two halves of region_size slots.  A shading sweep reads the live paths from one half and writes the survivors
 // (and the new camera samples) to the other, so nothing it writes can land on a slot it has not read yet, in whatever order
 // it reads and wherever it writes.  That freedom is used to GROUP the survivors: those with a pending shadow ray are packed
@@ -137,15 +142,16 @@ struct RegionCtl {
 // (Slot indices are 32-bit: a pool of 2^32 slots would be 650 GB of state.)
 struct RegionView {
     uint32_t base, n, ns, last;                   // last = region_size - 1
+    uint32_t more;                                // shade_region's result only: 1 while samples of the region's share are unstarted
     MSK_DEV uint32_t slot(uint32_t c) const { return base + (c < ns ? c : last - (c - ns)); }
 };
 MSK_DEV RegionView region_view(uint32_t region, uint32_t region_size, uint32_t count, uint32_t half_ns) {
     RegionView v;
-    v.base = (region * 2u + (half_ns & 1u)) * region_size; v.n = count; v.ns = half_ns >> 1; v.last = region_size - 1u;
+    v.base = (region * 2u + (half_ns & 1u)) * region_size; v.n = count; v.ns = half_ns >> 1; v.last = region_size - 1u; v.more = 0u;
     return v;
 }
 struct Ctrl {                                     // written by k_reduce_ctl, read by the host
-    unsigned long long live, remaining, segments, shadow_rays, samples_done, invalid;
+    unsigned long long live, remaining, segments, shadow_rays, samples_done, invalid, culled;
 };
 
 struct PassParams {
@@ -162,6 +168,9 @@ struct PassParams {
     uint32_t region_first, region_count;  // the regions this launch covers (the pool's halves run on two streams)
     uint32_t sort_scratch;        // 1: the shading launch has LDS for the material sort (3 bytes per slot of a region and wave)
     uint32_t trace_split;         // waves per region in k_trace (each takes every trace_split-th chunk); shading is one wave per region
+    uint32_t cull;                // 1: a camera ray that misses DeviceScene::cull_lo / cull_hi writes its (zero) record at once and takes
+                                  //    no slot.  0 where a miss is not a zero record (environment emitter, "aov" records), where the
+                                  //    tree has no root pair of boxes, and under MSK_CAMERA_CULL=0
     RegionCtl *regions;
     uint32_t *stack_ovf;          // traversal-stack overflow (LaneStack), (stack_total - stack_entries) x lanes words, or nullptr
     float4 *aov_rgb;              // nullptr, or per sample {R,G,B,pos.x} of the nested path integrator (aov.cpp:124-141)
@@ -1798,6 +1807,11 @@ MSK_DEV bool invalid_value(float a, float b, float c, bool warn_negative) {
     const bool neg = warn_negative && !(a >= -1e-5f && b >= -1e-5f && c >= -1e-5f);
     return !fin || neg;
 }
+// samples one regeneration may EXAMINE per sweep, in units of the region's size (a culled sample takes no slot: without a bound a
+// region whose share ends in background would finish it inside one launch; round 9: 2, see EXPERIMENTS.md)
+#ifndef MSK_CULL_SCAN
+#define MSK_CULL_SCAN 2
+#endif
 // returns how many of the wave's records ImageBlock::put would have warned about
 template <bool DIFFUSE_ONLY>
 MSK_DEV uint32_t emit_record(const DeviceScene &sc, const SceneTables &tb, const PassParams &pp, spec wl, spec res, uint32_t pix, uint32_t si) {
@@ -1919,7 +1933,9 @@ MSK_DEV bool sort_by_class(const PathState &st, const RegionView &in, const Sort
 // region's plain-diffuse range and its misses by the diffuse code at four waves per SIMD, the classes in between + the sweep's
 // tail by the general variant.  Bit-identical, and slower: config-5 / config-3 class renders +4.5 % / +3.7 % — every region is
 // visited, sorted and its counters read and written twice, and two thin launches drain twice.)
-template <bool DIFFUSE_ONLY, class TB>
+// CULL = false compiles the camera cull of the regeneration out (k_wavefront_d: with it the kernel needs 169 VGPRs and 36 bytes of
+// scratch, one more than three waves per SIMD allow; every sample then takes a slot, whatever PassParams::cull says — same records).
+template <bool DIFFUSE_ONLY, class TB, bool CULL = true>
 MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQueue &dq, const SortScratch &ss, const PathState &st,
                                 const PassParams &pp, uint32_t wave, uint32_t lane) {
     uint32_t n_queued = 0;
@@ -2222,75 +2238,141 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
         n_invalid += emit_record<DIFFUSE_ONLY>(sc, tb, pp, qwl, qres, qid.x, qid.y);       // (lane 0, which writes the counters back, is in here whenever anything is)
     }
     // ---- regeneration: fill the free tail with new camera samples (integrator.cpp:103-116)
+    // The region's unstarted samples are examined in share order, 64 at a time.  A sample whose camera ray fails the slab test
+    // on the scene's bounds (PassParams::cull; DeviceScene::cull_lo / cull_hi — the test and the box every traversal starts with,
+    // so the ray would have come back from the traversal with no hit, and from the next sweep as a record of zeros) is FINISHED
+    // here: its record {+0, +0, +0, x word} {y word} is written from what this loop holds in registers anyway, it takes no slot,
+    // draws no wavelengths, and is never a job of the traversal.  The others are compacted into the free tail (ballot + prefix
+    // popcount), contiguous at the end of the "no shadow ray" group.  A batch is 64 samples of ONE pixel unless spp is not a
+    // multiple of 64, so whole batches go one way or the other nearly always and the wavelengths' fp64 chains are skipped by
+    // the wave, not by lanes.  The loop ends when the tail is full, the share is used up, or MSK_CULL_SCAN x region_size samples
+    // have been examined: late in a pass whole rings of the spiral are background, and a wave that ate the rest of its share in
+    // one launch would be that launch's straggler.
     const uint32_t n_free = pp.region_size - (cur_s + cur_n);
     const unsigned long long first = rc.next_sample, left = rc.end_sample - rc.next_sample;
-    const uint32_t got = (uint32_t) (left < n_free ? left : n_free);
-    if (got > 0) {
-    // the camera, the pixel table and the sample partition: read here, where they are used (MSK_COLD_KARGS)
-    struct Cold { float s2c[16], to_world[16], near_clip, far_clip; int filter_border; const uint4 *pix_table; uint32_t spp_owned, n_regions; } k;
+    uint32_t got = 0, n_culled = 0, examined = 0;
+    if (n_free > 0 && left > 0) {
+    // the camera, the pixel table, the sample partition, the bounds and the record addresses: read here, where they are used (MSK_COLD_KARGS)
+    struct Cold { float s2c[16], to_world[16], near_clip, far_clip; int filter_border; const uint4 *pix_table; uint32_t spp_owned, n_regions;
+                  uint32_t cull, packed; float cull_lo[3], cull_hi[3], filter_radius, filter_scale; float4 *rec_a; float *rec_b; } k;
     if (MSK_COLD_KARGS) {
         const karg_ptr ka = karg_base();
 #pragma unroll
         for (int q = 0; q < 16; ++q) { k.s2c[q] = karg<float>(ka, offsetof(DeviceScene, s2c) + 4 * q); k.to_world[q] = karg<float>(ka, offsetof(DeviceScene, to_world) + 4 * q); }
         k.near_clip = MSK_KARG_SC(ka, float, near_clip); k.far_clip = MSK_KARG_SC(ka, float, far_clip); k.filter_border = MSK_KARG_SC(ka, int32_t, filter_border);
         k.pix_table = MSK_KARG_PP(ka, const uint4 *, pix_table); k.spp_owned = MSK_KARG_PP(ka, uint32_t, spp_owned); k.n_regions = MSK_KARG_PP(ka, uint32_t, n_regions);
+        k.cull = CULL ? MSK_KARG_PP(ka, uint32_t, cull) : 0u; k.packed = MSK_KARG_PP(ka, uint32_t, packed);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) { k.cull_lo[q] = karg<float>(ka, offsetof(DeviceScene, cull_lo) + 4 * q); k.cull_hi[q] = karg<float>(ka, offsetof(DeviceScene, cull_hi) + 4 * q); }
+        k.filter_radius = MSK_KARG_SC(ka, float, filter_radius); k.filter_scale = MSK_KARG_SC(ka, float, filter_scale);
+        k.rec_a = MSK_KARG_PP(ka, float4 *, rec_a); k.rec_b = MSK_KARG_PP(ka, float *, rec_b);
     } else {
 #pragma unroll
         for (int q = 0; q < 16; ++q) { k.s2c[q] = sc.s2c[q]; k.to_world[q] = sc.to_world[q]; }
         k.near_clip = sc.near_clip; k.far_clip = sc.far_clip; k.filter_border = sc.filter_border;
         k.pix_table = pp.pix_table; k.spp_owned = pp.spp_owned; k.n_regions = pp.n_regions;
+        k.cull = CULL ? pp.cull : 0u; k.packed = pp.packed;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) { k.cull_lo[q] = sc.cull_lo[q]; k.cull_hi[q] = sc.cull_hi[q]; }
+        k.filter_radius = sc.filter_radius; k.filter_scale = sc.filter_scale; k.rec_a = pp.rec_a; k.rec_b = pp.rec_b;
     }
-    // the linear sample index -> (pass pixel, sample) split is a 32-bit division whenever this sweep's indices fit (a pass
-    // of < 2^32 samples: every configuration but the largest single-GPU ones), the 64-bit one otherwise
-    const bool idx32 = (((((first + got - 1) >> 6) * k.n_regions + wave) << 6) | 63ull) < (1ull << 32);
-    for (uint32_t kk = lane; kk < got; kk += MSK_WAVE) {
-        const unsigned long long q = first + kk;
-        const unsigned long long sidx_lin = (((q >> 6) * k.n_regions + wave) << 6) | (q & 63ull);
-        uint32_t j, si;
-        if (idx32) { j = (uint32_t) sidx_lin / k.spp_owned; si = (uint32_t) sidx_lin - j * k.spp_owned; }
-        else { j = (uint32_t) (sidx_lin / k.spp_owned); si = (uint32_t) (sidx_lin % k.spp_owned); }
-        const uint4 pt = k.pix_table[j];
-        const uint32_t pix = pt.x;
-        const uint64_t key = counter_key(pp.seed, pix, pp.sample_first + si * pp.sample_stride);
-        const f2 jit = counter_pair(key, 0);
-        const float wsample = counter_pair(key, 1).x;
-        const float px = (float) pixel_x(k.filter_border, pt) + jit.x, py = (float) pixel_y(k.filter_border, pt) + jit.y;
-        spec wl;
+    // how many samples this sweep may examine: without the cull every one takes a slot
+    const unsigned long long scan = k.cull ? (unsigned long long) MSK_CULL_SCAN * pp.region_size : (unsigned long long) n_free;
+    const uint32_t limit = (uint32_t) (left < scan ? left : scan);
+    // the linear sample index -> (pass pixel, sample) split is a 32-bit division whenever the indices this sweep can examine fit
+    // (a pass of < 2^32 samples: every configuration but the largest single-GPU ones), the 64-bit one otherwise
+    const bool idx32 = (((((first + limit - 1) >> 6) * k.n_regions + wave) << 6) | 63ull) < (1ull << 32);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    while (examined < limit && got < n_free) {
+        const uint32_t kk = examined + lane;
+        uint32_t nb = limit - examined < MSK_WAVE ? limit - examined : MSK_WAVE;      // this batch: lanes 0 .. nb - 1
+        bool keep = false;
+        uint32_t j = 0, si = 0, pix = 0;
+        uint4 pt = make_uint4(0u, 0u, 0u, 0u);
+        float px = 0.f, py = 0.f, wsample = 0.f, tnear = 0.f, tfar = 0.f;
+        f3 ow = mk3(0.f, 0.f, 0.f), dw = ow;
+        if (lane < nb) {
+            const unsigned long long q = first + kk;
+            const unsigned long long sidx_lin = (((q >> 6) * k.n_regions + wave) << 6) | (q & 63ull);
+            if (idx32) { j = (uint32_t) sidx_lin / k.spp_owned; si = (uint32_t) sidx_lin - j * k.spp_owned; }
+            else { j = (uint32_t) (sidx_lin / k.spp_owned); si = (uint32_t) (sidx_lin % k.spp_owned); }
+            pt = k.pix_table[j];
+            pix = pt.x;
+            const uint64_t key = counter_key(pp.seed, pix, pp.sample_first + si * pp.sample_stride);
+            const f2 jit = counter_pair(key, 0);
+            wsample = counter_pair(key, 1).x;
+            px = (float) pixel_x(k.filter_border, pt) + jit.x; py = (float) pixel_y(k.filter_border, pt) + jit.y;
+            // PerspectiveCamera::sample_ray (perspective.cpp:22-42), Transform4f::apply_point/apply_vector
+            float r4[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { wl.v[q] = wavelength_of(wsample, q); __builtin_amdgcn_sched_barrier(0); }   // one fp64 chain at a time: interleaved they cost 28 VGPRs
-        // PerspectiveCamera::sample_ray (perspective.cpp:22-42), Transform4f::apply_point/apply_vector
-        float r4[4];
+            for (int q4 = 0; q4 < 4; ++q4)
+                r4[q4] = ((k.s2c[q4 * 4 + 0] * px + k.s2c[q4 * 4 + 1] * py) + k.s2c[q4 * 4 + 2] * 0.f) + k.s2c[q4 * 4 + 3] * 1.f;
+            const f3 near_p = mk3(r4[0] / r4[3], r4[1] / r4[3], r4[2] / r4[3]);
+            const f3 dl = normalized(near_p);
+            const float inv_z = 1.f / dl.z;
+            float o4[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-            r4[q] = ((k.s2c[q * 4 + 0] * px + k.s2c[q * 4 + 1] * py) + k.s2c[q * 4 + 2] * 0.f) + k.s2c[q * 4 + 3] * 1.f;
-        const f3 near_p = mk3(r4[0] / r4[3], r4[1] / r4[3], r4[2] / r4[3]);
-        const f3 dl = normalized(near_p);
-        const float inv_z = 1.f / dl.z;
-        float o4[4];
+            for (int q4 = 0; q4 < 4; ++q4)
+                o4[q4] = ((k.to_world[q4 * 4 + 0] * 0.f + k.to_world[q4 * 4 + 1] * 0.f) + k.to_world[q4 * 4 + 2] * 0.f) +
+                         k.to_world[q4 * 4 + 3] * 1.f;
+            ow = mk3(o4[0] / o4[3], o4[1] / o4[3], o4[2] / o4[3]);
+            const float *m = k.to_world;
+            dw = mk3(m[0] * dl.x + (m[1] * dl.y + m[2] * dl.z), m[4] * dl.x + (m[5] * dl.y + m[6] * dl.z),
+                     m[8] * dl.x + (m[9] * dl.y + m[10] * dl.z));
+            tnear = k.near_clip * inv_z; tfar = k.far_clip * inv_z;
+            keep = true;
+            if (k.cull) {        // the root's test of every traversal kernel, on the box that encloses the root's children in every tree form
+                const f3 idir = slab_idir(dw);
+                float t0;
+                keep = box_test(k.cull_lo[0], k.cull_lo[1], k.cull_lo[2], k.cull_hi[0], k.cull_hi[1], k.cull_hi[2], idir,
+                                mk3(ow.x * idir.x, ow.y * idir.y, ow.z * idir.z), tnear, tfar, &t0);
+            }
+        }
+        // the batch ends before the first kept sample the free tail has no slot for (samples start in share order)
+        unsigned long long m_keep = __ballot(keep);
+        const uint32_t room = n_free - got;
+        if (CULL && (uint32_t) __popcll(m_keep) > room) {      // (without the cull `limit` is the room)
+            nb = (uint32_t) __builtin_ctzll(__ballot(keep && (uint32_t) __popcll(m_keep & below) == room));
+            m_keep &= (1ull << nb) - 1ull;                                    // (nb < 64: some kept lane is left out)
+        }
+        keep = keep && lane < nb;
+        if (CULL && lane < nb && !keep) {                                             // finished here: render_sample's tail for a path that found nothing
+            const size_t r = (size_t) j * k.spp_owned + si;
+            float wx = px, wy = py;
+            if (k.packed) {
+                const SampleWeights sw = sample_weights(k.filter_radius, k.filter_scale, pt, px, py);
+                wx = __uint_as_float(sw.x); wy = __uint_as_float(sw.y);       // (finite values: MSK_W_NONFINITE stays clear)
+            }
+            st4<2>(k.rec_a + r, make_float4(0.f, 0.f, 0.f, wx));
+            if (MSK_NT >= 2) __builtin_nontemporal_store(wy, k.rec_b + r); else k.rec_b[r] = wy;
+        }
+        if (keep) {
+            spec wl;
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-            o4[q] = ((k.to_world[q * 4 + 0] * 0.f + k.to_world[q * 4 + 1] * 0.f) + k.to_world[q * 4 + 2] * 0.f) +
-                    k.to_world[q * 4 + 3] * 1.f;
-        const f3 ow = mk3(o4[0] / o4[3], o4[1] / o4[3], o4[2] / o4[3]);
-        const float *m = k.to_world;
-        const f3 dw = mk3(m[0] * dl.x + (m[1] * dl.y + m[2] * dl.z), m[4] * dl.x + (m[5] * dl.y + m[6] * dl.z),
-                          m[8] * dl.x + (m[9] * dl.y + m[10] * dl.z));
-        const uint32_t o = base_out + (last - (cur_n + kk));        // the new samples carry no shadow ray: they continue that group
-        st2<1>(st.id + o, make_uint2(pix, si | (1u << MSK_DEPTH_SHIFT)));
-        st4<1>(st.wl + o, to4(wl));                                      // thr = 1, res = 0: RegionCtl::n_new
-        st4<4>(st.ray_o + o, make_float4(ow.x, ow.y, ow.z, k.near_clip * inv_z));
-        st4<4>(st.ray_d + o, make_float4(dw.x, dw.y, dw.z, k.far_clip * inv_z));
-        if (!DIFFUSE_ONLY) st.aux[o] = make_float2(1.f, 0.f);
+            for (int q = 0; q < 4; ++q) { wl.v[q] = wavelength_of(wsample, q); __builtin_amdgcn_sched_barrier(0); }   // one fp64 chain at a time: interleaved they cost 28 VGPRs
+            const uint32_t o = base_out + (last - (cur_n + got + (uint32_t) __popcll(m_keep & below)));   // the new samples carry no shadow ray: they continue that group
+            st2<1>(st.id + o, make_uint2(pix, si | (1u << MSK_DEPTH_SHIFT)));
+            st4<1>(st.wl + o, to4(wl));                                      // thr = 1, res = 0: RegionCtl::n_new
+            st4<4>(st.ray_o + o, make_float4(ow.x, ow.y, ow.z, tnear));
+            st4<4>(st.ray_d + o, make_float4(dw.x, dw.y, dw.z, tfar));
+            if (!DIFFUSE_ONLY) st.aux[o] = make_float2(1.f, 0.f);
+        }
+        const uint32_t n_keep = (uint32_t) __popcll(m_keep);
+        got += n_keep; if (CULL) n_culled += nb - n_keep; examined += nb;
     }
     }
     const uint32_t n_out = cur_s + cur_n + got;
     rc.count = n_out; rc.half_ns = (cur_s << 1) | ((rc.half_ns & 1u) ^ 1u); rc.n_new = got;
     if (lane == 0) {
-        rc.next_sample = first + got;
-        rc.segments += n_out; rc.shadow_rays += cur_s; rc.samples_done += n_done; rc.invalid += n_invalid;
+        rc.next_sample = first + examined;
+        // a culled sample is one finished sample and one segment — its camera ray, as the oracle counts a ray that hits nothing
+        rc.segments += n_out + n_culled; rc.shadow_rays += cur_s; rc.samples_done += n_done + n_culled; rc.invalid += n_invalid;
+        rc.culled += n_culled;
         pp.regions[wave] = rc;
     }
-    return region_view(wave, pp.region_size, rc.count, rc.half_ns);
+    RegionView out = region_view(wave, pp.region_size, rc.count, rc.half_ns);
+    out.more = (unsigned long long) examined < left ? 1u : 0u;      // samples of the share not started yet (k_wavefront*: an empty region is not a finished one)
+    return out;
 }
 
 // this wave's done-queue: `base` + MSK_DONE_Q_F4 float4 per wave of the block
@@ -2382,11 +2464,11 @@ k_shade_gen<true, true>(DeviceScene sc, PathState st, PassParams pp) { shade_gen
     if (lwave >= pp.region_count) return;                                                                                                                          \
     const uint32_t wave = pp.region_first + lwave;                                                                                                                 \
     for (uint32_t it = 0; it < max_iters; ++it) {                                                                                                                  \
-        const RegionView rv = shade_region<DIFFUSE_ONLY>(sc, tb, dq, SortScratch{nullptr, nullptr}, st, pp, wave, lane);   /* (the thin end of a pass: no sort) */ \
+        const RegionView rv = shade_region<DIFFUSE_ONLY, TB, CULL>(sc, tb, dq, SortScratch{nullptr, nullptr}, st, pp, wave, lane);   /* (the thin end: no sort) */ \
         /* the rays this wave has just written are read back by the same wave (other lanes): program order through the */                                          \
         /* CU's own L1 after the stores have drained */                                                                                                            \
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");                                                                                                     \
-        if (rv.n == 0) break;   /* no live path, and regeneration found no sample to start */                                                                      \
+        if (rv.n == 0) { if (rv.more) continue; break; }   /* no live path and no sample left (an all-culled sweep leaves samples and no path) */                 \
         if (MSK_THIN_RAYS_LDS && rv.n + rv.ns <= MSK_WAVE) trace_thin<0>(sc, st, g, rv, stack, lane, 4);   /* one ray per lane (see trace_thin) */                 \
         else                                                                                                                                                       \
         for (uint32_t c = lane; c < rv.n; c += MSK_WAVE) {                                                                                                         \
@@ -2413,6 +2495,7 @@ template <bool DIFFUSE_ONLY, bool REGULAR = false>
 __global__ void __launch_bounds__(MSK_BLOCK)
 k_wavefront(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
     typedef typename std::conditional<REGULAR, SceneTablesR, SceneTables>::type TB;
+    constexpr bool CULL = true;
     MSK_WAVEFRONT_BODY
 }
 // the one scenes with a smooth `dielectric` run (see k_shade_gen_d)
@@ -2420,6 +2503,7 @@ __global__ void __launch_bounds__(MSK_BLOCK)
 k_wavefront_d(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
     typedef SceneTablesD TB;
     constexpr bool DIFFUSE_ONLY = false;
+    constexpr bool CULL = false;      // (see shade_region: the register budget of this instantiation)
     MSK_WAVEFRONT_BODY
 }
 #undef MSK_WAVEFRONT_BODY
@@ -2449,7 +2533,7 @@ k_wavefront_d(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, u
     for (uint32_t it = 0; it < max_iters; ++it) {                                                                                               \
         const RegionView rv = shade_region<DIFFUSE_ONLY>(sc, tb, dq, SortScratch{nullptr, nullptr}, st, pp, wave, lane);                        \
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   /* the rays just written are read back by this wave's other lanes */           \
-        if (rv.n == 0) break;                                                                                                                   \
+        if (rv.n == 0) { if (rv.more) continue; break; }   /* (an all-culled sweep leaves samples and no path) */                               \
         if (MSK_THIN_RAYS && rv.n + rv.ns <= MSK_WAVE) trace_thin<6>(sc, st, g, rv, stack, lane, 3);                                            \
         else                                                                                                                                    \
         for (uint32_t c = lane; c < rv.n; c += MSK_WAVE) {                                                                                      \
@@ -2549,24 +2633,25 @@ k_aov_primary(DeviceScene sc, PathState st, PassParams pp, AovParams ap) {
     }
 }
 
-// sums the per-region records for the host (termination test + statistics): each block reduces its slice and adds six
-// totals to *out (zeroed by the host before the launch) — 6 atomics per block, a few dozen per launch
+// sums the per-region records for the host (termination test + statistics): each block reduces its slice and adds seven
+// totals to *out (zeroed by the host before the launch) — 7 atomics per block, a few dozen per launch
 __global__ void __launch_bounds__(MSK_BLOCK) k_reduce_ctl(const RegionCtl *regions, uint32_t n_regions, Ctrl *out) {
-    __shared__ unsigned long long sh[6][MSK_BLOCK];
-    unsigned long long a[6] = {0, 0, 0, 0, 0, 0};
+    __shared__ unsigned long long sh[7][MSK_BLOCK];
+    unsigned long long a[7] = {0, 0, 0, 0, 0, 0, 0};
     for (uint32_t i = blockIdx.x * MSK_BLOCK + threadIdx.x; i < n_regions; i += gridDim.x * MSK_BLOCK) {
         const RegionCtl r = regions[i];
-        a[0] += r.count; a[1] += r.end_sample - r.next_sample; a[2] += r.segments; a[3] += r.shadow_rays; a[4] += r.samples_done; a[5] += r.invalid;
+        a[0] += r.count; a[1] += r.end_sample - r.next_sample; a[2] += r.segments; a[3] += r.shadow_rays; a[4] += r.samples_done; a[5] += r.invalid; a[6] += r.culled;
     }
-    for (int k = 0; k < 6; ++k) sh[k][threadIdx.x] = a[k];
+    for (int k = 0; k < 7; ++k) sh[k][threadIdx.x] = a[k];
     __syncthreads();
     for (uint32_t s = MSK_BLOCK / 2; s > 0; s >>= 1) {
-        if (threadIdx.x < s) for (int k = 0; k < 6; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + s];
+        if (threadIdx.x < s) for (int k = 0; k < 7; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + s];
         __syncthreads();
     }
     if (threadIdx.x == 0) {
         atomicAdd(&out->live, sh[0][0]); atomicAdd(&out->remaining, sh[1][0]); atomicAdd(&out->segments, sh[2][0]);
         atomicAdd(&out->shadow_rays, sh[3][0]); atomicAdd(&out->samples_done, sh[4][0]); atomicAdd(&out->invalid, sh[5][0]);
+        atomicAdd(&out->culled, sh[6][0]);
     }
 }
 
