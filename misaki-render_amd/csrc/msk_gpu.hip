@@ -7,6 +7,7 @@
 #include "msk_kernels.h"
 #include "msk_serial.h"
 #include "msk_bvh.h"
+#include "msk_plan.h"
 #include "msk_lbvh.h"
 #define MSK_WATCHDOG_SYNC
 #include "msk_watchdog.h"
@@ -23,8 +24,10 @@
 #include <string>
 #include <thread>
 #include <vector>
+#include <type_traits>
 
 using namespace msk;
+using mskplan::env_u32;
 
 static thread_local std::string g_last_error;
 
@@ -93,7 +96,6 @@ struct DevBuf {
     void leak() { p = nullptr; bytes = 0; }        // a lost context: hipFree would wait for a kernel that never finishes; the memory goes with the process
 };
 
-static uint32_t env_u32(const char *name, uint32_t def);
 // width of the tree for scenes that do not fit LDS: 4 (full-precision boxes) or 8 (quantised boxes); MSK_WIDE_BVH overrides, 0 = binary
 #ifndef MSK_WIDE_BVH_DEFAULT
 #define MSK_WIDE_BVH_DEFAULT 4
@@ -112,8 +114,7 @@ struct msk_scene {
     bool lds_scene = false, lds_tables = false, all_diffuse = true;
     bool has_dielectric = false;       // the scene holds a smooth `dielectric`: the instantiations with its delta lobes run (k_shade_gen_d, ...)
     bool has_regular = false;          // the scene holds tabulated spectra (ABI v7): the shading instantiations that evaluate them run
-    int trace_mode = 0;                // 0 binary tree in LDS, 1 binary tree in HBM/L2, 2 4-wide tree in HBM/L2, 4 8-wide quantised tree in HBM/L2,
-                                       // 5 4-wide tree with quantised boxes in HBM/L2 (64-byte nodes; the default for trees in HBM)
+    int trace_mode = 0;                // mskplan::TraceMode (msk_plan.h): which tree the traversal kernels walk, and where it lives
     size_t trace_lds_bytes = 0, shade_lds_bytes = 0;
     int bvh_depth = 0;
     uint32_t n_tris = 0;
@@ -659,7 +660,7 @@ extern "C" int msk_gpu_scene_create(msk_ctx *ctx, const msk_scene_desc *d, msk_s
         s->trace_mode = 3;
     }
     ds.stack_total = ds.stack_entries;
-    if (s->trace_mode == 1 || s->trace_mode == 2 || s->trace_mode == 4 || s->trace_mode == 5 || s->trace_mode == 6) {
+    if (mskplan::tree_in_hbm(s->trace_mode)) {
         // trees in HBM: only the first MSK_STACK_CAP entries of a lane's stack live in LDS, the rest in an HBM overflow
         // array (LaneStack) — any tree depth works within a fixed 16 KB (+ 4 KB of node4_step scratch) of LDS per block, which
         // leaves room for six blocks per CU.  (Measured: the cap does not change the trace time between 8 and 40 entries.)
@@ -778,11 +779,6 @@ struct AovPlan {
     bool rgba = false;                       // group n_groups: nested path integrator R,G,B (+ A = the weight sum)
 };
 
-static uint32_t env_u32(const char *name, uint32_t def) {
-    const char *v = getenv(name);
-    return v && *v ? (uint32_t) strtoul(v, nullptr, 10) : def;
-}
-
 struct EventPool {
     msk_ctx *ctx; size_t next = 0; std::vector<hipEvent_t> *pool = nullptr;       // pool: ctx->events unless told otherwise
     // nullptr when the runtime cannot create another event: the dispatch then simply carries no timestamps
@@ -826,400 +822,399 @@ static int ctx_sync(msk_ctx *ctx, hipStream_t stream, const char *what, double l
     return MSK_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// kernel dispatch: WHAT runs is decided in msk_plan.h (LaunchPlan); each function here picks the instantiation the plan names
+// and launches it, nothing else.
 // t0 / t1: events that take the kernel's own start / end timestamps (hipExtLaunchKernelGGL: no extra packets in the queue,
 // unlike hipEventRecord, which cost 2 % of a bench step at three records per iteration), or nullptr
-static void launch_trace(msk_scene *sc, hipStream_t stream, const PathState &st, const PassParams &pp, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
-    const uint32_t grid = (pp.region_count * MSK_WAVE + MSK_BLOCK - 1) / MSK_BLOCK;
-    // Lane replacement pays when rays are long (tree in HBM/L2: trace -35 % on the 70 k-triangle scene) and costs when they
-    // are short (LDS-resident cbox: +50 %): on by default for modes 1 and 2 only.  MSK_TRACE_REFILL=0 turns it off.
-    const int refill_env = getenv("MSK_TRACE_REFILL") ? atoi(getenv("MSK_TRACE_REFILL")) : -1;
-    const int max_inner = (int) env_u32("MSK_TRACE_QUANTUM", 3);       // (4 until round 5's better tree: 10.7 instead of 12.9 node visits per ray)
-    const int refill = (sc->trace_mode == 3) ? 0 : refill_env >= 0 ? refill_env : (sc->trace_mode == 0 ? 0 : 16);
-    const size_t lds = sc->trace_lds_bytes + (size_t) env_u32("MSK_TRACE_PAD_LDS_KB", 0) * 1024;      // occupancy experiments only
-    if (refill > 0) {        // k_trace_r
-        if (sc->trace_mode == 4) hipExtLaunchKernelGGL(k_trace_r<4>, dim3(grid), dim3(MSK_BLOCK), lds, stream, t0, t1, 0, sc->dev, st, pp, refill, max_inner);
-        else if (sc->trace_mode == 0) hipExtLaunchKernelGGL(k_trace_r<0>, dim3(grid), dim3(MSK_BLOCK), lds, stream, t0, t1, 0, sc->dev, st, pp, refill, max_inner);
-        else if (sc->trace_mode == 1) hipExtLaunchKernelGGL(k_trace_r<1>, dim3(grid), dim3(MSK_BLOCK), lds, stream, t0, t1, 0, sc->dev, st, pp, refill, max_inner);
-        else if (sc->trace_mode == 5) hipExtLaunchKernelGGL(k_trace_r<5>, dim3(grid), dim3(MSK_BLOCK), lds, stream, t0, t1, 0, sc->dev, st, pp, refill, max_inner);
-        else if (sc->trace_mode == 6) hipExtLaunchKernelGGL(k_trace_r<6>, dim3(grid), dim3(MSK_BLOCK), lds, stream, t0, t1, 0, sc->dev, st, pp, refill, max_inner);
-        else hipExtLaunchKernelGGL(k_trace_r<2>, dim3(grid), dim3(MSK_BLOCK), lds, stream, t0, t1, 0, sc->dev, st, pp, refill, max_inner);
-        return;
+// ------------------------------------------------------------------------------------------
+static_assert(mskplan::kWavesPerBlock == MSK_BLOCK / MSK_WAVE && mskplan::kDoneQueueBytes == (size_t) (MSK_BLOCK / MSK_WAVE) * MSK_DONE_Q_F4 * 16,
+              "msk_plan.h sizes the shading kernels' LDS with the constants of msk_kernels.h");
+
+// f(std::integral_constant<int, M>{}) with M = mode: the one place where a trace mode becomes a template argument
+template <typename F> static void with_trace_mode(int mode, F &&f) {
+    switch (mode) {
+    case 0: f(std::integral_constant<int, 0>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    default: f(std::integral_constant<int, 3>{}); break;
     }
-    // LDS-resident scenes: k_trace_q (job queues with lane replacement, refill when 32 lanes are idle); MSK_TRACE_QUEUE=0: k_trace<0>
-    const uint32_t queue_refill = refill_env >= 0 ? 0u : std::min(64u, env_u32("MSK_TRACE_QUEUE", 32));
-    const size_t bits_off = (lds + 15) & ~(size_t) 15;
-    const size_t lds_q = bits_off + (size_t) (MSK_BLOCK / MSK_WAVE) * (pp.region_size / 8);       // + one bit per slot and wave
-    if (sc->trace_mode == 0 && queue_refill && sc->lds_scene && lds_q <= 64 * 1024) {
-        const uint32_t grid_s = (pp.region_count * pp.trace_split * MSK_WAVE + MSK_BLOCK - 1) / MSK_BLOCK;
-        hipExtLaunchKernelGGL(k_trace_q, dim3(grid_s), dim3(MSK_BLOCK), lds_q, stream, t0, t1, 0, sc->dev, st, pp, queue_refill, (uint32_t) (bits_off / 16));
-        return;
-    }
-    if (sc->trace_mode == 0) {     // pp.trace_split waves per region (LDS-resident scene: no stack overflow array to size).
-        // Measured: 2 waves per region -6 % trace on the cbox (twice the waves to balance the tail of a launch), 4 the same.
-        const uint32_t grid_s = (pp.region_count * pp.trace_split * MSK_WAVE + MSK_BLOCK - 1) / MSK_BLOCK;
-        hipExtLaunchKernelGGL(k_trace<0>, dim3(grid_s), dim3(MSK_BLOCK), lds, stream, t0, t1, 0, sc->dev, st, pp);
-    }
-    else if (sc->trace_mode == 1) hipExtLaunchKernelGGL(k_trace<1>, dim3(grid), dim3(MSK_BLOCK), lds, stream, t0, t1, 0, sc->dev, st, pp);
-    else if (sc->trace_mode == 2) hipExtLaunchKernelGGL(k_trace<2>, dim3(grid), dim3(MSK_BLOCK), lds, stream, t0, t1, 0, sc->dev, st, pp);
-    else if (sc->trace_mode == 4) hipExtLaunchKernelGGL(k_trace<4>, dim3(grid), dim3(MSK_BLOCK), lds, stream, t0, t1, 0, sc->dev, st, pp);
-    else if (sc->trace_mode == 5) hipExtLaunchKernelGGL(k_trace<5>, dim3(grid), dim3(MSK_BLOCK), lds, stream, t0, t1, 0, sc->dev, st, pp);
-    else if (sc->trace_mode == 6) hipExtLaunchKernelGGL(k_trace<6>, dim3(grid), dim3(MSK_BLOCK), lds, stream, t0, t1, 0, sc->dev, st, pp);
-    else hipExtLaunchKernelGGL(k_trace<3>, dim3(grid), dim3(MSK_BLOCK), lds, stream, t0, t1, 0, sc->dev, st, pp);
 }
 
-// Renders the samples of `pix` (pass pixel table, host) into records; leaves records on device.
-static int run_wavefront(msk_scene *sc, hipStream_t stream, const msk_render_params *prm, uint32_t spp_owned,
-                         const uint4 *d_pix, const uint32_t *d_pix_to_j, uint64_t n_pix, float4 *rec_a, float *rec_b, StateBufs &sb,
-                         uint32_t region_size, uint32_t n_regions, msk_stats *stats, EventPool &ev,
-                         std::vector<std::pair<hipEvent_t, hipEvent_t>> &ev_trace,
-                         std::vector<std::pair<hipEvent_t, hipEvent_t>> &ev_shade,
-                         const AovParams *aov = nullptr, float4 *aov_rgb = nullptr, bool packed = false) {
+static void launch_trace(const msk_scene *sc, const mskplan::LaunchPlan &plan, hipStream_t stream, const PathState &st, const PassParams &pp,
+                         hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
+    const dim3 grid((pp.region_count * plan.trace_waves * MSK_WAVE + MSK_BLOCK - 1) / MSK_BLOCK), block(MSK_BLOCK);
+    const size_t lds = plan.trace_lds_bytes;
+    if (plan.trace_family == mskplan::TRACE_FAMILY_Q) {
+        hipExtLaunchKernelGGL(k_trace_q, grid, block, lds, stream, t0, t1, 0, sc->dev, st, pp, plan.queue_refill, (uint32_t) (plan.bits_off / 16));
+        return;
+    }
+    with_trace_mode(plan.trace_mode, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        if (plan.trace_family == mskplan::TRACE_FAMILY_PLAIN) hipExtLaunchKernelGGL(k_trace<M>, grid, block, lds, stream, t0, t1, 0, sc->dev, st, pp);
+        else if constexpr (M != mskplan::TRACE_WIDE4_LDS)         // (the tree in LDS is never walked with lane replacement: no k_trace_r<3>)
+            hipExtLaunchKernelGGL(k_trace_r<M>, grid, block, lds, stream, t0, t1, 0, sc->dev, st, pp, plan.refill, plan.max_inner);
+    });
+}
+
+template <bool LDS_TABLES>
+static void launch_shade_t(const msk_scene *sc, const mskplan::LaunchPlan &plan, dim3 grid, hipStream_t stream, const PathState &st, const PassParams &pp,
+                           hipEvent_t t0, hipEvent_t t1) {
+#define MSK_SHADE(...) hipExtLaunchKernelGGL((__VA_ARGS__), grid, dim3(MSK_BLOCK), plan.shade_lds_bytes, stream, t0, t1, 0, sc->dev, st, pp)
+    switch (plan.shade_kind) {
+    case mskplan::SHADE_DIELECTRIC: MSK_SHADE(k_shade_gen_d<LDS_TABLES>); break;
+    case mskplan::SHADE_DIFFUSE: MSK_SHADE(k_shade_gen<LDS_TABLES, true>); break;
+    case mskplan::SHADE_REGULAR: MSK_SHADE(k_shade_gen<LDS_TABLES, false, true>); break;
+    case mskplan::SHADE_GENERAL: MSK_SHADE(k_shade_gen<LDS_TABLES, false>); break;
+    }
+#undef MSK_SHADE
+}
+static void launch_shade(const msk_scene *sc, const mskplan::LaunchPlan &plan, dim3 grid, hipStream_t stream, const PathState &st, const PassParams &pp,
+                         hipEvent_t t0, hipEvent_t t1) {
+    if (plan.lds_tables) launch_shade_t<true>(sc, plan, grid, stream, st, pp, t0, t1);
+    else launch_shade_t<false>(sc, plan, grid, stream, st, pp, t0, t1);
+}
+
+// the iteration loop on the device: one bounded launch = up to plan.fused_iters sweeps of every region
+static void launch_fused(const msk_scene *sc, const mskplan::LaunchPlan &plan, dim3 grid, hipStream_t stream, const PathState &st, const PassParams &pp) {
+#define MSK_FUSED(...) hipExtLaunchKernelGGL((__VA_ARGS__), grid, dim3(MSK_BLOCK), plan.fused_lds_bytes, stream, nullptr, nullptr, 0, sc->dev, st, pp, \
+                                             plan.fused_iters, plan.fused_queue_f4, plan.fused_trace_f4)
+    if (plan.fused_h) switch (plan.shade_kind) {      // the tree in HBM (trace mode 6)
+    case mskplan::SHADE_DIELECTRIC: MSK_FUSED(k_wavefront_h_d); break;
+    case mskplan::SHADE_DIFFUSE: MSK_FUSED(k_wavefront_h<true>); break;
+    case mskplan::SHADE_REGULAR: MSK_FUSED(k_wavefront_h<false, true>); break;
+    case mskplan::SHADE_GENERAL: MSK_FUSED(k_wavefront_h<false>); break;
+    }
+    else switch (plan.shade_kind) {                   // everything in LDS (trace mode 0)
+    case mskplan::SHADE_DIELECTRIC: MSK_FUSED(k_wavefront_d); break;
+    case mskplan::SHADE_DIFFUSE: MSK_FUSED(k_wavefront<true>); break;
+    case mskplan::SHADE_REGULAR: MSK_FUSED(k_wavefront<false, true>); break;
+    case mskplan::SHADE_GENERAL: MSK_FUSED(k_wavefront<false>); break;
+    }
+#undef MSK_FUSED
+}
+
+// ------------------------------------------------------------------------------------------
+// the wavefront loop
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// what the parts of one run_wavefront call share
+struct Wavefront {
+    msk_scene *sc; StateBufs &sb; const mskplan::LaunchPlan &plan; const mskplan::RenderKnobs &knobs;
+    const AovParams *aov;              // the record groups of an "aov" render (k_aov_primary after every sweep), or nullptr
+    uint32_t region_size;
+    bool timing;                       // the caller asked for msk_stats
+    // A timed dispatch costs ~6 us more than an untimed one (completion signal + timestamps): 2 % of a bench step when every
+    // launch is timed.  MSK_TIMING_EVERY=n times the launches of every n-th sync group only (rotating from render to render so
+    // that repeated renders cover all groups); msk_stats::ms_trace / ms_shade / n_*_launches then describe that sample.
+    uint32_t phase;
+    mskwd::Waiter waiter;
+};
+
+// One part of the pool: the regions [first, first + count) and their wavefront loop on one stream.  The parts' loops run at the
+// same time: regions are independent — each owns its slots, its share of the samples and its counters — and a shading
+// launch of one part fills the gaps of a traversal launch of another (and the other way round), which one launch at a time
+// leaves open at its start, its end and wherever its waves wait.  Measured with two concurrent half-size renders before
+// this was built: 49.3 against 55.0 ms for the bench step.  WHO drives the loops is a separate choice (MSK_HOST_THREADS below).
+struct Part {
+    const Wavefront *wf = nullptr;
+    uint32_t first = 0, count = 0; hipStream_t stream = nullptr; Ctrl *d_ctrl = nullptr, *h_ctrl = nullptr; EventPool ev{nullptr};
+    msk_stats st; int rc = MSK_OK; unsigned long long expected = 0, culled = 0; std::string err; bool lost = false;
+    // the loop's state between two sync groups
+    PassParams pp; uint32_t grid = 0, it = 0, gi = 0, parity = 0, last_iters = 0; bool fused_now = false, done = false; size_t ev_mark = 0;
+    // Two alternating sets of events: a group's timestamps are read (hipEventElapsedTime is a host call of a few
+    // microseconds, 32 of them per group) after the NEXT group has been queued, not while the GPU waits for work.
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> cur_shade, cur_trace, pend_shade, pend_trace;
+    mskwd::Progress watchdog;                          // msk_watchdog.h: a wall limit per sync group + "the counters stand still"
+    mskwd::Ticket ticket;
+    explicit Part(const mskwd::Limits &l) : watchdog(l) { std::memset(&st, 0, sizeof st); }
+
+    void read_pending();
+    int queue_group();
+    int finish_group();
+};
+
+void Part::read_pending() {
+    if (!wf->timing) return;
+    sum_events(pend_shade, &st.ms_shade); sum_events(pend_trace, &st.ms_trace);
+    st.n_shade_launches += (uint32_t) pend_shade.size(); st.n_trace_launches += (uint32_t) pend_trace.size();
+    pend_shade.clear(); pend_trace.clear();
+}
+
+// MSK_DUMP_RAYS=<file> (+ MSK_DUMP_ITER, default 12; MSK_DUMP_STRIDE, default 32), measurements only: the rays the traversal
+// launch of that iteration is about to walk — every MSK_DUMP_STRIDE-th region of the first part, its live slots in the
+// order the kernel takes them (shadow-carrying slots first) — written to the file for the host-side scheduler model
+// (tools/micro/sched_model.cpp).  Header {'MSKR', regions, region_size, stride}; per region {count, ns}, then count x
+// {ray_o, ray_d (w = tmax as the kernel reads it), sh} float4.
+static void dump_rays(const Part &p) {
+    const StateBufs &sb = p.wf->sb;
+    const uint32_t region_size = p.wf->region_size, dump_stride = p.wf->knobs.dump_stride;
+    if (hipStreamSynchronize(p.stream) != hipSuccess) return;
+    std::vector<RegionCtl> ctl(p.count);
+    if (hipMemcpy(ctl.data(), sb.counts.as<RegionCtl>() + p.first, p.count * sizeof(RegionCtl), hipMemcpyDeviceToHost) != hipSuccess) return;
+    FILE *f = std::fopen(p.wf->knobs.dump_rays, "wb");
+    if (!f) return;
+    const uint32_t n_dump = (p.count + dump_stride - 1) / dump_stride;
+    const uint32_t head[4] = {0x524b534du, n_dump, region_size, dump_stride};
+    std::fwrite(head, 4, 4, f);
+    std::vector<float4> ho(2 * (size_t) region_size), hd(2 * (size_t) region_size), hs(2 * (size_t) region_size);
+    for (uint32_t r = 0; r < p.count; r += dump_stride) {
+        const size_t base = (size_t) (p.first + r) * 2 * region_size;
+        (void) hipMemcpy(ho.data(), sb.st.ray_o + base, ho.size() * 16, hipMemcpyDeviceToHost);
+        (void) hipMemcpy(hd.data(), sb.st.ray_d + base, hd.size() * 16, hipMemcpyDeviceToHost);
+        (void) hipMemcpy(hs.data(), sb.st.sh + base, hs.size() * 16, hipMemcpyDeviceToHost);
+        const uint32_t count = ctl[r].count, ns = ctl[r].half_ns >> 1, half = ctl[r].half_ns & 1u;
+        const uint32_t cn[2] = {count, ns};
+        std::fwrite(cn, 4, 2, f);
+        for (uint32_t c = 0; c < count; ++c) {
+            const size_t slot = (size_t) half * region_size + (c < ns ? c : region_size - 1 - (c - ns));
+            float4 rec[3] = {ho[slot], hd[slot], c < ns ? hs[slot] : make_float4(0, 0, 0, 0)};
+            if (std::signbit(rec[1].w)) rec[1].w = INFINITY;          // slot_tmax: a bounce ray keeps -pdf there
+            std::fwrite(rec, 16, 3, f);
+        }
+    }
+    std::fclose(f);
+}
+
+// queues one sync group of the part's loop: `sync_group` iterations (or one k_wavefront launch), the counters' reduction and
+// their copy to the host, and whatever the wait mode needs behind them
+int Part::queue_group() {
+    const Wavefront &w = *wf;
+    const mskplan::LaunchPlan &plan = w.plan;
+    ev.next = ev_mark + (size_t) parity * 4 * plan.sync_group;
+    const bool timed = w.timing && (gi + w.phase) % plan.timing_every == 0;
+    if (fused_now) {
+        // (not timed: msk_stats::ms_shade / ms_trace stay the sums of k_shade_gen / k_trace launches)
+        launch_fused(w.sc, plan, dim3(grid), stream, w.sb.st, pp);
+        it += plan.fused_iters; last_iters = plan.fused_iters;
+        st.launches_wavefront += 1;
+    } else {
+        for (uint32_t g = 0; g < plan.sync_group; ++g, ++it) {
+            hipEvent_t a = nullptr, b = nullptr, c = nullptr, d = nullptr;
+            if (timed) { a = ev.get(); b = ev.get(); c = ev.get(); d = ev.get(); }
+            const bool have_ev = a && b && c && d;
+            launch_shade(w.sc, plan, dim3(grid), stream, w.sb.st, pp, a, b);
+            if (w.knobs.dump_rays && it == w.knobs.dump_iter && first == 0) dump_rays(*this);      // (measurements only: MSK_DUMP_RAYS)
+            launch_trace(w.sc, plan, stream, w.sb.st, pp, c, d);
+            st.launches_shade += 1; st.launches_trace += 1;
+            if (w.aov && w.aov->n_groups) hipLaunchKernelGGL(k_aov_primary, dim3(grid), dim3(MSK_BLOCK), 0, stream, w.sc->dev, w.sb.st, pp, *w.aov);
+            if (timed && have_ev) { cur_shade.push_back({a, b}); cur_trace.push_back({c, d}); }
+        }
+        last_iters = plan.sync_group;
+    }
+    read_pending();                    // the previous group's, while this one runs
+    HIP_TRY_SLOT(&err, hipMemsetAsync(d_ctrl, 0, sizeof(Ctrl), stream));
+    hipLaunchKernelGGL(k_reduce_ctl, dim3(std::min(64u, (count + MSK_BLOCK - 1) / MSK_BLOCK)), dim3(MSK_BLOCK), 0, stream,
+                       w.sb.counts.as<RegionCtl>() + first, count, d_ctrl);
+    HIP_TRY_SLOT(&err, hipGetLastError());
+    HIP_TRY_SLOT(&err, hipMemcpyAsync(h_ctrl, d_ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, stream));
+    HIP_TRY_SLOT(&err, mskwd::arm(w.waiter, ticket));
+    return MSK_OK;
+}
+
+// after the group's last command has completed: is the part done, stalled, or ready for its thin end?
+int Part::finish_group() {
+    const mskplan::LaunchPlan &plan = wf->plan;
+    pend_shade.swap(cur_shade); pend_trace.swap(cur_trace); cur_shade.clear(); cur_trace.clear(); parity ^= 1u; ++gi;
+    const Ctrl &h = *h_ctrl;
+    if (h.remaining == 0 && h.live == 0) {
+        read_pending();
+        ev.next = ev_mark;                              // every timestamp has been read: the events are free again
+        st.samples = h.samples_done; st.segments = h.segments; st.shadow_rays = h.shadow_rays;
+        st.invalid_samples = h.invalid;
+        culled = h.culled;
+        st.iterations = it;
+        done = true;
+        if (h.samples_done != expected)
+            return fail_to(&err, MSK_ERR_HIP, "internal error: %llu of %llu samples finished", h.samples_done, expected);
+        return MSK_OK;
+    }
+    if (watchdog.group_done(mskwd::Counters{h.samples_done, h.segments, h.remaining, h.live}) == mskwd::STALLED) {
+        lost = true;
+        return fail_to(&err, MSK_ERR_HIP, "no progress: %u sync groups of the wavefront loop changed nothing (%llu samples finished, %llu live paths, "
+                       "%llu samples not started; MSK_WATCHDOG_GROUPS); the context is lost", watchdog.stalled(), h.samples_done, h.live, h.remaining);
+    }
+    if (plan.fused_ok && !fused_now && h.remaining == 0 && h.live * 100ull < (unsigned long long) plan.fused_tail_pct * count * wf->region_size)
+        fused_now = true;                         // the thinning end of the pass: no more launches and host round trips per sweep
+    if (it > 100000000u) return fail_to(&err, MSK_ERR_HIP, "wavefront loop did not terminate");
+    return MSK_OK;
+}
+
+}  // namespace
+
+// One host thread drives n of the parts: queues a group on each, then serves whichever finishes (wait_any), oldest first.
+static void drive(int device, const mskwd::Waiter &waiter, Part *const *mine, int n) {
+    (void) hipSetDevice(device);                    // the current device is per host thread
+    Part *active[MSK_MAX_STREAMS];
+    int n_active = 0;
+    for (int i = 0; i < n; ++i) {
+        mine[i]->rc = mine[i]->queue_group();
+        if (mine[i]->rc == MSK_OK) active[n_active++] = mine[i];
+    }
+    while (n_active) {
+        mskwd::Ticket *tickets[MSK_MAX_STREAMS];
+        for (int i = 0; i < n_active; ++i) tickets[i] = &active[i]->ticket;
+        hipError_t es = hipSuccess;
+        const int hit = mskwd::wait_any(waiter, tickets, n_active, active[0]->watchdog, &es);
+        if (hit < 0) {                              // the wall limit: nothing this thread waits for will be waited for again
+            for (int i = 0; i < n_active; ++i) {
+                Part &q = *active[i];
+                q.lost = true;
+                q.rc = fail_to(&q.err, MSK_ERR_HIP, "no progress: a sync group of the wavefront loop (iterations %u..%u, regions %u..%u) did not finish within "
+                               "%g s (MSK_WATCHDOG_S); the context is lost", q.it - q.last_iters, q.it, q.first, q.first + q.count, q.watchdog.limits().wall_s);
+            }
+            return;
+        }
+        Part &p = *active[hit];
+        for (int i = hit; i + 1 < n_active; ++i) active[i] = active[i + 1];
+        --n_active;
+        if (es != hipSuccess) { p.rc = fail_to(&p.err, MSK_ERR_HIP, "the wavefront loop's stream reported: %s", hipGetErrorString(es)); continue; }
+        p.rc = p.finish_group();
+        if (p.lost) return;                         // (stalled: the context is done, the other parts are not driven further)
+        if (p.rc == MSK_OK && !p.done) {
+            p.rc = p.queue_group();
+            if (p.rc == MSK_OK) active[n_active++] = &p;
+        }
+    }
+}
+
+// The regions' records at the start of a pass: each region's share of the samples (mskplan::region_share).  The initial records
+// are kept on the device and copied from there when the next render has the same shape.
+static int reset_regions(msk_scene *sc, hipStream_t stream, StateBufs &sb, unsigned long long total, uint32_t n_regions) {
     msk_ctx *ctx = sc->ctx;
-    int rc_sync = MSK_OK;
-    const unsigned long long total = (unsigned long long) n_pix * spp_owned;
-    // static, interleaved partition of the pass's samples over the regions (see RegionCtl); the initial records are kept
-    // on the device and copied from there when the next render has the same shape
     Workspace *wsp = sc->ws;
     if (!(wsp && wsp->counts_total == total && wsp->counts_regions == n_regions && wsp->counts_init.p)) {
         std::vector<RegionCtl> init(n_regions);
         std::memset(init.data(), 0, init.size() * sizeof(RegionCtl));
-        const unsigned long long n_chunks = (total + 63) / 64;
-        for (uint32_t r = 0; r < n_regions; ++r) {
-            const unsigned long long mine = n_chunks > r ? (n_chunks - r + n_regions - 1) / n_regions : 0;
-            unsigned long long n = mine * 64;
-            if (mine && (mine - 1) * n_regions + r == n_chunks - 1) n -= n_chunks * 64 - total;   // partial last chunk
-            init[r].next_sample = 0; init[r].end_sample = n;
-        }
+        for (uint32_t r = 0; r < n_regions; ++r) { init[r].next_sample = 0; init[r].end_sample = mskplan::region_share(total, n_regions, r); }
         if (wsp) {
             HIP_TRY(ctx, wsp->counts_init.reserve(init.size() * sizeof(RegionCtl)));
             HIP_TRY(ctx, hipMemcpy(wsp->counts_init.p, init.data(), init.size() * sizeof(RegionCtl), hipMemcpyHostToDevice));
             wsp->counts_total = total; wsp->counts_regions = n_regions;
         } else {
             HIP_TRY(ctx, hipMemcpyAsync(sb.counts.p, init.data(), init.size() * sizeof(RegionCtl), hipMemcpyHostToDevice, stream));
-            if ((rc_sync = ctx_sync(ctx, stream, "the upload of the regions' records"))) return rc_sync;
+            if (int rc = ctx_sync(ctx, stream, "the upload of the regions' records")) return rc;
         }
     }
     if (wsp) HIP_TRY(ctx, hipMemcpyAsync(sb.counts.p, wsp->counts_init.p, (size_t) n_regions * sizeof(RegionCtl), hipMemcpyDeviceToDevice, stream));
-    PassParams pp0;
-    pp0.seed = prm->seed; pp0.spp_owned = spp_owned; pp0.sample_first = prm->sample_first;
-    pp0.sample_stride = prm->sample_stride ? prm->sample_stride : 1;
-    pp0.rr_depth = prm->rr_depth; pp0.max_depth = prm->max_depth; pp0.hide_emitters = prm->hide_emitters;
-    pp0.pix_table = d_pix; pp0.pix_to_j = d_pix_to_j; pp0.rec_a = rec_a; pp0.rec_b = rec_b;
-    pp0.region_size = region_size; pp0.n_regions = n_regions; pp0.regions = sb.counts.as<RegionCtl>();
-    pp0.region_first = 0; pp0.region_count = n_regions;
-    pp0.trace_split = sc->trace_mode == 0 ? std::max(1u, env_u32("MSK_TRACE_SPLIT", 2)) : 1u;
-    pp0.aov_rgb = aov_rgb;
-    pp0.aov_groups = aov ? aov->n_groups : 0u;
-    for (uint32_t g = 0; g < MSK_MAX_AOV_GROUPS; ++g) pp0.aov_rec[g] = aov && g < aov->n_groups ? aov->rec[g] : nullptr;
-    pp0.packed = packed ? 1u : 0u;
-    pp0.stack_ovf = nullptr;
-    // camera samples that miss the scene's bounds are finished where they are made (shade_region's regeneration) — unless a miss
-    // is more than a record of zeros: an "aov" render's record groups and nested RGB record are written per sample by other code.
-    // MSK_CAMERA_CULL=0 (read per call): off
-    pp0.cull = (sc->cull_ok && !aov_rgb && !(aov && aov->n_groups) && env_u32("MSK_CAMERA_CULL", 1) != 0) ? 1u : 0u;
-    // (MSK_FORCE_GENERAL_SHADE=1, measurements only: an all-diffuse scene through the general variant — what a per-class diffuse
-    // instantiation could save a mixed scene's diffuse chunks)
-    const bool force_general = env_u32("MSK_FORCE_GENERAL_SHADE", 0) != 0;
-    // (the AOV RGB record and the validity test over an "aov" render's record groups live in the general shading variant)
-    const bool diffuse_only = sc->all_diffuse && !aov_rgb && !(aov && aov->n_groups) && !force_general;
-    // material-sorted shading (general variant): LDS for the permutation, 3 bytes per slot of a region and wave (MSK_SORT=0: off)
-    const size_t sort_lds = (size_t) (MSK_BLOCK / MSK_WAVE) * 3 * region_size;
-    const bool sort_on = !diffuse_only && (!sc->all_diffuse || force_general) && region_size <= 4096 && env_u32("MSK_SORT", 1) &&
-                         sc->shade_lds_bytes + sort_lds <= 64 * 1024;
-    pp0.sort_scratch = sort_on ? 1u : 0u;
-    const size_t shade_lds = sc->shade_lds_bytes + (sort_on ? sort_lds : 0);
-    const uint32_t group = env_u32("MSK_SYNC_GROUP", 8);
-    static const size_t shade_pad_lds = (size_t) env_u32("MSK_SHADE_PAD_LDS_KB", 0) * 1024;   // occupancy experiments only
-    const bool timing = stats != nullptr;
-    // A timed dispatch costs ~6 us more than an untimed one (completion signal + timestamps): 2 % of a bench step when every
-    // launch is timed.  MSK_TIMING_EVERY=n times the launches of every n-th sync group only (rotating from render to render so
-    // that repeated renders cover all groups); msk_stats::ms_trace / ms_shade / n_*_launches then describe that sample.
-    const uint32_t every = std::max(1u, env_u32("MSK_TIMING_EVERY", 1));
-    const uint32_t phase = ctx->timing_phase++;
-    // k_wavefront (iterations on the device): possible when tables and tree are LDS-resident and everything fits one block's LDS
-    // next to each other, and there is no per-iteration AOV kernel.  MSK_FUSED=1: the whole pass; MSK_FUSED_TAIL_PCT=p: from
-    // the point where every sample has been started and fewer than p % of the slots are live.
-    const uint32_t fused_queue_f4 = (uint32_t) ((sc->shade_lds_bytes - (size_t) (MSK_BLOCK / MSK_WAVE) * MSK_DONE_Q_F4 * 16) / 16);     // after the staged tables
-    const uint32_t fused_trace_f4 = (uint32_t) (sc->shade_lds_bytes / 16);
-    const size_t fused_lds = sc->shade_lds_bytes + sc->trace_lds_bytes;
-    // ... and k_wavefront_h for the default tree in HBM (trace mode 6): the VERY thin end only (MSK_FUSED_HBM=0: off).  Round 6, same
-    // box, config-5 / config-3 class renders: from 10 % live slots on (the LDS-resident scenes' threshold) 117.9 / 137.1 ms against
-    // 116.2 / 138.6 without — a wave's own longest rays bound both, and the fused kernel walks them at two waves per SIMD without lane
-    // replacement; from 1-3 % on — the ~40 last iterations, whose launches are a few dozen microseconds of latency each —
-    // 118.1-118.2 / 143.9-144.2 ms against 119.2 / 146.2 (profiles/r06_ab_fused_hbm.txt): the default, at 2 %.
-    const bool fused_h = sc->trace_mode == 6 && !sc->lds_tables && env_u32("MSK_FUSED_HBM", 1) != 0;
-    const bool fused_ok = ((sc->trace_mode == 0 && sc->lds_tables) || fused_h) && fused_lds <= 64 * 1024 && !(aov && aov->n_groups);
-    const bool fused_all = fused_ok && env_u32("MSK_FUSED", 0) != 0;
-    const uint32_t fused_iters = std::max(1u, env_u32("MSK_FUSED_ITERS", 16));
-    const uint32_t fused_tail_pct = fused_ok ? env_u32("MSK_FUSED_TAIL_PCT", fused_h ? 2 : 10) : 0u;
+    return MSK_OK;
+}
 
-    // The wavefront loop over the regions [first, first + count) on one stream.  The pool's two halves run this at the same
-    // time on two streams (two host threads): regions are independent — each owns its slots, its share of the samples and
-    // its counters — and a shading launch of one half fills the gaps of a traversal launch of the other (and the other way
-    // round), which one launch at a time leaves open at its start, its end and wherever its waves wait.  Measured with two
-    // concurrent half-size renders before this was built: 49.3 against 55.0 ms for the bench step.
-    // One part of the pool: the regions [first, first + count) and their wavefront loop on one stream.  The parts' loops run at the
-    // same time: regions are independent — each owns its slots, its share of the samples and its counters — and a shading
-    // launch of one part fills the gaps of a traversal launch of another (and the other way round), which one launch at a time
-    // leaves open at its start, its end and wherever its waves wait.  Measured with two concurrent half-size renders before
-    // this was built: 49.3 against 55.0 ms for the bench step.  WHO drives the loops is a separate choice (MSK_HOST_THREADS below).
-    struct Part {
-        uint32_t first = 0, count = 0; hipStream_t stream = nullptr; Ctrl *d_ctrl = nullptr, *h_ctrl = nullptr; EventPool ev{nullptr}; uint32_t *stack_ovf = nullptr;
-        msk_stats st; int rc = MSK_OK; unsigned long long expected = 0, culled = 0; std::string err; bool lost = false;
-        // the loop's state between two sync groups
-        PassParams pp; uint32_t grid = 0, it = 0, gi = 0, parity = 0, last_iters = 0; bool fused_now = false, done = false; size_t ev_mark = 0;
-        // Two alternating sets of events: a group's timestamps are read (hipEventElapsedTime is a host call of a few
-        // microseconds, 32 of them per group) after the NEXT group has been queued, not while the GPU waits for work.
-        std::vector<std::pair<hipEvent_t, hipEvent_t>> cur_shade, cur_trace, pend_shade, pend_trace;
-        mskwd::Progress watchdog;                          // msk_watchdog.h: a wall limit per sync group + "the counters stand still"
-        mskwd::Ticket ticket;
-        explicit Part(const mskwd::Limits &l) : watchdog(l) { std::memset(&st, 0, sizeof st); }
-    };
+// ABI v7: the bytes of SoA path state this pass's launches were asked to move (counted from what the kernels
+// read and write per live slot, not measured): a segment = a slot that is live after a shading sweep.
+//   shading  176 B/segment (id 8, wl, thr, res, ray_d, hit in; id 8, wl, thr, res, ray_o, ray_d out; + aux 8 in / 8 out in the
+//            general variant) - 64 B/sample (a new sample's thr = 1 and res = 0 are neither written nor read)
+//            + 48 B/shadow ray (contrib in; sh, contrib out) + 20 B/sample (its record)
+//   traversal 48 B/segment (ray_o, ray_d in; hit out) + per shadow ray: sh in, and ray_o again where the shadow rays are a
+//            second queue of the launch (k_trace_q / k_trace: 32 B; k_trace_r walks both rays of a slot together: 16 B —
+//            LaunchPlan::lane_refill, which leaves an LDS-resident scene forced onto k_trace_r<0> at 32 B)
+//   a CULLED sample (round 9; counted in samples and in segments) moves its 20-byte record and nothing else: it never
+//            holds a slot — 112 B less of shading (176 - 64; 128 with the general variant's aux) and 48 B less of traversal than the terms above give it
+static void add_part_stats(msk_stats *stats, const Part &p, const mskplan::LaunchPlan &plan) {
+    stats->samples += p.st.samples; stats->segments += p.st.segments; stats->shadow_rays += p.st.shadow_rays;
+    stats->invalid_samples += p.st.invalid_samples;
+    stats->iterations += p.st.iterations;
+    stats->ms_trace += p.st.ms_trace; stats->ms_shade += p.st.ms_shade;
+    stats->n_trace_launches += p.st.n_trace_launches; stats->n_shade_launches += p.st.n_shade_launches;
+    stats->launches_trace += p.st.launches_trace; stats->launches_shade += p.st.launches_shade; stats->launches_wavefront += p.st.launches_wavefront;
+    const unsigned long long seg = p.st.segments, smp = p.st.samples, shd = p.st.shadow_rays, cul = p.culled;
+    const unsigned long long aux = plan.diffuse_only ? 0ull : 16ull;
+    stats->bytes_shade += seg * (176ull + aux) + shd * 48ull + smp * 20ull - std::min(smp * 64ull, seg * 176ull) - cul * (112ull + aux);
+    stats->bytes_trace += seg * 48ull + shd * (plan.lane_refill ? 16ull : 32ull) - cul * 48ull;
+}
+
+static PassParams pass_params(const msk_render_params *prm, uint32_t spp_owned, const uint4 *d_pix, const uint32_t *d_pix_to_j, float4 *rec_a, float *rec_b,
+                              StateBufs &sb, uint32_t region_size, uint32_t n_regions, const mskplan::LaunchPlan &plan,
+                              const AovParams *aov, float4 *aov_rgb, bool packed) {
+    PassParams pp;
+    pp.seed = prm->seed; pp.spp_owned = spp_owned; pp.sample_first = prm->sample_first;
+    pp.sample_stride = prm->sample_stride ? prm->sample_stride : 1;
+    pp.rr_depth = prm->rr_depth; pp.max_depth = prm->max_depth; pp.hide_emitters = prm->hide_emitters;
+    pp.pix_table = d_pix; pp.pix_to_j = d_pix_to_j; pp.rec_a = rec_a; pp.rec_b = rec_b;
+    pp.region_size = region_size; pp.n_regions = n_regions; pp.regions = sb.counts.as<RegionCtl>();
+    pp.region_first = 0; pp.region_count = n_regions;
+    pp.trace_split = plan.trace_split;
+    pp.aov_rgb = aov_rgb;
+    pp.aov_groups = aov ? aov->n_groups : 0u;
+    for (uint32_t g = 0; g < MSK_MAX_AOV_GROUPS; ++g) pp.aov_rec[g] = aov && g < aov->n_groups ? aov->rec[g] : nullptr;
+    pp.packed = packed ? 1u : 0u;
+    pp.stack_ovf = nullptr;
+    pp.cull = plan.cull ? 1u : 0u;
+    pp.sort_scratch = plan.sort_on ? 1u : 0u;
+    return pp;
+}
+
+static mskplan::SceneFacts scene_facts(const msk_scene *sc) {
+    mskplan::SceneFacts f;
+    f.trace_mode = sc->trace_mode; f.lds_scene = sc->lds_scene; f.lds_tables = sc->lds_tables; f.all_diffuse = sc->all_diffuse;
+    f.has_regular = sc->has_regular; f.has_dielectric = sc->has_dielectric; f.cull_ok = sc->cull_ok;
+    f.trace_lds_bytes = sc->trace_lds_bytes; f.shade_lds_bytes = sc->shade_lds_bytes;
+    return f;
+}
+
+// Renders the samples of `pix` (pass pixel table, host) into records; leaves records on device.
+static int run_wavefront(msk_scene *sc, hipStream_t stream, const msk_render_params *prm, const mskplan::RenderKnobs &knobs, uint32_t spp_owned,
+                         const uint4 *d_pix, const uint32_t *d_pix_to_j, uint64_t n_pix, float4 *rec_a, float *rec_b, StateBufs &sb,
+                         uint32_t region_size, uint32_t n_regions, msk_stats *stats, EventPool &ev,
+                         const AovParams *aov = nullptr, float4 *aov_rgb = nullptr, bool packed = false) {
+    msk_ctx *ctx = sc->ctx;
+    const unsigned long long total = (unsigned long long) n_pix * spp_owned;
+    if (int rc = reset_regions(sc, stream, sb, total, n_regions)) return rc;
+    mskplan::CallFacts call;
+    call.region_size = region_size; call.aov_groups = aov ? aov->n_groups : 0u; call.aov_rgb = aov_rgb != nullptr;
+    const mskplan::LaunchPlan plan = mskplan::make_launch_plan(scene_facts(sc), call, knobs);
+    const PassParams pp0 = pass_params(prm, spp_owned, d_pix, d_pix_to_j, rec_a, rec_b, sb, region_size, n_regions, plan, aov, aov_rgb, packed);
+    const Wavefront wf{sc, sb, plan, knobs, aov, region_size, stats != nullptr, ctx->timing_phase++, mskwd::Waiter{mskwd::wait_mode_from_env(), ctx->hub}};
     const mskwd::Limits wd_limits = mskwd::limits_from_env();
-    const mskwd::Waiter waiter{mskwd::wait_mode_from_env(), ctx->hub};
-    auto read_pending = [&](Part &p) {
-        if (!timing) return;
-        sum_events(p.pend_shade, &p.st.ms_shade); sum_events(p.pend_trace, &p.st.ms_trace);
-        p.st.n_shade_launches += (uint32_t) p.pend_shade.size(); p.st.n_trace_launches += (uint32_t) p.pend_trace.size();
-        p.pend_shade.clear(); p.pend_trace.clear();
-    };
-    // MSK_DUMP_RAYS=<file> (+ MSK_DUMP_ITER, default 12; MSK_DUMP_STRIDE, default 32), measurements only: the rays the traversal
-    // launch of that iteration is about to walk — every MSK_DUMP_STRIDE-th region of the first part, its live slots in the
-    // order the kernel takes them (shadow-carrying slots first) — written to the file for the host-side scheduler model
-    // (tools/micro/sched_model.cpp).  Header {'MSKR', regions, region_size, stride}; per region {count, ns}, then count x
-    // {ray_o, ray_d (w = tmax as the kernel reads it), sh} float4.
-    const char *dump_path = getenv("MSK_DUMP_RAYS");
-    const uint32_t dump_iter = env_u32("MSK_DUMP_ITER", 12), dump_stride = std::max(1u, env_u32("MSK_DUMP_STRIDE", 32));
-    auto dump_rays = [&](Part &p) {
-        if (hipStreamSynchronize(p.stream) != hipSuccess) return;
-        std::vector<RegionCtl> ctl(p.count);
-        if (hipMemcpy(ctl.data(), sb.counts.as<RegionCtl>() + p.first, p.count * sizeof(RegionCtl), hipMemcpyDeviceToHost) != hipSuccess) return;
-        FILE *f = std::fopen(dump_path, "wb");
-        if (!f) return;
-        const uint32_t n_dump = (p.count + dump_stride - 1) / dump_stride;
-        const uint32_t head[4] = {0x524b534du, n_dump, region_size, dump_stride};
-        std::fwrite(head, 4, 4, f);
-        std::vector<float4> ho(2 * (size_t) region_size), hd(2 * (size_t) region_size), hs(2 * (size_t) region_size);
-        for (uint32_t r = 0; r < p.count; r += dump_stride) {
-            const size_t base = (size_t) (p.first + r) * 2 * region_size;
-            (void) hipMemcpy(ho.data(), sb.st.ray_o + base, ho.size() * 16, hipMemcpyDeviceToHost);
-            (void) hipMemcpy(hd.data(), sb.st.ray_d + base, hd.size() * 16, hipMemcpyDeviceToHost);
-            (void) hipMemcpy(hs.data(), sb.st.sh + base, hs.size() * 16, hipMemcpyDeviceToHost);
-            const uint32_t count = ctl[r].count, ns = ctl[r].half_ns >> 1, half = ctl[r].half_ns & 1u;
-            const uint32_t cn[2] = {count, ns};
-            std::fwrite(cn, 4, 2, f);
-            for (uint32_t c = 0; c < count; ++c) {
-                const size_t slot = (size_t) half * region_size + (c < ns ? c : region_size - 1 - (c - ns));
-                float4 rec[3] = {ho[slot], hd[slot], c < ns ? hs[slot] : make_float4(0, 0, 0, 0)};
-                if (std::signbit(rec[1].w)) rec[1].w = INFINITY;          // slot_tmax: a bounce ray keeps -pdf there
-                std::fwrite(rec, 16, 3, f);
-            }
-        }
-        std::fclose(f);
-    };
-    // queues one sync group of the part's loop: `group` iterations (or one k_wavefront launch), the counters' reduction and
-    // their copy to the host, and whatever the wait mode needs behind them
-    auto queue_group = [&](Part &p) -> int {
-        const PassParams &pp = p.pp;
-        hipStream_t stream_h = p.stream;
-        const uint32_t grid = p.grid;
-        p.ev.next = p.ev_mark + (size_t) p.parity * 4 * group;
-        const bool timed = timing && (p.gi + phase) % every == 0;
-        if (p.fused_now) {
-            // the iteration loop on the device (k_wavefront): one bounded launch = up to fused_iters sweeps of every region
-            // (not timed: msk_stats::ms_shade / ms_trace stay the sums of k_shade_gen / k_trace launches)
-            hipEvent_t a = nullptr, b = nullptr;
-            if (fused_h) {
-                if (sc->has_dielectric) hipExtLaunchKernelGGL(k_wavefront_h_d, dim3(grid), dim3(MSK_BLOCK), fused_lds, stream_h, a, b, 0, sc->dev, sb.st, pp, fused_iters, fused_queue_f4, fused_trace_f4);
-                else if (diffuse_only) hipExtLaunchKernelGGL((k_wavefront_h<true>), dim3(grid), dim3(MSK_BLOCK), fused_lds, stream_h, a, b, 0, sc->dev, sb.st, pp, fused_iters, fused_queue_f4, fused_trace_f4);
-                else if (sc->has_regular) hipExtLaunchKernelGGL((k_wavefront_h<false, true>), dim3(grid), dim3(MSK_BLOCK), fused_lds, stream_h, a, b, 0, sc->dev, sb.st, pp, fused_iters, fused_queue_f4, fused_trace_f4);
-                else hipExtLaunchKernelGGL((k_wavefront_h<false>), dim3(grid), dim3(MSK_BLOCK), fused_lds, stream_h, a, b, 0, sc->dev, sb.st, pp, fused_iters, fused_queue_f4, fused_trace_f4);
-            }
-            else if (sc->has_dielectric) hipExtLaunchKernelGGL(k_wavefront_d, dim3(grid), dim3(MSK_BLOCK), fused_lds, stream_h, a, b, 0, sc->dev, sb.st, pp, fused_iters, fused_queue_f4, fused_trace_f4);
-            else if (diffuse_only) hipExtLaunchKernelGGL((k_wavefront<true>), dim3(grid), dim3(MSK_BLOCK), fused_lds, stream_h, a, b, 0, sc->dev, sb.st, pp, fused_iters, fused_queue_f4, fused_trace_f4);
-            else if (sc->has_regular) hipExtLaunchKernelGGL((k_wavefront<false, true>), dim3(grid), dim3(MSK_BLOCK), fused_lds, stream_h, a, b, 0, sc->dev, sb.st, pp, fused_iters, fused_queue_f4, fused_trace_f4);
-            else hipExtLaunchKernelGGL((k_wavefront<false>), dim3(grid), dim3(MSK_BLOCK), fused_lds, stream_h, a, b, 0, sc->dev, sb.st, pp, fused_iters, fused_queue_f4, fused_trace_f4);
-            p.it += fused_iters; p.last_iters = fused_iters;
-            p.st.launches_wavefront += 1;
-        } else {
-            for (uint32_t g = 0; g < group; ++g, ++p.it) {
-                hipEvent_t a = nullptr, b = nullptr, c = nullptr, d = nullptr;
-                if (timed) { a = p.ev.get(); b = p.ev.get(); c = p.ev.get(); d = p.ev.get(); }
-                const bool have_ev = a && b && c && d;
-#define MSK_SHADE(...) hipExtLaunchKernelGGL((k_shade_gen<__VA_ARGS__>), dim3(grid), dim3(MSK_BLOCK), shade_lds + shade_pad_lds, stream_h, a, b, 0, sc->dev, sb.st, pp)
-                if (sc->has_dielectric) {          // (never diffuse_only: such a scene is not all_diffuse)
-                    if (sc->lds_tables) hipExtLaunchKernelGGL((k_shade_gen_d<true>), dim3(grid), dim3(MSK_BLOCK), shade_lds + shade_pad_lds, stream_h, a, b, 0, sc->dev, sb.st, pp);
-                    else hipExtLaunchKernelGGL((k_shade_gen_d<false>), dim3(grid), dim3(MSK_BLOCK), shade_lds + shade_pad_lds, stream_h, a, b, 0, sc->dev, sb.st, pp);
-                }
-                else if (sc->lds_tables) { if (diffuse_only) MSK_SHADE(true, true); else if (sc->has_regular) MSK_SHADE(true, false, true); else MSK_SHADE(true, false); }
-                else { if (diffuse_only) MSK_SHADE(false, true); else if (sc->has_regular) MSK_SHADE(false, false, true); else MSK_SHADE(false, false); }
-#undef MSK_SHADE
-                if (dump_path && p.it == dump_iter && p.first == 0) dump_rays(p);      // (measurements only: MSK_DUMP_RAYS)
-                launch_trace(sc, stream_h, sb.st, pp, c, d);
-                p.st.launches_shade += 1; p.st.launches_trace += 1;
-                if (aov && aov->n_groups) hipLaunchKernelGGL(k_aov_primary, dim3(grid), dim3(MSK_BLOCK), 0, stream_h, sc->dev, sb.st, pp, *aov);
-                if (timed && have_ev) { p.cur_shade.push_back({a, b}); p.cur_trace.push_back({c, d}); }
-            }
-            p.last_iters = group;
-        }
-        read_pending(p);                    // the previous group's, while this one runs
-        HIP_TRY_SLOT(&p.err, hipMemsetAsync(p.d_ctrl, 0, sizeof(Ctrl), stream_h));
-        hipLaunchKernelGGL(k_reduce_ctl, dim3(std::min(64u, (p.count + MSK_BLOCK - 1) / MSK_BLOCK)), dim3(MSK_BLOCK), 0, stream_h,
-                           sb.counts.as<RegionCtl>() + p.first, p.count, p.d_ctrl);
-        HIP_TRY_SLOT(&p.err, hipGetLastError());
-        HIP_TRY_SLOT(&p.err, hipMemcpyAsync(p.h_ctrl, p.d_ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, stream_h));
-        HIP_TRY_SLOT(&p.err, mskwd::arm(waiter, p.ticket));
-        return MSK_OK;
-    };
-    // after the group's last command has completed: is the part done, stalled, or ready for its thin end?
-    auto finish_group = [&](Part &p) -> int {
-        p.pend_shade.swap(p.cur_shade); p.pend_trace.swap(p.cur_trace); p.cur_shade.clear(); p.cur_trace.clear(); p.parity ^= 1u; ++p.gi;
-        const Ctrl &h = *p.h_ctrl;
-        if (h.remaining == 0 && h.live == 0) {
-            read_pending(p);
-            p.ev.next = p.ev_mark;                            // every timestamp has been read: the events are free again
-            p.st.samples = h.samples_done; p.st.segments = h.segments; p.st.shadow_rays = h.shadow_rays;
-            p.st.invalid_samples = h.invalid;
-            p.culled = h.culled;
-            p.st.iterations = p.it;
-            p.done = true;
-            if (h.samples_done != p.expected)
-                return fail_to(&p.err, MSK_ERR_HIP, "internal error: %llu of %llu samples finished", h.samples_done, p.expected);
-            return MSK_OK;
-        }
-        if (p.watchdog.group_done(mskwd::Counters{h.samples_done, h.segments, h.remaining, h.live}) == mskwd::STALLED) {
-            p.lost = true;
-            return fail_to(&p.err, MSK_ERR_HIP, "no progress: %u sync groups of the wavefront loop changed nothing (%llu samples finished, %llu live paths, "
-                           "%llu samples not started; MSK_WATCHDOG_GROUPS); the context is lost", p.watchdog.stalled(), h.samples_done, h.live, h.remaining);
-        }
-        if (fused_ok && !p.fused_now && h.remaining == 0 && h.live * 100ull < (unsigned long long) fused_tail_pct * p.count * region_size)
-            p.fused_now = true;                       // the thinning end of the pass: no more launches and host round trips per sweep
-        if (p.it > 100000000u) return fail_to(&p.err, MSK_ERR_HIP, "wavefront loop did not terminate");
-        return MSK_OK;
-    };
-    // One host thread drives n of the parts: queues a group on each, then serves whichever finishes (wait_any), oldest first.
-    auto drive = [&](Part *const *mine, int n) {
-        (void) hipSetDevice(ctx->device);               // the current device is per host thread
-        Part *active[MSK_MAX_STREAMS];
-        int n_active = 0;
-        for (int i = 0; i < n; ++i) {
-            mine[i]->rc = queue_group(*mine[i]);
-            if (mine[i]->rc == MSK_OK) active[n_active++] = mine[i];
-        }
-        while (n_active) {
-            mskwd::Ticket *tickets[MSK_MAX_STREAMS];
-            for (int i = 0; i < n_active; ++i) tickets[i] = &active[i]->ticket;
-            hipError_t es = hipSuccess;
-            const int hit = mskwd::wait_any(waiter, tickets, n_active, active[0]->watchdog, &es);
-            if (hit < 0) {                              // the wall limit: nothing this thread waits for will be waited for again
-                for (int i = 0; i < n_active; ++i) {
-                    Part &q = *active[i];
-                    q.lost = true;
-                    q.rc = fail_to(&q.err, MSK_ERR_HIP, "no progress: a sync group of the wavefront loop (iterations %u..%u, regions %u..%u) did not finish within "
-                                   "%g s (MSK_WATCHDOG_S); the context is lost", q.it - q.last_iters, q.it, q.first, q.first + q.count, q.watchdog.limits().wall_s);
-                }
-                return;
-            }
-            Part &p = *active[hit];
-            for (int i = hit; i + 1 < n_active; ++i) active[i] = active[i + 1];
-            --n_active;
-            if (es != hipSuccess) { p.rc = fail_to(&p.err, MSK_ERR_HIP, "the wavefront loop's stream reported: %s", hipGetErrorString(es)); continue; }
-            p.rc = finish_group(p);
-            if (p.lost) return;                         // (stalled: the context is done, the other parts are not driven further)
-            if (p.rc == MSK_OK && !p.done) {
-                p.rc = queue_group(p);
-                if (p.rc == MSK_OK) active[n_active++] = &p;
-            }
-        }
-    };
 
-    // samples the regions [first, first + count) own (the same static partition as the init above)
-    auto share = [&](uint32_t first, uint32_t count) {
-        const unsigned long long n_chunks = (total + 63) / 64;
-        unsigned long long sum = 0;
-        for (uint32_t r = first; r < first + count; ++r) {
-            const unsigned long long mine = n_chunks > r ? (n_chunks - r + n_regions - 1) / n_regions : 0;
-            unsigned long long n = mine * 64;
-            if (mine && (mine - 1) * n_regions + r == n_chunks - 1) n -= n_chunks * 64 - total;
-            sum += n;
-        }
-        return sum;
-    };
     // how many loops: 4 by default (DESIGN.md §6 has 1 / 2 / 3 / 4); one for small jobs and caller-supplied streams
-    uint32_t n_parts = std::min<uint32_t>(MSK_MAX_STREAMS, std::max(1u, env_u32("MSK_STREAMS", 4)));
+    uint32_t n_parts = std::min<uint32_t>(MSK_MAX_STREAMS, std::max(1u, knobs.streams));
     if (n_regions < 1024 || stream != ctx->stream) n_parts = 1;
     const uint32_t ovf_words = sc->dev.stack_total > sc->dev.stack_entries ? sc->dev.stack_total - sc->dev.stack_entries : 0;
+    const std::vector<uint32_t> cut = mskplan::part_ranges(n_regions, n_parts, knobs.stream_skew);
     std::vector<Part> parts;
     parts.reserve(n_parts);
-    // Parts of slightly different sizes: equal parts can fall into step (all launches starting and draining together, which
-    // is one big launch again; measured as a bimodal 48 / 52 ms), unequal ones keep sliding past each other.
-    const double skew = env_u32("MSK_STREAM_SKEW", 10) / 100.0;          // relative size step between neighbouring parts
-    std::vector<double> cum(n_parts + 1, 0.0);
-    for (uint32_t k = 0; k < n_parts; ++k) cum[k + 1] = cum[k] + 1.0 + skew * ((double) (n_parts - 1) / 2.0 - k);
     for (uint32_t k = 0; k < n_parts; ++k) {
-        const uint32_t first = (uint32_t) (n_regions * (cum[k] / cum[n_parts])), last = k + 1 == n_parts ? n_regions : (uint32_t) (n_regions * (cum[k + 1] / cum[n_parts]));
         parts.emplace_back(wd_limits);
         Part &p = parts.back();
-        p.first = first; p.count = last - first; p.stream = k ? ctx->more_streams[k - 1] : stream;
+        p.wf = &wf;
+        p.first = cut[k]; p.count = cut[k + 1] - cut[k]; p.stream = k ? ctx->more_streams[k - 1] : stream;
         p.d_ctrl = sb.ctrl.as<Ctrl>() + k; p.h_ctrl = ctx->h_ctrl + k;
         p.ev = k ? EventPool{ctx, 0, &ctx->more_events[k - 1]} : EventPool{ctx, ev.next, ev.pool};
         p.ev_mark = p.ev.next;
-        p.expected = share(first, last - first);
-        p.pp = pp0; p.pp.region_first = first; p.pp.region_count = p.count;
+        for (uint32_t r = p.first; r < p.first + p.count; ++r) p.expected += mskplan::region_share(total, n_regions, r);
+        p.pp = pp0; p.pp.region_first = p.first; p.pp.region_count = p.count;
         p.grid = (p.count * MSK_WAVE + MSK_BLOCK - 1) / MSK_BLOCK;
-        p.fused_now = fused_all;
+        p.fused_now = plan.fused_all;
         p.ticket.stream = p.stream; p.ticket.slot = (int) k; p.ticket.event = ctx->wait_events[k];
         if (ovf_words) {                                // LaneStack overflow: one word per lane per extra entry, per launch
-            const size_t lanes = (size_t) (((last - first) * MSK_WAVE + MSK_BLOCK - 1) / MSK_BLOCK) * MSK_BLOCK;
+            const size_t lanes = (size_t) p.grid * MSK_BLOCK;
             HIP_TRY(ctx, sb.stack_ovf[k].reserve((size_t) ovf_words * lanes * 4));
-            p.stack_ovf = sb.stack_ovf[k].as<uint32_t>();
+            p.pp.stack_ovf = sb.stack_ovf[k].as<uint32_t>();
         }
-        p.pp.stack_ovf = p.stack_ovf;
     }
     // Who drives the parts' loops (MSK_HOST_THREADS): ONE host thread for all of them by default since round 6 — it queues a
     // group on every stream and then serves whichever finishes; the device always holds the other streams' queued groups while
     // the host turns one around.  Rounds 2-5 used one thread per part (MSK_HOST_THREADS=4): three more threads per context,
     // spinning with the poll wait (DESIGN.md §7 has both under a CPU quota).
-    const uint32_t n_threads = std::min(n_parts, std::max(1u, env_u32("MSK_HOST_THREADS", 1)));
-    if (n_parts > 1) {
-        rc_sync = ctx_sync(ctx, stream, "the regions' initial records");     // (queued above) before the other streams read them
-        if (rc_sync) return rc_sync;
-    }
+    const uint32_t n_threads = std::min(n_parts, std::max(1u, knobs.host_threads));
+    if (n_parts > 1)       // the regions' records (queued above) before the other streams read them
+        if (int rc = ctx_sync(ctx, stream, "the regions' initial records")) return rc;
     {
         std::vector<std::vector<Part *>> mine(n_threads);
         for (uint32_t k = 0; k < n_parts; ++k) mine[k % n_threads].push_back(&parts[k]);
         std::vector<std::thread> others;
-        for (uint32_t j = 1; j < n_threads; ++j) others.emplace_back([&, j]() { drive(mine[j].data(), (int) mine[j].size()); });
-        drive(mine[0].data(), (int) mine[0].size());
+        for (uint32_t j = 1; j < n_threads; ++j) others.emplace_back([&, j]() { drive(ctx->device, wf.waiter, mine[j].data(), (int) mine[j].size()); });
+        drive(ctx->device, wf.waiter, mine[0].data(), (int) mine[0].size());
         for (auto &t : others) t.join();
     }
-    for (auto &hf : parts) if (hf.lost) ctx->lost = true;                                 // the watchdog gave up on a part: the context is done
-    for (auto &hf : parts) if (hf.rc) return fail(ctx, hf.rc, "%s", hf.err.c_str());     // first failing part, after the join
-    if (stats) {
-        for (const Part &hf : parts) {
-            stats->samples += hf.st.samples; stats->segments += hf.st.segments; stats->shadow_rays += hf.st.shadow_rays;
-            stats->invalid_samples += hf.st.invalid_samples;
-            stats->iterations += hf.st.iterations;
-            stats->ms_trace += hf.st.ms_trace; stats->ms_shade += hf.st.ms_shade;
-            stats->n_trace_launches += hf.st.n_trace_launches; stats->n_shade_launches += hf.st.n_shade_launches;
-            stats->launches_trace += hf.st.launches_trace; stats->launches_shade += hf.st.launches_shade; stats->launches_wavefront += hf.st.launches_wavefront;
-            // ABI v7: the bytes of SoA path state this pass's launches were asked to move (counted from what the kernels
-            // read and write per live slot, not measured): a segment = a slot that is live after a shading sweep.
-            //   shading  176 B/segment (id 8, wl, thr, res, ray_d, hit in; id 8, wl, thr, res, ray_o, ray_d out; + aux 8 in / 8 out in the
-            //            general variant) - 64 B/sample (a new sample's thr = 1 and res = 0 are neither written nor read)
-            //            + 48 B/shadow ray (contrib in; sh, contrib out) + 20 B/sample (its record)
-            //   traversal 48 B/segment (ray_o, ray_d in; hit out) + per shadow ray: sh in, and ray_o again where the shadow rays are a
-            //            second queue of the launch (k_trace_q / k_trace: 32 B; k_trace_r walks both rays of a slot together: 16 B)
-            //   a CULLED sample (round 9; counted in samples and in segments) moves its 20-byte record and nothing else: it never
-            //            holds a slot — 112 B less of shading (176 - 64; 128 with the general variant's aux) and 48 B less of traversal than the terms above give it
-            const unsigned long long seg = hf.st.segments, smp = hf.st.samples, shd = hf.st.shadow_rays;
-            const bool lane_refill = sc->trace_mode != 0 && sc->trace_mode != 3 && (getenv("MSK_TRACE_REFILL") ? atoi(getenv("MSK_TRACE_REFILL")) != 0 : true);
-            const unsigned long long cul = hf.culled;
-            stats->bytes_shade += seg * (176ull + (diffuse_only ? 0ull : 16ull)) + shd * 48ull + smp * 20ull - std::min(smp * 64ull, seg * 176ull) - cul * (112ull + (diffuse_only ? 0ull : 16ull));
-            stats->bytes_trace += seg * 48ull + shd * (lane_refill ? 16ull : 32ull) - cul * 48ull;
-        }
-    }
-    (void) ev_trace; (void) ev_shade;
+    for (auto &p : parts) if (p.lost) ctx->lost = true;                                // the watchdog gave up on a part: the context is done
+    for (auto &p : parts) if (p.rc) return fail(ctx, p.rc, "%s", p.err.c_str());      // first failing part, after the join
+    if (stats) for (const Part &p : parts) add_part_stats(stats, p, plan);
     return MSK_OK;
 }
 
@@ -1265,24 +1260,34 @@ static int check_params(msk_ctx *ctx, const msk_render_params *p, int block_min)
     return MSK_OK;
 }
 
-// Short rays (LDS-resident scene): many small regions, one chunk loop per wave: 8192 x 512 = 4 M path slots (0.6 GB of state;
-// measured 16384 / 12288 / 8192 / 6144 regions: 42.7 / 41.7 / 41.2 / 41.6 ms for the bench step — the shading kernel streams the
-// whole pool's state every iteration and a smaller pool keeps more of it in the 256 MB Infinity Cache, the traversal kernel
-// wants many waves per launch).  Long rays (k_trace_r): 4096 regions of 2048 slots = 8 M, so that lane replacement has a long
-// list of rays to keep the lanes busy with.
-static void pool_shape(const msk_scene *sc, uint64_t total_samples, uint32_t *region_size, uint32_t *n_regions) {
-    const bool big = sc->trace_mode == 1 || sc->trace_mode == 2 || sc->trace_mode == 4 || sc->trace_mode == 5 || sc->trace_mode == 6;
-    // trees in HBM: one traversal wave per region at 5 waves per SIMD = 5120 resident waves; with 4096 regions the four loops'
-    // launches never filled the GPU (8192 regions: config-5-class render 173 vs 191 ms, config-3-class 205 vs 227 ms)
-    // LDS-resident scenes: 6144 x 1024 (with the state's cache policy in place — msk_kernels.h, MSK_NT — fewer, longer regions
-    // win over round 1's 8192 x 512: 36.2 vs 37.0 ms per bench step; 5120 … 8192 x 896 … 1280 are within 1 % of each other)
-    uint32_t rs = env_u32("MSK_REGION_SIZE", big ? 2048 : 1024), nr = env_u32("MSK_REGIONS", big ? 8192 : 6144);
-    rs = std::max(64u, (rs + 63u) & ~63u);
-    while (rs > 256 && total_samples / rs < nr) rs = std::max(256u, rs / 2);       // small jobs: keep the GPU full first
-    const uint64_t need = (total_samples + rs - 1) / rs;
-    if (need < nr) nr = (uint32_t) std::max<uint64_t>(need, 1);
-    nr = (nr + 3u) & ~3u;
-    *region_size = rs; *n_regions = nr;
+// The blocks of the spiral schedule this call renders: every block_stride-th from block_first on, unless it owns no sample.  A block
+// whose bordered area misses the crop window adds nothing to the film (accumulate_2d clips it to nothing, imageblock.cpp:133-150):
+// it is not rendered.
+struct OwnedBlocks {
+    int nbx = 0, nby = 0;
+    std::vector<int32_t> block_of;         // [by * nbx + bx] -> index into `owned`, -1 = not rendered by this call
+    std::vector<uint32_t> spiral_id;       // [by * nbx + bx] -> place in the spiral order
+    std::vector<BlockInfo> owned;
+};
+static OwnedBlocks owned_blocks(const msk_scene *sc, const msk_render_params *prm) {
+    OwnedBlocks o;
+    const DeviceScene &ds = sc->dev;
+    const int border = ds.filter_border;
+    const std::vector<HostBlock> all = spiral_blocks(ds.width, ds.height, prm->block_size, &o.nbx, &o.nby);
+    const uint32_t bstride = prm->block_stride ? prm->block_stride : 1;
+    const bool nothing = owned_spp(prm) == 0;
+    o.block_of.assign((size_t) o.nbx * o.nby, -1);
+    o.spiral_id.assign((size_t) o.nbx * o.nby, 0);
+    for (size_t id = 0; id < all.size(); ++id) {
+        const HostBlock &b = all[id];
+        o.spiral_id[(size_t) b.by * o.nbx + b.bx] = (uint32_t) id;
+        if (id % bstride != prm->block_first || nothing) continue;
+        if (b.off_x - border >= ds.crop_x + ds.crop_w || b.off_x + b.size_x + border <= ds.crop_x ||
+            b.off_y - border >= ds.crop_y + ds.crop_h || b.off_y + b.size_y + border <= ds.crop_y) continue;
+        o.block_of[(size_t) b.by * o.nbx + b.bx] = (int32_t) o.owned.size();
+        o.owned.push_back(BlockInfo{b.off_x, b.off_y, b.size_x, b.size_y, 0u, (uint32_t) o.owned.size()});
+    }
+    return o;
 }
 
 
@@ -1294,28 +1299,16 @@ static int render_serial(msk_scene *sc, const msk_render_params *prm, float *d_f
     EventPool ev{ctx, 0};
     hipEvent_t t_begin = ev.get(), t_end = ev.get();
     if (t_begin) (void) hipEventRecord(t_begin, stream);
-    const int W = sc->dev.width, H = sc->dev.height, bs = prm->block_size;
-    int nbx, nby;
-    std::vector<HostBlock> all = spiral_blocks(W, H, bs, &nbx, &nby);
-    const uint32_t bstride = prm->block_stride ? prm->block_stride : 1;
-    std::vector<int32_t> block_of((size_t) nbx * nby, -1);
-    std::vector<uint32_t> spiral_id((size_t) nbx * nby, 0);
-    std::vector<BlockInfo> owned;
-    for (size_t id = 0; id < all.size(); ++id) {
-        spiral_id[(size_t) all[id].by * nbx + all[id].bx] = (uint32_t) id;
-        if (id % bstride != prm->block_first || owned_spp(prm) == 0) continue;
-        if (all[id].off_x - border >= sc->dev.crop_x + sc->dev.crop_w || all[id].off_x + all[id].size_x + border <= sc->dev.crop_x ||
-            all[id].off_y - border >= sc->dev.crop_y + sc->dev.crop_h || all[id].off_y + all[id].size_y + border <= sc->dev.crop_y) continue;
-        block_of[(size_t) all[id].by * nbx + all[id].bx] = (int32_t) owned.size();
-        owned.push_back(BlockInfo{all[id].off_x, all[id].off_y, all[id].size_x, all[id].size_y, 0u, (uint32_t) owned.size()});
-    }
+    const int bs = prm->block_size;
+    OwnedBlocks ob = owned_blocks(sc, prm);
+    std::vector<BlockInfo> &owned = ob.owned;
     const uint32_t buf_stride = (uint32_t) ((bs + 2 * border) * (bs + 2 * border)) * 5;
     if (!sc->ws) sc->ws = new Workspace();
     Workspace &ws = *sc->ws;
     ws.plan_key.clear();                                 // the block tables below replace whatever plan a wavefront render cached
     const size_t buf_bytes = std::max<size_t>(owned.size(), 1) * buf_stride * 4;
     HIP_TRY(ctx, ws.block_buf.reserve(buf_bytes));
-    HIP_TRY(ctx, ws.blocks.upload(owned)); HIP_TRY(ctx, ws.block_of.upload(block_of)); HIP_TRY(ctx, ws.spiral.upload(spiral_id));
+    HIP_TRY(ctx, ws.blocks.upload(owned)); HIP_TRY(ctx, ws.block_of.upload(ob.block_of)); HIP_TRY(ctx, ws.spiral.upload(ob.spiral_id));
     HIP_TRY(ctx, hipMemsetAsync(ws.block_buf.p, 0, buf_bytes, stream));
     DevBuf counters, ovf;
     HIP_TRY(ctx, counters.reserve(32));
@@ -1344,7 +1337,7 @@ static int render_serial(msk_scene *sc, const msk_render_params *prm, float *d_f
     fo.film = d_film; fo.stride = 5;
     for (int c = 0; c < 5; ++c) fo.ch[c] = c;
     hipLaunchKernelGGL(k_film_put, dim3((uint32_t) (((size_t) sc->dev.crop_w * sc->dev.crop_h + MSK_BLOCK - 1) / MSK_BLOCK)), dim3(MSK_BLOCK), 0, stream,
-                       sc->dev, ws.blocks.as<BlockInfo>(), ws.block_of.as<int32_t>(), ws.spiral.as<uint32_t>(), nbx, nby, bs,
+                       sc->dev, ws.blocks.as<BlockInfo>(), ws.block_of.as<int32_t>(), ws.spiral.as<uint32_t>(), ob.nbx, ob.nby, bs,
                        ws.block_buf.as<float>(), buf_stride, fo);
     if (t_end) (void) hipEventRecord(t_end, stream);
     HIP_TRY(ctx, hipGetLastError());
@@ -1377,25 +1370,10 @@ static int render_impl(msk_scene *sc, const msk_render_params *prm, float *d_fil
     hipEvent_t t_begin = ev.get(), t_end = ev.get();
     if (t_begin) (void) hipEventRecord(t_begin, stream);
     const int W = sc->dev.width, H = sc->dev.height, bs = prm->block_size;
-    int nbx, nby;
-    std::vector<HostBlock> all = spiral_blocks(W, H, bs, &nbx, &nby);
+    OwnedBlocks ob = owned_blocks(sc, prm);
+    std::vector<BlockInfo> &owned = ob.owned;
     const uint32_t bstride = prm->block_stride ? prm->block_stride : 1;
     const uint32_t spp_owned = (uint32_t) owned_spp(prm);            // <= 2^20 (check_params)
-    std::vector<int32_t> block_of((size_t) nbx * nby, -1);
-    std::vector<uint32_t> spiral_id((size_t) nbx * nby, 0);
-    std::vector<BlockInfo> owned;
-    std::vector<size_t> owned_all_index;
-    for (size_t id = 0; id < all.size(); ++id) {
-        spiral_id[(size_t) all[id].by * nbx + all[id].bx] = (uint32_t) id;
-        if (id % bstride != prm->block_first || spp_owned == 0) continue;
-        // a block whose bordered area misses the crop window adds nothing to the film (accumulate_2d clips it to nothing,
-        // imageblock.cpp:133-150): it is not rendered
-        if (all[id].off_x - border >= sc->dev.crop_x + sc->dev.crop_w || all[id].off_x + all[id].size_x + border <= sc->dev.crop_x ||
-            all[id].off_y - border >= sc->dev.crop_y + sc->dev.crop_h || all[id].off_y + all[id].size_y + border <= sc->dev.crop_y) continue;
-        block_of[(size_t) all[id].by * nbx + all[id].bx] = (int32_t) owned.size();
-        owned.push_back(BlockInfo{all[id].off_x, all[id].off_y, all[id].size_x, all[id].size_y, 0u, (uint32_t) owned.size()});
-        owned_all_index.push_back(id);
-    }
     const uint32_t per_block = (uint32_t) ((bs + 2 * border) * (bs + 2 * border));
     const uint32_t buf_stride = per_block * 5;
     if (!sc->ws) sc->ws = new Workspace();
@@ -1411,10 +1389,11 @@ static int render_impl(msk_scene *sc, const msk_render_params *prm, float *d_fil
     // ---- plan passes: consecutive owned blocks whose records fit the budget
     size_t free_b = 0, total_b = 0;
     HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
+    const mskplan::RenderKnobs knobs = mskplan::read_render_knobs();      // once per render: every pass runs under the same knobs
     uint32_t region_size, n_regions;
     uint64_t all_samples = 0;
     for (auto &b : owned) all_samples += (uint64_t) b.size_x * b.size_y * spp_owned;
-    pool_shape(sc, all_samples, &region_size, &n_regions);
+    mskplan::pool_shape(sc->trace_mode, all_samples, knobs, &region_size, &n_regions);
     const size_t n_slots = (size_t) region_size * n_regions;
     const size_t state_bytes = 2 * n_slots * 144 + 4096;                              // two halves per region (StateBufs::alloc)
     const size_t held = ws.rec_a.bytes + ws.rec_b.bytes + ws.sb.id.bytes * 144 / 8;     // reusable: counts as free
@@ -1449,11 +1428,11 @@ static int render_impl(msk_scene *sc, const msk_render_params *prm, float *d_fil
     const bool plan_cached = passes.size() == 1 && ws.plan_key == plan_key;
     if (!plan_cached) {
         ws.plan_key.clear();
-        HIP_TRY(ctx, d_blocks.upload(owned)); HIP_TRY(ctx, d_block_of.upload(block_of)); HIP_TRY(ctx, d_spiral.upload(spiral_id));
+        HIP_TRY(ctx, d_blocks.upload(owned)); HIP_TRY(ctx, d_block_of.upload(ob.block_of)); HIP_TRY(ctx, d_spiral.upload(ob.spiral_id));
     }
     StateBufs &sb = ws.sb;
     if (!owned.empty()) HIP_TRY(ctx, sb.alloc(n_slots, n_regions));
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_trace, ev_shade, ev_resolve;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_resolve;
     DevBuf &d_pix = ws.pix, &d_rec_a = ws.rec_a, &d_rec_b = ws.rec_b;
     for (auto &ps : passes) {
         uint64_t n_pix = ws.plan_n_pix;
@@ -1500,8 +1479,8 @@ static int render_impl(msk_scene *sc, const msk_render_params *prm, float *d_fil
             }
             if (aov->rgba) { HIP_TRY(ctx, ws.aov_rec[MSK_MAX_AOV_GROUPS].reserve(n_rec * 16)); aov_rgb = ws.aov_rec[MSK_MAX_AOV_GROUPS].as<float4>(); }
         }
-        rc = run_wavefront(sc, stream, prm, spp_owned, d_pix.as<uint4>(), ws.pix_inv.as<uint32_t>(), n_pix, d_rec_a.as<float4>(),
-                           d_rec_b.as<float>(), sb, region_size, n_regions, stats, ev, ev_trace, ev_shade, aov ? &ap : nullptr, aov_rgb, packed);
+        rc = run_wavefront(sc, stream, prm, knobs, spp_owned, d_pix.as<uint4>(), ws.pix_inv.as<uint32_t>(), n_pix, d_rec_a.as<float4>(),
+                           d_rec_b.as<float>(), sb, region_size, n_regions, stats, ev, aov ? &ap : nullptr, aov_rgb, packed);
         if (rc) return rc;
         const uint32_t nb = (uint32_t) (ps.second - ps.first);
         // tile of film pixels per thread: 1 wide (adjacent lanes read adjacent records -> full cache lines),
@@ -1549,7 +1528,7 @@ static int render_impl(msk_scene *sc, const msk_render_params *prm, float *d_fil
             fo.film = d_film; fo.stride = 5 + (int32_t) (aov ? aov->n_channels : 0u);
             for (int c = 0; c < 5; ++c) fo.ch[c] = g == 0 ? c : aov->out_ch[g - 1 < aov->n_groups ? g - 1 : MSK_MAX_AOV_GROUPS][c];
             hipLaunchKernelGGL(k_film_put, dim3((uint32_t) (((size_t) sc->dev.crop_w * sc->dev.crop_h + MSK_BLOCK - 1) / MSK_BLOCK)), dim3(MSK_BLOCK), 0, stream,
-                               sc->dev, d_blocks.as<BlockInfo>(), d_block_of.as<int32_t>(), d_spiral.as<uint32_t>(), nbx, nby, bs,
+                               sc->dev, d_blocks.as<BlockInfo>(), d_block_of.as<int32_t>(), d_spiral.as<uint32_t>(), ob.nbx, ob.nby, bs,
                                g == 0 ? d_block_buf.as<float>() : ws.aov_block_buf[slot].as<float>(), buf_stride, fo);
         }
         if (b) (void) hipEventRecord(b, stream);
@@ -1715,18 +1694,18 @@ extern "C" int msk_gpu_sample_pixels(msk_scene *scene, const msk_render_params *
     n_pixels = pix.size();
     msk_render_params p = *prm; p.sample_first = 0; p.sample_stride = 1;
     const uint64_t n_rec = n_pixels * p.spp;
+    const mskplan::RenderKnobs knobs = mskplan::read_render_knobs();
     uint32_t region_size, n_regions;
-    pool_shape(scene, n_rec, &region_size, &n_regions);
+    mskplan::pool_shape(scene->trace_mode, n_rec, knobs, &region_size, &n_regions);
     StateBufs sb; DevBuf d_pix, d_inv, ra, rb, ox, op;
     HIP_TRY(ctx, sb.alloc((size_t) region_size * n_regions, n_regions));
     HIP_TRY(ctx, d_pix.upload(pix)); HIP_TRY(ctx, d_inv.upload(inv)); HIP_TRY(ctx, ra.alloc(n_rec * 16)); HIP_TRY(ctx, rb.alloc(n_rec * 4));
     HIP_TRY(ctx, ox.alloc(n_rec * 12)); HIP_TRY(ctx, op.alloc(n_rec * 8));
     EventPool ev{ctx, 0};
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> e1, e2;
     // a lost context (the watchdog gave up): the local buffers are dropped without hipFree, which would wait for the device
     auto sb_leak = [&]() { if (ctx->lost) { sb.leak(); for (DevBuf *b : {&d_pix, &d_inv, &ra, &rb, &ox, &op}) b->leak(); } };
-    rc = run_wavefront(scene, ctx->stream, &p, p.spp, d_pix.as<uint4>(), d_inv.as<uint32_t>(), n_pixels, ra.as<float4>(), rb.as<float>(), sb,
-                       region_size, n_regions, nullptr, ev, e1, e2);
+    rc = run_wavefront(scene, ctx->stream, &p, knobs, p.spp, d_pix.as<uint4>(), d_inv.as<uint32_t>(), n_pixels, ra.as<float4>(), rb.as<float>(), sb,
+                       region_size, n_regions, nullptr, ev);
     if (rc) { sb_leak(); return rc; }
     hipLaunchKernelGGL(k_export_records, dim3((uint32_t) ((n_rec + 255) / 256)), dim3(256), 0, ctx->stream, ra.as<float4>(),
                        rb.as<float>(), n_pixels, p.spp, ox.as<float>(), op.as<float>());
@@ -1755,27 +1734,10 @@ static int trace_batch(msk_scene *scene, uint64_t n, const float *rays, float *o
     DevBuf d_ovf;
     if (scene->dev.stack_total > scene->dev.stack_entries)
         HIP_TRY(ctx, d_ovf.alloc((size_t) (scene->dev.stack_total - scene->dev.stack_entries) * grid * MSK_BLOCK * 4));
-    if (scene->trace_mode == 0)
-        hipLaunchKernelGGL(k_trace_batch<0>, dim3(grid), dim3(MSK_BLOCK), scene->trace_lds_bytes, ctx->stream, scene->dev,
+    with_trace_mode(scene->trace_mode, [&](auto m) {
+        hipLaunchKernelGGL(k_trace_batch<decltype(m)::value>, dim3(grid), dim3(MSK_BLOCK), scene->trace_lds_bytes, ctx->stream, scene->dev,
                            d_rays.as<float4>(), n, oh, oa, d_ovf.as<uint32_t>());
-    else if (scene->trace_mode == 1)
-        hipLaunchKernelGGL(k_trace_batch<1>, dim3(grid), dim3(MSK_BLOCK), scene->trace_lds_bytes, ctx->stream, scene->dev,
-                           d_rays.as<float4>(), n, oh, oa, d_ovf.as<uint32_t>());
-    else if (scene->trace_mode == 2)
-        hipLaunchKernelGGL(k_trace_batch<2>, dim3(grid), dim3(MSK_BLOCK), scene->trace_lds_bytes, ctx->stream, scene->dev,
-                           d_rays.as<float4>(), n, oh, oa, d_ovf.as<uint32_t>());
-    else if (scene->trace_mode == 4)
-        hipLaunchKernelGGL(k_trace_batch<4>, dim3(grid), dim3(MSK_BLOCK), scene->trace_lds_bytes, ctx->stream, scene->dev,
-                           d_rays.as<float4>(), n, oh, oa, d_ovf.as<uint32_t>());
-    else if (scene->trace_mode == 5)
-        hipLaunchKernelGGL(k_trace_batch<5>, dim3(grid), dim3(MSK_BLOCK), scene->trace_lds_bytes, ctx->stream, scene->dev,
-                           d_rays.as<float4>(), n, oh, oa, d_ovf.as<uint32_t>());
-    else if (scene->trace_mode == 6)
-        hipLaunchKernelGGL(k_trace_batch<6>, dim3(grid), dim3(MSK_BLOCK), scene->trace_lds_bytes, ctx->stream, scene->dev,
-                           d_rays.as<float4>(), n, oh, oa, d_ovf.as<uint32_t>());
-    else
-        hipLaunchKernelGGL(k_trace_batch<3>, dim3(grid), dim3(MSK_BLOCK), scene->trace_lds_bytes, ctx->stream, scene->dev,
-                           d_rays.as<float4>(), n, oh, oa, d_ovf.as<uint32_t>());
+    });
     HIP_TRY(ctx, hipGetLastError());
     if (int rcw = ctx_sync(ctx, ctx->stream, "k_trace_batch")) { d_rays.leak(); d_out.leak(); d_ovf.leak(); return rcw; }
     HIP_TRY(ctx, hipMemcpy(out_any ? (void *) out_any : (void *) out_hit, d_out.p, out_any ? n : n * 16, hipMemcpyDeviceToHost));

@@ -1,0 +1,242 @@
+// msk_plan.h — what a render launches, decided once per call and on the host alone: the environment knobs of the wavefront
+// driver (RenderKnobs), the shape of the path pool (pool_shape), which instantiation of the shading, traversal and fused kernels
+// runs with how much LDS (LaunchPlan), and how a pass's samples and regions are dealt out (region_share, part_ranges).
+// Plain C++17, no HIP: msk_gpu.hip only picks the instantiation the plan names (launch_shade / launch_trace / launch_fused), and
+// tests/native/launch_plan_check.cpp checks every decision on a CPU.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <cstdlib>
+#include <vector>
+
+namespace mskplan {
+
+// The tree the traversal kernels walk: msk_scene::trace_mode and the kernels' MODE parameter hold these values.
+enum TraceMode : int {
+    TRACE_BIN_LDS    = 0,    // binary tree, staged in LDS with the triangles (a scene of MSK_LDS_SCENE_KB or less)
+    TRACE_BIN_HBM    = 1,    // binary tree in HBM/L2 (MSK_WIDE_BVH=0, or a root that is a leaf)
+    TRACE_WIDE4      = 2,    // 4-wide tree, 128-byte nodes with full-precision child boxes (MSK_QUANT_BVH=0)
+    TRACE_WIDE4_LDS  = 3,    // 4-wide tree staged in LDS (the MSK_WIDE_LDS experiment); never walked with lane replacement
+    TRACE_WIDE8      = 4,    // 8-wide tree, quantised child boxes in 128-byte nodes (MSK_WIDE_BVH=8)
+    TRACE_WIDE4_BYTE = 5,    // 4-wide tree, 64-byte nodes with byte-quantised boxes (MSK_QUANT_BVH=1; the default of rounds 3-4)
+    TRACE_WIDE4_HALF = 6     // 4-wide tree, 80-byte nodes with half-float boxes: the default for a tree in HBM (MSK_QUANT_BVH=2)
+};
+// the tree stays in HBM/L2: a capped LDS stack with an overflow array, the larger pool, lane replacement by default
+constexpr bool tree_in_hbm(int mode) { return mode == TRACE_BIN_HBM || mode == TRACE_WIDE4 || mode == TRACE_WIDE8 || mode == TRACE_WIDE4_BYTE || mode == TRACE_WIDE4_HALF; }
+
+constexpr size_t kWavesPerBlock = 4;                        // MSK_BLOCK / MSK_WAVE   (msk_gpu.hip asserts both against msk_kernels.h)
+constexpr size_t kDoneQueueBytes = kWavesPerBlock * 320 * 16;     // the waves' done-queues of k_shade_gen: MSK_DONE_Q_F4 float4 per wave
+constexpr size_t kLdsLimit = 64 * 1024;
+
+inline uint32_t env_u32(const char *name, uint32_t def) {
+    const char *v = getenv(name);
+    return v && *v ? (uint32_t) strtoul(v, nullptr, 10) : def;
+}
+// the same where the default depends on the scene: -1 = unset (or empty)
+inline long long env_opt(const char *name) {
+    const char *v = getenv(name);
+    return v && *v ? (long long) (uint32_t) strtoul(v, nullptr, 10) : -1;
+}
+
+// Every environment knob of the wavefront driver, read ONCE per render call by the calling thread and never kept between calls
+// (the tests set knobs between two renders of one process).  The knobs of scene creation, of the film replay, of the watchdog
+// (msk_watchdog.h) and of group contexts (msk_multi.h) are read where they are used.
+struct RenderKnobs {
+    long long regions = -1, region_size = -1;   // MSK_REGIONS, MSK_REGION_SIZE; -1 = unset: the default of the tree's place (pool_shape)
+    uint32_t streams = 4, stream_skew = 10;     // MSK_STREAMS, MSK_STREAM_SKEW (per cent)
+    uint32_t host_threads = 1;                  // MSK_HOST_THREADS
+    uint32_t sync_group = 8;                    // MSK_SYNC_GROUP
+    uint32_t timing_every = 1;                  // MSK_TIMING_EVERY (at least 1)
+    bool sort = true;                           // MSK_SORT
+    bool camera_cull = true;                    // MSK_CAMERA_CULL
+    bool force_general_shade = false;           // MSK_FORCE_GENERAL_SHADE
+    bool fused = false, fused_hbm = true;       // MSK_FUSED, MSK_FUSED_HBM
+    uint32_t fused_iters = 16;                  // MSK_FUSED_ITERS (at least 1)
+    long long fused_tail_pct = -1;              // MSK_FUSED_TAIL_PCT; -1 = unset: 2 with k_wavefront_h, else 10
+    int trace_refill = -1;                      // MSK_TRACE_REFILL; -1 = unset, which is NOT 0: only an unset knob leaves k_trace_q on
+    int trace_quantum = 3;                      // MSK_TRACE_QUANTUM   (4 until round 5's better tree: 10.7 instead of 12.9 node visits per ray)
+    uint32_t trace_queue = 32;                  // MSK_TRACE_QUEUE (at most 64)
+    uint32_t trace_split = 2;                   // MSK_TRACE_SPLIT (at least 1)
+    size_t trace_pad_lds = 0, shade_pad_lds = 0;     // MSK_TRACE_PAD_LDS_KB, MSK_SHADE_PAD_LDS_KB, in bytes: occupancy experiments only
+    const char *dump_rays = nullptr;            // MSK_DUMP_RAYS (measurements only: dump_rays in msk_gpu.hip)
+    uint32_t dump_iter = 12, dump_stride = 32;  // MSK_DUMP_ITER, MSK_DUMP_STRIDE (at least 1)
+};
+
+inline RenderKnobs read_render_knobs() {
+    RenderKnobs k;
+    k.regions = env_opt("MSK_REGIONS"); k.region_size = env_opt("MSK_REGION_SIZE");
+    k.streams = env_u32("MSK_STREAMS", 4); k.stream_skew = env_u32("MSK_STREAM_SKEW", 10);
+    k.host_threads = env_u32("MSK_HOST_THREADS", 1);
+    k.sync_group = env_u32("MSK_SYNC_GROUP", 8);
+    k.timing_every = std::max(1u, env_u32("MSK_TIMING_EVERY", 1));
+    k.sort = env_u32("MSK_SORT", 1) != 0;
+    k.camera_cull = env_u32("MSK_CAMERA_CULL", 1) != 0;
+    k.force_general_shade = env_u32("MSK_FORCE_GENERAL_SHADE", 0) != 0;
+    k.fused = env_u32("MSK_FUSED", 0) != 0; k.fused_hbm = env_u32("MSK_FUSED_HBM", 1) != 0;
+    k.fused_iters = std::max(1u, env_u32("MSK_FUSED_ITERS", 16));
+    k.fused_tail_pct = env_opt("MSK_FUSED_TAIL_PCT");
+    k.trace_refill = getenv("MSK_TRACE_REFILL") ? atoi(getenv("MSK_TRACE_REFILL")) : -1;
+    k.trace_quantum = (int) env_u32("MSK_TRACE_QUANTUM", 3);
+    k.trace_queue = std::min(64u, env_u32("MSK_TRACE_QUEUE", 32));
+    k.trace_split = std::max(1u, env_u32("MSK_TRACE_SPLIT", 2));
+    k.trace_pad_lds = (size_t) env_u32("MSK_TRACE_PAD_LDS_KB", 0) * 1024; k.shade_pad_lds = (size_t) env_u32("MSK_SHADE_PAD_LDS_KB", 0) * 1024;
+    k.dump_rays = getenv("MSK_DUMP_RAYS");
+    k.dump_iter = env_u32("MSK_DUMP_ITER", 12); k.dump_stride = std::max(1u, env_u32("MSK_DUMP_STRIDE", 32));
+    return k;
+}
+
+// Short rays (LDS-resident scene): many small regions, one chunk loop per wave: 8192 x 512 = 4 M path slots (0.6 GB of state;
+// measured 16384 / 12288 / 8192 / 6144 regions: 42.7 / 41.7 / 41.2 / 41.6 ms for the bench step — the shading kernel streams the
+// whole pool's state every iteration and a smaller pool keeps more of it in the 256 MB Infinity Cache, the traversal kernel
+// wants many waves per launch).  Long rays (k_trace_r): 4096 regions of 2048 slots = 8 M, so that lane replacement has a long
+// list of rays to keep the lanes busy with.
+inline void pool_shape(int trace_mode, uint64_t total_samples, const RenderKnobs &knobs, uint32_t *region_size, uint32_t *n_regions) {
+    const bool big = tree_in_hbm(trace_mode);
+    // trees in HBM: one traversal wave per region at 5 waves per SIMD = 5120 resident waves; with 4096 regions the four loops'
+    // launches never filled the GPU (8192 regions: config-5-class render 173 vs 191 ms, config-3-class 205 vs 227 ms)
+    // LDS-resident scenes: 6144 x 1024 (with the state's cache policy in place — msk_kernels.h, MSK_NT — fewer, longer regions
+    // win over round 1's 8192 x 512: 36.2 vs 37.0 ms per bench step; 5120 … 8192 x 896 … 1280 are within 1 % of each other)
+    uint32_t rs = knobs.region_size >= 0 ? (uint32_t) knobs.region_size : (big ? 2048u : 1024u), nr = knobs.regions >= 0 ? (uint32_t) knobs.regions : (big ? 8192u : 6144u);
+    rs = std::max(64u, (rs + 63u) & ~63u);
+    while (rs > 256 && total_samples / rs < nr) rs = std::max(256u, rs / 2);       // small jobs: keep the GPU full first
+    const uint64_t need = (total_samples + rs - 1) / rs;
+    if (need < nr) nr = (uint32_t) std::max<uint64_t>(need, 1);
+    nr = (nr + 3u) & ~3u;
+    *region_size = rs; *n_regions = nr;
+}
+
+struct SceneFacts {
+    int trace_mode = 0;
+    bool lds_scene = false, lds_tables = false, all_diffuse = true, has_regular = false, has_dielectric = false, cull_ok = false;
+    size_t trace_lds_bytes = 0, shade_lds_bytes = 0;
+};
+struct CallFacts {
+    uint32_t region_size = 0;
+    uint32_t aov_groups = 0;      // an "aov" render's primary-hit record groups
+    bool aov_rgb = false;         // ... and its nested path integrator's RGB record
+};
+
+enum TraceFamily : int {
+    TRACE_FAMILY_R,        // k_trace_r<mode>: lane replacement, both rays of a slot walked together
+    TRACE_FAMILY_Q,        // k_trace_q: the LDS-resident scene's job queues
+    TRACE_FAMILY_PLAIN     // k_trace<mode>: the chunk loop
+};
+
+enum ShadeKind : int {     // in the order they are tried: a dielectric scene is never diffuse_only, a diffuse_only sweep evaluates no table
+    SHADE_DIELECTRIC,      // k_shade_gen_d<lds_tables>;                k_wavefront_d / k_wavefront_h_d
+    SHADE_DIFFUSE,         // k_shade_gen<lds_tables, true>;            k_wavefront<true> / k_wavefront_h<true>
+    SHADE_REGULAR,         // k_shade_gen<lds_tables, false, true>;     k_wavefront<false, true> / k_wavefront_h<false, true>
+    SHADE_GENERAL          // k_shade_gen<lds_tables, false>;           k_wavefront<false> / k_wavefront_h<false>
+};
+
+struct LaunchPlan {
+    // shading: the scene's and the call's flags, and the instantiation they select (shade_kind, also the fused kernels')
+    bool lds_tables = false, diffuse_only = false, regular = false, dielectric = false;
+    ShadeKind shade_kind = SHADE_GENERAL;
+    bool sort_on = false;              // PassParams::sort_scratch: material-sorted shading
+    size_t shade_lds_bytes = 0;        // tables + done-queues + the sort's permutation + MSK_SHADE_PAD_LDS_KB
+    // traversal
+    TraceFamily trace_family = TRACE_FAMILY_PLAIN;
+    int trace_mode = 0;
+    int refill = 0, max_inner = 3;     // k_trace_r's arguments
+    uint32_t queue_refill = 0;         // k_trace_q's
+    size_t trace_lds_bytes = 0;        // of the family that runs (k_trace_q: + one bit per slot and wave, from bits_off on)
+    size_t bits_off = 0;               // k_trace_q: byte offset of those bits
+    uint32_t trace_waves = 1;          // waves per region of the launch's grid
+    uint32_t trace_split = 1;          // PassParams::trace_split
+    bool lane_refill = false;          // msk_stats::bytes_trace: 16 B per shadow ray instead of 32
+    // the fused kernels (k_wavefront*, iterations on the device)
+    bool fused_ok = false, fused_h = false, fused_all = false;
+    uint32_t fused_iters = 16, fused_tail_pct = 0;
+    size_t fused_lds_bytes = 0;
+    uint32_t fused_queue_f4 = 0, fused_trace_f4 = 0;       // float4 offsets of the done-queues (after the staged tables) and of the traversal's LDS
+    // the loop
+    bool cull = false;                 // PassParams::cull
+    uint32_t sync_group = 8, timing_every = 1;
+};
+
+inline LaunchPlan make_launch_plan(const SceneFacts &sc, const CallFacts &call, const RenderKnobs &knobs) {
+    LaunchPlan p;
+    const bool aov_any = call.aov_rgb || call.aov_groups;
+    // camera samples that miss the scene's bounds are finished where they are made (shade_region's regeneration) — unless a miss
+    // is more than a record of zeros: an "aov" render's record groups and nested RGB record are written per sample by other code
+    p.cull = sc.cull_ok && !aov_any && knobs.camera_cull;
+    // (MSK_FORCE_GENERAL_SHADE=1, measurements only: an all-diffuse scene through the general variant — what a per-class diffuse
+    // instantiation could save a mixed scene's diffuse chunks)
+    // (the AOV RGB record and the validity test over an "aov" render's record groups live in the general shading variant)
+    p.lds_tables = sc.lds_tables; p.regular = sc.has_regular; p.dielectric = sc.has_dielectric;
+    p.diffuse_only = sc.all_diffuse && !aov_any && !knobs.force_general_shade;
+    p.shade_kind = p.dielectric ? SHADE_DIELECTRIC : p.diffuse_only ? SHADE_DIFFUSE : p.regular ? SHADE_REGULAR : SHADE_GENERAL;
+    // material-sorted shading (general variant): LDS for the permutation, 3 bytes per slot of a region and wave (MSK_SORT=0: off)
+    const size_t sort_lds = kWavesPerBlock * 3 * call.region_size;
+    p.sort_on = !p.diffuse_only && (!sc.all_diffuse || knobs.force_general_shade) && call.region_size <= 4096 && knobs.sort &&
+                sc.shade_lds_bytes + sort_lds <= kLdsLimit;
+    p.shade_lds_bytes = sc.shade_lds_bytes + (p.sort_on ? sort_lds : 0) + knobs.shade_pad_lds;
+
+    // Lane replacement pays when rays are long (tree in HBM/L2: trace -35 % on the 70 k-triangle scene) and costs when they
+    // are short (LDS-resident cbox: +50 %): on by default for trees in HBM only.  MSK_TRACE_REFILL=0 turns it off.
+    p.trace_mode = sc.trace_mode;
+    p.refill = sc.trace_mode == TRACE_WIDE4_LDS ? 0 : knobs.trace_refill >= 0 ? knobs.trace_refill : (sc.trace_mode == TRACE_BIN_LDS ? 0 : 16);
+    p.max_inner = knobs.trace_quantum;
+    p.trace_split = sc.trace_mode == TRACE_BIN_LDS ? knobs.trace_split : 1u;
+    const size_t lds = sc.trace_lds_bytes + knobs.trace_pad_lds;
+    // LDS-resident scenes: k_trace_q (job queues with lane replacement, refill when 32 lanes are idle); MSK_TRACE_QUEUE=0: k_trace<0>
+    p.queue_refill = knobs.trace_refill >= 0 ? 0u : knobs.trace_queue;
+    p.bits_off = (lds + 15) & ~(size_t) 15;
+    const size_t lds_q = p.bits_off + kWavesPerBlock * (call.region_size / 8);       // + one bit per slot and wave
+    p.trace_lds_bytes = lds;
+    if (p.refill > 0) p.trace_family = TRACE_FAMILY_R;
+    else if (sc.trace_mode == TRACE_BIN_LDS && p.queue_refill && sc.lds_scene && lds_q <= kLdsLimit) { p.trace_family = TRACE_FAMILY_Q; p.trace_lds_bytes = lds_q; }
+    else p.trace_family = TRACE_FAMILY_PLAIN;
+    // k_trace_q and k_trace<0>: trace_split waves per region (LDS-resident scene: no stack overflow array to size).
+    // Measured: 2 waves per region -6 % trace on the cbox (twice the waves to balance the tail of a launch), 4 the same.
+    p.trace_waves = p.trace_family != TRACE_FAMILY_R && sc.trace_mode == TRACE_BIN_LDS ? p.trace_split : 1u;
+    // (a scene in LDS that MSK_TRACE_REFILL forces onto k_trace_r<0> is still counted at 32 B per shadow ray: bench.py and the
+    // tests compare msk_stats::bytes_trace between builds)
+    p.lane_refill = p.refill > 0 && sc.trace_mode != TRACE_BIN_LDS;
+
+    // k_wavefront (iterations on the device): possible when tables and tree are LDS-resident and everything fits one block's LDS
+    // next to each other, and there is no per-iteration AOV kernel.  MSK_FUSED=1: the whole pass; MSK_FUSED_TAIL_PCT=p: from
+    // the point where every sample has been started and fewer than p % of the slots are live.
+    p.fused_queue_f4 = (uint32_t) ((sc.shade_lds_bytes - kDoneQueueBytes) / 16);
+    p.fused_trace_f4 = (uint32_t) (sc.shade_lds_bytes / 16);
+    p.fused_lds_bytes = sc.shade_lds_bytes + sc.trace_lds_bytes;
+    // ... and k_wavefront_h for the default tree in HBM (trace mode 6): the VERY thin end only (MSK_FUSED_HBM=0: off).  Round 6, same
+    // box, config-5 / config-3 class renders: from 10 % live slots on (the LDS-resident scenes' threshold) 117.9 / 137.1 ms against
+    // 116.2 / 138.6 without — a wave's own longest rays bound both, and the fused kernel walks them at two waves per SIMD without lane
+    // replacement; from 1-3 % on — the ~40 last iterations, whose launches are a few dozen microseconds of latency each —
+    // 118.1-118.2 / 143.9-144.2 ms against 119.2 / 146.2 (profiles/r06_ab_fused_hbm.txt): the default, at 2 %.
+    p.fused_h = sc.trace_mode == TRACE_WIDE4_HALF && !sc.lds_tables && knobs.fused_hbm;
+    p.fused_ok = ((sc.trace_mode == TRACE_BIN_LDS && sc.lds_tables) || p.fused_h) && p.fused_lds_bytes <= kLdsLimit && !call.aov_groups;
+    p.fused_all = p.fused_ok && knobs.fused;
+    p.fused_iters = knobs.fused_iters;
+    p.fused_tail_pct = p.fused_ok ? (knobs.fused_tail_pct >= 0 ? (uint32_t) knobs.fused_tail_pct : (p.fused_h ? 2u : 10u)) : 0u;
+
+    p.sync_group = knobs.sync_group; p.timing_every = knobs.timing_every;
+    return p;
+}
+
+// The static, interleaved partition of a pass's samples over the regions (RegionCtl): chunks of 64 samples dealt round robin,
+// the last chunk partial.  The regions' initial records and what a part of the pool expects to finish both come from here.
+inline unsigned long long region_share(unsigned long long total, uint32_t n_regions, uint32_t r) {
+    const unsigned long long n_chunks = (total + 63) / 64;
+    const unsigned long long mine = n_chunks > r ? (n_chunks - r + n_regions - 1) / n_regions : 0;
+    unsigned long long n = mine * 64;
+    if (mine && (mine - 1) * n_regions + r == n_chunks - 1) n -= n_chunks * 64 - total;   // partial last chunk
+    return n;
+}
+
+// Cuts the pool's regions into n_parts consecutive parts; part k is [out[k], out[k + 1]).  Parts of slightly different sizes:
+// equal parts can fall into step (all launches starting and draining together, which is one big launch again; measured as a
+// bimodal 48 / 52 ms), unequal ones keep sliding past each other.  skew_pct: relative size step between neighbouring parts.
+inline std::vector<uint32_t> part_ranges(uint32_t n_regions, uint32_t n_parts, uint32_t skew_pct) {
+    const double skew = skew_pct / 100.0;
+    std::vector<double> cum(n_parts + 1, 0.0);
+    for (uint32_t k = 0; k < n_parts; ++k) cum[k + 1] = cum[k] + 1.0 + skew * ((double) (n_parts - 1) / 2.0 - k);
+    std::vector<uint32_t> out(n_parts + 1, n_regions);
+    for (uint32_t k = 0; k < n_parts; ++k) out[k] = (uint32_t) (n_regions * (cum[k] / cum[n_parts]));
+    return out;
+}
+
+}  // namespace mskplan
