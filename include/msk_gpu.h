@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define MSK_ABI_VERSION 7
+#define MSK_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------- */
 #define MSK_OK                 0
@@ -59,6 +59,8 @@ extern "C" {
 #define MSK_BSDF_DIELECTRIC     3  /* "dielectric"     bsdfs/dielectric.cpp:105 (smooth interface: two delta lobes) */
 #define MSK_EMITTER_AREA       0   /* "area"     emitters/area.cpp:61          */
 #define MSK_TEXTURE_CHECKERBOARD 1 /* "checkerboard" textures/checkerboard.cpp:52 */
+#define MSK_TEXTURE_BITMAP       2 /* "bitmap", bilinear filter (ABI v8; semantics below, at msk_texture_desc) */
+#define MSK_TEXTURE_BITMAP_NEAREST 3 /* "bitmap", nearest-texel filter                                        */
 
 #define MSK_EMITTER_CONSTANT   1   /* "constant" emitters/constant.cpp:95 (environment; mesh_id = -1, at most one) */
 
@@ -171,13 +173,26 @@ typedef struct msk_bsdf_desc {
  * color1.  color0 / color1 are sigmoid-polynomial coefficients of two constant `srgb` spectra (nested
  * textures other than that are not flattened).  si.uv = the interpolated vertex texcoords, or the
  * hit's barycentrics for a mesh without them (mesh.cpp:66,68-72).
+ *
+ * MSK_TEXTURE_BITMAP / MSK_TEXTURE_BITMAP_NEAREST (ABI v8): an image of width x height texels, texels[first_texel ..] of the
+ * scene, row-major, row 0 first; a texel holds the three sigmoid-polynomial coefficients srgb_model_fetch() returned for its
+ * linear-sRGB colour (components clamped to [0, 1] first: a reflectance).  Texel row j covers v in [j/H, (j+1)/H), column i
+ * covers u in [i/W, (i+1)/W).  (The reference's textures/bitmap.cpp is RGB-typed and not built; this is its lookup in the
+ * spectral form.)  With uv' as above, fu = uv'.x - floor(uv'.x) (wrap = repeat; fu can be exactly 1 for a tiny negative uv'.x),
+ * all in fp32, one operation at a time:
+ *   nearest:  i = min((int) (fu * W), W - 1), j likewise; value(l) = S(texel[j][i], l)
+ *   bilinear: px = fu * W - 0.5; i0 = (int) floor(px); tx = px - i0; i0 < 0 -> W - 1; i0 >= W -> 0; i1 = i0 + 1, i1 >= W -> 0
+ *             (the same in y); s00 .. s11 = S(texel[j0|j1][i0|i1], l); a = s00 + tx (s10 - s00); b = s01 + tx (s11 - s01);
+ *             value = a + ty (b - a): spectral VALUES are interpolated, not coefficients.
+ * color0 / color1 are ignored for a bitmap.
  */
 typedef struct msk_texture_desc {
     int32_t type;
     float   color0[3];
     float   color1[3];
     float   to_uv[6];        /* m00 m01 m02 / m10 m11 m12 */
-    float   reserved[3];
+    uint32_t width, height;  /* bitmap: texels per row, rows (>= 1)                             */
+    uint32_t first_texel;    /* bitmap: offset into msk_scene_desc.texels, in texels            */
 } msk_texture_desc;
 
 /*
@@ -242,6 +257,9 @@ typedef struct msk_scene_desc {
     uint32_t n_regular_spectra, n_regular_values;
     const msk_regular_spectrum_desc *regular_spectra;
     const float *regular_values;
+    /* ABI v8: the texel pool of the bitmap textures (may be 0 / NULL) */
+    uint32_t n_texels;
+    const float *texels;        /* n_texels * 3 coefficients, a bitmap's texels row-major, row 0 first */
 } msk_scene_desc;
 
 /*
@@ -386,6 +404,13 @@ int  msk_gpu_trace_any(msk_scene *scene, uint64_t n, const float *rays, uint8_t 
 int  msk_gpu_sample_pixels(msk_scene *scene, const msk_render_params *params,
                            uint64_t n_pixels, const int32_t *pixels,
                            float *out_xyz, float *out_pos);
+
+/*
+ * A texture's value at n surface points (SmoothDiffuse::m_reflectance->eval(si) for given si.uv): uv n * 2 floats,
+ * wavelengths n * 4, out n * 4 floats; texture is 1-based, as msk_bsdf_desc::reflectance_texture.  The kernel calls the
+ * device function the shading kernels call, for checkerboards as for bitmaps.  Host pointers.  ABI v8.
+ */
+int  msk_gpu_eval_texture(msk_scene *scene, uint32_t texture, uint64_t n, const float *uv, const float *wavelengths, float *out);
 
 /* device + build information for logs: fills a NUL-terminated string */
 int  msk_gpu_describe(const msk_ctx *ctx, char *buf, uint64_t buf_size);

@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-MSK_ABI_VERSION = 7
+MSK_ABI_VERSION = 8
 MSK_REGULAR_MAX = 95
 MSK_OK = 0
 MSK_ERR_INVALID_ARG, MSK_ERR_NO_DEVICE, MSK_ERR_HIP, MSK_ERR_OOM, MSK_ERR_UNSUPPORTED = -1, -2, -3, -4, -5
@@ -19,6 +19,7 @@ MSK_BSDF_DIFFUSE, MSK_BSDF_ROUGHCONDUCTOR, MSK_BSDF_ROUGHDIELECTRIC = 0, 1, 2
 MSK_BSDF_DIELECTRIC = 3       # "dielectric" (bsdfs/dielectric.cpp): smooth interface, two delta lobes
 MSK_EMITTER_AREA, MSK_EMITTER_CONSTANT = 0, 1
 MSK_TEXTURE_CHECKERBOARD = 1
+MSK_TEXTURE_BITMAP, MSK_TEXTURE_BITMAP_NEAREST = 2, 3       # "bitmap": bilinear / nearest (ABI v8)
 MSK_EMITTER_AREA = 0
 MSK_RNG_PCG_BLOCK, MSK_RNG_COUNTER = 0, 1
 MSK_CIE_SAMPLES = 95
@@ -50,7 +51,7 @@ class BsdfDesc(C.Structure):
 
 class TextureDesc(C.Structure):
     _fields_ = [("type", C.c_int32), ("color0", C.c_float * 3), ("color1", C.c_float * 3), ("to_uv", C.c_float * 6),
-                ("reserved", C.c_float * 3)]
+                ("width", C.c_uint32), ("height", C.c_uint32), ("first_texel", C.c_uint32)]      # a bitmap's place in SceneDesc.texels
 
 
 class EmitterDesc(C.Structure):
@@ -80,7 +81,8 @@ class SceneDesc(C.Structure):
                 ("cie1931_xyz", C.POINTER(C.c_float)), ("d65", C.POINTER(C.c_float)),
                 ("n_textures", C.c_uint32), ("textures", C.POINTER(TextureDesc)),
                 ("n_regular_spectra", C.c_uint32), ("n_regular_values", C.c_uint32),
-                ("regular_spectra", C.POINTER(RegularSpectrumDesc)), ("regular_values", C.POINTER(C.c_float))]
+                ("regular_spectra", C.POINTER(RegularSpectrumDesc)), ("regular_values", C.POINTER(C.c_float)),
+                ("n_texels", C.c_uint32), ("texels", C.POINTER(C.c_float))]      # ABI v8: 3 coefficients per texel
 
 
 class RenderParams(C.Structure):
@@ -124,7 +126,8 @@ LIB_PATH = os.environ.get("MSK_GPU_LIB") or os.path.join(_PKG_DIR, "lib", "libms
 # every symbol include/msk_gpu.h declares
 EXPORTS = ["msk_gpu_init", "msk_gpu_shutdown", "msk_gpu_last_error", "msk_gpu_scene_create",
            "msk_gpu_scene_destroy", "msk_gpu_render", "msk_gpu_render_device", "msk_gpu_trace_closest",
-           "msk_gpu_trace_any", "msk_gpu_sample_pixels", "msk_gpu_describe", "msk_gpu_render_aov", "msk_gpu_aov_channels"]
+           "msk_gpu_trace_any", "msk_gpu_sample_pixels", "msk_gpu_describe", "msk_gpu_render_aov", "msk_gpu_aov_channels",
+           "msk_gpu_eval_texture"]
 
 # integrators/aov.cpp:21-28
 MSK_AOV_DEPTH, MSK_AOV_POSITION, MSK_AOV_UV, MSK_AOV_GEO_NORMAL, MSK_AOV_SH_NORMAL, MSK_AOV_PATH_RGBA = range(6)
@@ -169,6 +172,8 @@ def load_library(path=None):
     lib.msk_gpu_render_aov.restype = C.c_int
     lib.msk_gpu_aov_channels.argtypes = [vp, C.c_uint32]
     lib.msk_gpu_aov_channels.restype = C.c_uint32
+    lib.msk_gpu_eval_texture.argtypes = [vp, C.c_uint32, u64, vp, vp, vp]
+    lib.msk_gpu_eval_texture.restype = C.c_int
     lib.msk_gpu_describe.argtypes = [vp, C.c_char_p, u64]
     lib.msk_gpu_describe.restype = C.c_int
     if path is None:
@@ -283,6 +288,17 @@ class Scene:
         self.ctx.check(self.ctx.lib.msk_gpu_sample_pixels(self.handle, C.byref(params), n, _ptr(pixels),
                                                            _ptr(xyz), _ptr(pos)))
         return xyz, pos
+
+    def eval_texture(self, texture, uv, wavelengths):
+        """The value of texture `texture` (1-based, as BsdfDesc.reflectance_texture) at uv float32[n, 2] and wavelengths
+        float32[n, 4] -> float32[n, 4]: what the shading kernels evaluate at a hit with that si.uv."""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        wl = np.ascontiguousarray(wavelengths, np.float32).reshape(-1, 4)
+        if len(uv) != len(wl):
+            raise ValueError("uv and wavelengths must name the same number of points")
+        out = np.empty((len(uv), 4), np.float32)
+        self.ctx.check(self.ctx.lib.msk_gpu_eval_texture(self.handle, int(texture), len(uv), _ptr(uv), _ptr(wl), _ptr(out)))
+        return out
 
     def close(self):
         if self.handle:

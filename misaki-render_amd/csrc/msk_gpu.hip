@@ -110,9 +110,11 @@ struct msk_scene {
     void *group_host_film = nullptr; size_t group_host_film_bytes = 0;      // pinned staging of a group's copy-back (film_to_host)
     Workspace *ws = nullptr;           // render buffers, kept between calls (hipMalloc/hipFree of GBs costs milliseconds)
     DeviceScene dev;
-    DevBuf nodes, nodes4, nodes4q, nodes8, tris, tris3, tri_bounds, tri_verts, tri_frames, tri_normals, tri_uvs, mesh_info, bsdfs, emitters, emitter_d65, emitter_grid, spectra, cdf, cie;
+    DevBuf nodes, nodes4, nodes4q, nodes8, tris, tris3, tri_bounds, tri_verts, tri_frames, tri_normals, tri_uvs, mesh_info, bsdfs, emitters, emitter_d65, emitter_grid, spectra, texels, cdf, cie;
     bool lds_scene = false, lds_tables = false, all_diffuse = true;
     bool has_dielectric = false;       // the scene holds a smooth `dielectric`: the instantiations with its delta lobes run (k_shade_gen_d, ...)
+    bool has_bitmap = false;           // the scene holds a `bitmap` texture (ABI v8): the instantiations with the texel lookup run (k_shade_gen_b, ...)
+    uint32_t n_textures = 0, tex_base = 0;      // msk_gpu_eval_texture: texture k's record sits at float4 tex_base + 3 k of `bsdfs`
     bool has_regular = false;          // the scene holds tabulated spectra (ABI v7): the shading instantiations that evaluate them run
     int trace_mode = 0;                // mskplan::TraceMode (msk_plan.h): which tree the traversal kernels walk, and where it lives
     size_t trace_lds_bytes = 0, shade_lds_bytes = 0;
@@ -369,11 +371,30 @@ extern "C" int msk_gpu_scene_create(msk_ctx *ctx, const msk_scene_desc *d, msk_s
     if (d->n_textures && !d->textures) return fail(ctx, MSK_ERR_INVALID_ARG, "msk_gpu_scene_create: texture array missing");
     const uint32_t n_bsdf_f4 = std::max(1u, d->n_bsdfs) * MSK_BSDF_F4 + d->n_textures * 3;
     std::vector<float> bsdfs((size_t) n_bsdf_f4 * 4, 0.f);
+    bool any_bitmap = false;
     for (uint32_t t = 0; t < d->n_textures; ++t) {
         const msk_texture_desc &td = d->textures[t];
-        if (td.type != MSK_TEXTURE_CHECKERBOARD)
-            return fail(ctx, MSK_ERR_UNSUPPORTED, "texture %u: type %d is not supported by this back end (checkerboard)", t, td.type);
+        if (td.type != MSK_TEXTURE_CHECKERBOARD && td.type != MSK_TEXTURE_BITMAP && td.type != MSK_TEXTURE_BITMAP_NEAREST)
+            return fail(ctx, MSK_ERR_UNSUPPORTED, "texture %u: type %d is not supported by this back end (checkerboard, bitmap)", t, td.type);
         float *o = &bsdfs[((size_t) std::max(1u, d->n_bsdfs) * MSK_BSDF_F4 + (size_t) t * 3) * 4];
+        if (td.type != MSK_TEXTURE_CHECKERBOARD) {
+            if (td.width < 1 || td.height < 1)
+                return fail(ctx, MSK_ERR_INVALID_ARG, "texture %u: a bitmap of %u x %u texels (width and height must be at least 1)", t, td.width, td.height);
+            if ((uint64_t) td.first_texel + (uint64_t) td.width * td.height > d->n_texels)
+                return fail(ctx, MSK_ERR_INVALID_ARG, "texture %u: texels %u + %u x %u reach past the scene's n_texels %u", t, td.first_texel, td.width,
+                            td.height, d->n_texels);
+            if (!d->texels) return fail(ctx, MSK_ERR_INVALID_ARG, "texture %u: a bitmap, but the scene's texels array is missing", t);
+            const size_t n = (size_t) td.width * td.height * 3;
+            for (size_t k = 0; k < n; ++k)
+                if (std::isnan(d->texels[(size_t) td.first_texel * 3 + k]))
+                    return fail(ctx, MSK_ERR_INVALID_ARG, "texture %u: texel %zu holds a NaN coefficient", t, k / 3);
+            const uint32_t w[3] = {td.first_texel, td.width, td.height}, ty = (uint32_t) td.type;
+            std::memcpy(&o[0], w, 12); o[3] = td.to_uv[2];
+            std::memcpy(&o[4], &ty, 4); o[5] = 0.f; o[6] = 0.f; o[7] = td.to_uv[5];
+            o[8] = td.to_uv[0]; o[9] = td.to_uv[1]; o[10] = td.to_uv[3]; o[11] = td.to_uv[4];
+            any_bitmap = true;
+            continue;
+        }
         o[0] = td.color0[0]; o[1] = td.color0[1]; o[2] = td.color0[2]; o[3] = td.to_uv[2];
         o[4] = td.color1[0]; o[5] = td.color1[1]; o[6] = td.color1[2]; o[7] = td.to_uv[5];
         o[8] = td.to_uv[0]; o[9] = td.to_uv[1]; o[10] = td.to_uv[3]; o[11] = td.to_uv[4];
@@ -514,7 +535,8 @@ extern "C" int msk_gpu_scene_create(msk_ctx *ctx, const msk_scene_desc *d, msk_s
         }
 
     msk_scene *s = new msk_scene();
-    s->ctx = ctx; s->n_tris = d->n_faces; s->bvh_depth = bvh.max_depth; s->all_diffuse = all_diffuse; s->has_regular = any_regular; s->has_dielectric = any_dielectric;
+    s->ctx = ctx; s->n_tris = d->n_faces; s->bvh_depth = bvh.max_depth; s->all_diffuse = all_diffuse; s->has_regular = any_regular; s->has_dielectric = any_dielectric; s->has_bitmap = any_bitmap;
+    s->n_textures = d->n_textures; s->tex_base = std::max(1u, d->n_bsdfs) * MSK_BSDF_F4;
     std::vector<float> cie(d->cie1931_xyz, d->cie1931_xyz + 3 * MSK_CIE_SAMPLES);
     hipError_t e = hipSuccess;
     auto up = [&](DevBuf &b, const std::vector<float> &v) { if (e == hipSuccess) e = b.upload(v); };
@@ -522,6 +544,11 @@ extern "C" int msk_gpu_scene_create(msk_ctx *ctx, const msk_scene_desc *d, msk_s
     up(s->tri_verts, tv); up(s->tri_normals, tn); up(s->tri_uvs, tuv);
     up(s->bsdfs, bsdfs); up(s->emitters, emitters); up(s->emitter_d65, d65); up(s->cdf, cdf_all); up(s->cie, cie);
     up(s->emitter_grid, emitter_grid); up(s->spectra, spectra_pool);
+    if (any_bitmap) {      // one float4 per texel: a lookup is one 16-byte load per texel
+        std::vector<float> tx4((size_t) d->n_texels * 4, 0.f);
+        for (size_t k = 0; k < d->n_texels; ++k) { tx4[k * 4] = d->texels[k * 3]; tx4[k * 4 + 1] = d->texels[k * 3 + 1]; tx4[k * 4 + 2] = d->texels[k * 3 + 2]; }
+        up(s->texels, tx4);
+    }
     if (e == hipSuccess) e = s->mesh_info.upload(mesh_info);
     if (e == hipSuccess && gpu_build) {
         const size_t nf = d->n_faces;
@@ -559,6 +586,7 @@ extern "C" int msk_gpu_scene_create(msk_ctx *ctx, const msk_scene_desc *d, msk_s
     ds.mesh_info = s->mesh_info.as<int4>(); ds.bsdfs = s->bsdfs.as<float4>(); ds.emitters = s->emitters.as<float4>();
     ds.emitter_d65 = s->emitter_d65.as<float>(); ds.cdf = s->cdf.as<float>(); ds.cie = s->cie.as<float>();
     ds.emitter_grid = s->emitter_grid.as<float4>(); ds.spectra = s->spectra.as<float>(); ds.n_spectra = d->n_regular_values;
+    ds.texels = any_bitmap ? s->texels.as<float4>() : nullptr;
     ds.n_nodes = (uint32_t) (bvh.nodes.size() / 16); ds.n_tris = d->n_faces; ds.n_emitters = d->n_emitters;
     ds.n_meshes = d->n_meshes; ds.n_bsdfs = d->n_bsdfs; ds.n_bsdf_f4 = n_bsdf_f4; ds.cdf_len = (uint32_t) cdf_all.size();
     ds.root_ref = bvh.root_ref;
@@ -869,6 +897,7 @@ static void launch_shade_t(const msk_scene *sc, const mskplan::LaunchPlan &plan,
     case mskplan::SHADE_DIFFUSE: MSK_SHADE(k_shade_gen<LDS_TABLES, true>); break;
     case mskplan::SHADE_REGULAR: MSK_SHADE(k_shade_gen<LDS_TABLES, false, true>); break;
     case mskplan::SHADE_GENERAL: MSK_SHADE(k_shade_gen<LDS_TABLES, false>); break;
+    case mskplan::SHADE_BITMAP: MSK_SHADE(k_shade_gen_b<LDS_TABLES>); break;
     }
 #undef MSK_SHADE
 }
@@ -887,12 +916,14 @@ static void launch_fused(const msk_scene *sc, const mskplan::LaunchPlan &plan, d
     case mskplan::SHADE_DIFFUSE: MSK_FUSED(k_wavefront_h<true>); break;
     case mskplan::SHADE_REGULAR: MSK_FUSED(k_wavefront_h<false, true>); break;
     case mskplan::SHADE_GENERAL: MSK_FUSED(k_wavefront_h<false>); break;
+    case mskplan::SHADE_BITMAP: MSK_FUSED(k_wavefront_h_b); break;
     }
     else switch (plan.shade_kind) {                   // everything in LDS (trace mode 0)
     case mskplan::SHADE_DIELECTRIC: MSK_FUSED(k_wavefront_d); break;
     case mskplan::SHADE_DIFFUSE: MSK_FUSED(k_wavefront<true>); break;
     case mskplan::SHADE_REGULAR: MSK_FUSED(k_wavefront<false, true>); break;
     case mskplan::SHADE_GENERAL: MSK_FUSED(k_wavefront<false>); break;
+    case mskplan::SHADE_BITMAP: MSK_FUSED(k_wavefront_b); break;
     }
 #undef MSK_FUSED
 }
@@ -1151,7 +1182,7 @@ static PassParams pass_params(const msk_render_params *prm, uint32_t spp_owned, 
 static mskplan::SceneFacts scene_facts(const msk_scene *sc) {
     mskplan::SceneFacts f;
     f.trace_mode = sc->trace_mode; f.lds_scene = sc->lds_scene; f.lds_tables = sc->lds_tables; f.all_diffuse = sc->all_diffuse;
-    f.has_regular = sc->has_regular; f.has_dielectric = sc->has_dielectric; f.cull_ok = sc->cull_ok;
+    f.has_regular = sc->has_regular; f.has_dielectric = sc->has_dielectric; f.has_bitmap = sc->has_bitmap; f.cull_ok = sc->cull_ok;
     f.trace_lds_bytes = sc->trace_lds_bytes; f.shade_lds_bytes = sc->shade_lds_bytes;
     return f;
 }
@@ -1330,7 +1361,8 @@ static int render_serial(msk_scene *sc, const msk_render_params *prm, float *d_f
         sp.blocks = ws.blocks.as<BlockInfo>(); sp.n_blocks = (uint32_t) owned.size();
         sp.block_buf = ws.block_buf.as<float>(); sp.buf_stride = buf_stride;
         sp.stack_ovf = ovf.as<uint32_t>(); sp.counters = counters.as<unsigned long long>(); sp.per_wave = per_wave ? 1u : 0u;
-        if (sc->has_dielectric) hipLaunchKernelGGL(k_path_serial_d, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
+        if (sc->has_bitmap) hipLaunchKernelGGL(k_path_serial_b, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
+        else if (sc->has_dielectric) hipLaunchKernelGGL(k_path_serial_d, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
         else hipLaunchKernelGGL(k_path_serial, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
     }
     FilmOut fo;
@@ -1742,6 +1774,31 @@ static int trace_batch(msk_scene *scene, uint64_t n, const float *rays, float *o
     if (int rcw = ctx_sync(ctx, ctx->stream, "k_trace_batch")) { d_rays.leak(); d_out.leak(); d_ovf.leak(); return rcw; }
     HIP_TRY(ctx, hipMemcpy(out_any ? (void *) out_any : (void *) out_hit, d_out.p, out_any ? n : n * 16, hipMemcpyDeviceToHost));
     return MSK_OK;
+}
+
+static int eval_texture(msk_scene *scene, uint32_t texture, uint64_t n, const float *uv, const float *wavelengths, float *out) {
+    msk_ctx *ctx = scene->ctx;
+    MSK_REFUSE_LOST(ctx);
+    if (texture < 1 || texture > scene->n_textures)
+        return fail(ctx, MSK_ERR_INVALID_ARG, "msk_gpu_eval_texture: texture %u out of range (1 .. %u)", texture, scene->n_textures);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n == 0) return MSK_OK;
+    DevBuf d_uv, d_wl, d_out;
+    HIP_TRY(ctx, d_uv.alloc(n * 8)); HIP_TRY(ctx, d_wl.alloc(n * 16)); HIP_TRY(ctx, d_out.alloc(n * 16));
+    HIP_TRY(ctx, hipMemcpy(d_uv.p, uv, n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(d_wl.p, wavelengths, n * 16, hipMemcpyHostToDevice));
+    const uint32_t grid = (uint32_t) std::min<uint64_t>((n + MSK_BLOCK - 1) / MSK_BLOCK, 4096);
+    hipLaunchKernelGGL(k_eval_texture, dim3(grid), dim3(MSK_BLOCK), 0, ctx->stream, scene->dev, scene->tex_base + (texture - 1) * 3, n,
+                       d_uv.as<float2>(), d_wl.as<float4>(), d_out.as<float4>());
+    HIP_TRY(ctx, hipGetLastError());
+    if (int rcw = ctx_sync(ctx, ctx->stream, "k_eval_texture")) { d_uv.leak(); d_wl.leak(); d_out.leak(); return rcw; }
+    HIP_TRY(ctx, hipMemcpy(out, d_out.p, n * 16, hipMemcpyDeviceToHost));
+    return MSK_OK;
+}
+extern "C" int msk_gpu_eval_texture(msk_scene *scene, uint32_t texture, uint64_t n, const float *uv, const float *wavelengths, float *out) {
+    if (!scene || (n && (!uv || !wavelengths || !out))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_eval_texture: NULL argument");
+    if (scene->ctx->group) { const int rc = eval_texture(scene->parts[0], texture, n, uv, wavelengths, out); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
+    return eval_texture(scene, texture, n, uv, wavelengths, out);
 }
 
 extern "C" int msk_gpu_trace_closest(msk_scene *scene, uint64_t n, const float *rays, float *out_hit) {

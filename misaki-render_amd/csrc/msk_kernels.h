@@ -66,7 +66,7 @@ struct DeviceScene {
     const int4 *mesh_info;      // {bsdf_id, emitter_id, flags(1=normals,2=texcoords), first_face}
     const float4 *bsdfs;        // MSK_BSDF_F4 x float4 per bsdf (BsdfRec; spectra as spectrum records, reflectance_texture as the
                                 // float4 offset of the texture record), then 3 x float4 per texture: {color0, m02} {color1, m12}
-                                // {m00 m01 m10 m11}
+                                // {m00 m01 m10 m11}; a bitmap: {first_texel, W, H (uint bits), m02} {MSK_TEXTURE_* (uint bits), 0, 0, m12}
     uint32_t n_bsdf_f4;         // float4 count of `bsdfs` (records + textures)
     const float4 *emitters;     // 2 x float4 per emitter: {c0,c1,c2,inv_area} {mesh,first_face,face_count,cdf_off (uint bits)}
     const float *emitter_d65;   // 95 floats per emitter: d65 * d65_scale, or the values of a `regular` radiance (ABI v7)
@@ -94,6 +94,8 @@ struct DeviceScene {
     float cull_lo[3], cull_hi[3];   // union of the two child boxes of the binary tree's root (msk_bvh.h: cull_bounds): a camera ray that
                                 // fails the slab test on it hits nothing — its sample is finished where it is made
                                 // (shade_region's regeneration, PassParams::cull)
+    const float4 *texels;       // the bitmap textures' texel pool (ABI v8), one float4 per texel {c0, c1, c2, -} = one 16-byte load per
+                                // texel, or nullptr; always read from HBM / L2, never staged.  (Last: the older fields keep their offsets.)
 };
 
 struct PathState {
@@ -1394,6 +1396,7 @@ struct SceneTables {
     const float *emitter_d65, *cdf, *cie;
     const float4 *emitter_grid;
     const float *spectra;
+    const float4 *texels;
 };
 // The same tables for a scene that holds tabulated (`regular`) spectra: the TYPE selects the code that can evaluate them (spectrum
 // records of the table form, emitters' tables on their own grids).  Scenes without any — every BASELINE config — run the
@@ -1403,9 +1406,13 @@ struct SceneTablesR : SceneTables {};
 // estimation and the delta mark of the path state are compiled only into the instantiations that carry this type, which such
 // scenes alone run.  It carries the table forms of tabulated spectra always (as k_path_serial does): one set of instantiations.
 struct SceneTablesD : SceneTablesR {};
-template <class TB> struct tb_traits { static constexpr bool regular = false, dielectric = false; };
-template <> struct tb_traits<SceneTablesR> { static constexpr bool regular = true, dielectric = false; };
-template <> struct tb_traits<SceneTablesD> { static constexpr bool regular = true, dielectric = true; };
+// ... and of a scene that holds a `bitmap` texture (MSK_TEXTURE_BITMAP*), with or without glass: the texel lookup of reflectance_eval
+// is compiled only into the instantiations that carry this type (k_shade_gen_b, k_wavefront_b, k_wavefront_h_b, k_path_serial_b).
+struct SceneTablesB : SceneTablesD {};
+template <class TB> struct tb_traits { static constexpr bool regular = false, dielectric = false, bitmap = false; };
+template <> struct tb_traits<SceneTablesR> { static constexpr bool regular = true, dielectric = false, bitmap = false; };
+template <> struct tb_traits<SceneTablesD> { static constexpr bool regular = true, dielectric = true, bitmap = false; };
+template <> struct tb_traits<SceneTablesB> { static constexpr bool regular = true, dielectric = true, bitmap = true; };
 MSK_DEV uint32_t tables_lds_float4s(const DeviceScene &sc) {
     return sc.n_tris * 6 + sc.n_meshes + sc.n_bsdf_f4 + sc.n_emitters * 3 + (sc.n_emitters * 95 + 3) / 4 + (sc.cdf_len + 3) / 4 + 72 + (sc.n_spectra + 3) / 4;
 }
@@ -1422,7 +1429,7 @@ MSK_DEV uint32_t small_tables_float4s(const DeviceScene &sc) {
 template <bool LDS_TABLES>
 MSK_DEV SceneTables stage_tables(const DeviceScene &sc, float4 *lds) {
     SceneTables t;
-    t.tri_normals = sc.tri_normals; t.tri_uvs = sc.tri_uvs;
+    t.tri_normals = sc.tri_normals; t.tri_uvs = sc.tri_uvs; t.texels = sc.texels;
     float4 *p = lds;
     auto copy4 = [&](const float4 *src, uint32_t n) { for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) p[i] = src[i]; float4 *r = p; p += n; return r; };
     auto copy1 = [&](const float *src, uint32_t n) { float *d = (float *) p; for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) d[i] = src[i]; p += (n + 3) / 4; return d; };
@@ -1543,9 +1550,8 @@ MSK_DEV BsdfRec load_bsdf(const SceneTables &tb, int id) {
     r.a = p[0]; r.b = p[1]; r.eta = p[2]; r.k = p[3]; r.spec = p[4]; r.trans = p[5]; r.ior = p[6];
     return r;
 }
-// textures/checkerboard.cpp:24-33 at the hit's uv (mesh.cpp:66,68-72): the coefficients SmoothDiffuse::m_reflectance->eval(si)
-// evaluates.  `rec` = float4 offset of the texture record in tb.bsdfs.
-MSK_DEV f3 checkerboard_coeffs(const SceneTables &tb, uint32_t rec, float4 hit) {
+// si.uv of a hit (mesh.cpp:66,68-72): the interpolated vertex texcoords, or the hit's barycentrics for a mesh without them
+MSK_DEV f2 hit_uv(const SceneTables &tb, float4 hit) {
     const uint32_t prim = __float_as_uint(hit.w);
     const int4 mi = tb.mesh_info[__float_as_uint(tb.tri_verts[(size_t) prim * 3].w)];
     float u = hit.y, v = hit.z;
@@ -1555,11 +1561,8 @@ MSK_DEV f3 checkerboard_coeffs(const SceneTables &tb, uint32_t rec, float4 hit) 
         u = ua.x * b0 + ua.z * b1 + ub.x * b2;
         v = ua.y * b0 + ua.w * b1 + ub.y * b2;
     }
-    const float4 t0 = tb.bsdfs[rec], t1 = tb.bsdfs[rec + 1], m = tb.bsdfs[rec + 2];
-    const float x = m.x * u + (m.y * v + t0.w * 1.f), y = m.z * u + (m.w * v + t1.w * 1.f);
-    const float fu = x - floorf(x), fv = y - floorf(y);
-    const bool first = (fu > .5f) == (fv > .5f);
-    return first ? mk3(t0.x, t0.y, t0.z) : mk3(t1.x, t1.y, t1.z);
+    f2 r; r.x = u; r.y = v;
+    return r;
 }
 // a spectrum record: {c0, c1, c2, scale >= 0} = scale * S(c, l), or {lambda_min, inv_interval, first | last << 24, -1} = the
 // `regular` spectrum whose values start at tb.spectra[first] (msk_spectrum_desc::regular; RegularSpectrum::eval, regular.cpp:148)
@@ -1570,6 +1573,59 @@ MSK_DEV spec spectrum_eval(const TB &tb, float4 s, spec wl) {
         return regular_eval_grid(tb.spectra + (w & 0xffffffu), s.x, s.y, w >> 24, wl);
     }
     return srgb_model_eval(s.x, s.y, s.z, wl) * s.w;
+}
+// One axis of a bitmap lookup (msk_gpu.h, msk_texture_desc): the two texel indices around f * n - 0.5 with wrap = repeat, and
+// the weight of the second.  f in [0, 1] (1 itself for a tiny negative coordinate), n >= 1.
+MSK_DEV void bitmap_axis(float f, uint32_t n, uint32_t *i0, uint32_t *i1, float *t) {
+    const float p = f * (float) n - 0.5f;
+    const float fl = floorf(p);
+    int i = (int) fl;
+    *t = p - (float) i;
+    if (i < 0) i = (int) n - 1;
+    if (i >= (int) n) i = 0;                       // (only through f * n == n)
+    int j = i + 1;
+    if (j >= (int) n) j = 0;
+    *i0 = (uint32_t) i; *i1 = (uint32_t) j;
+}
+// SmoothDiffuse::m_reflectance->eval(si) (diffuse.cpp:31,44) at the path's wavelengths: the constant spectrum {c, scale} (scale -1:
+// a `regular` reflectance) when tex == 0, else the texture whose record sits at float4 offset `tex` of tb.bsdfs, at the uv that
+// uv_of() returns (the shading kernels: hit_uv of the hit; the probe kernel: the caller's).  textures/checkerboard.cpp:24-33: one of
+// two constant spectra; a bitmap (only with SceneTablesB): the texel lookup of msk_gpu.h, nearest or bilinear over spectral values.
+template <class TB, class UV>
+MSK_DEV spec reflectance_eval(const TB &tb, f3 c, float scale, uint32_t tex, UV uv_of, spec wl) {
+    if (tex) {
+        const f2 uv = uv_of();
+        const float4 t0 = tb.bsdfs[tex], t1 = tb.bsdfs[tex + 1], m = tb.bsdfs[tex + 2];
+        const float x = m.x * uv.x + (m.y * uv.y + t0.w * 1.f), y = m.z * uv.x + (m.w * uv.y + t1.w * 1.f);
+        const float fu = x - floorf(x), fv = y - floorf(y);
+        const uint32_t type = __float_as_uint(t1.x);
+        if (tb_traits<TB>::bitmap && (type == MSK_TEXTURE_BITMAP || type == MSK_TEXTURE_BITMAP_NEAREST)) {
+            const uint32_t W = __float_as_uint(t0.y), H = __float_as_uint(t0.z);
+            const float4 *tx = tb.texels + __float_as_uint(t0.x);
+            if (type == MSK_TEXTURE_BITMAP_NEAREST) {
+                uint32_t i = (uint32_t) (int) (fu * (float) W), j = (uint32_t) (int) (fv * (float) H);
+                i = i < W - 1u ? i : W - 1u; j = j < H - 1u ? j : H - 1u;
+                const float4 k = tx[(size_t) j * W + i];
+                return srgb_model_eval(k.x, k.y, k.z, wl) * 1.f;
+            }
+            uint32_t i0, i1, j0, j1; float wx, wy;
+            bitmap_axis(fu, W, &i0, &i1, &wx);
+            bitmap_axis(fv, H, &j0, &j1, &wy);
+            // the four gathers go out together, ahead of the first sigmoid: divergent 16-byte loads from L2 / HBM, one latency
+            const float4 k00 = tx[(size_t) j0 * W + i0], k10 = tx[(size_t) j0 * W + i1];
+            const float4 k01 = tx[(size_t) j1 * W + i0], k11 = tx[(size_t) j1 * W + i1];
+            // row by row: two spectra live at a time beside the first row's result (this sits at shade_region's register peak)
+            const spec s00 = srgb_model_eval(k00.x, k00.y, k00.z, wl) * 1.f, s10 = srgb_model_eval(k10.x, k10.y, k10.z, wl) * 1.f;
+            const spec a = s00 + (s10 - s00) * wx;
+            const spec s01 = srgb_model_eval(k01.x, k01.y, k01.z, wl) * 1.f, s11 = srgb_model_eval(k11.x, k11.y, k11.z, wl) * 1.f;
+            const spec b = s01 + (s11 - s01) * wx;
+            return a + (b - a) * wy;
+        }
+        const bool first = (fu > .5f) == (fv > .5f);
+        c = first ? mk3(t0.x, t0.y, t0.z) : mk3(t1.x, t1.y, t1.z);
+        scale = 1.f;
+    }
+    return spectrum_eval(tb, make_float4(c.x, c.y, c.z, scale), wl);
 }
 MSK_DEV float clamp_alpha(float a) { return fmax_std(a, 1e-4f); }
 
@@ -2074,11 +2130,8 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
                 spec refl = splat(0.f);                  // SmoothDiffuse::m_reflectance->eval(si) (diffuse.cpp:31,44): once per bounce
                 if (DIFFUSE_ONLY) refl = srgb_model_eval(bs.a.z, bs.a.w, bs.b.x, wl) * bs.ior.w;      // * reflectance_scale
                 else if (__float_as_int(bs.a.x) == 0) {
-                    f3 c = mk3(bs.a.z, bs.a.w, bs.b.x);
-                    float scale = bs.ior.w;
                     const uint32_t tex = __float_as_uint(bs.ior.z);
-                    if (tex) { c = checkerboard_coeffs(tb, tex, hit); scale = 1.f; }
-                    refl = spectrum_eval(tb, make_float4(c.x, c.y, c.z, scale), wl);      // (scale -1: a `regular` reflectance)
+                    refl = reflectance_eval(tb, mk3(bs.a.z, bs.a.w, bs.b.x), bs.ior.w, tex, [&]() { return hit_uv(tb, hit); }, wl);
                 }
                 // ---- next-event estimation (path.cpp:56-67, scene.cpp:68-103): not at a BSDF without a smooth lobe
                 delta_out = bsdf_is_delta<TB>(bs);
@@ -2383,14 +2436,16 @@ MSK_DEV DoneQueue done_queue(float4 *base) {
     return dq;
 }
 
-// the table type of an instantiation: plain, with tabulated spectra, with the smooth dielectric (which includes them)
-template <bool REGULAR, bool DIELECTRIC>
-using tables_of = typename std::conditional<DIELECTRIC, SceneTablesD, typename std::conditional<REGULAR, SceneTablesR, SceneTables>::type>::type;
+// the table type of an instantiation: plain, with tabulated spectra, with the smooth dielectric (which includes them), with bitmap
+// textures (which includes both)
+template <bool REGULAR, bool DIELECTRIC, bool BITMAP = false>
+using tables_of = typename std::conditional<BITMAP, SceneTablesB, typename std::conditional<DIELECTRIC, SceneTablesD,
+                                            typename std::conditional<REGULAR, SceneTablesR, SceneTables>::type>::type>::type;
 
-template <bool LDS_TABLES, bool DIFFUSE_ONLY, bool REGULAR = false, bool DIELECTRIC = false>
+template <bool LDS_TABLES, bool DIFFUSE_ONLY, bool REGULAR = false, bool DIELECTRIC = false, bool BITMAP = false>
 MSK_DEV void shade_gen_body(const DeviceScene &sc, const PathState &st, const PassParams &pp) {
     extern __shared__ float4 lds_dyn[];
-    tables_of<REGULAR, DIELECTRIC> tb;
+    tables_of<REGULAR, DIELECTRIC, BITMAP> tb;
     static_cast<SceneTables &>(tb) = stage_tables<LDS_TABLES>(sc, lds_dyn);
     const uint32_t lwave = (blockIdx.x * MSK_BLOCK + threadIdx.x) / MSK_WAVE;
     const uint32_t queue_f4 = LDS_TABLES ? tables_lds_float4s(sc) : small_tables_float4s(sc);   // after the staged tables
@@ -2429,6 +2484,10 @@ k_shade_gen<true, false, true>(DeviceScene sc, PathState st, PassParams pp) { sh
 template <bool LDS_TABLES>
 __global__ void __launch_bounds__(MSK_BLOCK) __attribute__((amdgpu_waves_per_eu(MSK_SHADE_GEN_WAVES)))
 k_shade_gen_d(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_TABLES, false, true, true>(sc, st, pp); }
+// ... and the two that scenes with a `bitmap` texture run, and only they (SceneTablesB), with or without glass
+template <bool LDS_TABLES>
+__global__ void __launch_bounds__(MSK_BLOCK) __attribute__((amdgpu_waves_per_eu(MSK_SHADE_GEN_WAVES)))
+k_shade_gen_b(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_TABLES, false, true, true, true>(sc, st, pp); }
 // The diffuse-only variants fit four waves per SIMD (128 VGPRs, no scratch); left alone, the allocator spends 24 more registers
 // on the explicit fp64 fma chains of det_sincos and lands at three.
 #ifndef MSK_NO_SHADE4
@@ -2506,6 +2565,14 @@ k_wavefront_d(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, u
     constexpr bool CULL = false;      // (see shade_region: the register budget of this instantiation)
     MSK_WAVEFRONT_BODY
 }
+// the one scenes with a `bitmap` texture run (see k_shade_gen_b)
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_wavefront_b(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
+    typedef SceneTablesB TB;
+    constexpr bool DIFFUSE_ONLY = false;
+    constexpr bool CULL = false;      // (as k_wavefront_d)
+    MSK_WAVEFRONT_BODY
+}
 #undef MSK_WAVEFRONT_BODY
 
 // k_wavefront_h (round 6): the same device-side loop for scenes whose TREE STAYS IN HBM / L2 (trace mode 6: the 4-wide tree with
@@ -2569,7 +2636,27 @@ k_wavefront_h_d(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters,
     constexpr bool DIFFUSE_ONLY = false;
     MSK_WAVEFRONT_H_BODY
 }
+// the one scenes with a `bitmap` texture run (see k_shade_gen_b)
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_wavefront_h_b(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
+    typedef SceneTablesB TB;
+    constexpr bool DIFFUSE_ONLY = false;
+    MSK_WAVEFRONT_H_BODY
+}
 #undef MSK_WAVEFRONT_H_BODY
+
+// msk_gpu_eval_texture: the value of the texture whose record sits at float4 offset `rec` of the BSDF table, at n given uv and
+// wavelengths, through the function the shading kernels call.  Tables from HBM (nothing staged), one point per thread.
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_eval_texture(DeviceScene sc, uint32_t rec, uint64_t n, const float2 *uv, const float4 *wl, float4 *out) {
+    SceneTablesB tb;
+    static_cast<SceneTables &>(tb) = stage_tables<false>(sc, nullptr);
+    for (uint64_t i = (uint64_t) blockIdx.x * MSK_BLOCK + threadIdx.x; i < n; i += (uint64_t) gridDim.x * MSK_BLOCK) {
+        const float2 p = uv[i];
+        const spec v = reflectance_eval(tb, mk3(0.f, 0.f, 0.f), 0.f, rec, [&]() { f2 r; r.x = p.x; r.y = p.y; return r; }, from4(wl[i]));
+        out[i] = make_float4(v.v[0], v.v[1], v.v[2], v.v[3]);
+    }
+}
 
 // AOVIntegrator::sample's primary-hit channels (aov.cpp:89-122): runs after k_trace, picks the slots whose camera ray
 // has just been traced (depth 1) and writes their record groups.  A miss writes zeros.

@@ -62,7 +62,7 @@ MSK_DEV void serial_put(const DeviceScene &sc, float *data, int sx, int sy, int 
     }
 }
 
-// The kernel's body lives in msk_serial_body.inc and is included into both kernels: TB = SceneTablesR, or SceneTablesD for a scene
+// The kernel's body lives in msk_serial_body.inc and is included into each kernel: TB = SceneTablesR, or SceneTablesD for a scene
 // that holds a smooth `dielectric` (k_path_serial_d), which alone compiles the guard around next-event estimation.
 __global__ void __launch_bounds__(MSK_BLOCK)
 k_path_serial(DeviceScene sc, SerialParams prm) {
@@ -72,6 +72,12 @@ k_path_serial(DeviceScene sc, SerialParams prm) {
 __global__ void __launch_bounds__(MSK_BLOCK)
 k_path_serial_d(DeviceScene sc, SerialParams prm) {
     typedef SceneTablesD TB;
+#include "msk_serial_body.inc"
+}
+// ... and SceneTablesB for a scene that holds a `bitmap` texture (with or without glass)
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_path_serial_b(DeviceScene sc, SerialParams prm) {
+    typedef SceneTablesB TB;
 #include "msk_serial_body.inc"
 }
 

@@ -1,4 +1,4 @@
-// msk_serial_body.inc — the body of k_path_serial / k_path_serial_d (msk_serial.h), included once into each: `TB` is the
+// msk_serial_body.inc — the body of k_path_serial / k_path_serial_d / k_path_serial_b (msk_serial.h), included once into each: `TB` is the
 // kernel's table type, `sc` and `prm` its arguments.  Written once and stamped, not shared through a function, so that
 // k_path_serial compiles from the token stream it always had.
     extern __shared__ float4 lds_dyn[];
@@ -78,11 +78,8 @@
                     if (depth >= prm.max_depth && prm.max_depth > 0) break;             // path.cpp:48-49
                     spec refl = splat(0.f);
                     if (__float_as_int(bs.a.x) == 0) {
-                        f3 c = mk3(bs.a.z, bs.a.w, bs.b.x);
-                        float scale = bs.ior.w;
                         const uint32_t tex = __float_as_uint(bs.ior.z);
-                        if (tex) { c = checkerboard_coeffs(tb, tex, hit); scale = 1.f; }
-                        refl = spectrum_eval(tb, make_float4(c.x, c.y, c.z, scale), wl);
+                        refl = reflectance_eval(tb, mk3(bs.a.z, bs.a.w, bs.b.x), bs.ior.w, tex, [&]() { return hit_uv(tb, hit); }, wl);
                     }
                     const float tmin = (1.f + max_abs(si.p)) * MSK_RAY_EPS_F;          // interaction.h:40-44
                     // ---- next-event estimation (path.cpp:56-67, scene.cpp:68-103); the draw is made whatever the scene holds —

@@ -16,6 +16,7 @@ class ReconstructionFilter; class ImageBlock; class Integrator;
 namespace math { constexpr float Epsilon = 5.9604644775390625e-08f; }       // std::numeric_limits<float>::epsilon() / 2
 #define MSK_CIE_Y_NORMALIZATION float(1.0 / 106.7502593994140625)
 
+struct FlatTables;
 // include/misaki/render/texture.h — spectra as the back end sees them
 class Texture : public Object {
 public:
@@ -25,8 +26,9 @@ public:
     struct Flat { float coeff[3] = {0, 0, 0}; float scale = 1.f; float d65_scale = 0.f; bool uses_d65 = false;
                   bool regular = false; float lambda_min = 0.f, lambda_max = 0.f; std::vector<float> values; };
     virtual bool flatten(Flat &out) const { (void) out; return false; }
-    // plugins whose value varies with si.uv describe themselves as an msk_texture_desc instead
-    virtual bool flatten_texture(msk_texture_desc &out) const { (void) out; return false; }
+    // plugins whose value varies with si.uv describe themselves as an msk_texture_desc instead (a bitmap adds its texels to
+    // the scene's pool, tables.texels)
+    virtual bool flatten_texture(msk_texture_desc &out, FlatTables &tables) const { (void) out; (void) tables; return false; }
     virtual float mean() const { return 0.f; }
     static ref<Texture> D65(float scale);
     MSK_DECLARE_CLASS()
@@ -36,11 +38,13 @@ protected:
 };
 
 // the scene-level tables a BSDF / emitter adds to while it flattens itself: textures that vary over the surface and
-// tabulated spectra (msk_scene_desc::textures / regular_spectra / regular_values)
+// tabulated spectra (msk_scene_desc::textures / regular_spectra / regular_values), and the bitmap textures' texel pool
+// (msk_scene_desc::texels, three coefficients per texel)
 struct FlatTables {
     std::vector<msk_texture_desc> &textures;
     std::vector<msk_regular_spectrum_desc> &regular;
     std::vector<float> &regular_values;
+    std::vector<float> &texels;
     uint32_t add_regular(const Texture::Flat &f) {          // -> the 1-based index msk_spectrum_desc::regular holds
         regular.push_back(msk_regular_spectrum_desc{f.lambda_min, f.lambda_max, (uint32_t) f.values.size(), (uint32_t) regular_values.size()});
         regular_values.insert(regular_values.end(), f.values.begin(), f.values.end());
@@ -267,6 +271,7 @@ struct FlatScene {
     std::vector<msk_texture_desc> textures;
     std::vector<msk_regular_spectrum_desc> regular;      // tabulated spectra (ABI v7) and their values
     std::vector<float> regular_values;
+    std::vector<float> texels;                           // the bitmap textures' coefficients (ABI v8), 3 per texel
     std::vector<float> vertices;
     std::vector<uint32_t> faces;
     msk_render_params params;
@@ -287,5 +292,9 @@ void rgb2spec_fetch_table(int res, const float *scale, const float *data, const 
 // image output (core/image.h): float RGBA
 void write_pfm(const std::string &path, int w, int h, int channels, const float *data);
 void write_exr(const std::string &path, int w, int h, const std::vector<std::string> &channels, const float *data);
+// image input for the `bitmap` texture: PFM (1 or 3 channels, either byte order; linear values) and binary PGM / PPM (P5 / P6,
+// maxval <= 65535; IEC 61966-2-1 sRGB decode unless `raw`) -> w * h * 3 linear RGB floats, the image's TOP row first, one channel
+// replicated to grey.  Throws with the file's name for a missing or truncated file and for a wrong magic number.
+void read_image(const std::string &path, bool raw, int &w, int &h, std::vector<float> &rgb);
 
 }  // namespace misaki

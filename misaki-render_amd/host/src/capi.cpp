@@ -71,6 +71,19 @@ int msk_host_render(msk_host_scene *h, float *film_xyzaw, float *rgba, const cha
     } catch (const std::exception &e) { return fail(e); }
 }
 
+// read_image (imageio.cpp): -> *w, *h and, when rgb is not NULL, w * h * 3 linear floats (top row first) into rgb[0 .. cap)
+int msk_host_read_image(const char *path, int raw, int *w, int *h, float *rgb, size_t cap) {
+    try {
+        std::vector<float> px;
+        read_image(path, raw != 0, *w, *h, px);
+        if (rgb) {
+            if (px.size() > cap) Throw("msk_host_read_image: buffer too small");
+            std::memcpy(rgb, px.data(), px.size() * sizeof(float));
+        }
+        return 0;
+    } catch (const std::exception &e) { return fail(e); }
+}
+
 // aov_names() of the scene's integrator, '\n'-separated; returns the number of names or -1
 int msk_host_aov_names(msk_host_scene *h, char *buf, size_t cap) {
     try {

@@ -305,7 +305,7 @@ public:
         m_color1 = props.texture("color1", .2f);
         m_to_uv = props.transform("to_uv", Transform4f());
     }
-    bool flatten_texture(msk_texture_desc &out) const override {
+    bool flatten_texture(msk_texture_desc &out, FlatTables &) const override {
         Flat c0, c1;
         if (!m_color0->flatten(c0) || !m_color1->flatten(c1) || c0.uses_d65 || c1.uses_d65 || c0.regular || c1.regular || c0.scale != 1.f || c1.scale != 1.f) return false;
         std::memset(&out, 0, sizeof out);
@@ -324,6 +324,55 @@ private:
 };
 MSK_IMPLEMENT_CLASS(CheckerboardTexture, Texture)
 MSK_REGISTER_INSTANCE(CheckerboardTexture, "checkerboard")
+
+// The `bitmap` texture: an image file as the diffuse reflectance (the reference's textures/bitmap.cpp is RGB-typed and not built;
+// this is its lookup in spectral form, include/msk_gpu.h at msk_texture_desc).  Properties: filename (through the file resolver),
+// filter_type "bilinear" (default) | "nearest", to_uv, wrap_mode "repeat" only, raw (default false: PGM / PPM samples are sRGB
+// encoded; PFM values are linear either way).  The image's top row is texel row 0: the OBJ loader stores 1 - v, so the image sits
+// upright on a conventionally unwrapped mesh.
+class BitmapTexture final : public Texture {
+public:
+    BitmapTexture(const Properties &props) : Texture(props) {
+        m_filename = props.string("filename");
+        const std::string filter = props.string("filter_type", "bilinear"), wrap = props.string("wrap_mode", "repeat");
+        if (filter != "bilinear" && filter != "nearest")
+            Throw("bitmap \"{}\": filter_type \"{}\" is not supported (bilinear, nearest)", m_filename, filter);
+        if (wrap != "repeat")
+            Throw("bitmap \"{}\": wrap_mode \"{}\" is not supported by the GPU path integrator (repeat)", m_filename, wrap);
+        m_nearest = filter == "nearest";
+        m_to_uv = props.transform("to_uv", Transform4f());
+        read_image(get_file_resolver()->resolve(m_filename), props.bool_("raw", false), m_width, m_height, m_rgb);
+    }
+    bool flatten_texture(msk_texture_desc &out, FlatTables &tables) const override {
+        std::memset(&out, 0, sizeof out);
+        out.type = m_nearest ? MSK_TEXTURE_BITMAP_NEAREST : MSK_TEXTURE_BITMAP;
+        out.width = (uint32_t) m_width; out.height = (uint32_t) m_height; out.first_texel = (uint32_t) (tables.texels.size() / 3);
+        for (int r = 0; r < 2; ++r) for (int c = 0; c < 3; ++c) out.to_uv[r * 3 + c] = (float) m_to_uv.matrix().m[r][c];
+        std::map<std::array<float, 3>, Color3> seen;                 // one fetch per distinct colour
+        for (size_t k = 0; k < (size_t) m_width * m_height; ++k) {
+            std::array<float, 3> rgb;
+            for (int c = 0; c < 3; ++c) { const float v = m_rgb[k * 3 + c]; rgb[c] = v >= 0.f ? (v <= 1.f ? v : 1.f) : 0.f; }      // a reflectance (NaN -> 0)
+            auto it = seen.find(rgb);
+            if (it == seen.end()) it = seen.emplace(rgb, srgb_model_fetch(Color3{rgb[0], rgb[1], rgb[2]})).first;
+            tables.texels.push_back(it->second.r); tables.texels.push_back(it->second.g); tables.texels.push_back(it->second.b);
+        }
+        return true;
+    }
+    float mean() const override {
+        double s = 0.0;
+        for (float v : m_rgb) s += v;
+        return m_rgb.empty() ? 0.f : (float) (s / (double) m_rgb.size());
+    }
+    MSK_DECLARE_CLASS()
+private:
+    std::string m_filename;
+    bool m_nearest = false;
+    Transform4f m_to_uv;
+    int m_width = 0, m_height = 0;
+    std::vector<float> m_rgb;
+};
+MSK_IMPLEMENT_CLASS(BitmapTexture, Texture)
+MSK_REGISTER_INSTANCE(BitmapTexture, "bitmap")
 
 // =========================================================================== filter, sampler, film
 // filters/gaussian.cpp:10-20
@@ -449,7 +498,7 @@ public:
         } else if (m_reflectance->flatten(f) && !f.uses_d65) {
             std::memcpy(out.reflectance, f.coeff, sizeof f.coeff);
             out.reflectance_scale = f.scale;
-        } else if (m_reflectance->flatten_texture(td)) {            // a reflectance that varies over the surface
+        } else if (m_reflectance->flatten_texture(td, tables)) {            // a reflectance that varies over the surface
             tables.textures.push_back(td);
             out.reflectance_texture = (uint32_t) tables.textures.size();
         } else {
@@ -818,8 +867,8 @@ MSK_REGISTER_INSTANCE(OBJMesh, "obj")
 // =========================================================================== flatten
 void flatten_scene(const Scene *scene, const Sensor *sensor, FlatScene &out) {
     out.meshes.clear(); out.bsdfs.clear(); out.emitters.clear(); out.textures.clear(); out.vertices.clear(); out.faces.clear();
-    out.regular.clear(); out.regular_values.clear();
-    FlatTables tables{out.textures, out.regular, out.regular_values};
+    out.regular.clear(); out.regular_values.clear(); out.texels.clear();
+    FlatTables tables{out.textures, out.regular, out.regular_values, out.texels};
     // Scene::m_emitters order (scene.cpp:27-41) decides which emitter sample_emitter_direct picks (scene.cpp:80-84)
     std::map<const Emitter *, int> emitter_index;
     for (auto &e : scene->emitters()) {
@@ -880,6 +929,7 @@ void flatten_scene(const Scene *scene, const Sensor *sensor, FlatScene &out) {
     d.n_textures = (uint32_t) out.textures.size(); d.textures = out.textures.data();
     d.n_regular_spectra = (uint32_t) out.regular.size(); d.n_regular_values = (uint32_t) out.regular_values.size();
     d.regular_spectra = out.regular.data(); d.regular_values = out.regular_values.data();
+    d.n_texels = (uint32_t) (out.texels.size() / 3); d.texels = out.texels.empty() ? nullptr : out.texels.data();
 }
 
 // "0,1,2" -> {0,1,2}; empty -> {single}

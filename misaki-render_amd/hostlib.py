@@ -37,6 +37,7 @@ def load():
         lib.msk_host_rgb2spec_build.argtypes = [C.c_int, C.c_char_p, C.c_int]
         lib.msk_host_srgb_model_source.argtypes = [C.c_char_p, C.c_size_t]
         lib.msk_host_write_image.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, vp]
+        lib.msk_host_read_image.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), vp, C.c_size_t]
         lib.msk_host_set_log_level.argtypes = [C.c_int]
         lib.msk_host_set_log_level(3)
         _lib = lib
@@ -126,6 +127,15 @@ def srgb_model_source():
     buf = C.create_string_buffer(4096)
     _check(load().msk_host_srgb_model_source(buf, len(buf)))
     return buf.value.decode()
+
+
+def read_image(path, raw=False):
+    """The `bitmap` texture's reader (PFM, binary PGM / PPM) -> float32 [H, W, 3] linear RGB, the image's top row first."""
+    w, h = C.c_int(), C.c_int()
+    _check(load().msk_host_read_image(str(path).encode(), int(raw), C.byref(w), C.byref(h), None, 0))
+    out = np.zeros((h.value, w.value, 3), np.float32)
+    _check(load().msk_host_read_image(str(path).encode(), int(raw), C.byref(w), C.byref(h), out.ctypes.data_as(C.c_void_p), out.size))
+    return out
 
 
 def write_image(path, img):

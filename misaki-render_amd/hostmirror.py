@@ -181,7 +181,9 @@ class MeshSpec:
         {"type": "dielectric", "int_ior": 1.49, "ext_ior": 1.00028, "specular_reflectance": rgb | c, "specular_transmittance": rgb | c}
         (the smooth interface; a scalar c = the `uniform` spectrum <spectrum value="c"/>), or
         {"type": "diffuse", "twosided": bool, "texture": {"type": "checkerboard", "color0": rgb, "color1": rgb,
-         "scale": (sx, sy) | "matrix": 16 floats (the to_uv 4x4, row-major)}} (texture absent = `reflectance`).
+         "scale": (sx, sy) | "matrix": 16 floats (the to_uv 4x4, row-major)}} (texture absent = `reflectance`), or the texture
+        {"type": "bitmap", "pixels": float32 [H, W, 3] linear RGB (row 0 = texel row 0 = the image's top row),
+         "filter": "bilinear" (default) | "nearest", "scale" | "matrix" (default: identity)}.
         texcoords: None, or per face a tuple of (u, v) per corner as written in the OBJ `vt` lines (the loader stores 1 - v)."""
         self.name, self.faces, self.reflectance, self.radiance = name, faces, reflectance, radiance
         self.translate, self.normals, self.bsdf, self.texcoords = translate, normals, bsdf, texcoords
@@ -225,8 +227,27 @@ def write_obj(mesh, path):
             n += len(f)
 
 
-def _bsdf_xml(m, v3):
-    """The <bsdf> element of one shape (reference plugin parameter names)."""
+def write_pfm(path, pixels, little_endian=True):
+    """pixels float32 [H, W, 3] (or [H, W]: one channel), row 0 = the top row -> a PFM file, which stores the bottom row first."""
+    a = np.asarray(pixels, np.float32)
+    h, w = a.shape[:2]
+    with open(path, "wb") as fh:
+        fh.write(b"%s\n%d %d\n%s\n" % (b"PF" if a.ndim == 3 else b"Pf", w, h, b"-1.0" if little_endian else b"1.0"))
+        fh.write(a[::-1].astype("<f4" if little_endian else ">f4").tobytes())
+
+
+def _to_uv_xml(tex):
+    if "scale" in tex:
+        return ['    <transform name="to_uv">', '        <scale x="%.9g" y="%.9g"/>' % tuple(tex["scale"]), '    </transform>']
+    if "matrix" in tex:
+        return ['    <transform name="to_uv">', '        <matrix value="%s"/>' % " ".join("%.9g" % float(np.float32(x)) for x in tex["matrix"]),
+                '    </transform>']
+    return []
+
+
+def _bsdf_xml(m, v3, directory=None):
+    """The <bsdf> element of one shape (reference plugin parameter names); a bitmap texture's pixels go to
+    <directory>/textures/<shape>.pfm."""
     spec = m.bsdf
     refl_xml = '<spectrum name="reflectance" value="%s"/>' % m.reflectance.text if isinstance(m.reflectance, Regular) else \
                '<spectrum name="reflectance" value="%.9g"/>' % float(m.reflectance) if np.isscalar(m.reflectance) else \
@@ -237,6 +258,11 @@ def _bsdf_xml(m, v3):
         tex = spec.get("texture")
         if tex is None:
             body = [refl_xml]
+        elif tex["type"] == "bitmap":
+            os.makedirs(os.path.join(directory, "textures"), exist_ok=True)
+            write_pfm(os.path.join(directory, "textures", m.name + ".pfm"), tex["pixels"])
+            body = ['<texture name="reflectance" type="bitmap">', '    <string name="filename" value="textures/%s.pfm"/>' % m.name] + \
+                   (['    <string name="filter_type" value="%s"/>' % tex["filter"]] if "filter" in tex else []) + _to_uv_xml(tex) + ['</texture>']
         else:     # textures/checkerboard.cpp:11-15 parameter names, as in results/Figure_2_RoughConductor/roughconductor.xml:35-41
             xf = '<scale x="%.9g" y="%.9g"/>' % tuple(tex["scale"]) if "scale" in tex else \
                  '<matrix value="%s"/>' % " ".join("%.9g" % float(np.float32(x)) for x in tex["matrix"])
@@ -309,7 +335,7 @@ def write_scene_xml(meshes, directory, width, height, spp, camera=None, integrat
         if any(float(t) != 0 for t in m.translate):
             out += ['        <transform name="to_world">', '            <translate x="%.9g" y="%.9g" z="%.9g"/>' % tuple(m.translate),
                     '        </transform>']
-        out += _bsdf_xml(m, v3)
+        out += _bsdf_xml(m, v3, directory)
         if m.radiance is not None:
             out += ['        <emitter type="area">', '            <spectrum name="radiance" value="%s"/>' % m.radiance.text if isinstance(m.radiance, Regular)
                     else '            <rgb name="radiance" value="%s"/>' % v3(m.radiance), '        </emitter>']
@@ -452,23 +478,41 @@ def spectrum_desc(rgb, fetch, pool=None):
     return abi.SpectrumDesc((C.c_float * 3)(*fetch(tuple(float(x) for x in rgb / scale))), float(scale))
 
 
-def _texture_desc(tex, fetch):
-    """textures/checkerboard.cpp:11-15: m_transform = the top-left 3x3 of the to_uv 4x4 (transform.h:142-148)."""
-    if tex["type"] != "checkerboard":
-        raise ValueError(tex["type"])
+def _texture_desc(tex, fetch, texels=None):
+    """textures/checkerboard.cpp:11-15: m_transform = the top-left 3x3 of the to_uv 4x4 (transform.h:142-148).  A bitmap
+    (msk_gpu.h, msk_texture_desc): its texels' coefficients are appended to `texels`, the scene's pool (a list of float32 [n, 3]
+    arrays) — components clamped to [0, 1], fetched once per distinct colour."""
     t = abi.TextureDesc()
-    t.type = abi.MSK_TEXTURE_CHECKERBOARD
-    t.color0[:] = fetch(tuple(tex["color0"]))
-    t.color1[:] = fetch(tuple(tex["color1"]))
+    if tex["type"] == "bitmap":
+        px = np.asarray(tex["pixels"], np.float32)
+        if px.ndim != 3 or px.shape[2] != 3 or px.shape[0] < 1 or px.shape[1] < 1:
+            raise ValueError("bitmap pixels must be float32 [H, W, 3]")
+        filt = tex.get("filter", "bilinear")
+        if filt not in ("bilinear", "nearest"):
+            raise ValueError("bitmap filter %r (bilinear or nearest)" % (filt,))
+        t.type = abi.MSK_TEXTURE_BITMAP if filt == "bilinear" else abi.MSK_TEXTURE_BITMAP_NEAREST
+        t.height, t.width, t.first_texel = px.shape[0], px.shape[1], sum(len(c) for c in texels)
+        flat = np.where(px >= 0, np.minimum(px, np.float32(1)), np.float32(0)).astype(np.float32).reshape(-1, 3) + np.float32(0)   # (NaN -> 0, -0 -> +0)
+        colours, inverse = np.unique(flat, axis=0, return_inverse=True)
+        coeffs = np.array([fetch(tuple(float(x) for x in rgb)) for rgb in colours], np.float32).reshape(-1, 3)
+        texels.append(coeffs[inverse.reshape(-1)])
+    elif tex["type"] == "checkerboard":
+        t.type = abi.MSK_TEXTURE_CHECKERBOARD
+        t.color0[:] = fetch(tuple(tex["color0"]))
+        t.color1[:] = fetch(tuple(tex["color1"]))
+    else:
+        raise ValueError(tex["type"])
     if "scale" in tex:
         m4 = np.diag([tex["scale"][0], tex["scale"][1], 1.0, 1.0]).astype(np.float32)
-    else:
+    elif "matrix" in tex:
         m4 = np.asarray(tex["matrix"], np.float32).reshape(4, 4)
+    else:
+        m4 = np.eye(4, dtype=np.float32)
     t.to_uv[:] = [float(x) for x in (m4[0, 0], m4[0, 1], m4[0, 2], m4[1, 0], m4[1, 1], m4[1, 2])]
     return t
 
 
-def _bsdf_desc(m, fetch, index, textures=None, pool=None):
+def _bsdf_desc(m, fetch, index, textures=None, pool=None, texels=None):
     b = abi.BsdfDesc()
     b.back_bsdf = -1
     one = abi.SpectrumDesc((C.c_float * 3)(0.0, 0.0, float("inf")), 1.0)
@@ -487,7 +531,7 @@ def _bsdf_desc(m, fetch, index, textures=None, pool=None):
             b.reflectance[:] = fetch(tuple(m.reflectance))
             b.reflectance_scale = 1.0
         if spec.get("texture") is not None:
-            textures.append(_texture_desc(spec["texture"], fetch))
+            textures.append(_texture_desc(spec["texture"], fetch, texels))
             b.reflectance_texture = len(textures)
     elif spec["type"] == "roughconductor":
         b.type = abi.MSK_BSDF_ROUGHCONDUCTOR
@@ -543,18 +587,21 @@ def _radiance_desc(radiance, fetch, scale_in=1.0):
     return ce, float(np.float32(np.float32(scale_in) * scale) * (np.float32(1.0) / np.float32(10568.0)))
 
 
-def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=None, env=None, crop=None):
+def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=None, env=None, crop=None, extra_textures=()):
     """Scene -> msk_scene_desc, the step the `"path"` plugin's render() performs before calling
     the C ABI.  coeff_lookup(rgb)->(c0,c1,c2) overrides the spectral upsampling
     (tests pass the reference's own rgb2spec_fetch results); default = this package's rgb2spec.
     env: None, or {"radiance": rgb | None (= D65), "scale": 1.0, "first": False} = a top-level
     <emitter type="constant"> placed after (or, with first=True, before) the shapes in the XML.
-    crop: None, or (offset_x, offset_y, width, height) = the film's crop_offset_x/_y, crop_width/_height (film.cpp:12-21)."""
+    crop: None, or (offset_x, offset_y, width, height) = the film's crop_offset_x/_y, crop_width/_height (film.cpp:12-21).
+    extra_textures: texture specs (as MeshSpec.bsdf["texture"]) appended to the scene's textures after those the BSDFs name:
+    no surface shows them, Scene.eval_texture evaluates them."""
     from . import rgb2spec
     fetch = coeff_lookup or rgb2spec.srgb_model_fetch
     camera = camera or CBOX_CAMERA
     fs = FlatScene()
     all_v, all_f, md, bd, ed, td = [], [], [], [], [], []
+    texels = []                # the bitmap textures' texel pool: float32 [n, 3] arrays of coefficients, in order
     pool = _RegularPool()
     nv = nf = 0
 
@@ -570,7 +617,7 @@ def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=
         ed.append(env_desc())
     for i, m in enumerate(meshes):
         v, f = triangulate(m)
-        bd.append(_bsdf_desc(m, fetch, len(bd), td, pool))
+        bd.append(_bsdf_desc(m, fetch, len(bd), td, pool, texels))
         eid = -1
         if m.radiance is not None:
             ed.append(emitter_desc(abi.MSK_EMITTER_AREA, i, m.radiance))
@@ -582,6 +629,8 @@ def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=
         nf += len(f)
     if env is not None and not env.get("first"):
         ed.append(env_desc())
+    for tex in extra_textures:
+        td.append(_texture_desc(tex, fetch, texels))
     verts = np.ascontiguousarray(np.concatenate(all_v + [np.zeros((0, 8), np.float32)]), np.float32).reshape(-1, 8)
     faces = np.ascontiguousarray(np.concatenate(all_f + [np.zeros((0, 3), np.uint32)]), np.uint32).reshape(-1, 3)
     cie, d65 = cie_tables()
@@ -591,7 +640,8 @@ def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=
     tex_a = (abi.TextureDesc * max(1, len(td)))(*td)
     reg_a = (abi.RegularSpectrumDesc * max(1, len(pool.descs)))(*pool.descs)
     reg_v = np.ascontiguousarray(np.array(pool.values + ([] if pool.values else [0.0]), np.float32))
-    fs.keep += [verts, faces, cie, d65, meshes_a, bsdfs_a, emit_a, tex_a, reg_a, reg_v]
+    tex_v = np.ascontiguousarray(np.concatenate(texels + [np.zeros((0 if texels else 1, 3), np.float32)]), np.float32).reshape(-1, 3)
+    fs.keep += [verts, faces, cie, d65, meshes_a, bsdfs_a, emit_a, tex_a, reg_a, reg_v, tex_v]
     d = fs.desc
     d.abi_version = abi.MSK_ABI_VERSION
     d.n_meshes, d.n_bsdfs, d.n_emitters = len(md), len(bd), len(ed)
@@ -600,6 +650,9 @@ def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=
     d.n_regular_spectra, d.n_regular_values = len(pool.descs), len(pool.values)
     d.regular_spectra = reg_a
     d.regular_values = reg_v.ctypes.data_as(C.POINTER(C.c_float))
+    d.n_texels = len(tex_v) if texels else 0
+    d.texels = tex_v.ctypes.data_as(C.POINTER(C.c_float)) if texels else None
+    fs.texels = tex_v
     d.vertices = verts.ctypes.data_as(C.POINTER(C.c_float))
     d.faces = faces.ctypes.data_as(C.POINTER(C.c_uint32))
     d.n_vertices, d.n_faces = nv, nf

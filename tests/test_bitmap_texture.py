@@ -1,0 +1,575 @@
+"""The `bitmap` texture on the diffuse reflectance (ABI v8): image textures from the kernel to the XML.
+
+The reference's textures/bitmap.cpp is RGB-typed and not built, so nothing runnable pins its lookup.  Two things do here:
+tests/bitmap_ref.py, a float32 restatement of the semantics written in include/msk_gpu.h (at msk_texture_desc), and the
+oracle wherever a bitmap degenerates to something the oracle already renders — an image of equal texels is a constant
+reflectance, a nearest-filtered 2x2 image is a checkerboard.  The oracle itself never sees a bitmap (it reads any texture
+as a checkerboard)."""
+import ctypes as C
+import importlib
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import bitmap_ref as R
+import test_launch_plan as LP
+import test_table_placement as T
+from test_textures import C0, C1, checker_floor_scene
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = np.float32
+SKEW = [7, 1.5, 0.3, 0, -2, 6, -0.2, 0, 0, 0, 1, 0, 0, 0, 0, 1]          # the matrix of test_gpu_matches_oracle_on_textured_floors
+TO_UVS = {"identity": {}, "scale10": {"scale": (10, 10)}, "skew": {"matrix": SKEW}}
+
+
+def to_uv6(spec):
+    if "scale" in spec:
+        return [spec["scale"][0], 0, 0, 0, spec["scale"][1], 0]
+    if "matrix" in spec:
+        m = spec["matrix"]
+        return [m[0], m[1], m[2], m[4], m[5], m[6]]
+    return [1, 0, 0, 0, 1, 0]
+
+
+def bitmap(pixels, filt="bilinear", **to_uv):
+    return dict({"type": "bitmap", "pixels": np.asarray(pixels, F), "filter": filt}, **to_uv)
+
+
+def checker_pixels(c0=C0, c1=C1):
+    """the 2x2 image a nearest lookup turns into the checkerboard of c0 / c1: c0 where the two half-cells agree"""
+    return np.array([[c0, c1], [c1, c0]], F)
+
+
+# ===================================================================================================== CPU
+def test_layout_and_exports(abi, tmp_path):
+    """(1) 64 / 132 bytes as before; the new fields where the header puts them; the probe entry point is exported."""
+    assert C.sizeof(abi.TextureDesc) == 64 and C.sizeof(abi.BsdfDesc) == 132
+    src = tmp_path / "off.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "msk_gpu.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %d %d %d\\n",'
+                   'offsetof(msk_texture_desc,width),offsetof(msk_texture_desc,height),offsetof(msk_texture_desc,first_texel),'
+                   'offsetof(msk_scene_desc,n_texels),offsetof(msk_scene_desc,texels),sizeof(msk_scene_desc),'
+                   'MSK_ABI_VERSION,MSK_TEXTURE_BITMAP,MSK_TEXTURE_BITMAP_NEAREST);return 0;}\n')
+    exe = tmp_path / "off"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    assert got == [abi.TextureDesc.width.offset, abi.TextureDesc.height.offset, abi.TextureDesc.first_texel.offset,
+                   abi.SceneDesc.n_texels.offset, abi.SceneDesc.texels.offset, C.sizeof(abi.SceneDesc),
+                   abi.MSK_ABI_VERSION, abi.MSK_TEXTURE_BITMAP, abi.MSK_TEXTURE_BITMAP_NEAREST]
+    assert got[:3] == [52, 56, 60] and got[6:] == [8, 2, 3]
+    assert abi.SceneDesc.n_texels.offset > abi.SceneDesc.regular_values.offset          # appended: the v7 fields stay put
+    import __graft_entry__ as ge
+    ge.build_gpu_library()
+    assert "msk_gpu_eval_texture" in abi.EXPORTS and C.CDLL(abi.LIB_PATH).msk_gpu_eval_texture is not None
+    blob = open(abi.LIB_PATH, "rb").read()
+    for k in (b"k_shade_gen_b", b"k_wavefront_b", b"k_wavefront_h_b", b"k_path_serial_b", b"k_eval_texture"):
+        assert k in blob, k
+
+
+@pytest.mark.parametrize("w,h", [(1, 1), (2, 2), (3, 5)])
+def test_restatement_against_hand_checked_values(w, h):
+    """(2) bitmap_ref on grey images whose texel (j, i) holds 1 + j * W + i... scaled to exact binary fractions, so that every
+    expected value below is exact in fp32 and written down from the semantics, not computed by the restatement."""
+    lev = (np.arange(w * h, dtype=F).reshape(h, w) + F(1)) / F(64)
+    tex = R.grey_texels(lev)
+    ident = [1, 0, 0, 0, 1, 0]
+    wl = np.full((1, 4), 550, F)
+    at = lambda filt, u, v: R.lookup(tex, w, h, filt, ident, [[u, v]], wl)[0, 0]
+    # texel centres return the texel, in both filters; W != H catches a transposed index
+    for j in range(h):
+        for i in range(w):
+            u, v = (i + 0.5) / w, (j + 0.5) / h
+            assert at("nearest", u, v) == lev[j, i], (j, i)
+            assert abs(at("bilinear", u, v) - lev[j, i]) <= 2 ** -20, (j, i)       # (u * W in fp32: tx within a few ulp of 0)
+    # u = i / W: halfway between column i - 1 (wrapping) and column i
+    for i in range(w):
+        for j in (0, h - 1):
+            want = (lev[j, (i - 1) % w] + lev[j, i]) / 2
+            assert abs(at("bilinear", i / w, (j + 0.5) / h) - want) <= 2 ** -20, (i, j)
+    # wrap across u = 0 and v = 0: a quarter texel left of the edge, 3/4 of the last column and 1/4 of the first
+    want = F(0.75) * lev[0, w - 1] + F(0.25) * lev[0, 0]
+    assert abs(at("bilinear", -0.25 / w, 0.5 / h) - want) <= 2 ** -20
+    want = F(0.75) * lev[h - 1, 0] + F(0.25) * lev[0, 0]
+    assert abs(at("bilinear", 0.5 / w, -0.25 / h) - want) <= 2 ** -20
+    assert at("nearest", -0.25 / w, 0.5 / h) == lev[0, w - 1] and at("nearest", 1 + 0.25 / w, 0.5 / h) == lev[0, 0]
+    # fu == 1.0f: x - floor(x) of a tiny negative x rounds to 1
+    fu, fv = R.frac_uv(ident, [[-1e-9, -1e-9]])
+    assert fu[0] == F(1) and fv[0] == F(1)
+    assert at("nearest", -1e-9, -1e-9) == lev[h - 1, w - 1]                          # min(W, W - 1)
+    want = (lev[h - 1, w - 1] + lev[h - 1, 0] + lev[0, w - 1] + lev[0, 0]) / 4      # px = W - 0.5: halfway between the last texel and the first
+    assert abs(at("bilinear", -1e-9, -1e-9) - want) <= 2 ** -20
+    # a uniform image returns the constant EXACTLY, whatever the weights (a + t * (b - a) with b == a)
+    rng = np.random.RandomState(3)
+    uv = rng.uniform(-2, 3, (500, 2)).astype(F)
+    const = R.grey_texels(np.full((h, w), F(0.7312)))
+    for filt in ("nearest", "bilinear"):
+        for m in (ident, to_uv6(TO_UVS["skew"])):
+            got = R.lookup(const, w, h, filt, m, uv, np.full((500, 4), 500, F))
+            assert np.all(got.view(np.uint32) == F(0.7312).view(np.uint32)), filt
+
+
+def floor_meshes(hm, texture, n=3, twosided=False):
+    meshes = hm.cbox_meshes()[:n]
+    floor = next(m for m in meshes if m.name == "cbox_floor")
+    floor.bsdf = {"type": "diffuse", "texture": texture, "twosided": twosided}
+    floor.texcoords = [((0, 0), (1, 0), (1, 1), (0, 1)) for _ in floor.faces]
+    return meshes
+
+
+def host_library():
+    import __graft_entry__ as ge
+    ge.build_gpu_library()
+    ge.build_host_library()
+    return importlib.import_module("misaki-render_amd.hostlib")
+
+
+def texels_of(desc):
+    return np.ctypeslib.as_array(desc.texels, (desc.n_texels * 3,)).reshape(-1, 3).copy() if desc.n_texels else np.zeros((0, 3), F)
+
+
+def test_the_two_flatteners_agree(hostmirror, abi, tmp_path):
+    """(3) write_scene_xml writes the pixels as a PFM and the <texture type="bitmap"> element; the C++ host reads them back into
+    the descriptor the mirror makes.  Coefficients within the tolerance test_xml_round_trip_through_the_host_library uses."""
+    hostlib = host_library()
+    rng = np.random.RandomState(11)
+    img = rng.uniform(0, 1, (3, 5, 3)).astype(F)                      # 5 x 3: W = 5, H = 3
+    img2 = rng.uniform(0, 1, (2, 4, 3)).astype(F)
+    mat = [3, 0.5, 0.25, 9, -0.5, 4, 0.125, 9, 9, 9, 9, 9, 0, 0, 0, 1]
+    meshes = floor_meshes(hostmirror, bitmap(img, "nearest", matrix=mat))
+    ceiling = next(m for m in meshes if m.name == "cbox_ceiling")
+    ceiling.bsdf = {"type": "diffuse", "texture": bitmap(img2, "bilinear", scale=(2, 3))}
+    xml = hostmirror.write_scene_xml(meshes, str(tmp_path), 16, 16, 1)
+    assert os.path.exists(tmp_path / "textures" / "cbox_floor.pfm") and 'type="bitmap"' in open(xml).read()
+    d, r = hostlib.HostScene(xml).flatten().desc, hostmirror.flatten(meshes, 16, 16).desc
+    assert d.n_textures == r.n_textures == 2 and d.n_texels == r.n_texels == 15 + 8
+    for k in range(2):
+        a, b = d.textures[k], r.textures[k]
+        assert (a.type, a.width, a.height, a.first_texel) == (b.type, b.width, b.height, b.first_texel) and list(a.to_uv) == list(b.to_uv)
+    assert (r.textures[0].type, r.textures[0].width, r.textures[0].height, r.textures[0].first_texel) == (abi.MSK_TEXTURE_BITMAP_NEAREST, 5, 3, 0)
+    assert (r.textures[1].type, r.textures[1].width, r.textures[1].height, r.textures[1].first_texel) == (abi.MSK_TEXTURE_BITMAP, 4, 2, 15)   # consecutive
+    assert list(r.textures[0].to_uv) == [3, 0.5, 0.25, -0.5, 4, 0.125]
+    ta, tb = texels_of(d), texels_of(r)
+    assert np.allclose(ta, tb, rtol=2e-4, atol=2e-6)
+    r2s = importlib.import_module("misaki-render_amd.rgb2spec")
+    assert np.array_equal(tb[7], F(r2s.srgb_model_fetch(tuple(float(x) for x in img[1, 2]))))      # row-major, row 0 first: texel 7 = (j 1, i 2)
+    for i in range(3):
+        assert d.bsdfs[d.meshes[i].bsdf_id].reflectance_texture == r.bsdfs[r.meshes[i].bsdf_id].reflectance_texture
+    # defaults of the plugin: bilinear, identity to_uv
+    text = open(xml).read()
+    start, end = text.index('<texture name="reflectance"'), text.index('</texture>') + len('</texture>')
+    (tmp_path / "dflt.xml").write_text(text[:start] + '<texture name="reflectance" type="bitmap"><string name="filename" value="textures/cbox_floor.pfm"/></texture>' + text[end:])
+    t = hostlib.HostScene(str(tmp_path / "dflt.xml")).flatten().desc.textures[0]
+    assert t.type == abi.MSK_TEXTURE_BITMAP and list(t.to_uv) == [1, 0, 0, 0, 1, 0] and (t.width, t.height) == (5, 3)
+    m = hostmirror.flatten(floor_meshes(hostmirror, {"type": "bitmap", "pixels": img}), 16, 16).desc.textures[0]
+    assert m.type == abi.MSK_TEXTURE_BITMAP and list(m.to_uv) == [1, 0, 0, 0, 1, 0]
+    # components are clamped to [0, 1] before the fetch (a reflectance), and equal colours are fetched once: equal coefficients
+    hot = np.array([[[1.5, -0.25, 0.5], [1.0, 0.0, 0.5]]], F)
+    tx = hostmirror.flatten(floor_meshes(hostmirror, bitmap(hot)), 16, 16).texels
+    assert np.array_equal(tx[0].view(np.uint32), tx[1].view(np.uint32))
+    # a texture on anything but the diffuse reflectance remains an error
+    b0, b1 = text.rindex('<bsdf type="diffuse">', 0, start), text.index('</bsdf>', end) + len('</bsdf>')
+    (tmp_path / "spec.xml").write_text(text[:b0] + '<bsdf type="roughconductor"><rgb name="eta" value="0.2, 0.92, 1.1"/><rgb name="k" value="3.9, 2.45, 2.14"/>'
+                                       '<texture name="specular_reflectance" type="bitmap"><string name="filename" value="textures/cbox_floor.pfm"/></texture></bsdf>' + text[b1:])
+    with pytest.raises(hostlib.HostError) as e:
+        hostlib.HostScene(str(tmp_path / "spec.xml")).flatten()
+    assert "cannot be evaluated by the GPU path integrator" in str(e.value)
+
+
+def srgb_decode(v):
+    """IEC 61966-2-1 in double, rounded once to float"""
+    v = np.asarray(v, np.float64)
+    hi = np.vectorize(lambda x: math.pow((x + 0.055) / 1.055, 2.4), otypes=[np.float64])       # (the C library's pow, element by element)
+    return np.where(v <= 0.04045, v / 12.92, hi(v)).astype(F)
+
+
+def test_image_readers(hostmirror, tmp_path):
+    """(4) PFM (1 / 3 channels, both byte orders, bottom row first in the file) and binary PGM / PPM (maxval 255 and 65535, sRGB
+    decode unless raw); the image's TOP row is texel row 0; errors name the file."""
+    hostlib = host_library()
+    rng = np.random.RandomState(7)
+    img = rng.uniform(-1, 2, (4, 3, 3)).astype(F)                     # rows differ; values outside [0, 1] survive the reader
+    img[0, 0] = [np.inf, -0.0, 1e-42]
+    for little in (True, False):
+        p = tmp_path / ("le.pfm" if little else "be.pfm")
+        hostmirror.write_pfm(str(p), img, little_endian=little)
+        got = hostlib.read_image(p)
+        assert got.shape == (4, 3, 3) and np.array_equal(got.view(np.uint32), img.view(np.uint32)), little
+    hostlib.write_image(tmp_path / "host.pfm", img)                   # the host's own writer (top row first in memory)
+    assert np.array_equal(hostlib.read_image(tmp_path / "host.pfm").view(np.uint32), img.view(np.uint32))
+    # the file stores the bottom row first: its first scanline is the image's last row
+    raw = open(tmp_path / "le.pfm", "rb").read()
+    assert raw.startswith(b"PF\n3 4\n-1.0\n") and np.array_equal(np.frombuffer(raw[-4 * 36:][:36], "<f4"), img[3].reshape(-1))
+    grey = rng.uniform(0, 1, (2, 5)).astype(F)
+    hostmirror.write_pfm(str(tmp_path / "g.pfm"), grey)
+    assert np.array_equal(hostlib.read_image(tmp_path / "g.pfm"), np.repeat(grey[..., None], 3, 2))
+    # P6 at maxval 255 (a comment in the header) and at 65535 (two bytes, most significant first)
+    b8 = rng.randint(0, 256, (3, 4, 3)).astype(np.uint8)
+    b8[0, 0] = [0, 10, 11]                                            # both sides of the 0.04045 knee (10.3 / 255)
+    (tmp_path / "a.ppm").write_bytes(b"P6\n# made by a test\n4 3\n255\n" + b8.tobytes())
+    assert np.array_equal(hostlib.read_image(tmp_path / "a.ppm"), srgb_decode(b8 / 255.0))
+    assert np.array_equal(hostlib.read_image(tmp_path / "a.ppm", raw=True), (b8 / 255.0).astype(F))
+    b16 = rng.randint(0, 65536, (2, 3, 3)).astype(np.uint16)
+    (tmp_path / "b.ppm").write_bytes(b"P6 3 2 65535\n" + b16.astype(">u2").tobytes())
+    assert np.array_equal(hostlib.read_image(tmp_path / "b.ppm"), srgb_decode(b16 / 65535.0))
+    # P5 replicates to grey; rows top first
+    g8 = rng.randint(0, 256, (3, 2)).astype(np.uint8)
+    (tmp_path / "c.pgm").write_bytes(b"P5\n2 3\n255\n" + g8.tobytes())
+    assert np.array_equal(hostlib.read_image(tmp_path / "c.pgm"), np.repeat(srgb_decode(g8 / 255.0)[..., None], 3, 2))
+    # the plugin keeps the orientation: the image's top row becomes texel row 0, and `raw` reaches the reader
+    meshes = floor_meshes(hostmirror, bitmap(np.zeros((1, 1, 3), F)))
+    xml = hostmirror.write_scene_xml(meshes, str(tmp_path), 16, 16, 1)
+    text = open(xml).read()
+    start, end = text.index('<texture name="reflectance"'), text.index('</texture>') + len('</texture>')
+    r2s = importlib.import_module("misaki-render_amd.rgb2spec")
+
+    def load(body, name):
+        (tmp_path / name).write_text(text[:start] + '<texture name="reflectance" type="bitmap">' + body + '</texture>' + text[end:])
+        return hostlib.HostScene(str(tmp_path / name)).flatten().desc
+    d = load('<string name="filename" value="a.ppm"/><boolean name="raw" value="true"/>', "raw.xml")
+    want = np.array([r2s.srgb_model_fetch(tuple(float(x) for x in px)) for px in (b8 / 255.0).astype(F).reshape(-1, 3)], F)
+    assert (d.textures[0].width, d.textures[0].height) == (4, 3) and np.allclose(texels_of(d), want, rtol=2e-4, atol=2e-6)
+    # the four errors, each naming the file
+    cases = {"missing.pfm": None, "short.pfm": raw[:-5], "magic.pfm": b"P3\n1 1\n255\n0 0 0\n"}
+    for name, content in cases.items():
+        if content is not None:
+            (tmp_path / name).write_bytes(content)
+        with pytest.raises(hostlib.HostError) as e:
+            load('<string name="filename" value="%s"/>' % name, "bad.xml")
+        assert name in str(e.value), str(e.value)
+        with pytest.raises(hostlib.HostError) as e:
+            hostlib.read_image(tmp_path / name)
+        assert name in str(e.value)
+    with pytest.raises(hostlib.HostError) as e:
+        load('<string name="filename" value="le.pfm"/><string name="wrap_mode" value="clamp"/>', "clamp.xml")
+    assert "le.pfm" in str(e.value) and "wrap_mode" in str(e.value) and "clamp" in str(e.value)
+    with pytest.raises(hostlib.HostError) as e:
+        load('<string name="filename" value="le.pfm"/><string name="filter_type" value="cubic"/>', "cubic.xml")
+    assert "filter_type" in str(e.value)
+
+
+@pytest.fixture(scope="module")
+def plan_exe(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("launch_plan_bitmap") / "launch_plan_bitmap_check")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-o", out, os.path.join(ROOT, "tests", "native", "launch_plan_bitmap_check.cpp")])
+    return out
+
+
+@pytest.mark.parametrize("knobs", LP.KNOB_SETS, ids=lambda k: ",".join(f"{a}={b}" for a, b in k.items()) or "defaults")
+def test_plan_with_a_bitmap(plan_exe, knobs):
+    """(5) has_bitmap selects SHADE_BITMAP everywhere and changes nothing else: every other field equals the plan of the same
+    facts with a dielectric instead (the fused kernels are not withheld)."""
+    env = {k: v for k, v in os.environ.items() if not k.startswith("MSK_")}
+    env.update(knobs)
+    r = subprocess.run([plan_exe], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr
+    assert r.stdout.split() == ["cases", str(7 * 32 * 4 * len(LP.REGION_SIZES) * len(LP.LDS))]
+
+
+# ===================================================================================================== GPU: the probe
+def probe_points(rng, w, h, n=4096):
+    """random points in [-2, 3]^2 and the crafted ones: every texel centre and edge, 0, 1, -0.0, -1e-9, 0.5"""
+    us = sorted({i / w for i in range(w + 1)} | {(i + 0.5) / w for i in range(w)} | {0.0, 1.0, -1e-9, 0.5})
+    vs = sorted({j / h for j in range(h + 1)} | {(j + 0.5) / h for j in range(h)} | {0.0, 1.0, -1e-9, 0.5})
+    crafted = [(u, v) for u in us + [-0.0] for v in vs + [-0.0]]
+    if len(crafted) > 1500:                                            # 16 x 16: the full grid along the diagonal and both axes
+        crafted = [(u, v) for u, v in crafted if u in (0.0, 0.5, -1e-9) or v in (0.0, 0.5, -1e-9) or abs(u - v) < 0.04]
+    uv = np.concatenate([rng.uniform(-2, 3, (n, 2)), np.array(crafted)]).astype(F)
+    uv[n] = [-0.0, -0.0]
+    return uv
+
+
+PROBE_IMAGES = ["1x1", "2x2", "3x5", "5x3", "16x16", "black", "white"]
+
+
+@pytest.fixture(scope="module")
+def probe_scene(gpu_ctx, hostmirror, abi):
+    """ONE scene that holds every texture of the probe tests (no surface shows them): images x filters x to_uv, then the
+    checkerboards and the 2x2 nearest images of tests 7 and 8."""
+    rng = np.random.RandomState(21)
+    images = {}
+    for name in PROBE_IMAGES:
+        if "x" in name:
+            w, h = (int(x) for x in name.split("x"))
+            images[name] = rng.uniform(0, 1, (h, w, 3)).astype(F)
+        else:
+            images[name] = np.full((1, 1, 3), 0.0 if name == "black" else 1.0, F)
+    specs, index = [], {}
+    for name in PROBE_IMAGES:
+        for filt in ("bilinear", "nearest"):
+            for uvn, uvspec in TO_UVS.items():
+                specs.append(bitmap(images[name], filt, **uvspec))
+                index[(name, filt, uvn)] = len(specs) + 1                 # 1-based, after the floor's own texture
+    for uvn, uvspec in TO_UVS.items():
+        specs.append(dict({"type": "checkerboard", "color0": C0, "color1": C1}, **uvspec))
+        index[("checker", uvn)] = len(specs) + 1
+        specs.append(bitmap(checker_pixels(), "nearest", **uvspec))
+        index[("checker2x2", uvn)] = len(specs) + 1
+    meshes = floor_meshes(hostmirror, bitmap(images["2x2"]), n=8)
+    flat = hostmirror.flatten(meshes, 16, 16, extra_textures=specs)
+    scene = abi.Scene(gpu_ctx, flat)
+    yield scene, flat, images, index
+    scene.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", PROBE_IMAGES)
+def test_probe_equals_the_restatement_bit_for_bit(probe_scene, oracle, name):
+    """(6) k_eval_texture — the shading kernels' lookup function — against bitmap_ref, as uint32."""
+    scene, flat, images, index = probe_scene
+    h, w = images[name].shape[:2]
+    rng = np.random.RandomState(5)
+    uv = probe_points(rng, w, h)
+    wl = rng.uniform(360, 830, (len(uv), 4)).astype(F)
+    for filt in ("bilinear", "nearest"):
+        for uvn, uvspec in TO_UVS.items():
+            k = index[(name, filt, uvn)]
+            t = flat.desc.textures[k - 1]
+            assert (t.width, t.height) == (w, h)
+            coeffs = flat.texels[t.first_texel:t.first_texel + w * h].reshape(h, w, 3)
+            want = R.lookup(R.oracle_texels(oracle, coeffs), w, h, filt, list(t.to_uv), uv, wl)
+            got = scene.eval_texture(k, uv, wl)
+            bad = (got.view(np.uint32) != want.view(np.uint32)).any(-1)
+            print("BITMAP probe %s %s %s: %d points, %d differ" % (name, filt, uvn, len(uv), int(bad.sum())))
+            assert not bad.any(), (name, filt, uvn, int(bad.sum()), uv[bad][:3], got[bad][:3], want[bad][:3])
+    if name == "white":
+        assert got.min() > 0.9
+    if name == "black":
+        assert got.max() == 0
+
+
+@pytest.mark.gpu
+def test_probe_on_a_checkerboard_equals_the_oracle(probe_scene, oracle, abi):
+    """(7) the refactored uv code from the other side: the probe on checkerboards against oracle.checkerboard + srgb_model_eval."""
+    scene, flat, images, index = probe_scene
+    rng = np.random.RandomState(6)
+    uv = probe_points(rng, 2, 2, n=1024)
+    wl = rng.uniform(360, 830, (len(uv), 4)).astype(F)
+    for uvn in TO_UVS:
+        k = index[("checker", uvn)]
+        t = flat.desc.textures[k - 1]
+        assert t.type == abi.MSK_TEXTURE_CHECKERBOARD
+        which = np.array([oracle.checkerboard(t, float(a), float(b)) for a, b in uv])
+        want = np.stack([oracle.srgb_model_eval(t.color1[:] if c else t.color0[:], wl[i]) for i, c in enumerate(which)])
+        got = scene.eval_texture(k, uv, wl)
+        assert 0 < which.sum() < len(which)
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), uvn
+
+
+@pytest.mark.gpu
+def test_probe_nearest_2x2_is_the_checkerboard(probe_scene):
+    """(8) same to_uv, random uv: a nearest 2x2 image of the two colours returns what the checkerboard returns, but where fu or
+    fv is exactly 0.5 (`> .5` against floor(2 fu)).  Those points are taken out, and they must be rare."""
+    scene, flat, images, index = probe_scene
+    rng = np.random.RandomState(8)
+    uv = rng.uniform(-2, 3, (8192, 2)).astype(F)
+    wl = rng.uniform(360, 830, (len(uv), 4)).astype(F)
+    for uvn in TO_UVS:
+        a, b = index[("checker", uvn)], index[("checker2x2", uvn)]
+        fu, fv = R.frac_uv(list(flat.desc.textures[a - 1].to_uv), uv)
+        keep = (fu != F(0.5)) & (fv != F(0.5))
+        assert (~keep).mean() < 1e-3
+        got_c, got_b = scene.eval_texture(a, uv[keep], wl[keep]), scene.eval_texture(b, uv[keep], wl[keep])
+        assert np.array_equal(got_c.view(np.uint32), got_b.view(np.uint32)), uvn
+        assert len(got_c) > 8000
+
+
+# ===================================================================================================== GPU: renders
+def pcg(abi, **kw):
+    return abi.render_params(rng_mode=abi.MSK_RNG_PCG_BLOCK, **kw)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("filt", ["bilinear", "nearest"])
+def test_uniform_image_is_the_constant_reflectance(gpu_ctx, oracle, hostmirror, abi, filt):
+    """(9) a 3x5 image whose texels all equal C0 on the Cornell floor: the film equals, bit for bit, the oracle's film of the same
+    scene (same texcoords: they turn the tangent frame) with the constant reflectance C0.  Counter RNG, and the PCG block mode
+    (k_path_serial_b)."""
+    img = np.broadcast_to(np.asarray(C0, F), (5, 3, 3))
+    plain = hostmirror.cbox_meshes()
+    floor = next(m for m in plain if m.name == "cbox_floor")
+    floor.reflectance = C0
+    floor.texcoords = [((0, 0), (1, 0), (1, 1), (0, 1)) for _ in floor.faces]
+    for (w, prm) in ((64, abi.render_params(spp=8, seed=3)), (32, pcg(abi, spp=2, seed=3))):
+        flat = checker_floor_scene(hostmirror, w, w, bitmap(img, filt, scale=(3, 2)))
+        assert flat.desc.textures[0].width == 3 and flat.desc.textures[0].height == 5
+        g, o = abi.Scene(gpu_ctx, flat), oracle.scene(hostmirror.flatten(plain, w, w))
+        film, st = g.render(prm)
+        ref, rst = o.render(prm, threads=8)
+        g.close(); o.close()
+        assert st.samples == rst.samples == w * w * prm.spp
+        assert np.array_equal(film.view(np.uint32), ref.view(np.uint32)), (filt, prm.rng_mode, float(np.abs(film - ref).max()))
+
+
+def glass_ball(hm):
+    """a small smooth-dielectric blob on the floor: 40 triangles, so that tables, tree and traversal stacks of the scene fit one
+    block's LDS side by side, which is what the fused k_wavefront_b needs"""
+    ball = hm.blob_mesh("glass", (370, 90, 170), 80, 5, 5, hm.WHITE, seed=2)
+    ball.bsdf = {"type": "dielectric"}
+    return ball
+
+
+def floor_cases(hm):
+    """the three cases of test_gpu_matches_oracle_on_textured_floors and a fourth with a `dielectric` ball: per case the to_uv of
+    the floor's texture and the rest of checker_floor_scene's arguments"""
+    ball = hm.blob_mesh("ball", (370, 90, 170), 80, 20, 20, hm.WHITE, seed=2)
+    ball.bsdf = {"type": "roughconductor", "alpha": 0.15, "eta": (0.2, 0.92, 1.1), "k": (3.9, 2.45, 2.14), "twosided": True}
+    return {"texcoords_twosided": (dict(scale=(10, 10)), C0, C1, dict(texcoords=True, twosided=True)),
+            "barycentric": (dict(scale=(4, 4)), C0, C1, dict(texcoords=False)),
+            "skew_conductor": (dict(matrix=SKEW), C1, C0, dict(texcoords=True, extra=[ball])),
+            "glass": (dict(scale=(6, 6)), C0, C1, dict(texcoords=True, extra=[glass_ball(hm)]))}
+
+
+def twin_scenes(hm, case, w=96, pads=()):
+    """-> (flat with the nearest 2x2 bitmap, flat with the checkerboard of the same colours)"""
+    uvspec, c0, c1, kw = floor_cases(hm)[case]
+    kw = dict(kw, extra=list(kw.get("extra", [])) + list(pads))
+    return (checker_floor_scene(hm, w, w, bitmap(checker_pixels(c0, c1), "nearest", **uvspec), **kw),
+            checker_floor_scene(hm, w, w, dict({"type": "checkerboard", "color0": c0, "color1": c1}, **uvspec), **kw))
+
+
+def floor_pixels():
+    rng = np.random.RandomState(4)
+    return np.concatenate([rng.randint(0, 96, (40, 2)), np.c_[rng.randint(16, 80, 40), rng.randint(76, 84, 40)]]).astype(np.int32)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["texcoords_twosided", "barycentric", "skew_conductor", "glass"])
+def test_nearest_2x2_renders_the_checkerboard(gpu_ctx, oracle, hostmirror, abi, case):
+    """(10) the device renders the bitmap scene, the oracle the checkerboard scene of the same two colours: samples and films
+    bit-equal, counter RNG and PCG block.  This shows that the shading kernels hand the hit's uv to the lookup (interpolated
+    texcoords, and barycentrics for a mesh without them).  A hit exactly on a cell edge (fu or fv == 0.5) would differ — about
+    1e-7 per textured hit; none does with these seeds."""
+    fb, fc = twin_scenes(hostmirror, case)
+    assert fb.desc.textures[0].type == abi.MSK_TEXTURE_BITMAP_NEAREST and fc.desc.textures[0].type == abi.MSK_TEXTURE_CHECKERBOARD
+    g, o = abi.Scene(gpu_ctx, fb), oracle.scene(fc)
+    prm = abi.render_params(spp=16, seed=11)
+    gx, gp = g.sample_pixels(prm, floor_pixels())
+    ox, op = o.sample_pixels(prm, floor_pixels())
+    assert np.array_equal(gp, op)
+    bad = (gx.view(np.uint32) != ox.view(np.uint32)).any(-1)
+    assert not bad.any(), (int(bad.sum()), gx[bad][:3], ox[bad][:3])
+    for prm in (abi.render_params(spp=8, seed=5), pcg(abi, spp=8, seed=5)):
+        film, st = g.render(prm)
+        ref, rst = o.render(prm, threads=16)
+        differ = int((film.view(np.uint32) != ref.view(np.uint32)).any(-1).sum())
+        print("BITMAP end to end %s rng %d: %d pixels differ" % (case, prm.rng_mode, differ))
+        assert differ == 0, (case, prm.rng_mode, differ, float(np.abs(film - ref).max()))
+        assert st.samples == rst.samples
+    g.close(); o.close()
+
+
+SPLIT, FUSED_PART, FUSED_ALL, ANY = "split", "fused part", "fused all", "any"
+KNOBS = ("MSK_FUSED", "MSK_SORT", "MSK_STREAMS", "MSK_FUSED_HBM", "MSK_FUSED_TAIL_PCT", "MSK_BVH_BUILD", "MSK_WIDE_BVH", "MSK_QUANT_BVH", "MSK_LDS_SCENE_KB")
+# the knob sets of test_dielectric_parity.VARIANTS on the glass + bitmap scene (tables and tree in LDS: k_shade_gen_b<true>,
+# k_wavefront_b), and what msk_stats must show; with MSK_LDS_SCENE_KB=0 the tree leaves LDS and the tables stay: no fused kernel
+LDS_VARIANTS = [({}, ANY), ({"MSK_FUSED": "1"}, FUSED_ALL), ({"MSK_SORT": "0", "MSK_STREAMS": "1"}, ANY), ({"MSK_FUSED_TAIL_PCT": "50"}, FUSED_PART),
+                ({"MSK_BVH_BUILD": "gpu"}, ANY), ({"MSK_WIDE_BVH": "8"}, ANY), ({"MSK_QUANT_BVH": "1"}, ANY),
+                ({"MSK_LDS_SCENE_KB": "0", "MSK_FUSED": "1"}, SPLIT), ({"MSK_LDS_SCENE_KB": "0", "MSK_WIDE_BVH": "8"}, SPLIT),
+                ({"MSK_LDS_SCENE_KB": "0", "MSK_QUANT_BVH": "1", "MSK_BVH_BUILD": "gpu"}, SPLIT)]
+# the same scene padded past the small-table limit, tree in HBM: k_shade_gen_b<false> with every table from HBM, k_wavefront_h_b
+HBM_VARIANTS = [({"MSK_LDS_SCENE_KB": "0", "MSK_FUSED_HBM": "0"}, SPLIT), ({"MSK_LDS_SCENE_KB": "0"}, ANY),
+                ({"MSK_LDS_SCENE_KB": "0", "MSK_FUSED_TAIL_PCT": "50"}, FUSED_PART), ({"MSK_LDS_SCENE_KB": "0", "MSK_FUSED": "1"}, FUSED_ALL)]
+variant_id = lambda e: ",".join("%s=%s" % kv for kv in sorted(e.items())) or "defaults"
+
+
+def hbm_pads(hm):
+    """faceless meshes that push the small tables past their LDS limit, as test_table_placement.py pads; the glass ball's 40
+    triangles alone do not fill the 40 KB of the per-triangle tables, so a diffuse blob joins them"""
+    filler = hm.blob_mesh("filler", (150, 420, 400), 60, 16, 16, hm.WHITE, seed=9)
+    fb, _ = twin_scenes(hm, "glass", pads=[filler])
+    return [filler] + T.faceless_pads(hm, T.SMALL_TABLES_F4 + 1 - T.table_plan(fb)["small_f4"])
+
+
+@pytest.fixture(scope="module")
+def variant_reference(oracle, hostmirror, abi):
+    """the oracle's checkerboard samples and film of the glass scene, plain and padded: computed once, never changed"""
+    out = {}
+    for name, pads in (("lds", []), ("hbm", hbm_pads(hostmirror))):
+        fb, fc = twin_scenes(hostmirror, "glass", pads=pads)
+        o = oracle.scene(fc)
+        xyz, pos = o.sample_pixels(abi.render_params(spp=16, seed=5), floor_pixels())
+        film, st = o.render(abi.render_params(spp=8, seed=5), threads=16)
+        o.close()
+        for a in (xyz, pos, film):
+            a.setflags(write=False)
+        out[name] = dict(flat=fb, plan=T.table_plan(fb), xyz=xyz, pos=pos, film=film, samples=st.samples)
+    return out
+
+
+def test_variant_scenes_sit_where_the_tests_say(variant_reference):
+    lds, hbm = variant_reference["lds"]["plan"], variant_reference["hbm"]["plan"]
+    assert lds["lds_tables"] and lds["small_staged"]
+    assert not hbm["lds_tables"] and not hbm["small_staged"] and hbm["small_f4"] == T.SMALL_TABLES_F4 + 1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which,env,expect", [("lds", e, x) for e, x in LDS_VARIANTS] + [("hbm", e, x) for e, x in HBM_VARIANTS],
+                         ids=lambda v: variant_id(v) if isinstance(v, dict) else str(v).replace(" ", "_"))
+def test_every_execution_variant(gpu_ctx, abi, variant_reference, monkeypatch, which, env, expect):
+    """(11) the glass + bitmap scene under the library's execution variants; msk_stats says which kernels made the film."""
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    want = variant_reference[which]
+    g = abi.Scene(gpu_ctx, want["flat"])
+    gx, gp = g.sample_pixels(abi.render_params(spp=16, seed=5), floor_pixels())
+    film, st = g.render(abi.render_params(spp=8, seed=5))
+    g.close()
+    got = "trace %d shade %d wavefront %d" % (st.launches_trace, st.launches_shade, st.launches_wavefront)
+    print("BITMAP variant %s %s: %s" % (which, variant_id(env), got))
+    assert np.array_equal(gp.view(np.uint32), want["pos"].view(np.uint32))
+    assert np.array_equal(gx.view(np.uint32), want["xyz"].view(np.uint32)), env
+    assert np.array_equal(film.view(np.uint32), want["film"].view(np.uint32)), (env, float(np.abs(film - want["film"]).max()))
+    assert st.samples == want["samples"]
+    if expect == SPLIT:
+        assert st.launches_wavefront == 0 and st.launches_shade > 0 and st.launches_trace > 0, got
+    elif expect == FUSED_PART:
+        assert st.launches_wavefront > 0 and st.launches_shade > 0 and st.launches_trace > 0, got
+    elif expect == FUSED_ALL:
+        assert st.launches_wavefront > 0 and st.launches_shade == 0 and st.launches_trace == 0, got
+    else:
+        assert st.launches_shade > 0 and st.launches_trace > 0, got
+
+
+@pytest.mark.gpu
+def test_gpu_rejects_bad_bitmap_descriptors(gpu_ctx, hostmirror, abi):
+    """(12) each with its own message"""
+    def fresh():
+        return checker_floor_scene(hostmirror, 16, 16, bitmap(np.full((2, 3, 3), 0.5, F)))
+
+    def refused(flat, text, code=None):
+        with pytest.raises(abi.MskError) as e:
+            abi.Scene(gpu_ctx, flat)
+        assert text in str(e.value), str(e.value)
+        assert code is None or e.value.code == code
+    abi.Scene(gpu_ctx, fresh()).close()                                # the scene itself is fine
+    flat = fresh()
+    flat.desc.textures[0].width = 0
+    refused(flat, "texture 0: a bitmap of 0 x 2 texels", abi.MSK_ERR_INVALID_ARG)
+    flat = fresh()
+    flat.desc.textures[0].first_texel = 1
+    refused(flat, "reach past the scene's n_texels 6", abi.MSK_ERR_INVALID_ARG)
+    flat = fresh()
+    flat.desc.textures[0].first_texel = 0xffffffff                     # no wrap-around in the sum
+    refused(flat, "reach past the scene's n_texels 6")
+    flat = fresh()
+    flat.desc.texels = None
+    refused(flat, "texels array is missing", abi.MSK_ERR_INVALID_ARG)
+    flat = fresh()
+    flat.texels[4, 1] = np.nan
+    refused(flat, "texel 4 holds a NaN coefficient", abi.MSK_ERR_INVALID_ARG)
+    flat = fresh()
+    flat.desc.abi_version = 7
+    refused(flat, "abi_version 7 != 8", abi.MSK_ERR_INVALID_ARG)
+    flat = fresh()
+    flat.desc.textures[0].type = 7
+    refused(flat, "texture 0: type 7")
+    flat = fresh()
+    g = abi.Scene(gpu_ctx, flat)
+    with pytest.raises(abi.MskError) as e:
+        g.eval_texture(2, np.zeros((1, 2), F), np.full((1, 4), 500, F))
+    assert "texture 2 out of range" in str(e.value)
+    g.close()
