@@ -63,6 +63,8 @@ extern "C" {
 #define MSK_TEXTURE_BITMAP_NEAREST 3 /* "bitmap", nearest-texel filter                                        */
 
 #define MSK_EMITTER_CONSTANT   1   /* "constant" emitters/constant.cpp:95 (environment; mesh_id = -1, at most one) */
+#define MSK_EMITTER_ENVMAP     2   /* "envmap": a lat-long radiance image, importance-sampled (environment; mesh_id = -1; at most one environment
+                                      emitter per scene, `constant` or `envmap`; msk_envmap_desc + msk_gpu_scene_create_env below) */
 
 /* AOV channel groups of the "aov" integrator (integrators/aov.cpp:21-28,87-144); channels per type: 1 3 2 3 3 4 */
 #define MSK_AOV_DEPTH          0   /* si.t, 0 on a miss                                  (aov.cpp:97-99)   */
@@ -213,6 +215,49 @@ typedef struct msk_emitter_desc {
                                   sigmoid; radiance / d65_scale unused); 0 = the srgb_d65 form above */
 } msk_emitter_desc;
 
+/*
+ * The image of an MSK_EMITTER_ENVMAP emitter.  Its msk_emitter_desc has mesh_id = -1, radiance = {0, 0, +inf}, d65_scale =
+ * scale / 10568 and radiance_regular = 0: the emitter's own table T_e(l) = d65(l) * d65_scale, as for every srgb_d65 radiance.
+ * (The reference's emitters/envmap.cpp is RGB-typed and not built; kept from it: the lat-long convention, dist = 2 * radius, the
+ * Jacobian 1 / (2 pi^2 sin theta), to_world applied to directions.  Not kept: core/distribution.h's Distribution2D and
+ * path.cpp's stale records on an environment hit)  Everything below is fp32, one operation at a time.
+ *
+ * Radiance.  width x height texels, row-major, row 0 = the image's top row = theta near 0.  A texel of linear RGB c >= 0 is
+ * {c0, c1, c2, w}: the coefficients srgb_model_fetch(c / (2 max c)) and the factor w = 2 max c, the srgb_d65 flattening; a black
+ * texel is {0, 0, 0, 0}.  L(u, v, l) = T_e(l) * bilerp_k(w_k * S(coeff_k, l)) with the bilinear form of MSK_TEXTURE_BITMAP
+ * (px = u * W - 0.5, ..., a + t (b - a): spectral VALUES are interpolated), except that v CLAMPS at the poles (j0 < 0 -> 0,
+ * j1 >= H -> H - 1) while u wraps.
+ *
+ * Direction to uv.  dl = R^T d with R = to_world (row-major 3x3; must be a rotation: |R R^T - 1| <= 1e-4 per entry and
+ * det > 0, anything else is refused).  u = atan2(dl.x, -dl.z) / (2 pi), then u - floor(u) (a result of 1 becomes 0);
+ * v = atan2(sqrt(dl.x^2 + dl.z^2), dl.y) / pi.  atan2(y, x) = x == 0 ? (y > 0 ? pi/2 : y < 0 ? -pi/2 : 0) : det_atan(y / x)
+ * (+ pi for x < 0 and y >= 0, - pi for x < 0 and y < 0); pi and 2 pi are the fp32 constants.  uv to direction:
+ * theta = pi v, phi = 2 pi u, (st, ct) = det_sincos(theta), (sp, cp) = det_sincos(phi), dl = (sp st, ct, -cp st), d = R dl.
+ *
+ * Distribution.  Piecewise constant over the texels from the host's weights (one per texel, finite, >= 0, not all zero; the
+ * host plugin supplies (sum of the luminance of the 3x3 neighbourhood, u wrapped, v clamped) * sin(pi (j + .5) / H), which is
+ * positive wherever the bilinear lookup is).  The library builds, in double and stored as float, per row a cumulative table of
+ * W + 1 entries (0 .. 1; a row of zero weight is 0 .. 0 1) and the marginal of H + 1 entries over the row sums.
+ * Sampling (u.x, u.y): row j from u.y in the marginal, then column i from u.x in row j, both by the upper-bound search + clamp
+ * + sample_reuse of core/distribution.h:106-116; the reused fractions dv, du are clamped to <= 1 - 2^-24;
+ * uv = ((i + du) / W, (j + dv) / H) (either can still round up to 1: the lookup wraps u and clamps v); p(uv) = (marg[j+1] - marg[j]) * (cond[j][i+1] - cond[j][i]) * (float) W * (float) H;
+ * sin theta = sqrt(max(dl.x^2 + dl.z^2, eps^2)) with eps = 2^-24; pdf_omega = p / (2 pi^2 sin theta) (2 pi^2 = 2 * (pi * pi) in fp32).
+ * pdf(direction): uv as above, i = min((int) (u W), W - 1), j likewise, the same product.  For a direction the sampler produced
+ * this is the number the sampler returned, bit for bit, when to_world is the identity (R^T (R dl) is then dl exactly) and the
+ * direction comes back into the cell it was drawn from; it does not when uv lies within the few 2^-24 of a cell border that
+ * det_sincos, the rotation and det_atan move it by (tests/envmap_ref.py: the excluded case, below 0.1 % of random numbers).
+ * Under a rotation R^T (R dl) differs from dl by three roundings per component, 2^-22 absolute on sin theta: the two numbers then
+ * agree within 2^-21 / sin theta + 2^-21 relative.  Next-event value = L(uv) / pdf_omega,
+ * dist = 2 * env_radius; pdf 0 gives no contribution.  On the miss branch the value is L(ray direction) and the emitter density
+ * of the MIS weight pdf(ray direction) / n_emitters (0 after a delta lobe).
+ */
+typedef struct msk_envmap_desc {
+    uint32_t width, height;
+    const float *texels;     /* width * height * 4: c0 c1 c2 w */
+    const float *weights;    /* width * height                 */
+    float to_world[9];       /* row-major rotation             */
+} msk_envmap_desc;
+
 /* PerspectiveCamera (sensors/perspective.cpp:8-42); matrices are row-major 4x4. */
 typedef struct msk_camera_desc {
     float sample_to_camera[16];  /* m_sample_to_camera, sample space in PIXELS */
@@ -348,6 +393,11 @@ const char *msk_gpu_last_error(const msk_ctx *ctx); /* ctx may be NULL */
    part at 1e-8 — the rule keeps a factor of ~100.  The environment variable MSK_PAD_SCALE (margin tests only; the oracle
    reads it too) replaces the 1e-5; a value that is not a number in [1e-7, 1e-3] fails the call with MSK_ERR_INVALID_ARG. */
 int  msk_gpu_scene_create(msk_ctx *ctx, const msk_scene_desc *desc, msk_scene **out_scene);
+/* The same with the image of an MSK_EMITTER_ENVMAP emitter; msk_gpu_scene_create(c, d, o) is msk_gpu_scene_create_env(c, d, NULL, o).
+   A type-2 emitter without `env`, `env` without a type-2 emitter, a second environment emitter, a zero size, a texel factor or
+   weight that is negative or not finite, weights that are all zero and a to_world that is no rotation are MSK_ERR_INVALID_ARG.
+   A group context creates the image on every member. */
+int  msk_gpu_scene_create_env(msk_ctx *ctx, const msk_scene_desc *desc, const msk_envmap_desc *env, msk_scene **out_scene);
 void msk_gpu_scene_destroy(msk_scene *scene);
 
 /* ---- the hot path --------------------------------------------------------- */
@@ -411,6 +461,15 @@ int  msk_gpu_sample_pixels(msk_scene *scene, const msk_render_params *params,
  * device function the shading kernels call, for checkerboards as for bitmaps.  Host pointers.  ABI v8.
  */
 int  msk_gpu_eval_texture(msk_scene *scene, uint32_t texture, uint64_t n, const float *uv, const float *wavelengths, float *out);
+
+/*
+ * The environment image at n directions (unit vectors): dirs n * 3, wavelengths n * 4;
+ * out_radiance n * 4 = L(direction, l), out_pdf n = pdf_omega(direction) (without the 1 / n_emitters of light selection).
+ * msk_gpu_env_sample: u n * 2 -> the direction, uv and pdf_omega the next-event branch draws.  Both run the device functions the
+ * shading kernels call.  Host pointers; MSK_ERR_INVALID_ARG for a scene without an MSK_EMITTER_ENVMAP emitter.
+ */
+int  msk_gpu_env_eval(msk_scene *scene, uint64_t n, const float *dirs, const float *wavelengths, float *out_radiance, float *out_pdf);
+int  msk_gpu_env_sample(msk_scene *scene, uint64_t n, const float *u, float *out_dir, float *out_uv, float *out_pdf);
 
 /* device + build information for logs: fills a NUL-terminated string */
 int  msk_gpu_describe(const msk_ctx *ctx, char *buf, uint64_t buf_size);

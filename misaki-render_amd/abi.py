@@ -18,6 +18,7 @@ MSK_ERR_INVALID_ARG, MSK_ERR_NO_DEVICE, MSK_ERR_HIP, MSK_ERR_OOM, MSK_ERR_UNSUPP
 MSK_BSDF_DIFFUSE, MSK_BSDF_ROUGHCONDUCTOR, MSK_BSDF_ROUGHDIELECTRIC = 0, 1, 2
 MSK_BSDF_DIELECTRIC = 3       # "dielectric" (bsdfs/dielectric.cpp): smooth interface, two delta lobes
 MSK_EMITTER_AREA, MSK_EMITTER_CONSTANT = 0, 1
+MSK_EMITTER_ENVMAP = 2        # "envmap": a lat-long radiance image, importance-sampled (EnvmapDesc, msk_gpu_scene_create_env)
 MSK_TEXTURE_CHECKERBOARD = 1
 MSK_TEXTURE_BITMAP, MSK_TEXTURE_BITMAP_NEAREST = 2, 3       # "bitmap": bilinear / nearest (ABI v8)
 MSK_EMITTER_AREA = 0
@@ -57,6 +58,11 @@ class TextureDesc(C.Structure):
 class EmitterDesc(C.Structure):
     _fields_ = [("type", C.c_int32), ("mesh_id", C.c_int32), ("radiance", C.c_float * 3),
                 ("d65_scale", C.c_float), ("radiance_regular", C.c_uint32)]
+
+
+class EnvmapDesc(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("texels", C.POINTER(C.c_float)),      # width * height * 4: c0 c1 c2 w
+                ("weights", C.POINTER(C.c_float)), ("to_world", C.c_float * 9)]                       # width * height; row-major rotation
 
 
 class CameraDesc(C.Structure):
@@ -127,7 +133,7 @@ LIB_PATH = os.environ.get("MSK_GPU_LIB") or os.path.join(_PKG_DIR, "lib", "libms
 EXPORTS = ["msk_gpu_init", "msk_gpu_shutdown", "msk_gpu_last_error", "msk_gpu_scene_create",
            "msk_gpu_scene_destroy", "msk_gpu_render", "msk_gpu_render_device", "msk_gpu_trace_closest",
            "msk_gpu_trace_any", "msk_gpu_sample_pixels", "msk_gpu_describe", "msk_gpu_render_aov", "msk_gpu_aov_channels",
-           "msk_gpu_eval_texture"]
+           "msk_gpu_eval_texture", "msk_gpu_scene_create_env", "msk_gpu_env_eval", "msk_gpu_env_sample"]
 
 # integrators/aov.cpp:21-28
 MSK_AOV_DEPTH, MSK_AOV_POSITION, MSK_AOV_UV, MSK_AOV_GEO_NORMAL, MSK_AOV_SH_NORMAL, MSK_AOV_PATH_RGBA = range(6)
@@ -174,6 +180,12 @@ def load_library(path=None):
     lib.msk_gpu_aov_channels.restype = C.c_uint32
     lib.msk_gpu_eval_texture.argtypes = [vp, C.c_uint32, u64, vp, vp, vp]
     lib.msk_gpu_eval_texture.restype = C.c_int
+    lib.msk_gpu_scene_create_env.argtypes = [vp, C.POINTER(SceneDesc), C.POINTER(EnvmapDesc), C.POINTER(vp)]
+    lib.msk_gpu_scene_create_env.restype = C.c_int
+    lib.msk_gpu_env_eval.argtypes = [vp, u64, vp, vp, vp, vp]
+    lib.msk_gpu_env_eval.restype = C.c_int
+    lib.msk_gpu_env_sample.argtypes = [vp, u64, vp, vp, vp, vp]
+    lib.msk_gpu_env_sample.restype = C.c_int
     lib.msk_gpu_describe.argtypes = [vp, C.c_char_p, u64]
     lib.msk_gpu_describe.restype = C.c_int
     if path is None:
@@ -226,11 +238,16 @@ class Context:
 class Scene:
     """msk_scene: geometry + BVH + light tables resident in HBM."""
 
-    def __init__(self, ctx, flat):
-        """flat: hostmirror.FlatScene (keeps the numpy arrays the desc points into alive)."""
+    def __init__(self, ctx, flat, envmap=None):
+        """flat: hostmirror.FlatScene (keeps the numpy arrays the desc points into alive).  envmap: the EnvmapDesc of the scene's
+        MSK_EMITTER_ENVMAP emitter; by default the one the flattener made (flat.envmap), if any."""
         self.ctx, self.flat = ctx, flat
         self.handle = C.c_void_p()
-        ctx.check(ctx.lib.msk_gpu_scene_create(ctx.handle, C.byref(flat.desc), C.byref(self.handle)))
+        self.envmap = envmap if envmap is not None else getattr(flat, "envmap", None)
+        if self.envmap is not None:
+            ctx.check(ctx.lib.msk_gpu_scene_create_env(ctx.handle, C.byref(flat.desc), C.byref(self.envmap), C.byref(self.handle)))
+        else:
+            ctx.check(ctx.lib.msk_gpu_scene_create(ctx.handle, C.byref(flat.desc), C.byref(self.handle)))
 
     @property
     def width(self):
@@ -299,6 +316,25 @@ class Scene:
         out = np.empty((len(uv), 4), np.float32)
         self.ctx.check(self.ctx.lib.msk_gpu_eval_texture(self.handle, int(texture), len(uv), _ptr(uv), _ptr(wl), _ptr(out)))
         return out
+
+    def env_eval(self, dirs, wavelengths):
+        """The envmap emitter at unit directions float32[n, 3] and wavelengths float32[n, 4] -> (radiance float32[n, 4], solid-angle
+        density float32[n]): what the shading kernels evaluate for a ray that leaves the scene in that direction."""
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        wl = np.ascontiguousarray(wavelengths, np.float32).reshape(-1, 4)
+        if len(d) != len(wl):
+            raise ValueError("dirs and wavelengths must name the same number of points")
+        rad, pdf = np.empty((len(d), 4), np.float32), np.empty(len(d), np.float32)
+        self.ctx.check(self.ctx.lib.msk_gpu_env_eval(self.handle, len(d), _ptr(d), _ptr(wl), _ptr(rad), _ptr(pdf)))
+        return rad, pdf
+
+    def env_sample(self, u):
+        """The light direction next-event estimation draws from the envmap emitter for the random numbers u float32[n, 2]
+        -> (direction float32[n, 3], uv float32[n, 2], solid-angle density float32[n])."""
+        u = np.ascontiguousarray(u, np.float32).reshape(-1, 2)
+        d, uv, pdf = np.empty((len(u), 3), np.float32), np.empty((len(u), 2), np.float32), np.empty(len(u), np.float32)
+        self.ctx.check(self.ctx.lib.msk_gpu_env_sample(self.handle, len(u), _ptr(u), _ptr(d), _ptr(uv), _ptr(pdf)))
+        return d, uv, pdf
 
     def close(self):
         if self.handle:

@@ -8,6 +8,7 @@
 #include "msk_serial.h"
 #include "msk_bvh.h"
 #include "msk_plan.h"
+#include "msk_envmap.h"
 #include "msk_lbvh.h"
 #define MSK_WATCHDOG_SYNC
 #include "msk_watchdog.h"
@@ -114,6 +115,7 @@ struct msk_scene {
     bool lds_scene = false, lds_tables = false, all_diffuse = true;
     bool has_dielectric = false;       // the scene holds a smooth `dielectric`: the instantiations with its delta lobes run (k_shade_gen_d, ...)
     bool has_bitmap = false;           // the scene holds a `bitmap` texture (ABI v8): the instantiations with the texel lookup run (k_shade_gen_b, ...)
+    bool has_envmap = false;           // the scene's environment emitter is an image (MSK_EMITTER_ENVMAP): the instantiations with its lookup run (k_shade_gen_e, ...)
     uint32_t n_textures = 0, tex_base = 0;      // msk_gpu_eval_texture: texture k's record sits at float4 tex_base + 3 k of `bsdfs`
     bool has_regular = false;          // the scene holds tabulated spectra (ABI v7): the shading instantiations that evaluate them run
     int trace_mode = 0;                // mskplan::TraceMode (msk_plan.h): which tree the traversal kernels walk, and where it lives
@@ -234,11 +236,12 @@ extern "C" int msk_gpu_describe(const msk_ctx *ctx, char *buf, uint64_t buf_size
 // ------------------------------------------------------------------------------------------
 static inline float h_dot(const float *a, const float *b) { return a[0] * b[0] + (a[1] * b[1] + a[2] * b[2]); }
 
-extern "C" int msk_gpu_scene_create(msk_ctx *ctx, const msk_scene_desc *d, msk_scene **out) {
+extern "C" int msk_gpu_scene_create(msk_ctx *ctx, const msk_scene_desc *d, msk_scene **out) { return msk_gpu_scene_create_env(ctx, d, nullptr, out); }
+extern "C" int msk_gpu_scene_create_env(msk_ctx *ctx, const msk_scene_desc *d, const msk_envmap_desc *env, msk_scene **out) {
     if (!ctx || !d || !out) return fail(ctx, MSK_ERR_INVALID_ARG, "msk_gpu_scene_create: NULL argument");
     *out = nullptr;
     MSK_REFUSE_LOST(ctx);
-    if (ctx->group) return group_scene_create(ctx, d, out);
+    if (ctx->group) return group_scene_create(ctx, d, env, out);
     if (d->abi_version != MSK_ABI_VERSION)
         return fail(ctx, MSK_ERR_INVALID_ARG, "msk_gpu_scene_create: abi_version %u != %u", d->abi_version, MSK_ABI_VERSION);
     if (d->film.width <= 0 || d->film.height <= 0 || !(d->film.filter_radius > 0.f))
@@ -445,16 +448,25 @@ extern "C" int msk_gpu_scene_create(msk_ctx *ctx, const msk_scene_desc *d, msk_s
     std::vector<float> emitters((size_t) std::max(1u, d->n_emitters) * 8, 0.f), d65((size_t) std::max(1u, d->n_emitters) * 95, 0.f), cdf_all;
     std::vector<float> emitter_grid((size_t) std::max(1u, d->n_emitters) * 4, 0.f);
     int env_emitter = -1;
+    bool any_envmap = false;
     for (uint32_t e = 0; e < d->n_emitters; ++e) {
         const msk_emitter_desc &ed = d->emitters[e];
         float *o = &emitters[e * 8];
         o[0] = ed.radiance[0]; o[1] = ed.radiance[1]; o[2] = ed.radiance[2];
-        if (ed.type == MSK_EMITTER_CONSTANT) {
+        if (ed.type == MSK_EMITTER_CONSTANT || ed.type == MSK_EMITTER_ENVMAP) {
+            if (ed.type == MSK_EMITTER_ENVMAP) {
+                if (!env) return fail(ctx, MSK_ERR_INVALID_ARG, "emitter %u: an envmap emitter needs its image (msk_gpu_scene_create_env with an msk_envmap_desc)", e);
+                if (ed.radiance_regular) return fail(ctx, MSK_ERR_INVALID_ARG, "emitter %u: an envmap emitter has no tabulated radiance (radiance_regular must be 0)", e);
+                if (!(ed.d65_scale >= 0.f) || !std::isfinite(ed.d65_scale)) return fail(ctx, MSK_ERR_INVALID_ARG, "emitter %u: envmap: the scale must be finite and non-negative", e);
+                any_envmap = true;
+                o[0] = 0.f; o[1] = 0.f; o[2] = INFINITY;      // the emitter's own factor is its table alone: S = 1
+            }
             if (env_emitter >= 0) return fail(ctx, MSK_ERR_INVALID_ARG, "Can only have one environment light");   // scene.cpp:38-39
             if (ed.mesh_id != -1) return fail(ctx, MSK_ERR_INVALID_ARG, "emitter %u: an environment emitter has no mesh (mesh_id must be -1)", e);
             env_emitter = (int) e;
             o[3] = 0.f;
-            const uint32_t meta[4] = {0xffffffffu, 0u, 0u, 0u};
+            // (an envmap: word 1 = the float4 offset of its block in the texel pool, behind the bitmaps' texels — msk_kernels.h, EnvView)
+            const uint32_t meta[4] = {0xffffffffu, ed.type == MSK_EMITTER_ENVMAP ? d->n_texels : 0u, 0u, 0u};
             std::memcpy(&o[4], meta, 16);
         } else if (ed.type == MSK_EMITTER_AREA) {
             if (ed.mesh_id < 0 || (uint32_t) ed.mesh_id >= d->n_meshes || d->meshes[ed.mesh_id].emitter_id != (int32_t) e)
@@ -466,7 +478,7 @@ extern "C" int msk_gpu_scene_create(msk_ctx *ctx, const msk_scene_desc *d, msk_s
             std::memcpy(&o[4], meta, 16);
             cdf_all.insert(cdf_all.end(), mesh_cdf[ed.mesh_id].begin(), mesh_cdf[ed.mesh_id].end());
         } else {
-            return fail(ctx, MSK_ERR_UNSUPPORTED, "emitter %u: type %d is not supported (area, constant)", e, ed.type);
+            return fail(ctx, MSK_ERR_UNSUPPORTED, "emitter %u: type %d is not supported (area, constant, envmap)", e, ed.type);
         }
         float *gr = &emitter_grid[(size_t) e * 4];
         if (ed.radiance_regular) {          // a `regular` radiance: its own table on its own grid, no sigmoid factor (area.cpp:51-54, regular.cpp:148)
@@ -482,6 +494,25 @@ extern "C" int msk_gpu_scene_create(msk_ctx *ctx, const msk_scene_desc *d, msk_s
             const uint32_t last = 93u;
             gr[0] = 360.f; gr[1] = (float) (1.0 / ((830.0 - 360.0) / 94.0)); std::memcpy(&gr[2], &last, 4); gr[3] = 0.f;
         }
+    }
+    // the image of the envmap emitter (msk_gpu.h: msk_envmap_desc; msk_envmap.h): validated here, before any kernel indexes with it
+    mskenv::Tables env_tables;
+    if (env && !any_envmap) return fail(ctx, MSK_ERR_INVALID_ARG, "envmap: an image was given, but the scene has no envmap emitter (type %d)", MSK_EMITTER_ENVMAP);
+    if (any_envmap) {
+        if (env->width < 1 || env->height < 1) return fail(ctx, MSK_ERR_INVALID_ARG, "envmap: an image of %u x %u texels (width and height must be at least 1)", env->width, env->height);
+        if ((uint64_t) env->width * env->height >= (1ull << 28)) return fail(ctx, MSK_ERR_UNSUPPORTED, "envmap: %u x %u texels, this back end takes fewer than 2^28", env->width, env->height);
+        if (!env->texels || !env->weights) return fail(ctx, MSK_ERR_INVALID_ARG, "envmap: texels / weights array missing");
+        const size_t n = (size_t) env->width * env->height;
+        for (size_t k = 0; k < n; ++k) {
+            const float *t = env->texels + k * 4;
+            if (!std::isfinite(t[3]) || t[3] < 0.f) return fail(ctx, MSK_ERR_INVALID_ARG, "envmap: texel %zu: the factor w must be finite and non-negative", k);
+            if (std::isnan(t[0]) || std::isnan(t[1]) || std::isnan(t[2])) return fail(ctx, MSK_ERR_INVALID_ARG, "envmap: texel %zu holds a NaN coefficient", k);
+        }
+        if (const char *msg = mskenv::check_weights(env->weights, env->width, env->height)) return fail(ctx, MSK_ERR_INVALID_ARG, "%s", msg);
+        if (!mskenv::is_rotation(env->to_world)) return fail(ctx, MSK_ERR_INVALID_ARG, "envmap: to_world must be a rotation");
+        if ((uint64_t) d->n_texels + 3u + n + ((uint64_t) env->height + 4u) / 4u + ((uint64_t) env->height * (env->width + 1u) + 3u) / 4u >= (1ull << 31))
+            return fail(ctx, MSK_ERR_UNSUPPORTED, "envmap: %u x %u texels do not fit the texel pool's 32-bit offsets", env->width, env->height);
+        env_tables = mskenv::build_tables(env->weights, env->width, env->height);
     }
     if (any_regular) all_diffuse = false;              // tabulated spectra are evaluated by the general shading variant only
     std::vector<float> spectra_pool(d->regular_values, d->regular_values + d->n_regular_values);
@@ -535,7 +566,7 @@ extern "C" int msk_gpu_scene_create(msk_ctx *ctx, const msk_scene_desc *d, msk_s
         }
 
     msk_scene *s = new msk_scene();
-    s->ctx = ctx; s->n_tris = d->n_faces; s->bvh_depth = bvh.max_depth; s->all_diffuse = all_diffuse; s->has_regular = any_regular; s->has_dielectric = any_dielectric; s->has_bitmap = any_bitmap;
+    s->ctx = ctx; s->n_tris = d->n_faces; s->bvh_depth = bvh.max_depth; s->all_diffuse = all_diffuse; s->has_regular = any_regular; s->has_dielectric = any_dielectric; s->has_bitmap = any_bitmap; s->has_envmap = any_envmap;
     s->n_textures = d->n_textures; s->tex_base = std::max(1u, d->n_bsdfs) * MSK_BSDF_F4;
     std::vector<float> cie(d->cie1931_xyz, d->cie1931_xyz + 3 * MSK_CIE_SAMPLES);
     hipError_t e = hipSuccess;
@@ -544,9 +575,21 @@ extern "C" int msk_gpu_scene_create(msk_ctx *ctx, const msk_scene_desc *d, msk_s
     up(s->tri_verts, tv); up(s->tri_normals, tn); up(s->tri_uvs, tuv);
     up(s->bsdfs, bsdfs); up(s->emitters, emitters); up(s->emitter_d65, d65); up(s->cdf, cdf_all); up(s->cie, cie);
     up(s->emitter_grid, emitter_grid); up(s->spectra, spectra_pool);
-    if (any_bitmap) {      // one float4 per texel: a lookup is one 16-byte load per texel
+    if (any_bitmap || any_envmap) {      // one float4 per texel: a lookup is one 16-byte load per texel
         std::vector<float> tx4((size_t) d->n_texels * 4, 0.f);
-        for (size_t k = 0; k < d->n_texels; ++k) { tx4[k * 4] = d->texels[k * 3]; tx4[k * 4 + 1] = d->texels[k * 3 + 1]; tx4[k * 4 + 2] = d->texels[k * 3 + 2]; }
+        if (d->texels) for (size_t k = 0; k < d->n_texels; ++k) { tx4[k * 4] = d->texels[k * 3]; tx4[k * 4 + 1] = d->texels[k * 3 + 1]; tx4[k * 4 + 2] = d->texels[k * 3 + 2]; }
+        if (any_envmap) {                // the envmap emitter's block behind them (msk_kernels.h, EnvView): header, texels, marginal, rows
+            const size_t n = (size_t) env->width * env->height;
+            float head[12] = {};
+            std::memcpy(&head[0], &env->width, 4); std::memcpy(&head[1], &env->height, 4);
+            std::memcpy(&head[2], env->to_world, 36);
+            tx4.insert(tx4.end(), head, head + 12);
+            tx4.insert(tx4.end(), env->texels, env->texels + n * 4);
+            tx4.insert(tx4.end(), env_tables.marg.begin(), env_tables.marg.end());
+            tx4.resize((tx4.size() + 3) & ~(size_t) 3, 0.f);
+            tx4.insert(tx4.end(), env_tables.cond.begin(), env_tables.cond.end());
+            tx4.resize((tx4.size() + 3) & ~(size_t) 3, 0.f);
+        }
         up(s->texels, tx4);
     }
     if (e == hipSuccess) e = s->mesh_info.upload(mesh_info);
@@ -586,7 +629,7 @@ extern "C" int msk_gpu_scene_create(msk_ctx *ctx, const msk_scene_desc *d, msk_s
     ds.mesh_info = s->mesh_info.as<int4>(); ds.bsdfs = s->bsdfs.as<float4>(); ds.emitters = s->emitters.as<float4>();
     ds.emitter_d65 = s->emitter_d65.as<float>(); ds.cdf = s->cdf.as<float>(); ds.cie = s->cie.as<float>();
     ds.emitter_grid = s->emitter_grid.as<float4>(); ds.spectra = s->spectra.as<float>(); ds.n_spectra = d->n_regular_values;
-    ds.texels = any_bitmap ? s->texels.as<float4>() : nullptr;
+    ds.texels = (any_bitmap || any_envmap) ? s->texels.as<float4>() : nullptr;
     ds.n_nodes = (uint32_t) (bvh.nodes.size() / 16); ds.n_tris = d->n_faces; ds.n_emitters = d->n_emitters;
     ds.n_meshes = d->n_meshes; ds.n_bsdfs = d->n_bsdfs; ds.n_bsdf_f4 = n_bsdf_f4; ds.cdf_len = (uint32_t) cdf_all.size();
     ds.root_ref = bvh.root_ref;
@@ -898,6 +941,7 @@ static void launch_shade_t(const msk_scene *sc, const mskplan::LaunchPlan &plan,
     case mskplan::SHADE_REGULAR: MSK_SHADE(k_shade_gen<LDS_TABLES, false, true>); break;
     case mskplan::SHADE_GENERAL: MSK_SHADE(k_shade_gen<LDS_TABLES, false>); break;
     case mskplan::SHADE_BITMAP: MSK_SHADE(k_shade_gen_b<LDS_TABLES>); break;
+    case mskplan::SHADE_ENVMAP: MSK_SHADE(k_shade_gen_e<LDS_TABLES>); break;
     }
 #undef MSK_SHADE
 }
@@ -917,6 +961,7 @@ static void launch_fused(const msk_scene *sc, const mskplan::LaunchPlan &plan, d
     case mskplan::SHADE_REGULAR: MSK_FUSED(k_wavefront_h<false, true>); break;
     case mskplan::SHADE_GENERAL: MSK_FUSED(k_wavefront_h<false>); break;
     case mskplan::SHADE_BITMAP: MSK_FUSED(k_wavefront_h_b); break;
+    case mskplan::SHADE_ENVMAP: MSK_FUSED(k_wavefront_h_e); break;
     }
     else switch (plan.shade_kind) {                   // everything in LDS (trace mode 0)
     case mskplan::SHADE_DIELECTRIC: MSK_FUSED(k_wavefront_d); break;
@@ -924,6 +969,7 @@ static void launch_fused(const msk_scene *sc, const mskplan::LaunchPlan &plan, d
     case mskplan::SHADE_REGULAR: MSK_FUSED(k_wavefront<false, true>); break;
     case mskplan::SHADE_GENERAL: MSK_FUSED(k_wavefront<false>); break;
     case mskplan::SHADE_BITMAP: MSK_FUSED(k_wavefront_b); break;
+    case mskplan::SHADE_ENVMAP: MSK_FUSED(k_wavefront_e); break;
     }
 #undef MSK_FUSED
 }
@@ -1182,7 +1228,7 @@ static PassParams pass_params(const msk_render_params *prm, uint32_t spp_owned, 
 static mskplan::SceneFacts scene_facts(const msk_scene *sc) {
     mskplan::SceneFacts f;
     f.trace_mode = sc->trace_mode; f.lds_scene = sc->lds_scene; f.lds_tables = sc->lds_tables; f.all_diffuse = sc->all_diffuse;
-    f.has_regular = sc->has_regular; f.has_dielectric = sc->has_dielectric; f.has_bitmap = sc->has_bitmap; f.cull_ok = sc->cull_ok;
+    f.has_regular = sc->has_regular; f.has_dielectric = sc->has_dielectric; f.has_bitmap = sc->has_bitmap; f.has_envmap = sc->has_envmap; f.cull_ok = sc->cull_ok;
     f.trace_lds_bytes = sc->trace_lds_bytes; f.shade_lds_bytes = sc->shade_lds_bytes;
     return f;
 }
@@ -1361,7 +1407,8 @@ static int render_serial(msk_scene *sc, const msk_render_params *prm, float *d_f
         sp.blocks = ws.blocks.as<BlockInfo>(); sp.n_blocks = (uint32_t) owned.size();
         sp.block_buf = ws.block_buf.as<float>(); sp.buf_stride = buf_stride;
         sp.stack_ovf = ovf.as<uint32_t>(); sp.counters = counters.as<unsigned long long>(); sp.per_wave = per_wave ? 1u : 0u;
-        if (sc->has_bitmap) hipLaunchKernelGGL(k_path_serial_b, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
+        if (sc->has_envmap) hipLaunchKernelGGL(k_path_serial_e, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
+        else if (sc->has_bitmap) hipLaunchKernelGGL(k_path_serial_b, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
         else if (sc->has_dielectric) hipLaunchKernelGGL(k_path_serial_d, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
         else hipLaunchKernelGGL(k_path_serial, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
     }
@@ -1799,6 +1846,44 @@ extern "C" int msk_gpu_eval_texture(msk_scene *scene, uint32_t texture, uint64_t
     if (!scene || (n && (!uv || !wavelengths || !out))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_eval_texture: NULL argument");
     if (scene->ctx->group) { const int rc = eval_texture(scene->parts[0], texture, n, uv, wavelengths, out); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
     return eval_texture(scene, texture, n, uv, wavelengths, out);
+}
+
+// msk_gpu_env_eval (sample == 0: `in` = n * 3 directions) / msk_gpu_env_sample (sample == 1: `in` = n * 2 random numbers)
+static int env_probe(msk_scene *scene, const char *who, uint32_t sample, uint64_t n, const float *in, const float *wavelengths, float *out_rad, float *out_dir,
+                     float *out_uv, float *out_pdf) {
+    msk_ctx *ctx = scene->ctx;
+    MSK_REFUSE_LOST(ctx);
+    if (!scene->has_envmap) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: the scene has no envmap emitter", who);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n == 0) return MSK_OK;
+    const size_t in_f = sample ? 2 : 3;
+    DevBuf d_in, d_wl, d_rad, d_dir, d_uv, d_pdf;
+    HIP_TRY(ctx, d_in.alloc(n * in_f * 4)); HIP_TRY(ctx, d_pdf.alloc(n * 4));
+    HIP_TRY(ctx, hipMemcpy(d_in.p, in, n * in_f * 4, hipMemcpyHostToDevice));
+    if (sample) { HIP_TRY(ctx, d_dir.alloc(n * 12)); HIP_TRY(ctx, d_uv.alloc(n * 8)); }
+    else {
+        HIP_TRY(ctx, d_wl.alloc(n * 16)); HIP_TRY(ctx, d_rad.alloc(n * 16));
+        HIP_TRY(ctx, hipMemcpy(d_wl.p, wavelengths, n * 16, hipMemcpyHostToDevice));
+    }
+    const uint32_t grid = (uint32_t) std::min<uint64_t>((n + MSK_BLOCK - 1) / MSK_BLOCK, 4096);
+    hipLaunchKernelGGL(k_env_probe, dim3(grid), dim3(MSK_BLOCK), 0, ctx->stream, scene->dev, sample, n, d_in.as<float>(), d_wl.as<float4>(), d_rad.as<float4>(),
+                       d_dir.as<float>(), d_uv.as<float2>(), d_pdf.as<float>());
+    HIP_TRY(ctx, hipGetLastError());
+    if (int rcw = ctx_sync(ctx, ctx->stream, "k_env_probe")) { d_in.leak(); d_wl.leak(); d_rad.leak(); d_dir.leak(); d_uv.leak(); d_pdf.leak(); return rcw; }
+    if (sample) { HIP_TRY(ctx, hipMemcpy(out_dir, d_dir.p, n * 12, hipMemcpyDeviceToHost)); HIP_TRY(ctx, hipMemcpy(out_uv, d_uv.p, n * 8, hipMemcpyDeviceToHost)); }
+    else HIP_TRY(ctx, hipMemcpy(out_rad, d_rad.p, n * 16, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out_pdf, d_pdf.p, n * 4, hipMemcpyDeviceToHost));
+    return MSK_OK;
+}
+extern "C" int msk_gpu_env_eval(msk_scene *scene, uint64_t n, const float *dirs, const float *wavelengths, float *out_radiance, float *out_pdf) {
+    if (!scene || (n && (!dirs || !wavelengths || !out_radiance || !out_pdf))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_env_eval: NULL argument");
+    if (scene->ctx->group) { const int rc = env_probe(scene->parts[0], "msk_gpu_env_eval", 0, n, dirs, wavelengths, out_radiance, nullptr, nullptr, out_pdf); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
+    return env_probe(scene, "msk_gpu_env_eval", 0, n, dirs, wavelengths, out_radiance, nullptr, nullptr, out_pdf);
+}
+extern "C" int msk_gpu_env_sample(msk_scene *scene, uint64_t n, const float *u, float *out_dir, float *out_uv, float *out_pdf) {
+    if (!scene || (n && (!u || !out_dir || !out_uv || !out_pdf))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_env_sample: NULL argument");
+    if (scene->ctx->group) { const int rc = env_probe(scene->parts[0], "msk_gpu_env_sample", 1, n, u, nullptr, nullptr, out_dir, out_uv, out_pdf); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
+    return env_probe(scene, "msk_gpu_env_sample", 1, n, u, nullptr, nullptr, out_dir, out_uv, out_pdf);
 }
 
 extern "C" int msk_gpu_trace_closest(msk_scene *scene, uint64_t n, const float *rays, float *out_hit) {

@@ -68,7 +68,8 @@ struct DeviceScene {
                                 // float4 offset of the texture record), then 3 x float4 per texture: {color0, m02} {color1, m12}
                                 // {m00 m01 m10 m11}; a bitmap: {first_texel, W, H (uint bits), m02} {MSK_TEXTURE_* (uint bits), 0, 0, m12}
     uint32_t n_bsdf_f4;         // float4 count of `bsdfs` (records + textures)
-    const float4 *emitters;     // 2 x float4 per emitter: {c0,c1,c2,inv_area} {mesh,first_face,face_count,cdf_off (uint bits)}
+    const float4 *emitters;     // 2 x float4 per emitter: {c0,c1,c2,inv_area} {mesh,first_face,face_count,cdf_off (uint bits)}; an environment
+                                // emitter: mesh = ~0 and, for an `envmap`, first_face = the float4 offset of its block in `texels` (EnvView)
     const float *emitter_d65;   // 95 floats per emitter: d65 * d65_scale, or the values of a `regular` radiance (ABI v7)
     const float4 *emitter_grid; // per emitter {lambda_min, inv_interval, last segment (uint bits), 1 = the table IS the radiance (no
                                 // sigmoid factor)} of that table: {360, 0.2, 93, 0} for the D65 form.  Read by the general shading
@@ -89,13 +90,16 @@ struct DeviceScene {
     float filter_radius, filter_scale;
     int32_t filter_border;
     float lut[33];
-    int32_t env_emitter;        // index of the constant environment emitter in `emitters`, or -1 (scene.cpp:35-41)
+    int32_t env_emitter;        // index of the environment emitter (`constant`, or `envmap`: then the scene runs the SceneTablesE kernels) in
+                                // `emitters`, or -1 (scene.cpp:35-41)
     float env_radius;           // ConstantBackgroundEmitter::m_bsphere.radius after set_scene (constant.cpp:21-28)
     float cull_lo[3], cull_hi[3];   // union of the two child boxes of the binary tree's root (msk_bvh.h: cull_bounds): a camera ray that
                                 // fails the slab test on it hits nothing — its sample is finished where it is made
                                 // (shade_region's regeneration, PassParams::cull)
     const float4 *texels;       // the bitmap textures' texel pool (ABI v8), one float4 per texel {c0, c1, c2, -} = one 16-byte load per
                                 // texel, or nullptr; always read from HBM / L2, never staged.  (Last: the older fields keep their offsets.)
+                                // Behind the bitmaps' texels: the block of the `envmap` emitter (EnvView below), whose float4 offset
+                                // the emitter's record carries — this struct, a kernel argument of every kernel, does not change for it
 };
 
 struct PathState {
@@ -1409,10 +1413,15 @@ struct SceneTablesD : SceneTablesR {};
 // ... and of a scene that holds a `bitmap` texture (MSK_TEXTURE_BITMAP*), with or without glass: the texel lookup of reflectance_eval
 // is compiled only into the instantiations that carry this type (k_shade_gen_b, k_wavefront_b, k_wavefront_h_b, k_path_serial_b).
 struct SceneTablesB : SceneTablesD {};
-template <class TB> struct tb_traits { static constexpr bool regular = false, dielectric = false, bitmap = false; };
-template <> struct tb_traits<SceneTablesR> { static constexpr bool regular = true, dielectric = false, bitmap = false; };
-template <> struct tb_traits<SceneTablesD> { static constexpr bool regular = true, dielectric = true, bitmap = false; };
-template <> struct tb_traits<SceneTablesB> { static constexpr bool regular = true, dielectric = true, bitmap = true; };
+// ... and of a scene whose environment emitter is an image (MSK_EMITTER_ENVMAP), whatever else it holds: the image lookup, its
+// density and the sampling of light directions from it are compiled only into the instantiations that carry this type
+// (k_shade_gen_e, k_wavefront_e, k_wavefront_h_e, k_path_serial_e).  In them the scene's environment emitter IS the image.
+struct SceneTablesE : SceneTablesB {};
+template <class TB> struct tb_traits { static constexpr bool regular = false, dielectric = false, bitmap = false, envmap = false; };
+template <> struct tb_traits<SceneTablesR> { static constexpr bool regular = true, dielectric = false, bitmap = false, envmap = false; };
+template <> struct tb_traits<SceneTablesD> { static constexpr bool regular = true, dielectric = true, bitmap = false, envmap = false; };
+template <> struct tb_traits<SceneTablesB> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = false; };
+template <> struct tb_traits<SceneTablesE> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = true; };
 MSK_DEV uint32_t tables_lds_float4s(const DeviceScene &sc) {
     return sc.n_tris * 6 + sc.n_meshes + sc.n_bsdf_f4 + sc.n_emitters * 3 + (sc.n_emitters * 95 + 3) / 4 + (sc.cdf_len + 3) / 4 + 72 + (sc.n_spectra + 3) / 4;
 }
@@ -1626,6 +1635,105 @@ MSK_DEV spec reflectance_eval(const TB &tb, f3 c, float scale, uint32_t tex, UV 
         scale = 1.f;
     }
     return spectrum_eval(tb, make_float4(c.x, c.y, c.z, scale), wl);
+}
+
+// ------------------------------------------------------------------------------------------
+// The `envmap` emitter (msk_gpu.h: msk_envmap_desc — the text these functions follow, fp32, one operation at a time; no libm).
+// Image and cumulative tables are read from HBM / L2.
+// ------------------------------------------------------------------------------------------
+#define MSK_TWO_PI_F (2.f * MSK_PI_F)
+// The emitter's block in the texel pool, at float4 offset emitters[2 e + 1].y of it: {W, H (uint bits), r0, r1} {r2 r3 r4 r5}
+// {r6 r7 r8 -} (to_world's 3x3, row-major), W * H texels {c0, c1, c2, w} (row 0 = the top row), the marginal's cumulative table
+// (H + 1 floats, padded to a float4) and the rows' (H rows of W + 1 floats; msk_envmap.h).
+struct EnvView { const float4 *texels; const float *marg, *cond; uint32_t W, H; float R[9]; };
+template <class TB>
+MSK_DEV EnvView env_view(const TB &tb, int e) {
+    const float4 *blk = tb.texels + __float_as_uint(tb.emitters[2 * e + 1].y);
+    const float4 h0 = blk[0], h1 = blk[1], h2 = blk[2];
+    EnvView v;
+    v.W = __float_as_uint(h0.x); v.H = __float_as_uint(h0.y);
+    v.R[0] = h0.z; v.R[1] = h0.w; v.R[2] = h1.x; v.R[3] = h1.y; v.R[4] = h1.z; v.R[5] = h1.w; v.R[6] = h2.x; v.R[7] = h2.y; v.R[8] = h2.z;
+    v.texels = blk + 3;
+    v.marg = (const float *) (blk + 3 + (size_t) v.W * v.H);
+    v.cond = v.marg + ((v.H + 1u + 3u) & ~3u);
+    return v;
+}
+MSK_DEV float env_atan2(float y, float x) {
+    if (x == 0.f) return y > 0.f ? MSK_PI_F * .5f : y < 0.f ? -(MSK_PI_F * .5f) : 0.f;
+    float r = det_atan(y / x);
+    if (x < 0.f) r = y >= 0.f ? r + MSK_PI_F : r - MSK_PI_F;
+    return r;
+}
+// world direction -> the image's uv and sin theta of the Jacobian
+MSK_DEV f2 env_dir_to_uv(const EnvView &ev, f3 d, float *sin_theta) {
+    const float *R = ev.R;
+    const float lx = R[0] * d.x + (R[3] * d.y + R[6] * d.z), ly = R[1] * d.x + (R[4] * d.y + R[7] * d.z), lz = R[2] * d.x + (R[5] * d.y + R[8] * d.z);
+    const float s2 = lx * lx + lz * lz;
+    float u = env_atan2(lx, -lz) / MSK_TWO_PI_F;
+    u = u - floorf(u);
+    if (!(u < 1.f)) u = 0.f;
+    f2 uv; uv.x = u; uv.y = env_atan2(__builtin_sqrtf(s2), ly) / MSK_PI_F;
+    *sin_theta = __builtin_sqrtf(fmax_std(s2, MSK_EPSILON_F * MSK_EPSILON_F));
+    return uv;
+}
+// L(u, v, l): bilinear over spectral values, u wraps, v clamps at the poles; e = the emitter (its table carries scale / 10568)
+template <class TB>
+MSK_DEV spec env_radiance(const EnvView &ev, const TB &tb, int e, f2 uv, spec wl) {
+    const uint32_t W = ev.W, H = ev.H;
+    uint32_t i0, i1; float wx;
+    bitmap_axis(uv.x, W, &i0, &i1, &wx);
+    const float py = uv.y * (float) H - 0.5f;
+    const int j = (int) floorf(py);
+    const float wy = py - (float) j;
+    const int hm = (int) H - 1;
+    const uint32_t j0 = (uint32_t) (j < 0 ? 0 : j > hm ? hm : j), j1 = (uint32_t) (j + 1 < 0 ? 0 : j + 1 > hm ? hm : j + 1);
+    // the four gathers go out together, ahead of the first sigmoid (as reflectance_eval's)
+    const float4 k00 = ev.texels[(size_t) j0 * W + i0], k10 = ev.texels[(size_t) j0 * W + i1];
+    const float4 k01 = ev.texels[(size_t) j1 * W + i0], k11 = ev.texels[(size_t) j1 * W + i1];
+    const spec s00 = srgb_model_eval(k00.x, k00.y, k00.z, wl) * k00.w, s10 = srgb_model_eval(k10.x, k10.y, k10.z, wl) * k10.w;
+    const spec a = s00 + (s10 - s00) * wx;
+    const spec s01 = srgb_model_eval(k01.x, k01.y, k01.z, wl) * k01.w, s11 = srgb_model_eval(k11.x, k11.y, k11.z, wl) * k11.w;
+    const spec b = s01 + (s11 - s01) * wx;
+    return emitter_radiance(tb, e, wl) * (a + (b - a) * wy);
+}
+// solid-angle density of cell (i, j)
+MSK_DEV float env_pdf_cell(const EnvView &ev, uint32_t i, uint32_t j, float sin_theta) {
+    const float *row = ev.cond + (size_t) j * (ev.W + 1u);
+    const float pr = ev.marg[j + 1] - ev.marg[j], pc = row[i + 1] - row[i];
+    const float p = ((pr * pc) * (float) ev.W) * (float) ev.H;
+    return p / ((2.f * (MSK_PI_F * MSK_PI_F)) * sin_theta);
+}
+MSK_DEV float env_pdf(const EnvView &ev, f2 uv, float sin_theta) {
+    uint32_t i = (uint32_t) (int) (uv.x * (float) ev.W), j = (uint32_t) (int) (uv.y * (float) ev.H);
+    i = i < ev.W - 1u ? i : ev.W - 1u; j = j < ev.H - 1u ? j : ev.H - 1u;
+    return env_pdf_cell(ev, i, j, sin_theta);
+}
+// Distribution1D::sample_reuse (core/distribution.h:106-116) on a table of n + 1 entries, the reused fraction kept below 1
+MSK_DEV uint32_t env_search(const float *cdf, uint32_t n, float u, float *frac) {
+    uint32_t lo = 0, hi = n + 1;
+    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (!(u < cdf[mid])) lo = mid + 1; else hi = mid; }
+    int k = (int) lo - 1;
+    k = k < 0 ? 0 : k; k = k > (int) n - 1 ? (int) n - 1 : k;
+    const float c0 = cdf[k], c1 = cdf[k + 1];
+    *frac = fmin_std((u - c0) / (c1 - c0), 0x1.fffffep-1f);
+    return (uint32_t) k;
+}
+// a light direction from the image: row from u.y, column from u.x; the direction (world), its uv and its solid-angle density
+MSK_DEV f3 env_sample(const EnvView &ev, f2 u, f2 *uv_out, float *pdf) {
+    const uint32_t W = ev.W, H = ev.H;
+    float du, dv;
+    const uint32_t j = env_search(ev.marg, H, u.y, &dv);
+    const uint32_t i = env_search(ev.cond + (size_t) j * (W + 1u), W, u.x, &du);
+    f2 uv; uv.x = ((float) i + du) / (float) W; uv.y = ((float) j + dv) / (float) H;
+    float st, ct, sp, cp;
+    det_sincos(MSK_PI_F * uv.y, &st, &ct);
+    det_sincos(MSK_TWO_PI_F * uv.x, &sp, &cp);
+    const float lx = sp * st, ly = ct, lz = -(cp * st);
+    const float *R = ev.R;
+    const float sin_theta = __builtin_sqrtf(fmax_std(lx * lx + lz * lz, MSK_EPSILON_F * MSK_EPSILON_F));
+    *pdf = env_pdf_cell(ev, i, j, sin_theta);
+    *uv_out = uv;
+    return mk3(R[0] * lx + (R[1] * ly + R[2] * lz), R[3] * lx + (R[4] * ly + R[5] * lz), R[6] * lx + (R[7] * ly + R[8] * lz));
 }
 MSK_DEV float clamp_alpha(float a) { return fmax_std(a, 1e-4f); }
 
@@ -2069,6 +2177,21 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
         bool has_shadow = false;
 
         if (alive && hit.x == MSK_INF_F) {                                 // path.cpp:34-41 / 89-97
+            if (tb_traits<TB>::envmap) {
+                // an image: value and density are those of the ray's own direction (msk_gpu.h, msk_envmap_desc)
+                const EnvView ev = env_view(tb, sc.env_emitter);
+                float sin_t;
+                const f2 uv = env_dir_to_uv(ev, rd, &sin_t);
+                const spec le = env_radiance(ev, tb, sc.env_emitter, uv, wl);
+                if (depth == 1) {
+                    if (!pp.hide_emitters && pp.max_depth != 0) res = res + thr * le;
+                } else {
+                    float pdf = env_pdf(ev, uv, sin_t);
+                    if (n_em != 1) pdf = pdf * (1.f / n_em);
+                    if (delta_in) pdf = 0.f;
+                    res = res + thr * le * mis_weight(bs_pdf, pdf);
+                }
+            } else
             if (!DIFFUSE_ONLY && sc.env_emitter >= 0) {
                 // depth 1: the camera ray left the scene.  depth > 1: the BSDF sample did; its MIS weight uses the NEE
                 // sample's record, which the reference does not re-query on this branch (path.cpp:90-95,103-108).
@@ -2148,6 +2271,15 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
                     }
                     const float4 e0 = tb.emitters[2 * e], e1 = tb.emitters[2 * e + 1];
                     f3 d; float dist, pdf; spec emitter_val;
+                    if (tb_traits<TB>::envmap && (int) e == sc.env_emitter) {
+                        const EnvView ev = env_view(tb, (int) e);
+                        f2 uv;
+                        d = env_sample(ev, u, &uv, &pdf);
+                        dist = 2.f * sc.env_radius;
+                        emitter_val = splat(0.f);
+                        if (pdf != 0.f) emitter_val = env_radiance(ev, tb, (int) e, uv, wl) / pdf;
+                        nee_pdf = pdf;
+                    } else
                     if (!DIFFUSE_ONLY && (int) e == sc.env_emitter) {
                         // constant.cpp:53-72 (radiance at the path's wavelengths, oracle D8)
                         d = square_to_uniform_sphere(u);
@@ -2438,14 +2570,14 @@ MSK_DEV DoneQueue done_queue(float4 *base) {
 
 // the table type of an instantiation: plain, with tabulated spectra, with the smooth dielectric (which includes them), with bitmap
 // textures (which includes both)
-template <bool REGULAR, bool DIELECTRIC, bool BITMAP = false>
-using tables_of = typename std::conditional<BITMAP, SceneTablesB, typename std::conditional<DIELECTRIC, SceneTablesD,
-                                            typename std::conditional<REGULAR, SceneTablesR, SceneTables>::type>::type>::type;
+template <bool REGULAR, bool DIELECTRIC, bool BITMAP = false, bool ENVMAP = false>
+using tables_of = typename std::conditional<ENVMAP, SceneTablesE, typename std::conditional<BITMAP, SceneTablesB, typename std::conditional<DIELECTRIC, SceneTablesD,
+                                            typename std::conditional<REGULAR, SceneTablesR, SceneTables>::type>::type>::type>::type;
 
-template <bool LDS_TABLES, bool DIFFUSE_ONLY, bool REGULAR = false, bool DIELECTRIC = false, bool BITMAP = false>
+template <bool LDS_TABLES, bool DIFFUSE_ONLY, bool REGULAR = false, bool DIELECTRIC = false, bool BITMAP = false, bool ENVMAP = false>
 MSK_DEV void shade_gen_body(const DeviceScene &sc, const PathState &st, const PassParams &pp) {
     extern __shared__ float4 lds_dyn[];
-    tables_of<REGULAR, DIELECTRIC, BITMAP> tb;
+    tables_of<REGULAR, DIELECTRIC, BITMAP, ENVMAP> tb;
     static_cast<SceneTables &>(tb) = stage_tables<LDS_TABLES>(sc, lds_dyn);
     const uint32_t lwave = (blockIdx.x * MSK_BLOCK + threadIdx.x) / MSK_WAVE;
     const uint32_t queue_f4 = LDS_TABLES ? tables_lds_float4s(sc) : small_tables_float4s(sc);   // after the staged tables
@@ -2488,6 +2620,11 @@ k_shade_gen_d(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_
 template <bool LDS_TABLES>
 __global__ void __launch_bounds__(MSK_BLOCK) __attribute__((amdgpu_waves_per_eu(MSK_SHADE_GEN_WAVES)))
 k_shade_gen_b(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_TABLES, false, true, true, true>(sc, st, pp); }
+// ... and the two that scenes with an `envmap` emitter run, and only they (SceneTablesE), whatever else they hold.  Not held at
+// three waves per SIMD: at 168 VGPRs the image's sampling (two table searches, two det_sincos, four gathers) spills 8 bytes
+template <bool LDS_TABLES>
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_shade_gen_e(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_TABLES, false, true, true, true, true>(sc, st, pp); }
 // The diffuse-only variants fit four waves per SIMD (128 VGPRs, no scratch); left alone, the allocator spends 24 more registers
 // on the explicit fp64 fma chains of det_sincos and lands at three.
 #ifndef MSK_NO_SHADE4
@@ -2573,6 +2710,14 @@ k_wavefront_b(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, u
     constexpr bool CULL = false;      // (as k_wavefront_d)
     MSK_WAVEFRONT_BODY
 }
+// the one scenes with an `envmap` emitter run (see k_shade_gen_e)
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_wavefront_e(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
+    typedef SceneTablesE TB;
+    constexpr bool DIFFUSE_ONLY = false;
+    constexpr bool CULL = false;      // (no camera cull with an environment emitter)
+    MSK_WAVEFRONT_BODY
+}
 #undef MSK_WAVEFRONT_BODY
 
 // k_wavefront_h (round 6): the same device-side loop for scenes whose TREE STAYS IN HBM / L2 (trace mode 6: the 4-wide tree with
@@ -2643,6 +2788,13 @@ k_wavefront_h_b(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters,
     constexpr bool DIFFUSE_ONLY = false;
     MSK_WAVEFRONT_H_BODY
 }
+// the one scenes with an `envmap` emitter run (see k_shade_gen_e)
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_wavefront_h_e(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
+    typedef SceneTablesE TB;
+    constexpr bool DIFFUSE_ONLY = false;
+    MSK_WAVEFRONT_H_BODY
+}
 #undef MSK_WAVEFRONT_H_BODY
 
 // msk_gpu_eval_texture: the value of the texture whose record sits at float4 offset `rec` of the BSDF table, at n given uv and
@@ -2655,6 +2807,30 @@ k_eval_texture(DeviceScene sc, uint32_t rec, uint64_t n, const float2 *uv, const
         const float2 p = uv[i];
         const spec v = reflectance_eval(tb, mk3(0.f, 0.f, 0.f), 0.f, rec, [&]() { f2 r; r.x = p.x; r.y = p.y; return r; }, from4(wl[i]));
         out[i] = make_float4(v.v[0], v.v[1], v.v[2], v.v[3]);
+    }
+}
+
+// msk_gpu_env_eval / msk_gpu_env_sample: the image's radiance and density at n directions (sample == 0), or the direction, uv and
+// density drawn for n pairs of random numbers (sample == 1), through the functions the shading kernels call.  One point per thread.
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_env_probe(DeviceScene sc, uint32_t sample, uint64_t n, const float *in, const float4 *wl, float4 *out_rad, float *out_dir, float2 *out_uv, float *out_pdf) {
+    SceneTablesE tb;
+    static_cast<SceneTables &>(tb) = stage_tables<false>(sc, nullptr);
+    const EnvView ev = env_view(tb, sc.env_emitter);
+    for (uint64_t i = (uint64_t) blockIdx.x * MSK_BLOCK + threadIdx.x; i < n; i += (uint64_t) gridDim.x * MSK_BLOCK) {
+        if (sample) {
+            f2 u; u.x = in[i * 2]; u.y = in[i * 2 + 1];
+            f2 uv; float pdf;
+            const f3 d = env_sample(ev, u, &uv, &pdf);
+            out_dir[i * 3] = d.x; out_dir[i * 3 + 1] = d.y; out_dir[i * 3 + 2] = d.z;
+            out_uv[i] = make_float2(uv.x, uv.y); out_pdf[i] = pdf;
+        } else {
+            float sin_t;
+            const f2 uv = env_dir_to_uv(ev, mk3(in[i * 3], in[i * 3 + 1], in[i * 3 + 2]), &sin_t);
+            const spec v = env_radiance(ev, tb, sc.env_emitter, uv, from4(wl[i]));
+            out_rad[i] = make_float4(v.v[0], v.v[1], v.v[2], v.v[3]);
+            out_pdf[i] = env_pdf(ev, uv, sin_t);
+        }
     }
 }
 

@@ -80,5 +80,11 @@ k_path_serial_b(DeviceScene sc, SerialParams prm) {
     typedef SceneTablesB TB;
 #include "msk_serial_body.inc"
 }
+// ... and SceneTablesE for a scene whose environment emitter is an image (whatever else it holds)
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_path_serial_e(DeviceScene sc, SerialParams prm) {
+    typedef SceneTablesE TB;
+#include "msk_serial_body.inc"
+}
 
 }  // namespace msk

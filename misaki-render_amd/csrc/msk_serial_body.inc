@@ -1,4 +1,4 @@
-// msk_serial_body.inc — the body of k_path_serial / k_path_serial_d / k_path_serial_b (msk_serial.h), included once into each: `TB` is the
+// msk_serial_body.inc — the body of k_path_serial / k_path_serial_d / k_path_serial_b / k_path_serial_e (msk_serial.h), included once into each: `TB` is the
 // kernel's table type, `sc` and `prm` its arguments.  Written once and stamped, not shared through a function, so that
 // k_path_serial compiles from the token stream it always had.
     extern __shared__ float4 lds_dyn[];
@@ -62,6 +62,9 @@
                 float4 hit = closest(ro, rd, sc.near_clip * inv_z, sc.far_clip * inv_z);
                 for (int depth = 1; depth <= prm.max_depth || prm.max_depth < 0; ++depth) {
                     if (hit.x == MSK_INF_F) {                                          // path.cpp:34-41
+                        if (tb_traits<TB>::envmap) {
+                            if (depth == 1 && !prm.hide_emitters) { const EnvView ev = env_view(tb, sc.env_emitter); float sin_t; const f2 uv = env_dir_to_uv(ev, rd, &sin_t); res = res + thr * env_radiance(ev, tb, sc.env_emitter, uv, wl); }
+                        } else
                         if (depth == 1 && !prm.hide_emitters && sc.env_emitter >= 0) res = res + thr * emitter_radiance(tb, sc.env_emitter, wl);
                         break;
                     }
@@ -100,6 +103,15 @@
                             }
                             const float4 e0 = tb.emitters[2 * e], e1 = tb.emitters[2 * e + 1];
                             f3 d; float dist, pdf; spec emitter_val;
+                            if (tb_traits<TB>::envmap && (int) e == sc.env_emitter) {  // the image (msk_gpu.h, msk_envmap_desc)
+                                const EnvView ev = env_view(tb, (int) e);
+                                f2 uv;
+                                d = env_sample(ev, u, &uv, &pdf);
+                                dist = 2.f * sc.env_radius;
+                                emitter_val = splat(0.f);
+                                if (pdf != 0.f) emitter_val = env_radiance(ev, tb, (int) e, uv, wl) / pdf;
+                                nee_pdf = pdf;
+                            } else
                             if ((int) e == sc.env_emitter) {                           // constant.cpp:53-72
                                 d = square_to_uniform_sphere(u);
                                 dist = 2.f * sc.env_radius;
@@ -180,6 +192,14 @@
                             emitter_pdf = pdf;
                             hit_emitter = true;
                         }
+                    } else if (tb_traits<TB>::envmap) {                                 // value and density of the ray's own direction
+                        const EnvView ev = env_view(tb, sc.env_emitter);
+                        float sin_t;
+                        const f2 uv = env_dir_to_uv(ev, rd, &sin_t);
+                        value = env_radiance(ev, tb, sc.env_emitter, uv, wl);
+                        emitter_pdf = env_pdf(ev, uv, sin_t);
+                        if (n_em != 1) emitter_pdf = emitter_pdf * (1.f / n_em);
+                        hit_emitter = true;
                     } else if (sc.env_emitter >= 0) {                                   // path.cpp:90-95: `ds` is the NEE sample's record
                         value = emitter_radiance(tb, sc.env_emitter, wl);
                         emitter_pdf = nee_pdf;

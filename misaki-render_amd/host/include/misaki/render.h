@@ -147,6 +147,9 @@ public:
     virtual bool flatten(msk_emitter_desc &out, FlatTables &tables) const { (void) out; (void) tables; return false; }
     virtual bool is_environment() const { return false; }
     virtual bool is_surface() const { return false; }
+    // an emitter that flattens to MSK_EMITTER_ENVMAP fills the image's descriptor too: size and to_world in `out`, the texels
+    // {c0, c1, c2, w} and the weights of the distribution into the two arrays (flatten_scene points `out` at them)
+    virtual bool flatten_envmap(msk_envmap_desc &out, std::vector<float> &texels, std::vector<float> &weights) const { (void) out; (void) texels; (void) weights; return false; }
     void set_shape(Shape *shape);
     Shape *shape() const { return m_shape; }
     MSK_DECLARE_CLASS()
@@ -275,6 +278,11 @@ struct FlatScene {
     std::vector<float> vertices;
     std::vector<uint32_t> faces;
     msk_render_params params;
+    // the image of the scene's `envmap` emitter (msk_gpu_scene_create_env), when it has one
+    bool has_envmap = false;
+    msk_envmap_desc envmap;
+    std::vector<float> env_texels, env_weights;
+    const msk_envmap_desc *envmap_ptr() const { return has_envmap ? &envmap : nullptr; }
 };
 void flatten_scene(const Scene *scene, const Sensor *sensor, FlatScene &out);
 
@@ -292,7 +300,9 @@ void rgb2spec_fetch_table(int res, const float *scale, const float *data, const 
 // image output (core/image.h): float RGBA
 void write_pfm(const std::string &path, int w, int h, int channels, const float *data);
 void write_exr(const std::string &path, int w, int h, const std::vector<std::string> &channels, const float *data);
-// image input for the `bitmap` texture: PFM (1 or 3 channels, either byte order; linear values) and binary PGM / PPM (P5 / P6,
+// image input for the `bitmap` texture and the `envmap` emitter: PFM (1 or 3 channels, either byte order; linear values), Radiance
+// RGBE .hdr (FORMAT=32-bit_rle_rgbe, "-Y H +X W" only, flat and run-length-encoded scanlines; linear values, the header's EXPOSURE
+// is not applied; anything else is refused by name) and binary PGM / PPM (P5 / P6,
 // maxval <= 65535; IEC 61966-2-1 sRGB decode unless `raw`) -> w * h * 3 linear RGB floats, the image's TOP row first, one channel
 // replicated to grey.  Throws with the file's name for a missing or truncated file and for a wrong magic number.
 void read_image(const std::string &path, bool raw, int &w, int &h, std::vector<float> &rgb);

@@ -55,6 +55,14 @@ int msk_host_flatten(msk_host_scene *h, msk_scene_desc *desc, msk_render_params 
     } catch (const std::exception &e) { return fail(e); }
 }
 
+// the image of the flattened scene's `envmap` emitter (after msk_host_flatten): 1 and *env filled, 0 when the scene has none;
+// pointers inside *env stay valid until the scene is freed
+int msk_host_envmap(msk_host_scene *h, msk_envmap_desc *env) {
+    if (!h->flat.has_envmap) return 0;
+    *env = h->flat.envmap;
+    return 1;
+}
+
 // scene->integrator()->render(scene, sensor) followed by HDRFilm::image(); optionally develop() to a file
 int msk_host_render(msk_host_scene *h, float *film_xyzaw, float *rgba, const char *develop_to, msk_stats *stats) {
     try {

@@ -1,6 +1,6 @@
 // imageio.cpp — float image output for HDRFilm::develop (the reference goes through OpenImageIO,
 // src/librender/image.cpp:20-43): PFM and uncompressed scanline OpenEXR (32-bit float channels); image input for the
-// `bitmap` texture: PFM and binary PGM / PPM.
+// `bitmap` texture and the `envmap` emitter: PFM, Radiance RGBE (.hdr) and binary PGM / PPM.
 #include <misaki/render.h>
 
 #include <algorithm>
@@ -32,14 +32,91 @@ std::string header_token(std::istream &is) {
 }
 // IEC 61966-2-1: encoded value in [0, 1] -> linear, in double, rounded once
 float srgb_to_linear(double v) { return (float) (v <= 0.04045 ? v / 12.92 : std::pow((v + 0.055) / 1.055, 2.4)); }
+// Radiance RGBE (.hdr): "#?RADIANCE" / "#?RGBE", header lines up to an empty one, "-Y H +X W", then H scanlines, each flat
+// (W x 4 bytes) or run-length encoded per channel (2 2 W_hi W_lo, then per channel counts > 128 = a run, <= 128 = literals; only
+// for 8 <= W < 32768).  A pixel (r, g, b, e) is (m + 0.5) * 2^(e - 136) per channel, 0 for e == 0.
+void read_hdr(std::istream &is, const std::string &path, int &w, int &h, std::vector<float> &rgb) {
+    std::string line;
+    bool format_seen = false;
+    std::getline(is, line);                                        // the magic line (checked by the caller)
+    while (std::getline(is, line)) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty()) break;
+        if (line.compare(0, 7, "FORMAT=") == 0) {
+            format_seen = true;
+            if (line != "FORMAT=32-bit_rle_rgbe") Throw("\"{}\": Radiance image with {} is not supported (32-bit_rle_rgbe only)", path, line);
+        }
+    }
+    if (!is) Throw("\"{}\": truncated or invalid image header", path);
+    (void) format_seen;                                            // (a file without a FORMAT line is rgbe by definition)
+    if (!std::getline(is, line)) Throw("\"{}\": truncated or invalid image header", path);
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    long lh = 0, lw = 0;
+    char sy[3] = "", sx[3] = "", tail = 0;
+    if (std::sscanf(line.c_str(), "%2s %ld %2s %ld %c", sy, &lh, sx, &lw, &tail) != 4)
+        Throw("\"{}\": truncated or invalid image header (resolution \"{}\")", path, line);
+    if (std::strcmp(sy, "-Y") != 0 || std::strcmp(sx, "+X") != 0)
+        Throw("\"{}\": Radiance image orientation \"{}\" is not supported (-Y H +X W only)", path, line);
+    if (lw < 1 || lh < 1 || lw > 65536 || lh > 65536) Throw("\"{}\": truncated or invalid image header (resolution \"{}\")", path, line);
+    w = (int) lw; h = (int) lh;
+    rgb.assign((size_t) w * h * 3, 0.f);
+    std::vector<unsigned char> scan((size_t) w * 4);
+    auto need = [&](unsigned char *dst, size_t n) {
+        is.read((char *) dst, (std::streamsize) n);
+        if ((size_t) is.gcount() != n) Throw("\"{}\": truncated image file (scanline data)", path);
+    };
+    for (int y = 0; y < h; ++y) {
+        unsigned char head[4];
+        need(head, 4);
+        const bool rle = w >= 8 && w < 32768 && head[0] == 2 && head[1] == 2 && !(head[2] & 0x80);
+        if (rle) {
+            if (((int) head[2] << 8 | head[3]) != w) Throw("\"{}\": run-length encoded scanline {} has length {}, the image is {} wide", path, y, (int) head[2] << 8 | head[3], w);
+            for (int c = 0; c < 4; ++c) {
+                int x = 0;
+                while (x < w) {
+                    unsigned char cnt, val;
+                    need(&cnt, 1);
+                    if (cnt > 128) {
+                        const int run = cnt - 128;
+                        need(&val, 1);
+                        if (x + run > w) Throw("\"{}\": run-length encoded scanline {} overruns the image width", path, y);
+                        for (int k = 0; k < run; ++k) scan[(size_t) (x++) * 4 + c] = val;
+                    } else {
+                        if (cnt == 0 || x + cnt > w) Throw("\"{}\": run-length encoded scanline {} overruns the image width", path, y);
+                        for (int k = 0; k < cnt; ++k) { need(&val, 1); scan[(size_t) (x++) * 4 + c] = val; }
+                    }
+                }
+            }
+        } else {
+            std::memcpy(scan.data(), head, 4);
+            if (w > 1) need(scan.data() + 4, (size_t) (w - 1) * 4);
+            for (int x = 0; x < w; ++x)
+                if (scan[(size_t) x * 4] == 1 && scan[(size_t) x * 4 + 1] == 1 && scan[(size_t) x * 4 + 2] == 1)
+                    Throw("\"{}\": old-style run-length encoded Radiance scanlines are not supported", path);
+        }
+        for (int x = 0; x < w; ++x) {
+            const unsigned char *p = &scan[(size_t) x * 4];
+            if (p[3] == 0) continue;
+            const double f = std::ldexp(1.0, (int) p[3] - 136);
+            for (int c = 0; c < 3; ++c) rgb[((size_t) y * w + x) * 3 + c] = (float) (((double) p[c] + 0.5) * f);
+        }
+    }
+}
 }  // namespace
 
 void read_image(const std::string &path, bool raw, int &w, int &h, std::vector<float> &rgb) {
     std::ifstream is(path, std::ios::binary);
     if (!is) Throw("Could not open the image file \"{}\"", path);
+    {   // a Radiance file starts with "#?", which the PNM header rules would skip as a comment
+        char m[11] = "";
+        is.read(m, 10);
+        const std::string start(m, (size_t) is.gcount());
+        is.clear(); is.seekg(0);
+        if (start.compare(0, 10, "#?RADIANCE") == 0 || start.compare(0, 6, "#?RGBE") == 0) { read_hdr(is, path, w, h, rgb); return; }
+    }
     const std::string magic = header_token(is);
     const bool pfm = magic == "PF" || magic == "Pf", pnm = magic == "P5" || magic == "P6";
-    if (!pfm && !pnm) Throw("\"{}\": not a PFM or binary PGM / PPM image (magic number \"{}\")", path, magic.substr(0, 8));
+    if (!pfm && !pnm) Throw("\"{}\": not a PFM, Radiance RGBE or binary PGM / PPM image (magic number \"{}\")", path, magic.substr(0, 8));
     const int channels = (magic == "PF" || magic == "P6") ? 3 : 1;
     const std::string ws = header_token(is), hs = header_token(is), third = header_token(is);
     char *end = nullptr;

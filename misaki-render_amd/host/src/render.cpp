@@ -2,6 +2,7 @@
 // Plugin names, property keys, defaults and error texts follow the reference (files cited inline);
 // per-sample work is NOT here: PathTracer::render() hands the flattened scene to the C ABI.
 #include <misaki/render.h>
+#include "../../csrc/msk_envmap.h"      // mskenv::is_rotation: the back end's own test of an envmap's to_world (plain C++)
 
 #include <algorithm>
 #include <cctype>
@@ -702,6 +703,87 @@ private:
 MSK_IMPLEMENT_CLASS(ConstantBackgroundEmitter, Emitter)
 MSK_REGISTER_INSTANCE(ConstantBackgroundEmitter, "constant")
 
+// The `envmap` emitter: a lat-long radiance image around the scene, importance-sampled on the device (include/msk_gpu.h at
+// msk_envmap_desc; the reference's emitters/envmap.cpp is RGB-typed and not built).  Properties: filename (through the file
+// resolver: PFM, Radiance .hdr, PGM / PPM), scale (default 1), to_world (a rotation; anything else is refused here, by the back end's own
+// test, and again at scene creation), raw (as the bitmap's: PGM / PPM samples are sRGB encoded unless it is set).
+// The image's top row is theta = 0 (+y of the emitter's frame).  A texel is flattened as an srgb_d65 radiance of its colour is
+// (spectra/srgb_d65.cpp:18-22): w = 2 max(rgb), coefficients fetch(rgb / w), one fetch per distinct colour; negative components
+// and NaNs count as 0, a black texel is {0, 0, 0, 0}.  The weight of a texel for light sampling: the luminance of its 3x3
+// neighbourhood (u wrapped, v clamped; summed in double, rows outer) times sin(pi (j + .5) / H), rounded to float — positive
+// wherever the bilinear lookup is.
+class EnvironmentMapEmitter final : public Emitter {
+public:
+    EnvironmentMapEmitter(const Properties &props) : Emitter(props) {
+        m_filename = props.string("filename");
+        m_scale = props.float_("scale", 1.f);
+        m_to_world = props.transform("to_world", Transform4f());
+        {   // a rotation and nothing else: the test the back end applies to the 3x3, and no translation or projective row beside it
+            const auto &m = m_to_world.matrix().m;
+            float r[9];
+            for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) r[a * 3 + b] = (float) m[a][b];
+            if (!mskenv::is_rotation(r) || m[0][3] != 0 || m[1][3] != 0 || m[2][3] != 0 || m[3][0] != 0 || m[3][1] != 0 || m[3][2] != 0 || m[3][3] != 1)
+                Throw("envmap \"{}\": to_world must be a rotation", m_filename);
+        }
+        read_image(get_file_resolver()->resolve(m_filename), props.bool_("raw", false), m_width, m_height, m_rgb);
+        for (float &v : m_rgb) v = v >= 0.f ? v : 0.f;
+    }
+    bool is_environment() const override { return true; }
+    bool flatten(msk_emitter_desc &out, FlatTables &) const override {
+        Texture::Flat f;
+        if (!Texture::D65(m_scale)->flatten(f)) return false;
+        std::memset(&out, 0, sizeof out);
+        out.type = MSK_EMITTER_ENVMAP;
+        out.mesh_id = -1;
+        out.radiance[0] = out.radiance[1] = 0.f; out.radiance[2] = INFINITY;
+        out.d65_scale = f.d65_scale;                    // scale / 10568
+        return true;
+    }
+    bool flatten_envmap(msk_envmap_desc &out, std::vector<float> &texels, std::vector<float> &weights) const override {
+        const size_t W = (size_t) m_width, H = (size_t) m_height;
+        std::memset(&out, 0, sizeof out);
+        out.width = (uint32_t) W; out.height = (uint32_t) H;
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) out.to_world[r * 3 + c] = (float) m_to_world.matrix().m[r][c];
+        texels.assign(W * H * 4, 0.f);
+        std::map<std::array<float, 3>, std::array<float, 4>> seen;          // one fetch per distinct colour
+        for (size_t k = 0; k < W * H; ++k) {
+            const std::array<float, 3> rgb{m_rgb[k * 3], m_rgb[k * 3 + 1], m_rgb[k * 3 + 2]};
+            auto it = seen.find(rgb);
+            if (it == seen.end()) {
+                std::array<float, 4> t{0.f, 0.f, 0.f, 0.f};
+                const float w = std::max(rgb[0], std::max(rgb[1], rgb[2])) * 2.f;
+                if (w != 0.f) { const Color3 c = srgb_model_fetch(Color3{rgb[0] / w, rgb[1] / w, rgb[2] / w}); t = {c.r, c.g, c.b, w}; }
+                it = seen.emplace(rgb, t).first;
+            }
+            std::memcpy(&texels[k * 4], it->second.data(), 16);
+        }
+        std::vector<double> lum(W * H);
+        for (size_t k = 0; k < W * H; ++k) lum[k] = (0.212671 * (double) m_rgb[k * 3] + 0.715160 * (double) m_rgb[k * 3 + 1]) + 0.072169 * (double) m_rgb[k * 3 + 2];
+        weights.assign(W * H, 0.f);
+        for (size_t j = 0; j < H; ++j) {
+            const double sin_theta = std::sin(M_PI * ((double) j + 0.5) / (double) H);
+            for (size_t i = 0; i < W; ++i) {
+                double sum = 0.0;
+                for (int dj = -1; dj <= 1; ++dj) {
+                    const size_t jj = (size_t) std::min<long>(std::max<long>((long) j + dj, 0), (long) H - 1);
+                    for (int di = -1; di <= 1; ++di) sum += lum[jj * W + (size_t) (((long) i + di + (long) W) % (long) W)];
+                }
+                weights[j * W + i] = (float) (sum * sin_theta);
+            }
+        }
+        return true;
+    }
+    MSK_DECLARE_CLASS()
+private:
+    std::string m_filename;
+    float m_scale = 1.f;
+    Transform4f m_to_world;
+    int m_width = 0, m_height = 0;
+    std::vector<float> m_rgb;
+};
+MSK_IMPLEMENT_CLASS(EnvironmentMapEmitter, Emitter)
+MSK_REGISTER_INSTANCE(EnvironmentMapEmitter, "envmap")
+
 // sensors/perspective.cpp:8-42
 class PerspectiveCamera final : public ProjectiveCamera {
 public:
@@ -868,6 +950,7 @@ MSK_REGISTER_INSTANCE(OBJMesh, "obj")
 void flatten_scene(const Scene *scene, const Sensor *sensor, FlatScene &out) {
     out.meshes.clear(); out.bsdfs.clear(); out.emitters.clear(); out.textures.clear(); out.vertices.clear(); out.faces.clear();
     out.regular.clear(); out.regular_values.clear(); out.texels.clear();
+    out.has_envmap = false; out.env_texels.clear(); out.env_weights.clear();
     FlatTables tables{out.textures, out.regular, out.regular_values, out.texels};
     // Scene::m_emitters order (scene.cpp:27-41) decides which emitter sample_emitter_direct picks (scene.cpp:80-84)
     std::map<const Emitter *, int> emitter_index;
@@ -877,6 +960,11 @@ void flatten_scene(const Scene *scene, const Sensor *sensor, FlatScene &out) {
             Throw("Emitter \"{}\" cannot be evaluated by the GPU path integrator", e->clazz()->name());
         if (!e->is_surface() && !e->is_environment())
             Throw("Emitter \"{}\" is not attached to a shape: not supported by the GPU path integrator", e->clazz()->name());
+        if (ed.type == MSK_EMITTER_ENVMAP) {
+            if (out.has_envmap) Throw("Can only have one environment light");            // scene.cpp:38-39
+            if (!e->flatten_envmap(out.envmap, out.env_texels, out.env_weights)) Throw("Emitter \"{}\" has no image to flatten", e->clazz()->name());
+            out.has_envmap = true;
+        }
         emitter_index[e.get()] = (int) out.emitters.size();
         out.emitters.push_back(ed);
     }
@@ -930,6 +1018,7 @@ void flatten_scene(const Scene *scene, const Sensor *sensor, FlatScene &out) {
     d.n_regular_spectra = (uint32_t) out.regular.size(); d.n_regular_values = (uint32_t) out.regular_values.size();
     d.regular_spectra = out.regular.data(); d.regular_values = out.regular_values.data();
     d.n_texels = (uint32_t) (out.texels.size() / 3); d.texels = out.texels.empty() ? nullptr : out.texels.data();
+    if (out.has_envmap) { out.envmap.texels = out.env_texels.data(); out.envmap.weights = out.env_weights.data(); }
 }
 
 // "0,1,2" -> {0,1,2}; empty -> {single}
@@ -991,7 +1080,7 @@ public:
         fill_params(sensor, flat.params);
         if (!m_ctx && msk_gpu_init(m_devices.data(), (int) m_devices.size(), &m_ctx) != MSK_OK) Throw("{}", msk_gpu_last_error(nullptr));
         msk_scene *gs = nullptr;
-        if (msk_gpu_scene_create(m_ctx, &flat.desc, &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(m_ctx));
+        if (msk_gpu_scene_create_env(m_ctx, &flat.desc, flat.envmap_ptr(), &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(m_ctx));
         ref<ImageBlock> whole = new ImageBlock(film->crop_size(), 5);        // the crop window (the whole film by default), as the storage holds it
         whole->set_offset(film->crop_offset());
         msk_stats st;
@@ -1083,7 +1172,7 @@ public:
         fill_params(sensor, flat.params);
         if (!m_ctx && msk_gpu_init(m_devices.data(), (int) m_devices.size(), &m_ctx) != MSK_OK) Throw("{}", msk_gpu_last_error(nullptr));
         msk_scene *gs = nullptr;
-        if (msk_gpu_scene_create(m_ctx, &flat.desc, &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(m_ctx));
+        if (msk_gpu_scene_create_env(m_ctx, &flat.desc, flat.envmap_ptr(), &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(m_ctx));
         ref<ImageBlock> whole = new ImageBlock(film->crop_size(), channels.size());   // the crop window, as the storage holds it (as in "path")
         whole->set_offset(film->crop_offset());
         msk_stats st;

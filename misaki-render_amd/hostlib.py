@@ -28,6 +28,7 @@ def load():
         lib.msk_host_load_scene.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp)]
         lib.msk_host_free_scene.argtypes = [vp]
         lib.msk_host_flatten.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.RenderParams)]
+        lib.msk_host_envmap.argtypes = [vp, C.POINTER(abi.EnvmapDesc)]
         lib.msk_host_render.argtypes = [vp, vp, vp, C.c_char_p, C.POINTER(abi.Stats)]
         lib.msk_host_film_size.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         lib.msk_host_film_crop.argtypes = [vp, C.POINTER(C.c_int * 4)]
@@ -52,8 +53,9 @@ def _check(rc):
 class HostFlat:
     """Same shape as hostmirror.FlatScene: .desc plus the numpy views tests use."""
 
-    def __init__(self, desc, params, owner):
+    def __init__(self, desc, params, owner, envmap=None):
         self.desc, self.params, self.owner = desc, params, owner
+        self.envmap = envmap              # abi.EnvmapDesc of the scene's `envmap` emitter, or None (abi.Scene picks it up)
         self.vertices = np.ctypeslib.as_array(desc.vertices, (desc.n_vertices, 8)) if desc.n_vertices else np.zeros((0, 8), np.float32)
         self.faces = np.ctypeslib.as_array(desc.faces, (desc.n_faces, 3)) if desc.n_faces else np.zeros((0, 3), np.uint32)
 
@@ -80,7 +82,8 @@ class HostScene:
         """The flatten step of the "path" plugin -> (msk_scene_desc, msk_render_params)."""
         d, p = abi.SceneDesc(), abi.RenderParams()
         _check(self.lib.msk_host_flatten(self.h, C.byref(d), C.byref(p)))
-        return HostFlat(d, p, self)
+        env = abi.EnvmapDesc()
+        return HostFlat(d, p, self, env if self.lib.msk_host_envmap(self.h, C.byref(env)) == 1 else None)
 
     def aov_names(self):
         buf = C.create_string_buffer(1 << 16)
@@ -130,7 +133,7 @@ def srgb_model_source():
 
 
 def read_image(path, raw=False):
-    """The `bitmap` texture's reader (PFM, binary PGM / PPM) -> float32 [H, W, 3] linear RGB, the image's top row first."""
+    """The image reader of the `bitmap` texture and the `envmap` emitter (PFM, Radiance .hdr, binary PGM / PPM) -> float32 [H, W, 3] linear RGB, the image's top row first."""
     w, h = C.c_int(), C.c_int()
     _check(load().msk_host_read_image(str(path).encode(), int(raw), C.byref(w), C.byref(h), None, 0))
     out = np.zeros((h.value, w.value, 3), np.float32)

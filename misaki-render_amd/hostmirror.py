@@ -322,6 +322,16 @@ def write_scene_xml(meshes, directory, width, height, spp, camera=None, integrat
            ['            <integer name="%s" value="%d"/>' % (k, int(v)) for k, v in (film_props or {}).items()] + ['        </film>', '    </sensor>']
 
     def env_xml():
+        if env.get("type") == "envmap":       # the image goes to <directory>/textures/envmap.pfm
+            os.makedirs(os.path.join(directory, "textures"), exist_ok=True)
+            write_pfm(os.path.join(directory, "textures", "envmap.pfm"), env["pixels"])
+            body = ['        <string name="filename" value="textures/envmap.pfm"/>']
+            if "scale" in env:
+                body.append('        <float name="scale" value="%.9g"/>' % float(np.float32(env["scale"])))
+            if "to_world" in env:
+                body += ['        <transform name="to_world">', '            <matrix value="%s"/>' % " ".join("%.9g" % float(x) for x in _env_to_world4(env).reshape(-1)),
+                         '        </transform>']
+            return ['    <emitter type="envmap">'] + body + ['    </emitter>']
         rad = env.get("radiance")
         body = ['        <spectrum name="radiance" value="%s"/>' % rad.text] if isinstance(rad, Regular) else \
                ['        <rgb name="radiance" value="%s"/>' % v3(rad)] if rad is not None else \
@@ -573,6 +583,7 @@ class FlatScene:
     def __init__(self):
         self.desc = abi.SceneDesc()
         self.keep = []
+        self.envmap = None            # abi.EnvmapDesc of the scene's `envmap` emitter, if it has one
 
 
 def _radiance_desc(radiance, fetch, scale_in=1.0):
@@ -587,12 +598,70 @@ def _radiance_desc(radiance, fetch, scale_in=1.0):
     return ce, float(np.float32(np.float32(scale_in) * scale) * (np.float32(1.0) / np.float32(10568.0)))
 
 
+def _env_to_world4(env):
+    """env["to_world"] (3x3 or 4x4, a rotation) -> float32 [4, 4]"""
+    m = np.asarray(env.get("to_world", np.eye(3)), np.float32)
+    if m.shape == (3, 3):
+        m4 = np.eye(4, dtype=np.float32)
+        m4[:3, :3] = m
+        m = m4
+    if m.shape != (4, 4):
+        raise ValueError("envmap to_world must be 3x3 or 4x4")
+    # a rotation and nothing else (csrc/msk_envmap.h, is_rotation: R R^T within 1e-4 of 1 per entry, in double, and det > 0), with no
+    # translation or projective row beside it: refused here as at scene creation
+    r = m[:3, :3].astype(np.float64)
+    ok = bool(np.all(np.abs(r @ r.T - np.eye(3)) <= 1e-4)) and float(np.linalg.det(r)) > 0
+    if not ok or np.any(m[:3, 3] != 0) or np.any(m[3] != (0, 0, 0, 1)):
+        raise ValueError("envmap: to_world must be a rotation")
+    return m
+
+
+def envmap_desc(env, fetch):
+    """{"type": "envmap", "pixels": float32 [H, W, 3] linear RGB (row 0 = the top row = theta 0), "scale": 1.0, "to_world": rotation}
+    -> (abi.EnvmapDesc, [arrays to keep alive]): the texels {c0, c1, c2, w} and the sampling weights, by the arithmetic of the C++
+    plugin (host/src/render.cpp, EnvironmentMapEmitter): w = 2 max(rgb), coefficients fetch(rgb / w) once per distinct colour,
+    negative components and NaNs 0, a black texel all zeros; weight = (luminance of the 3x3 neighbourhood, u wrapped, v clamped,
+    summed in double, rows outer) * sin(pi (j + .5) / H), rounded to float."""
+    px = np.asarray(env["pixels"], np.float32)
+    if px.ndim != 3 or px.shape[2] != 3 or px.shape[0] < 1 or px.shape[1] < 1:
+        raise ValueError("envmap pixels must be float32 [H, W, 3]")
+    H, W = px.shape[:2]
+    px = np.where(px >= 0, px, np.float32(0)).astype(np.float32)
+    flat = px.reshape(-1, 3)
+    colours, inverse = np.unique(flat, axis=0, return_inverse=True)
+    tex = np.zeros((len(colours), 4), np.float32)
+    for k, rgb in enumerate(colours):
+        w = np.float32(rgb.max() * np.float32(2.0))
+        if w != 0:
+            tex[k, :3] = fetch(tuple(float(x) for x in (rgb / w)))
+            tex[k, 3] = w
+    texels = np.ascontiguousarray(tex[inverse.reshape(-1)], np.float32)
+    p64 = px.astype(np.float64)
+    lum = (0.212671 * p64[..., 0] + 0.715160 * p64[..., 1]) + 0.072169 * p64[..., 2]
+    acc = np.zeros((H, W), np.float64)
+    rows, cols = np.arange(H), np.arange(W)
+    for dj in (-1, 0, 1):
+        rj = np.clip(rows + dj, 0, H - 1)
+        for di in (-1, 0, 1):
+            acc = acc + lum[rj][:, (cols + di + W) % W]
+    sin_theta = np.array([math.sin(math.pi * (j + 0.5) / H) for j in range(H)], np.float64)
+    weights = np.ascontiguousarray((acc * sin_theta[:, None]).astype(np.float32).reshape(-1))
+    e = abi.EnvmapDesc()
+    e.width, e.height = W, H
+    e.texels = texels.ctypes.data_as(C.POINTER(C.c_float))
+    e.weights = weights.ctypes.data_as(C.POINTER(C.c_float))
+    e.to_world[:] = [float(x) for x in _env_to_world4(env)[:3, :3].reshape(-1)]
+    return e, [texels, weights]
+
+
 def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=None, env=None, crop=None, extra_textures=()):
     """Scene -> msk_scene_desc, the step the `"path"` plugin's render() performs before calling
     the C ABI.  coeff_lookup(rgb)->(c0,c1,c2) overrides the spectral upsampling
     (tests pass the reference's own rgb2spec_fetch results); default = this package's rgb2spec.
     env: None, or {"radiance": rgb | None (= D65), "scale": 1.0, "first": False} = a top-level
-    <emitter type="constant"> placed after (or, with first=True, before) the shapes in the XML.
+    <emitter type="constant"> placed after (or, with first=True, before) the shapes in the XML; or
+    {"type": "envmap", "pixels": float32 [H, W, 3], "scale": 1.0, "to_world": rotation, "first": False} = an <emitter type="envmap">
+    (envmap_desc above; the result's .envmap is its abi.EnvmapDesc).
     crop: None, or (offset_x, offset_y, width, height) = the film's crop_offset_x/_y, crop_width/_height (film.cpp:12-21).
     extra_textures: texture specs (as MeshSpec.bsdf["texture"]) appended to the scene's textures after those the BSDFs name:
     no surface shows them, Scene.eval_texture evaluates them."""
@@ -612,6 +681,11 @@ def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=
         return abi.EmitterDesc(kind, mesh_id, (C.c_float * 3)(*ce), float(sc), 0)
 
     def env_desc():
+        if env.get("type") == "envmap":           # the image itself: fs.envmap (abi.Scene hands it to msk_gpu_scene_create_env)
+            fs.envmap, keep = envmap_desc(env, fetch)
+            fs.keep += keep
+            fs.env_texels, fs.env_weights = keep
+            return abi.EmitterDesc(abi.MSK_EMITTER_ENVMAP, -1, (C.c_float * 3)(0.0, 0.0, float("inf")), _radiance_desc(None, fetch, env.get("scale", 1.0))[1], 0)
         return emitter_desc(abi.MSK_EMITTER_CONSTANT, -1, env.get("radiance"), env.get("scale", 1.0))
     if env is not None and env.get("first"):
         ed.append(env_desc())
