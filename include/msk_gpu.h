@@ -57,6 +57,7 @@ extern "C" {
 #define MSK_BSDF_ROUGHCONDUCTOR 1  /* "roughconductor" bsdfs/roughconductor.cpp:139 (GGX only) */
 #define MSK_BSDF_ROUGHDIELECTRIC 2 /* "roughdielectric" bsdfs/roughdielectric.cpp:209 (GGX only) */
 #define MSK_BSDF_DIELECTRIC     3  /* "dielectric"     bsdfs/dielectric.cpp:105 (smooth interface: two delta lobes) */
+#define MSK_BSDF_CONDUCTOR      4  /* "conductor"      bsdfs/conductor.cpp (smooth metal: one delta reflection lobe; semantics at msk_bsdf_desc) */
 #define MSK_EMITTER_AREA       0   /* "area"     emitters/area.cpp:61          */
 #define MSK_TEXTURE_CHECKERBOARD 1 /* "checkerboard" textures/checkerboard.cpp:52 */
 #define MSK_TEXTURE_BITMAP       2 /* "bitmap", bilinear filter (ABI v8; semantics below, at msk_texture_desc) */
@@ -65,6 +66,8 @@ extern "C" {
 #define MSK_EMITTER_CONSTANT   1   /* "constant" emitters/constant.cpp:95 (environment; mesh_id = -1, at most one) */
 #define MSK_EMITTER_ENVMAP     2   /* "envmap": a lat-long radiance image, importance-sampled (environment; mesh_id = -1; at most one environment
                                       emitter per scene, `constant` or `envmap`; msk_envmap_desc + msk_gpu_scene_create_env below) */
+#define MSK_EMITTER_POINT      3   /* "point" emitters/point.cpp: an isotropic delta light (mesh_id = -1; any number; its position comes in an
+                                      msk_point_desc through msk_gpu_scene_create_ext; semantics at msk_point_desc below) */
 
 /* AOV channel groups of the "aov" integrator (integrators/aov.cpp:21-28,87-144); channels per type: 1 3 2 3 3 4 */
 #define MSK_AOV_DEPTH          0   /* si.t, 0 on a miss                                  (aov.cpp:97-99)   */
@@ -146,6 +149,17 @@ typedef struct msk_spectrum_desc {
  * ext_ior 1.00028); alpha_* and sample_visible are ignored.  eval and pdf are zero: no next-event sample is taken at such a
  * hit (path.cpp:56) and the emitter the sampled ray reaches counts with MIS weight 1 (path.cpp:104-106).  back_bsdf must be
  * -1 (twosided.cpp:33-35: no transmission under "twosided").
+ * MSK_BSDF_CONDUCTOR (bsdfs/conductor.cpp, whose RGB-typed code is not built; evaluated at the path's four wavelengths, like
+ * MSK_BSDF_ROUGHCONDUCTOR): a smooth conductor, one delta reflection lobe.  It reads eta, k, specular_reflectance and back_bsdf;
+ * alpha_*, sample_visible and reflectance* are ignored; ior_eta / ior_inv_eta are 1 / 1 (or 0 / 0, unset): a conductor has no
+ * relative index, and a type-4 descriptor that carries one (a descriptor of another kind with its type overwritten — type 4 was
+ * unassigned before) is refused with MSK_ERR_INVALID_ARG, "type 4 is not supported for a descriptor with ...".  sample: cos_i = wi.z; cos_i <= 0 fails (no direction); otherwise
+ * wo = (-wi.x, -wi.y, wi.z), pdf = 1, eta = 1, value(l) = specular_reflectance(l) * fresnel_conductor(cos_i, eta(l), k(l))
+ * (render/fresnel.h, fp32 as msk_device.h has it; one product).  eval and pdf are zero: no next-event sample is taken at such a
+ * hit and the emitter the sampled ray reaches counts with MIS weight 1, as for MSK_BSDF_DIELECTRIC.  Under "twosided" (back_bsdf
+ * = its own index) it mirrors on both faces; one-sided (back_bsdf = -1) it is black from behind.  The reference's defaults,
+ * which the flatteners write when a parameter is absent, are eta = 0, k = 1, specular_reflectance = 1 (uniform spectra): for them
+ * fresnel_conductor is exactly 1.0f for every cos_i in (0, 1], a perfect mirror.
  * back_bsdf implements the "twosided" adapter (bsdfs/twosided.cpp:38-101): the BSDF evaluated with
  * flipped wi/wo when cos(theta_i) < 0; the entry's own index for twosided(A), -1 for a one-sided BSDF.
  * reflectance_texture: 0 = the diffuse reflectance is the constant `reflectance`; k > 0 = it is
@@ -257,6 +271,39 @@ typedef struct msk_envmap_desc {
     const float *weights;    /* width * height                 */
     float to_world[9];       /* row-major rotation             */
 } msk_envmap_desc;
+
+/*
+ * The position of an MSK_EMITTER_POINT emitter (emitters/point.cpp).  Its msk_emitter_desc has mesh_id = -1 and holds the
+ * INTENSITY I(l) (W / sr per nm) in radiance / d65_scale / radiance_regular, in the two forms every emitter's radiance has; its
+ * index in `emitters` is its place in Scene::m_emitters (XML order, scene.cpp:27-41).  Exactly one msk_point_desc per such
+ * emitter, in any order.  Everything below is fp32, one operation at a time, IEEE sqrt and division, no contraction.
+ *
+ * Next-event sample from a reference point p:  d = position - p;  dist = sqrt(d.x d.x + (d.y d.y + d.z d.z));  inv = 1 / dist;
+ * d = d * inv;  pdf = 1;  value(l) = (I(l) * inv) * inv.  dist == 0 gives pdf = 0 and no contribution.  The two random numbers of
+ * the bounce are drawn and, with several emitters, u.x is rescaled as for every emitter; selection is the existing one
+ * (pdf *= 1 / n, value *= n).  The shadow ray is the existing one: direction d, length dist * (1 - MSK_SHADOW_EPS).
+ * Not kept from path.cpp as written: the reference would weight this sample mis_weight(1, bsdf_pdf); a delta emitter cannot be
+ * reached by a BSDF sample, so that weight loses energy.  Here the next-event term is thr * value * bsdf_val, weight 1
+ * (DESIGN.md section 9).  A point light is never hit or seen: no term at depth 1, no emitter density for a BSDF sample, and
+ * hide_emitters does not concern it.  It may lie outside the scene's bounds and does not switch the camera cull off.
+ *
+ * In a scene that holds a point emitter or an MSK_BSDF_CONDUCTOR (the kernels with these branches), a `constant` environment hit
+ * by a BSDF sample counts with the emitter density of the ray's own direction, (1 / 4 pi) / n_emitters, or 0 after a delta lobe:
+ * the rule MSK_EMITTER_ENVMAP follows.  (The older kernels keep path.cpp's stale next-event record there; with a point light that
+ * record holds no density and the two weights would no longer sum to 1.)
+ */
+typedef struct msk_point_desc {
+    uint32_t emitter;        /* index into msk_scene_desc.emitters: an MSK_EMITTER_POINT entry */
+    float    position[3];    /* world space, finite                                            */
+} msk_point_desc;
+
+/* What a scene holds beyond msk_scene_desc (whose layout is fixed by ABI v8): the envmap emitter's image (or NULL) and the
+   point emitters' positions (n_points may be 0, points then unused). */
+typedef struct msk_scene_ext {
+    const msk_envmap_desc *envmap;
+    uint32_t n_points;
+    const msk_point_desc *points;
+} msk_scene_ext;
 
 /* PerspectiveCamera (sensors/perspective.cpp:8-42); matrices are row-major 4x4. */
 typedef struct msk_camera_desc {
@@ -398,6 +445,11 @@ int  msk_gpu_scene_create(msk_ctx *ctx, const msk_scene_desc *desc, msk_scene **
    weight that is negative or not finite, weights that are all zero and a to_world that is no rotation are MSK_ERR_INVALID_ARG.
    A group context creates the image on every member. */
 int  msk_gpu_scene_create_env(msk_ctx *ctx, const msk_scene_desc *desc, const msk_envmap_desc *env, msk_scene **out_scene);
+/* The same with everything msk_scene_ext holds; msk_gpu_scene_create_env(c, d, e, o) is msk_gpu_scene_create_ext(c, d, &{e, 0, NULL}, o)
+   and ext == NULL is {NULL, 0, NULL}.  MSK_ERR_INVALID_ARG, with a message that names the emitter: an MSK_EMITTER_POINT emitter
+   without its msk_point_desc, with two of them, an msk_point_desc whose emitter is of another type (or out of range), a position
+   that is not finite, a point emitter whose mesh_id is not -1.  A group context passes the extension to every member. */
+int  msk_gpu_scene_create_ext(msk_ctx *ctx, const msk_scene_desc *desc, const msk_scene_ext *ext, msk_scene **out_scene);
 void msk_gpu_scene_destroy(msk_scene *scene);
 
 /* ---- the hot path --------------------------------------------------------- */
@@ -470,6 +522,16 @@ int  msk_gpu_eval_texture(msk_scene *scene, uint32_t texture, uint64_t n, const 
  */
 int  msk_gpu_env_eval(msk_scene *scene, uint64_t n, const float *dirs, const float *wavelengths, float *out_radiance, float *out_pdf);
 int  msk_gpu_env_sample(msk_scene *scene, uint64_t n, const float *u, float *out_dir, float *out_uv, float *out_pdf);
+
+/*
+ * The next-event sample of point emitter `emitter` (index into `emitters`) from n reference points: ref_points n * 3,
+ * wavelengths n * 4; out_d_dist n * 4 = {d.x, d.y, d.z, dist}, out_value n * 4 = value(l) (without the light-selection factor);
+ * all zeros where dist == 0.  msk_gpu_conductor_sample: the lobe's value of BSDF `bsdf` (index into `bsdfs`) for n cos_theta_i:
+ * out_value n * 4, zeros for cos_i <= 0.  Both run the device functions the shading kernels call.  Host pointers;
+ * MSK_ERR_INVALID_ARG for an index that is out of range or of another type.
+ */
+int  msk_gpu_point_sample(msk_scene *scene, uint32_t emitter, uint64_t n, const float *ref_points, const float *wavelengths, float *out_d_dist, float *out_value);
+int  msk_gpu_conductor_sample(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *cos_theta_i, const float *wavelengths, float *out_value);
 
 /* device + build information for logs: fills a NUL-terminated string */
 int  msk_gpu_describe(const msk_ctx *ctx, char *buf, uint64_t buf_size);

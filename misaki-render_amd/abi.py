@@ -17,8 +17,10 @@ MSK_OK = 0
 MSK_ERR_INVALID_ARG, MSK_ERR_NO_DEVICE, MSK_ERR_HIP, MSK_ERR_OOM, MSK_ERR_UNSUPPORTED = -1, -2, -3, -4, -5
 MSK_BSDF_DIFFUSE, MSK_BSDF_ROUGHCONDUCTOR, MSK_BSDF_ROUGHDIELECTRIC = 0, 1, 2
 MSK_BSDF_DIELECTRIC = 3       # "dielectric" (bsdfs/dielectric.cpp): smooth interface, two delta lobes
+MSK_BSDF_CONDUCTOR = 4        # "conductor": smooth metal, one delta reflection lobe
 MSK_EMITTER_AREA, MSK_EMITTER_CONSTANT = 0, 1
 MSK_EMITTER_ENVMAP = 2        # "envmap": a lat-long radiance image, importance-sampled (EnvmapDesc, msk_gpu_scene_create_env)
+MSK_EMITTER_POINT = 3         # "point": an isotropic delta light (PointDesc + SceneExt, msk_gpu_scene_create_ext)
 MSK_TEXTURE_CHECKERBOARD = 1
 MSK_TEXTURE_BITMAP, MSK_TEXTURE_BITMAP_NEAREST = 2, 3       # "bitmap": bilinear / nearest (ABI v8)
 MSK_EMITTER_AREA = 0
@@ -63,6 +65,14 @@ class EmitterDesc(C.Structure):
 class EnvmapDesc(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("texels", C.POINTER(C.c_float)),      # width * height * 4: c0 c1 c2 w
                 ("weights", C.POINTER(C.c_float)), ("to_world", C.c_float * 9)]                       # width * height; row-major rotation
+
+
+class PointDesc(C.Structure):
+    _fields_ = [("emitter", C.c_uint32), ("position", C.c_float * 3)]      # index into SceneDesc.emitters; world space
+
+
+class SceneExt(C.Structure):
+    _fields_ = [("envmap", C.POINTER(EnvmapDesc)), ("n_points", C.c_uint32), ("points", C.POINTER(PointDesc))]
 
 
 class CameraDesc(C.Structure):
@@ -133,7 +143,8 @@ LIB_PATH = os.environ.get("MSK_GPU_LIB") or os.path.join(_PKG_DIR, "lib", "libms
 EXPORTS = ["msk_gpu_init", "msk_gpu_shutdown", "msk_gpu_last_error", "msk_gpu_scene_create",
            "msk_gpu_scene_destroy", "msk_gpu_render", "msk_gpu_render_device", "msk_gpu_trace_closest",
            "msk_gpu_trace_any", "msk_gpu_sample_pixels", "msk_gpu_describe", "msk_gpu_render_aov", "msk_gpu_aov_channels",
-           "msk_gpu_eval_texture", "msk_gpu_scene_create_env", "msk_gpu_env_eval", "msk_gpu_env_sample"]
+           "msk_gpu_eval_texture", "msk_gpu_scene_create_env", "msk_gpu_env_eval", "msk_gpu_env_sample",
+           "msk_gpu_scene_create_ext", "msk_gpu_point_sample", "msk_gpu_conductor_sample"]
 
 # integrators/aov.cpp:21-28
 MSK_AOV_DEPTH, MSK_AOV_POSITION, MSK_AOV_UV, MSK_AOV_GEO_NORMAL, MSK_AOV_SH_NORMAL, MSK_AOV_PATH_RGBA = range(6)
@@ -186,6 +197,12 @@ def load_library(path=None):
     lib.msk_gpu_env_eval.restype = C.c_int
     lib.msk_gpu_env_sample.argtypes = [vp, u64, vp, vp, vp, vp]
     lib.msk_gpu_env_sample.restype = C.c_int
+    lib.msk_gpu_scene_create_ext.argtypes = [vp, C.POINTER(SceneDesc), C.POINTER(SceneExt), C.POINTER(vp)]
+    lib.msk_gpu_scene_create_ext.restype = C.c_int
+    lib.msk_gpu_point_sample.argtypes = [vp, C.c_uint32, u64, vp, vp, vp, vp]
+    lib.msk_gpu_point_sample.restype = C.c_int
+    lib.msk_gpu_conductor_sample.argtypes = [vp, C.c_uint32, u64, vp, vp, vp]
+    lib.msk_gpu_conductor_sample.restype = C.c_int
     lib.msk_gpu_describe.argtypes = [vp, C.c_char_p, u64]
     lib.msk_gpu_describe.restype = C.c_int
     if path is None:
@@ -238,13 +255,22 @@ class Context:
 class Scene:
     """msk_scene: geometry + BVH + light tables resident in HBM."""
 
-    def __init__(self, ctx, flat, envmap=None):
+    def __init__(self, ctx, flat, envmap=None, points=None):
         """flat: hostmirror.FlatScene (keeps the numpy arrays the desc points into alive).  envmap: the EnvmapDesc of the scene's
-        MSK_EMITTER_ENVMAP emitter; by default the one the flattener made (flat.envmap), if any."""
+        MSK_EMITTER_ENVMAP emitter; by default the one the flattener made (flat.envmap), if any.  points: the PointDesc array of
+        its MSK_EMITTER_POINT emitters (a ctypes array or a list); by default flat.points.  A scene with points is created
+        through msk_gpu_scene_create_ext, one with an image alone through _create_env, any other through msk_gpu_scene_create."""
         self.ctx, self.flat = ctx, flat
         self.handle = C.c_void_p()
         self.envmap = envmap if envmap is not None else getattr(flat, "envmap", None)
-        if self.envmap is not None:
+        pts = points if points is not None else getattr(flat, "points", None)
+        if pts is not None and not isinstance(pts, C.Array):
+            pts = (PointDesc * max(1, len(pts)))(*pts) if len(pts) else None
+        self.points = pts if (pts is not None and len(pts)) else None
+        if self.points is not None:
+            self.ext = SceneExt(C.pointer(self.envmap) if self.envmap is not None else None, len(self.points), self.points)
+            ctx.check(ctx.lib.msk_gpu_scene_create_ext(ctx.handle, C.byref(flat.desc), C.byref(self.ext), C.byref(self.handle)))
+        elif self.envmap is not None:
             ctx.check(ctx.lib.msk_gpu_scene_create_env(ctx.handle, C.byref(flat.desc), C.byref(self.envmap), C.byref(self.handle)))
         else:
             ctx.check(ctx.lib.msk_gpu_scene_create(ctx.handle, C.byref(flat.desc), C.byref(self.handle)))
@@ -335,6 +361,28 @@ class Scene:
         d, uv, pdf = np.empty((len(u), 3), np.float32), np.empty((len(u), 2), np.float32), np.empty(len(u), np.float32)
         self.ctx.check(self.ctx.lib.msk_gpu_env_sample(self.handle, len(u), _ptr(u), _ptr(d), _ptr(uv), _ptr(pdf)))
         return d, uv, pdf
+
+    def point_sample(self, emitter, ref_points, wavelengths):
+        """The next-event sample of point emitter `emitter` (index into the scene's emitters) from the reference points
+        float32[n, 3] at wavelengths float32[n, 4] -> ({d.x, d.y, d.z, dist} float32[n, 4], value float32[n, 4])."""
+        p = np.ascontiguousarray(ref_points, np.float32).reshape(-1, 3)
+        wl = np.ascontiguousarray(wavelengths, np.float32).reshape(-1, 4)
+        if len(p) != len(wl):
+            raise ValueError("ref_points and wavelengths must name the same number of points")
+        dd, val = np.empty((len(p), 4), np.float32), np.empty((len(p), 4), np.float32)
+        self.ctx.check(self.ctx.lib.msk_gpu_point_sample(self.handle, int(emitter), len(p), _ptr(p), _ptr(wl), _ptr(dd), _ptr(val)))
+        return dd, val
+
+    def conductor_sample(self, bsdf, cos_theta_i, wavelengths):
+        """The value of the delta lobe of conductor `bsdf` (index into the scene's bsdfs) for cos_theta_i float32[n] at
+        wavelengths float32[n, 4] -> float32[n, 4], zeros for cos_theta_i <= 0."""
+        c = np.ascontiguousarray(cos_theta_i, np.float32).reshape(-1)
+        wl = np.ascontiguousarray(wavelengths, np.float32).reshape(-1, 4)
+        if len(c) != len(wl):
+            raise ValueError("cos_theta_i and wavelengths must name the same number of points")
+        val = np.empty((len(c), 4), np.float32)
+        self.ctx.check(self.ctx.lib.msk_gpu_conductor_sample(self.handle, int(bsdf), len(c), _ptr(c), _ptr(wl), _ptr(val)))
+        return val
 
     def close(self):
         if self.handle:

@@ -70,6 +70,7 @@ struct DeviceScene {
     uint32_t n_bsdf_f4;         // float4 count of `bsdfs` (records + textures)
     const float4 *emitters;     // 2 x float4 per emitter: {c0,c1,c2,inv_area} {mesh,first_face,face_count,cdf_off (uint bits)}; an environment
                                 // emitter: mesh = ~0 and, for an `envmap`, first_face = the float4 offset of its block in `texels` (EnvView)
+                                // and face_count = 1 (0: the `constant` sky); a `point` emitter: {MSK_EMITTER_MARK_POINT, x, y, z}, its position
     const float *emitter_d65;   // 95 floats per emitter: d65 * d65_scale, or the values of a `regular` radiance (ABI v7)
     const float4 *emitter_grid; // per emitter {lambda_min, inv_interval, last segment (uint bits), 1 = the table IS the radiance (no
                                 // sigmoid factor)} of that table: {360, 0.2, 93, 0} for the D65 form.  Read by the general shading
@@ -1417,11 +1418,18 @@ struct SceneTablesB : SceneTablesD {};
 // density and the sampling of light directions from it are compiled only into the instantiations that carry this type
 // (k_shade_gen_e, k_wavefront_e, k_wavefront_h_e, k_path_serial_e).  In them the scene's environment emitter IS the image.
 struct SceneTablesE : SceneTablesB {};
-template <class TB> struct tb_traits { static constexpr bool regular = false, dielectric = false, bitmap = false, envmap = false; };
-template <> struct tb_traits<SceneTablesR> { static constexpr bool regular = true, dielectric = false, bitmap = false, envmap = false; };
-template <> struct tb_traits<SceneTablesD> { static constexpr bool regular = true, dielectric = true, bitmap = false, envmap = false; };
-template <> struct tb_traits<SceneTablesB> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = false; };
-template <> struct tb_traits<SceneTablesE> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = true; };
+// ... and of a scene that holds a `point` emitter (MSK_EMITTER_POINT) or a smooth `conductor` (MSK_BSDF_CONDUCTOR), whatever else
+// it holds: the delta light's next-event branch, the mirror lobe and the `constant` sky's own density on the miss branch are compiled
+// only into the instantiations that carry this type (k_shade_gen_p, k_wavefront_p, k_wavefront_h_p, k_path_serial_p).  In them the
+// environment emitter, if any, is the image OR the `constant` sky: the emitter's record says which (env_is_image).
+struct SceneTablesP : SceneTablesE {};
+#define MSK_EMITTER_MARK_POINT 0xfffffffeu      /* word 0 of a point emitter's second float4 (an environment emitter's: 0xffffffff) */
+template <class TB> struct tb_traits { static constexpr bool regular = false, dielectric = false, bitmap = false, envmap = false, delta = false; };
+template <> struct tb_traits<SceneTablesR> { static constexpr bool regular = true, dielectric = false, bitmap = false, envmap = false, delta = false; };
+template <> struct tb_traits<SceneTablesD> { static constexpr bool regular = true, dielectric = true, bitmap = false, envmap = false, delta = false; };
+template <> struct tb_traits<SceneTablesB> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = false, delta = false; };
+template <> struct tb_traits<SceneTablesE> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = true, delta = false; };
+template <> struct tb_traits<SceneTablesP> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = true, delta = true; };
 MSK_DEV uint32_t tables_lds_float4s(const DeviceScene &sc) {
     return sc.n_tris * 6 + sc.n_meshes + sc.n_bsdf_f4 + sc.n_emitters * 3 + (sc.n_emitters * 95 + 3) / 4 + (sc.cdf_len + 3) / 4 + 72 + (sc.n_spectra + 3) / 4;
 }
@@ -1735,6 +1743,20 @@ MSK_DEV f3 env_sample(const EnvView &ev, f2 u, f2 *uv_out, float *pdf) {
     *uv_out = uv;
     return mk3(R[0] * lx + (R[1] * ly + R[2] * lz), R[3] * lx + (R[4] * ly + R[5] * lz), R[6] * lx + (R[7] * ly + R[8] * lz));
 }
+// Is the scene's environment emitter the image?  SceneTablesE: always (that is what selects those kernels).  SceneTablesP: the
+// emitter's record says (word 2 of its second float4: 1 = image, 0 = the `constant` sky); without an environment emitter, no.
+// (Called behind `tb_traits<TB>::envmap && (!tb_traits<TB>::delta || ...)`, which the other instantiations fold away where it is written.)
+template <class TB>
+MSK_DEV bool env_is_image(const TB &tb, const DeviceScene &sc) {
+    return sc.env_emitter >= 0 && __float_as_uint(tb.emitters[2 * sc.env_emitter + 1].z) != 0u;
+}
+// The `point` emitter's next-event sample from p (msk_gpu.h: msk_point_desc; point.cpp): direction, distance and 1 / distance
+MSK_DEV f3 point_sample(f3 position, f3 p, float *dist, float *inv) {
+    const f3 d = position - p;
+    *dist = __builtin_sqrtf(dot(d, d));
+    *inv = 1.f / *dist;
+    return d * *inv;
+}
 MSK_DEV float clamp_alpha(float a) { return fmax_std(a, 1e-4f); }
 
 // bsdfs/roughdielectric.cpp:118-190 eval + pdf (both lobes, TransportMode::Radiance)
@@ -1821,9 +1843,25 @@ MSK_DEV spec dielectric_sample(const TB &tb, const BsdfRec &b, f3 wi, f2 sample,
     *wo = mk3(-eta_ti * wi.x, -eta_ti * wi.y, cos_t);
     return spectrum_eval(tb, b.trans, wl) * eta_ti * eta_ti;
 }
-// BSDFFlags::Smooth (path.cpp:56): every lobe but the delta ones of `dielectric` takes a next-event sample
+// The smooth `conductor` (msk_gpu.h: MSK_BSDF_CONDUCTOR; conductor.cpp): one delta reflection lobe, wi on the front side
 template <class TB>
-MSK_DEV bool bsdf_is_delta(const BsdfRec &b) { return tb_traits<TB>::dielectric && __float_as_int(b.a.x) == MSK_BSDF_DIELECTRIC; }
+MSK_DEV spec conductor_sample(const TB &tb, const BsdfRec &b, f3 wi, spec wl, f3 *wo, float *pdf, bool *ok) {
+    const float cos_i = wi.z;
+    if (cos_i <= 0.f) return splat(0.f);
+    *ok = true;
+    *wo = mk3(-wi.x, -wi.y, wi.z);
+    *pdf = 1.f;
+    const spec eta = spectrum_eval(tb, b.eta, wl), kk = spectrum_eval(tb, b.k, wl);
+    spec F;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) F.v[i] = fresnel_conductor(cos_i, eta.v[i], kk.v[i]);
+    return spectrum_eval(tb, b.spec, wl) * F;
+}
+// BSDFFlags::Smooth (path.cpp:56): every lobe but the delta ones of `dielectric` and `conductor` takes a next-event sample
+template <class TB>
+MSK_DEV bool bsdf_is_delta(const BsdfRec &b) {
+    return (tb_traits<TB>::dielectric && __float_as_int(b.a.x) == MSK_BSDF_DIELECTRIC) || (tb_traits<TB>::delta && __float_as_int(b.a.x) == MSK_BSDF_CONDUCTOR);
+}
 
 // eval + pdf with wi on the front side (roughconductor.cpp:82-117 / diffuse.cpp:35-57)
 // `refl` = the diffuse reflectance spectrum at wl, evaluated once per bounce by the caller (used by eval and by sample)
@@ -1840,6 +1878,7 @@ MSK_DEV void bsdf_eval_pdf(const TB &tb, const BsdfRec &b, f3 wi, f3 wo, spec wl
     }
     if (__float_as_int(b.a.x) == MSK_BSDF_ROUGHDIELECTRIC) { roughdielectric_eval_pdf(tb, b, wi, wo, wl, val, pdf); return; }
     if (tb_traits<TB>::dielectric && __float_as_int(b.a.x) == MSK_BSDF_DIELECTRIC) return;      // dielectric.cpp:74-82: zero
+    if (tb_traits<TB>::delta && __float_as_int(b.a.x) == MSK_BSDF_CONDUCTOR) return;            // the mirror likewise
     const float au = clamp_alpha(b.b.y), av = clamp_alpha(b.b.z);
     if (cos_i > 0.f && cos_o > 0.f) {
         const f3 H = normalized(wo + wi);
@@ -1870,6 +1909,8 @@ MSK_DEV spec bsdf_sample(const TB &tb, const BsdfRec &b, f3 wi, float sample1, f
         return roughdielectric_sample(tb, b, wi, sample1, sample, wl, wo, pdf, eta_out, ok);
     if (!DIFFUSE_ONLY && tb_traits<TB>::dielectric && __float_as_int(b.a.x) == MSK_BSDF_DIELECTRIC)
         return dielectric_sample(tb, b, wi, sample, wl, wo, pdf, eta_out, ok);
+    if (!DIFFUSE_ONLY && tb_traits<TB>::delta && __float_as_int(b.a.x) == MSK_BSDF_CONDUCTOR)
+        return conductor_sample(tb, b, wi, wl, wo, pdf, ok);
     const float cos_i = wi.z;
     if (cos_i <= 0.f) return splat(0.f);
     *ok = true;
@@ -2177,7 +2218,7 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
         bool has_shadow = false;
 
         if (alive && hit.x == MSK_INF_F) {                                 // path.cpp:34-41 / 89-97
-            if (tb_traits<TB>::envmap) {
+            if (tb_traits<TB>::envmap && (!tb_traits<TB>::delta || env_is_image(tb, sc))) {
                 // an image: value and density are those of the ray's own direction (msk_gpu.h, msk_envmap_desc)
                 const EnvView ev = env_view(tb, sc.env_emitter);
                 float sin_t;
@@ -2190,6 +2231,20 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
                     if (n_em != 1) pdf = pdf * (1.f / n_em);
                     if (delta_in) pdf = 0.f;
                     res = res + thr * le * mis_weight(bs_pdf, pdf);
+                }
+            } else
+            if (tb_traits<TB>::delta) {
+                // the `constant` sky beside a delta light: the density of the ray's own direction, as for an image (msk_gpu.h, msk_point_desc)
+                if (sc.env_emitter >= 0) {
+                    const spec le = emitter_radiance(tb, sc.env_emitter, wl);
+                    if (depth == 1) {
+                        if (!pp.hide_emitters && pp.max_depth != 0) res = res + thr * le;
+                    } else {
+                        float pdf = MSK_INV_FOUR_PI_F;
+                        if (n_em != 1) pdf = pdf * (1.f / n_em);
+                        if (delta_in) pdf = 0.f;
+                        res = res + thr * le * mis_weight(bs_pdf, pdf);
+                    }
                 }
             } else
             if (!DIFFUSE_ONLY && sc.env_emitter >= 0) {
@@ -2271,7 +2326,8 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
                     }
                     const float4 e0 = tb.emitters[2 * e], e1 = tb.emitters[2 * e + 1];
                     f3 d; float dist, pdf; spec emitter_val;
-                    if (tb_traits<TB>::envmap && (int) e == sc.env_emitter) {
+                    bool point = false;
+                    if (tb_traits<TB>::envmap && (int) e == sc.env_emitter && (!tb_traits<TB>::delta || env_is_image(tb, sc))) {
                         const EnvView ev = env_view(tb, (int) e);
                         f2 uv;
                         d = env_sample(ev, u, &uv, &pdf);
@@ -2279,6 +2335,15 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
                         emitter_val = splat(0.f);
                         if (pdf != 0.f) emitter_val = env_radiance(ev, tb, (int) e, uv, wl) / pdf;
                         nee_pdf = pdf;
+                    } else
+                    if (tb_traits<TB>::delta && __float_as_uint(e1.x) == MSK_EMITTER_MARK_POINT) {
+                        // point.cpp (msk_gpu.h, msk_point_desc): pdf 1, value = I / dist^2, weight 1 below
+                        float inv;
+                        d = point_sample(mk3(e1.y, e1.z, e1.w), si.p, &dist, &inv);
+                        point = true;
+                        pdf = 1.f; nee_pdf = 0.f;
+                        emitter_val = emitter_radiance(tb, (int) e, wl) * inv * inv;
+                        if (dist == 0.f) { pdf = 0.f; emitter_val = splat(0.f); }
                     } else
                     if (!DIFFUSE_ONLY && (int) e == sc.env_emitter) {
                         // constant.cpp:53-72 (radiance at the path's wavelengths, oracle D8)
@@ -2332,7 +2397,7 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
                         if (flipped) wo.z = -wo.z;
                         spec bsdf_val; float bsdf_pdf;
                         bsdf_eval_pdf<DIFFUSE_ONLY>(tb, bs, wi_s, wo, wl, refl, &bsdf_val, &bsdf_pdf);
-                        const float w = mis_weight(pdf, bsdf_pdf);
+                        const float w = (tb_traits<TB>::delta && point) ? 1.f : mis_weight(pdf, bsdf_pdf);
                         contrib = thr * emitter_val * bsdf_val * w;
                         if (any_nonzero(contrib)) {
                             has_shadow = true;                             // scene.cpp:91-95
@@ -2570,14 +2635,14 @@ MSK_DEV DoneQueue done_queue(float4 *base) {
 
 // the table type of an instantiation: plain, with tabulated spectra, with the smooth dielectric (which includes them), with bitmap
 // textures (which includes both)
-template <bool REGULAR, bool DIELECTRIC, bool BITMAP = false, bool ENVMAP = false>
-using tables_of = typename std::conditional<ENVMAP, SceneTablesE, typename std::conditional<BITMAP, SceneTablesB, typename std::conditional<DIELECTRIC, SceneTablesD,
-                                            typename std::conditional<REGULAR, SceneTablesR, SceneTables>::type>::type>::type>::type;
+template <bool REGULAR, bool DIELECTRIC, bool BITMAP = false, bool ENVMAP = false, bool DELTA = false>
+using tables_of = typename std::conditional<DELTA, SceneTablesP, typename std::conditional<ENVMAP, SceneTablesE, typename std::conditional<BITMAP, SceneTablesB, typename std::conditional<DIELECTRIC, SceneTablesD,
+                                            typename std::conditional<REGULAR, SceneTablesR, SceneTables>::type>::type>::type>::type>::type;
 
-template <bool LDS_TABLES, bool DIFFUSE_ONLY, bool REGULAR = false, bool DIELECTRIC = false, bool BITMAP = false, bool ENVMAP = false>
+template <bool LDS_TABLES, bool DIFFUSE_ONLY, bool REGULAR = false, bool DIELECTRIC = false, bool BITMAP = false, bool ENVMAP = false, bool DELTA = false>
 MSK_DEV void shade_gen_body(const DeviceScene &sc, const PathState &st, const PassParams &pp) {
     extern __shared__ float4 lds_dyn[];
-    tables_of<REGULAR, DIELECTRIC, BITMAP, ENVMAP> tb;
+    tables_of<REGULAR, DIELECTRIC, BITMAP, ENVMAP, DELTA> tb;
     static_cast<SceneTables &>(tb) = stage_tables<LDS_TABLES>(sc, lds_dyn);
     const uint32_t lwave = (blockIdx.x * MSK_BLOCK + threadIdx.x) / MSK_WAVE;
     const uint32_t queue_f4 = LDS_TABLES ? tables_lds_float4s(sc) : small_tables_float4s(sc);   // after the staged tables
@@ -2625,6 +2690,11 @@ k_shade_gen_b(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_
 template <bool LDS_TABLES>
 __global__ void __launch_bounds__(MSK_BLOCK)
 k_shade_gen_e(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_TABLES, false, true, true, true, true>(sc, st, pp); }
+// ... and the two that scenes with a `point` emitter or a smooth `conductor` run, and only they (SceneTablesP), whatever else they
+// hold.  Not held at three waves per SIMD either: they carry everything k_shade_gen_e does
+template <bool LDS_TABLES>
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_shade_gen_p(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_TABLES, false, true, true, true, true, true>(sc, st, pp); }
 // The diffuse-only variants fit four waves per SIMD (128 VGPRs, no scratch); left alone, the allocator spends 24 more registers
 // on the explicit fp64 fma chains of det_sincos and lands at three.
 #ifndef MSK_NO_SHADE4
@@ -2718,6 +2788,14 @@ k_wavefront_e(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, u
     constexpr bool CULL = false;      // (no camera cull with an environment emitter)
     MSK_WAVEFRONT_BODY
 }
+// the one scenes with a `point` emitter or a smooth `conductor` run (see k_shade_gen_p)
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_wavefront_p(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
+    typedef SceneTablesP TB;
+    constexpr bool DIFFUSE_ONLY = false;
+    constexpr bool CULL = false;      // (as k_wavefront_d)
+    MSK_WAVEFRONT_BODY
+}
 #undef MSK_WAVEFRONT_BODY
 
 // k_wavefront_h (round 6): the same device-side loop for scenes whose TREE STAYS IN HBM / L2 (trace mode 6: the 4-wide tree with
@@ -2795,6 +2873,13 @@ k_wavefront_h_e(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters,
     constexpr bool DIFFUSE_ONLY = false;
     MSK_WAVEFRONT_H_BODY
 }
+// the one scenes with a `point` emitter or a smooth `conductor` run (see k_shade_gen_p)
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_wavefront_h_p(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
+    typedef SceneTablesP TB;
+    constexpr bool DIFFUSE_ONLY = false;
+    MSK_WAVEFRONT_H_BODY
+}
 #undef MSK_WAVEFRONT_H_BODY
 
 // msk_gpu_eval_texture: the value of the texture whose record sits at float4 offset `rec` of the BSDF table, at n given uv and
@@ -2830,6 +2915,34 @@ k_env_probe(DeviceScene sc, uint32_t sample, uint64_t n, const float *in, const 
             const spec v = env_radiance(ev, tb, sc.env_emitter, uv, from4(wl[i]));
             out_rad[i] = make_float4(v.v[0], v.v[1], v.v[2], v.v[3]);
             out_pdf[i] = env_pdf(ev, uv, sin_t);
+        }
+    }
+}
+
+// msk_gpu_point_sample (conductor == 0: `in` = n * 3 reference points; out_a = {d, dist}, out_b = value) / msk_gpu_conductor_sample
+// (conductor == 1: `in` = n cosines; out_b = the lobe's value, zeros for cos_i <= 0), through the functions the shading kernels call.
+// `index` = the emitter / the BSDF, checked by the host.  One point per thread.
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_delta_probe(DeviceScene sc, uint32_t conductor, uint32_t index, uint64_t n, const float *in, const float4 *wl, float4 *out_a, float4 *out_b) {
+    SceneTablesP tb;
+    static_cast<SceneTables &>(tb) = stage_tables<false>(sc, nullptr);
+    for (uint64_t i = (uint64_t) blockIdx.x * MSK_BLOCK + threadIdx.x; i < n; i += (uint64_t) gridDim.x * MSK_BLOCK) {
+        const spec w = from4(wl[i]);
+        if (conductor) {
+            const BsdfRec bs = load_bsdf(tb, (int) index);
+            const float c = in[i];
+            f3 wo; float pdf = 0.f; bool ok = false;
+            // (wi = (0, 0, cos_i): the lobe's value depends on wi.z alone)
+            const spec v = conductor_sample(tb, bs, mk3(0.f, 0.f, c), w, &wo, &pdf, &ok);
+            out_b[i] = make_float4(v.v[0], v.v[1], v.v[2], v.v[3]);
+        } else {
+            const float4 e1 = tb.emitters[2 * index + 1];
+            float dist, inv;
+            const f3 d = point_sample(mk3(e1.y, e1.z, e1.w), mk3(in[i * 3], in[i * 3 + 1], in[i * 3 + 2]), &dist, &inv);
+            spec v = emitter_radiance(tb, (int) index, w) * inv * inv;
+            float4 a = make_float4(d.x, d.y, d.z, dist);
+            if (dist == 0.f) { v = splat(0.f); a = make_float4(0.f, 0.f, 0.f, 0.f); }
+            out_a[i] = a; out_b[i] = make_float4(v.v[0], v.v[1], v.v[2], v.v[3]);
         }
     }
 }

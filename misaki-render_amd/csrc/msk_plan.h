@@ -111,6 +111,8 @@ struct SceneFacts {
     bool lds_scene = false, lds_tables = false, all_diffuse = true, has_regular = false, has_dielectric = false, cull_ok = false;
     bool has_bitmap = false;      // a `bitmap` texture (ABI v8): the instantiations with the texel lookup run, whatever else the scene holds
     bool has_envmap = false;      // an `envmap` emitter (MSK_EMITTER_ENVMAP): the instantiations with the image lookup and its sampling run
+    bool has_delta = false;       // a `point` emitter or a smooth `conductor` (MSK_EMITTER_POINT, MSK_BSDF_CONDUCTOR): the instantiations with the
+                                  // delta light, the mirror lobe and the `constant` sky's own density run, whatever else the scene holds
     size_t trace_lds_bytes = 0, shade_lds_bytes = 0;
 };
 struct CallFacts {
@@ -132,8 +134,10 @@ enum ShadeKind : int {     // in the order they are tried: a dielectric scene is
     SHADE_GENERAL,         // k_shade_gen<lds_tables, false>;           k_wavefront<false> / k_wavefront_h<false>
     SHADE_BITMAP,          // k_shade_gen_b<lds_tables>;                k_wavefront_b / k_wavefront_h_b.  Tried before the older ones (a scene
                            // with a bitmap runs these whatever else it holds); behind them in the enum, whose older values are indices elsewhere
-    SHADE_ENVMAP           // k_shade_gen_e<lds_tables>;                k_wavefront_e / k_wavefront_h_e.  Tried FIRST: a scene with an `envmap`
-                           // emitter runs these whatever else it holds (they carry the bitmap lookup and the delta lobes)
+    SHADE_ENVMAP,          // k_shade_gen_e<lds_tables>;                k_wavefront_e / k_wavefront_h_e.  Tried before those above: a scene with
+                           // an `envmap` emitter runs these whatever else it holds (they carry the bitmap lookup and the delta lobes)
+    SHADE_DELTA            // k_shade_gen_p<lds_tables>;                k_wavefront_p / k_wavefront_h_p.  Tried FIRST: a scene with a `point`
+                           // emitter or a smooth `conductor` runs these whatever else it holds (they carry the envmap lookup as well)
 };
 
 struct LaunchPlan {
@@ -171,9 +175,9 @@ inline LaunchPlan make_launch_plan(const SceneFacts &sc, const CallFacts &call, 
     // (MSK_FORCE_GENERAL_SHADE=1, measurements only: an all-diffuse scene through the general variant — what a per-class diffuse
     // instantiation could save a mixed scene's diffuse chunks)
     // (the AOV RGB record and the validity test over an "aov" render's record groups live in the general shading variant)
-    p.lds_tables = sc.lds_tables; p.regular = sc.has_regular; p.dielectric = sc.has_dielectric || sc.has_bitmap || sc.has_envmap;      // (the bitmap / envmap instantiations carry the delta lobes)
+    p.lds_tables = sc.lds_tables; p.regular = sc.has_regular; p.dielectric = sc.has_dielectric || sc.has_bitmap || sc.has_envmap || sc.has_delta;      // (the bitmap / envmap / delta instantiations carry the delta lobes)
     p.diffuse_only = sc.all_diffuse && !aov_any && !knobs.force_general_shade;
-    p.shade_kind = sc.has_envmap ? SHADE_ENVMAP : sc.has_bitmap ? SHADE_BITMAP : p.dielectric ? SHADE_DIELECTRIC : p.diffuse_only ? SHADE_DIFFUSE : p.regular ? SHADE_REGULAR : SHADE_GENERAL;
+    p.shade_kind = sc.has_delta ? SHADE_DELTA : sc.has_envmap ? SHADE_ENVMAP : sc.has_bitmap ? SHADE_BITMAP : p.dielectric ? SHADE_DIELECTRIC : p.diffuse_only ? SHADE_DIFFUSE : p.regular ? SHADE_REGULAR : SHADE_GENERAL;
     // material-sorted shading (general variant): LDS for the permutation, 3 bytes per slot of a region and wave (MSK_SORT=0: off)
     const size_t sort_lds = kWavesPerBlock * 3 * call.region_size;
     p.sort_on = !p.diffuse_only && (!sc.all_diffuse || knobs.force_general_shade) && call.region_size <= 4096 && knobs.sort &&

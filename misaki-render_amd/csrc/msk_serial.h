@@ -86,5 +86,11 @@ k_path_serial_e(DeviceScene sc, SerialParams prm) {
     typedef SceneTablesE TB;
 #include "msk_serial_body.inc"
 }
+// ... and SceneTablesP for a scene that holds a `point` emitter or a smooth `conductor` (whatever else it holds)
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_path_serial_p(DeviceScene sc, SerialParams prm) {
+    typedef SceneTablesP TB;
+#include "msk_serial_body.inc"
+}
 
 }  // namespace msk

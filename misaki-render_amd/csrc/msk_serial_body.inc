@@ -1,4 +1,4 @@
-// msk_serial_body.inc — the body of k_path_serial / k_path_serial_d / k_path_serial_b / k_path_serial_e (msk_serial.h), included once into each: `TB` is the
+// msk_serial_body.inc — the body of k_path_serial / k_path_serial_d / k_path_serial_b / k_path_serial_e / k_path_serial_p (msk_serial.h), included once into each: `TB` is the
 // kernel's table type, `sc` and `prm` its arguments.  Written once and stamped, not shared through a function, so that
 // k_path_serial compiles from the token stream it always had.
     extern __shared__ float4 lds_dyn[];
@@ -62,7 +62,7 @@
                 float4 hit = closest(ro, rd, sc.near_clip * inv_z, sc.far_clip * inv_z);
                 for (int depth = 1; depth <= prm.max_depth || prm.max_depth < 0; ++depth) {
                     if (hit.x == MSK_INF_F) {                                          // path.cpp:34-41
-                        if (tb_traits<TB>::envmap) {
+                        if (tb_traits<TB>::envmap && (!tb_traits<TB>::delta || env_is_image(tb, sc))) {
                             if (depth == 1 && !prm.hide_emitters) { const EnvView ev = env_view(tb, sc.env_emitter); float sin_t; const f2 uv = env_dir_to_uv(ev, rd, &sin_t); res = res + thr * env_radiance(ev, tb, sc.env_emitter, uv, wl); }
                         } else
                         if (depth == 1 && !prm.hide_emitters && sc.env_emitter >= 0) res = res + thr * emitter_radiance(tb, sc.env_emitter, wl);
@@ -103,7 +103,16 @@
                             }
                             const float4 e0 = tb.emitters[2 * e], e1 = tb.emitters[2 * e + 1];
                             f3 d; float dist, pdf; spec emitter_val;
-                            if (tb_traits<TB>::envmap && (int) e == sc.env_emitter) {  // the image (msk_gpu.h, msk_envmap_desc)
+                            bool point = false;
+                            if (tb_traits<TB>::delta && __float_as_uint(e1.x) == MSK_EMITTER_MARK_POINT) {   // point.cpp (msk_gpu.h, msk_point_desc)
+                                float inv;
+                                d = point_sample(mk3(e1.y, e1.z, e1.w), si.p, &dist, &inv);
+                                point = true;
+                                pdf = 1.f;
+                                emitter_val = emitter_radiance(tb, (int) e, wl) * inv * inv;
+                                if (dist == 0.f) { pdf = 0.f; emitter_val = splat(0.f); }
+                            } else
+                            if (tb_traits<TB>::envmap && (int) e == sc.env_emitter && (!tb_traits<TB>::delta || env_is_image(tb, sc))) {  // the image (msk_gpu.h, msk_envmap_desc)
                                 const EnvView ev = env_view(tb, (int) e);
                                 f2 uv;
                                 d = env_sample(ev, u, &uv, &pdf);
@@ -156,7 +165,7 @@
                                 if (flipped) wo.z = -wo.z;
                                 spec bsdf_val; float bsdf_pdf;
                                 bsdf_eval_pdf<false>(tb, bs, wi_s, wo, wl, refl, &bsdf_val, &bsdf_pdf);
-                                const float w = mis_weight(pdf, bsdf_pdf);
+                                const float w = (tb_traits<TB>::delta && point) ? 1.f : mis_weight(pdf, bsdf_pdf);     // a delta light: weight 1
                                 const spec contrib = thr * emitter_val * bsdf_val * w;
                                 if (any_nonzero(contrib)) {                            // scene.cpp:91-95: an occluded sample adds nothing
                                     ++n_shadow;
@@ -192,12 +201,17 @@
                             emitter_pdf = pdf;
                             hit_emitter = true;
                         }
-                    } else if (tb_traits<TB>::envmap) {                                 // value and density of the ray's own direction
+                    } else if (tb_traits<TB>::envmap && (!tb_traits<TB>::delta || env_is_image(tb, sc))) {                                  // value and density of the ray's own direction
                         const EnvView ev = env_view(tb, sc.env_emitter);
                         float sin_t;
                         const f2 uv = env_dir_to_uv(ev, rd, &sin_t);
                         value = env_radiance(ev, tb, sc.env_emitter, uv, wl);
                         emitter_pdf = env_pdf(ev, uv, sin_t);
+                        if (n_em != 1) emitter_pdf = emitter_pdf * (1.f / n_em);
+                        hit_emitter = true;
+                    } else if (tb_traits<TB>::delta && sc.env_emitter >= 0) {           // the `constant` sky beside a delta light: its own density
+                        value = emitter_radiance(tb, sc.env_emitter, wl);
+                        emitter_pdf = MSK_INV_FOUR_PI_F;
                         if (n_em != 1) emitter_pdf = emitter_pdf * (1.f / n_em);
                         hit_emitter = true;
                     } else if (sc.env_emitter >= 0) {                                   // path.cpp:90-95: `ds` is the NEE sample's record

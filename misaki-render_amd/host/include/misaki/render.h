@@ -150,6 +150,8 @@ public:
     // an emitter that flattens to MSK_EMITTER_ENVMAP fills the image's descriptor too: size and to_world in `out`, the texels
     // {c0, c1, c2, w} and the weights of the distribution into the two arrays (flatten_scene points `out` at them)
     virtual bool flatten_envmap(msk_envmap_desc &out, std::vector<float> &texels, std::vector<float> &weights) const { (void) out; (void) texels; (void) weights; return false; }
+    // a `point` emitter (MSK_EMITTER_POINT): its world-space position, for the scene's msk_point_desc
+    virtual bool flatten_point(float position[3]) const { (void) position; return false; }
     void set_shape(Shape *shape);
     Shape *shape() const { return m_shape; }
     MSK_DECLARE_CLASS()
@@ -283,6 +285,10 @@ struct FlatScene {
     msk_envmap_desc envmap;
     std::vector<float> env_texels, env_weights;
     const msk_envmap_desc *envmap_ptr() const { return has_envmap ? &envmap : nullptr; }
+    // the positions of the scene's `point` emitters, and the whole extension (msk_gpu_scene_create_ext)
+    std::vector<msk_point_desc> points;
+    msk_scene_ext ext = {nullptr, 0, nullptr};
+    const msk_scene_ext *ext_ptr() const { return &ext; }
 };
 void flatten_scene(const Scene *scene, const Sensor *sensor, FlatScene &out);
 

@@ -1,6 +1,7 @@
 // capi.cpp — C entry points over the host library for scripting hosts and tests (ctypes).
 #include <misaki/render.h>
 
+#include <algorithm>
 #include <cstring>
 
 namespace misaki {
@@ -61,6 +62,14 @@ int msk_host_envmap(msk_host_scene *h, msk_envmap_desc *env) {
     if (!h->flat.has_envmap) return 0;
     *env = h->flat.envmap;
     return 1;
+}
+
+// the positions of the flattened scene's `point` emitters (after msk_host_flatten): returns their number and, when `points` is
+// not NULL, copies up to `cap` of them
+int msk_host_points(msk_host_scene *h, msk_point_desc *points, size_t cap) {
+    const size_t n = h->flat.points.size();
+    if (points) std::memcpy(points, h->flat.points.data(), std::min(n, cap) * sizeof(msk_point_desc));
+    return (int) n;
 }
 
 // scene->integrator()->render(scene, sensor) followed by HDRFilm::image(); optionally develop() to a file

@@ -635,6 +635,48 @@ private:
 MSK_IMPLEMENT_CLASS(SmoothDielectric, BSDF)
 MSK_REGISTER_INSTANCE(SmoothDielectric, "dielectric")
 
+// The smooth `conductor`: a mirror with the Fresnel reflectance of a metal (include/msk_gpu.h at MSK_BSDF_CONDUCTOR; the
+// reference's bsdfs/conductor.cpp is RGB-typed and not built).  eta / k / specular_reflectance are constant spectra or rgb,
+// defaults eta = 0, k = 1, specular_reflectance = 1 (a perfect mirror); a nested texture that varies over the surface is refused.
+class SmoothConductor final : public BSDF {
+public:
+    SmoothConductor(const Properties &props) : BSDF(props) {
+        m_eta = constant_spectrum(props, "eta", 0.f); m_k = constant_spectrum(props, "k", 1.f);
+        m_specular_reflectance = constant_spectrum(props, "specular_reflectance", 1.f);
+    }
+    // absent or a float: a `uniform` spectrum (the defaults 0 / 1 / 1 are then exact on the device); an <rgb> may lie above 1
+    // (metal eta, k): srgb_unbounded, as for `roughconductor`; a nested spectrum must flatten to a constant
+    static ref<Texture> constant_spectrum(const Properties &props, const std::string &name, float def) {
+        if (props.has_property(name) && props.type(name) == Properties::Type::Object) {
+            ref<Texture> t = props.texture(name);
+            Texture::Flat f;
+            if (!t->flatten(f) || f.uses_d65)
+                Throw("conductor: \"{}\" must be a constant spectrum or an rgb (a texture that varies over the surface is not supported)", name);
+            return t;
+        }
+        if (props.has_property(name) && props.type(name) == Properties::Type::Color) {
+            Properties p("srgb_unbounded");
+            p.set_color("color", props.color(name));
+            return InstanceManager::get()->create_instance<Texture>(p);
+        }
+        Properties p("uniform");
+        p.set_float("value", props.float_(name, def));
+        return InstanceManager::get()->create_instance<Texture>(p);
+    }
+    bool flatten(msk_bsdf_desc &out, FlatTables &tables) const override {
+        Texture::Flat e, k, s;
+        if (!m_eta->flatten(e) || !m_k->flatten(k) || !m_specular_reflectance->flatten(s) || e.uses_d65 || k.uses_d65 || s.uses_d65) return false;
+        init_bsdf_desc(out);
+        out.type = MSK_BSDF_CONDUCTOR;
+        return tables.put(out.eta, e) && tables.put(out.k, k) && tables.put(out.specular_reflectance, s);
+    }
+    MSK_DECLARE_CLASS()
+private:
+    ref<Texture> m_eta, m_k, m_specular_reflectance;
+};
+MSK_IMPLEMENT_CLASS(SmoothConductor, BSDF)
+MSK_REGISTER_INSTANCE(SmoothConductor, "conductor")
+
 // bsdfs/twosided.cpp:12-36
 class TwoSidedBRDF final : public BSDF {
 public:
@@ -702,6 +744,37 @@ private:
 };
 MSK_IMPLEMENT_CLASS(ConstantBackgroundEmitter, Emitter)
 MSK_REGISTER_INSTANCE(ConstantBackgroundEmitter, "constant")
+
+// emitters/point.cpp: an isotropic point light.  `position`, or a `to_world` whose translation is used (both: an error);
+// `intensity` is a spectrum in emitter context (W / sr per nm), D65 by default.  The device side: include/msk_gpu.h at msk_point_desc.
+class PointLight final : public Emitter {
+public:
+    PointLight(const Properties &props) : Emitter(props) {
+        if (props.has_property("position") && props.has_property("to_world"))
+            Throw("point: only one of the parameters \"position\" and \"to_world\" can be specified at the same time!");
+        if (props.has_property("position")) m_position = props.vector3("position");
+        else m_position = props.transform("to_world", Transform4f()).apply_point(Vector3f{0.f, 0.f, 0.f});
+        m_intensity = props.texture("intensity", Texture::D65(1.f));
+    }
+    bool flatten(msk_emitter_desc &out, FlatTables &tables) const override {
+        Texture::Flat f;
+        if (!m_intensity->flatten(f) || !(f.uses_d65 || f.regular)) return false;
+        std::memset(&out, 0, sizeof out);
+        out.type = MSK_EMITTER_POINT;
+        out.mesh_id = -1;
+        if (f.regular) { out.radiance_regular = tables.add_regular(f); return true; }      // a `regular` intensity as it stands
+        std::memcpy(out.radiance, f.coeff, sizeof f.coeff);
+        out.d65_scale = f.d65_scale;
+        return true;
+    }
+    bool flatten_point(float position[3]) const override { position[0] = m_position.x; position[1] = m_position.y; position[2] = m_position.z; return true; }
+    MSK_DECLARE_CLASS()
+private:
+    Vector3f m_position;
+    ref<Texture> m_intensity;
+};
+MSK_IMPLEMENT_CLASS(PointLight, Emitter)
+MSK_REGISTER_INSTANCE(PointLight, "point")
 
 // The `envmap` emitter: a lat-long radiance image around the scene, importance-sampled on the device (include/msk_gpu.h at
 // msk_envmap_desc; the reference's emitters/envmap.cpp is RGB-typed and not built).  Properties: filename (through the file
@@ -950,7 +1023,7 @@ MSK_REGISTER_INSTANCE(OBJMesh, "obj")
 void flatten_scene(const Scene *scene, const Sensor *sensor, FlatScene &out) {
     out.meshes.clear(); out.bsdfs.clear(); out.emitters.clear(); out.textures.clear(); out.vertices.clear(); out.faces.clear();
     out.regular.clear(); out.regular_values.clear(); out.texels.clear();
-    out.has_envmap = false; out.env_texels.clear(); out.env_weights.clear();
+    out.has_envmap = false; out.env_texels.clear(); out.env_weights.clear(); out.points.clear();
     FlatTables tables{out.textures, out.regular, out.regular_values, out.texels};
     // Scene::m_emitters order (scene.cpp:27-41) decides which emitter sample_emitter_direct picks (scene.cpp:80-84)
     std::map<const Emitter *, int> emitter_index;
@@ -958,6 +1031,12 @@ void flatten_scene(const Scene *scene, const Sensor *sensor, FlatScene &out) {
         msk_emitter_desc ed;
         if (!e->flatten(ed, tables))
             Throw("Emitter \"{}\" cannot be evaluated by the GPU path integrator", e->clazz()->name());
+        if (ed.type == MSK_EMITTER_POINT) {
+            msk_point_desc pd;
+            pd.emitter = (uint32_t) out.emitters.size();
+            if (!e->flatten_point(pd.position)) Throw("Emitter \"{}\" has no position to flatten", e->clazz()->name());
+            out.points.push_back(pd);
+        } else
         if (!e->is_surface() && !e->is_environment())
             Throw("Emitter \"{}\" is not attached to a shape: not supported by the GPU path integrator", e->clazz()->name());
         if (ed.type == MSK_EMITTER_ENVMAP) {
@@ -1019,6 +1098,7 @@ void flatten_scene(const Scene *scene, const Sensor *sensor, FlatScene &out) {
     d.regular_spectra = out.regular.data(); d.regular_values = out.regular_values.data();
     d.n_texels = (uint32_t) (out.texels.size() / 3); d.texels = out.texels.empty() ? nullptr : out.texels.data();
     if (out.has_envmap) { out.envmap.texels = out.env_texels.data(); out.envmap.weights = out.env_weights.data(); }
+    out.ext.envmap = out.envmap_ptr(); out.ext.n_points = (uint32_t) out.points.size(); out.ext.points = out.points.empty() ? nullptr : out.points.data();
 }
 
 // "0,1,2" -> {0,1,2}; empty -> {single}
@@ -1080,7 +1160,7 @@ public:
         fill_params(sensor, flat.params);
         if (!m_ctx && msk_gpu_init(m_devices.data(), (int) m_devices.size(), &m_ctx) != MSK_OK) Throw("{}", msk_gpu_last_error(nullptr));
         msk_scene *gs = nullptr;
-        if (msk_gpu_scene_create_env(m_ctx, &flat.desc, flat.envmap_ptr(), &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(m_ctx));
+        if (msk_gpu_scene_create_ext(m_ctx, &flat.desc, flat.ext_ptr(), &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(m_ctx));
         ref<ImageBlock> whole = new ImageBlock(film->crop_size(), 5);        // the crop window (the whole film by default), as the storage holds it
         whole->set_offset(film->crop_offset());
         msk_stats st;
@@ -1172,7 +1252,7 @@ public:
         fill_params(sensor, flat.params);
         if (!m_ctx && msk_gpu_init(m_devices.data(), (int) m_devices.size(), &m_ctx) != MSK_OK) Throw("{}", msk_gpu_last_error(nullptr));
         msk_scene *gs = nullptr;
-        if (msk_gpu_scene_create_env(m_ctx, &flat.desc, flat.envmap_ptr(), &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(m_ctx));
+        if (msk_gpu_scene_create_ext(m_ctx, &flat.desc, flat.ext_ptr(), &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(m_ctx));
         ref<ImageBlock> whole = new ImageBlock(film->crop_size(), channels.size());   // the crop window, as the storage holds it (as in "path")
         whole->set_offset(film->crop_offset());
         msk_stats st;

@@ -29,6 +29,7 @@ def load():
         lib.msk_host_free_scene.argtypes = [vp]
         lib.msk_host_flatten.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.RenderParams)]
         lib.msk_host_envmap.argtypes = [vp, C.POINTER(abi.EnvmapDesc)]
+        lib.msk_host_points.argtypes = [vp, C.POINTER(abi.PointDesc), C.c_size_t]
         lib.msk_host_render.argtypes = [vp, vp, vp, C.c_char_p, C.POINTER(abi.Stats)]
         lib.msk_host_film_size.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         lib.msk_host_film_crop.argtypes = [vp, C.POINTER(C.c_int * 4)]
@@ -53,9 +54,10 @@ def _check(rc):
 class HostFlat:
     """Same shape as hostmirror.FlatScene: .desc plus the numpy views tests use."""
 
-    def __init__(self, desc, params, owner, envmap=None):
+    def __init__(self, desc, params, owner, envmap=None, points=None):
         self.desc, self.params, self.owner = desc, params, owner
         self.envmap = envmap              # abi.EnvmapDesc of the scene's `envmap` emitter, or None (abi.Scene picks it up)
+        self.points = points              # (abi.PointDesc * n) of the scene's `point` emitters, or None (likewise: msk_scene_ext)
         self.vertices = np.ctypeslib.as_array(desc.vertices, (desc.n_vertices, 8)) if desc.n_vertices else np.zeros((0, 8), np.float32)
         self.faces = np.ctypeslib.as_array(desc.faces, (desc.n_faces, 3)) if desc.n_faces else np.zeros((0, 3), np.uint32)
 
@@ -83,7 +85,12 @@ class HostScene:
         d, p = abi.SceneDesc(), abi.RenderParams()
         _check(self.lib.msk_host_flatten(self.h, C.byref(d), C.byref(p)))
         env = abi.EnvmapDesc()
-        return HostFlat(d, p, self, env if self.lib.msk_host_envmap(self.h, C.byref(env)) == 1 else None)
+        n = self.lib.msk_host_points(self.h, None, 0)
+        pts = None
+        if n > 0:
+            pts = (abi.PointDesc * n)()
+            self.lib.msk_host_points(self.h, pts, n)
+        return HostFlat(d, p, self, env if self.lib.msk_host_envmap(self.h, C.byref(env)) == 1 else None, pts)
 
     def aov_names(self):
         buf = C.create_string_buffer(1 << 16)

@@ -180,6 +180,8 @@ class MeshSpec:
          "specular_reflectance": rgb (default 1), "sample_visible": bool, "twosided": bool}, a rough dielectric,
         {"type": "dielectric", "int_ior": 1.49, "ext_ior": 1.00028, "specular_reflectance": rgb | c, "specular_transmittance": rgb | c}
         (the smooth interface; a scalar c = the `uniform` spectrum <spectrum value="c"/>), or
+        {"type": "conductor", "eta": rgb | c (default 0), "k": rgb | c (default 1), "specular_reflectance": rgb | c (default 1),
+         "twosided": bool} (the smooth conductor: a mirror), or
         {"type": "diffuse", "twosided": bool, "texture": {"type": "checkerboard", "color0": rgb, "color1": rgb,
          "scale": (sx, sy) | "matrix": 16 floats (the to_uv 4x4, row-major)}} (texture absent = `reflectance`), or the texture
         {"type": "bitmap", "pixels": float32 [H, W, 3] linear RGB (row 0 = texel row 0 = the image's top row),
@@ -274,7 +276,7 @@ def _bsdf_xml(m, v3, directory=None):
             inner = ['<bsdf type="twosided">'] + ['    ' + b for b in inner] + ['</bsdf>']
         return ['        ' + b for b in inner]
     body = []
-    if spec["type"] != "dielectric":          # (bsdfs/dielectric.cpp reads no microfacet parameters)
+    if spec["type"] not in ("dielectric", "conductor"):          # (the smooth BSDFs read no microfacet parameters)
         a = spec.get("alpha", 0.1)
         if np.isscalar(a):
             body.append('<float name="alpha" value="%r"/>' % float(a))
@@ -285,7 +287,8 @@ def _bsdf_xml(m, v3, directory=None):
             body.append('<boolean name="sample_visible" value="true"/>')
     keys = {"roughconductor": ("eta", "k", "specular_reflectance"),
             "roughdielectric": ("specular_reflectance", "specular_transmittance"),
-            "dielectric": ("specular_reflectance", "specular_transmittance")}[spec["type"]]
+            "dielectric": ("specular_reflectance", "specular_transmittance"),
+            "conductor": ("eta", "k", "specular_reflectance")}[spec["type"]]
     for k in keys:
         if k in spec:
             body.append('<spectrum name="%s" value="%s"/>' % (k, spec[k].text) if isinstance(spec[k], Regular) else
@@ -301,7 +304,7 @@ def _bsdf_xml(m, v3, directory=None):
 
 
 def write_scene_xml(meshes, directory, width, height, spp, camera=None, integrator_props=None, film_type="hdrfilm",
-                    filename="scene.xml", env=None, film_props=None):
+                    filename="scene.xml", env=None, film_props=None, points=()):
     """Writes <directory>/meshes/*.obj and a Mitsuba-style scene XML the C++ host (and the reference's
     loader) understands; same structure as results/Figure_1_Pathtrace/scene.xml, $-parameters for spp/size."""
     camera = camera or CBOX_CAMERA
@@ -337,8 +340,21 @@ def write_scene_xml(meshes, directory, width, height, spp, camera=None, integrat
                ['        <rgb name="radiance" value="%s"/>' % v3(rad)] if rad is not None else \
                (['        <spectrum name="radiance" value="%r"/>' % float(env["scale"])] if "scale" in env else [])   # D65 * scale
         return ['    <emitter type="constant">'] + body + ['    </emitter>']
+    def point_xml(pt):
+        inten = _point_intensity(pt)
+        body = ['        <point name="position" x="%.9g" y="%.9g" z="%.9g"/>' % tuple(float(np.float32(x)) for x in pt["position"])] if "position" in pt else []
+        if "to_world" in pt:
+            body += ['        <transform name="to_world">', '            <matrix value="%s"/>' % " ".join("%.9g" % float(np.float32(x)) for x in np.asarray(pt["to_world"]).reshape(-1)),
+                     '        </transform>']
+        body += ['        <spectrum name="intensity" value="%s"/>' % inten.text] if isinstance(inten, Regular) else \
+                ['        <spectrum name="intensity" value="%.9g"/>' % float(inten)] if np.isscalar(inten) else \
+                ['        <rgb name="intensity" value="%s"/>' % v3(inten)]
+        return ['    <emitter type="point">'] + body + ['    </emitter>']
     if env is not None and env.get("first"):
         out += env_xml()
+    for pt in points:
+        if pt.get("first"):
+            out += point_xml(pt)
     for m in meshes:
         write_obj(m, os.path.join(directory, "meshes", m.name + ".obj"))
         out += ['    <shape type="obj">', '        <string name="filename" value="meshes/%s.obj"/>' % m.name]
@@ -352,6 +368,9 @@ def write_scene_xml(meshes, directory, width, height, spp, camera=None, integrat
         out.append('    </shape>')
     if env is not None and not env.get("first"):
         out += env_xml()
+    for pt in points:
+        if not pt.get("first"):
+            out += point_xml(pt)
     out.append('</scene>')
     path = os.path.join(directory, filename)
     open(path, "w").write("\n".join(out) + "\n")
@@ -560,6 +579,14 @@ def _bsdf_desc(m, fetch, index, textures=None, pool=None, texels=None):
         b.ior_eta, b.ior_inv_eta = float(int_ior / ext_ior), float(ext_ior / int_ior)
         b.specular_reflectance = spectrum_desc(spec.get("specular_reflectance", (1.0, 1.0, 1.0)), fetch, pool)
         b.specular_transmittance = spectrum_desc(spec.get("specular_transmittance", (1.0, 1.0, 1.0)), fetch, pool)
+    elif spec["type"] == "conductor":
+        # the smooth conductor (msk_gpu.h, MSK_BSDF_CONDUCTOR): defaults eta = 0, k = 1, specular_reflectance = 1 as `uniform` spectra
+        b.type = abi.MSK_BSDF_CONDUCTOR
+        for key, default in (("eta", 0.0), ("k", 1.0), ("specular_reflectance", 1.0)):
+            v = spec.get(key, default)
+            if isinstance(v, dict):
+                raise ValueError('conductor: "%s" must be a constant spectrum or an rgb (a texture that varies over the surface is not supported)' % key)
+            setattr(b, key, spectrum_desc(v, fetch, pool))
     elif spec["type"] == "dielectric":
         # bsdfs/dielectric.cpp:14-20: m_eta = int_ior / ext_ior in fp32, defaults 1.49 / 1.00028; no microfacet parameters
         if spec.get("twosided"):
@@ -584,6 +611,7 @@ class FlatScene:
         self.desc = abi.SceneDesc()
         self.keep = []
         self.envmap = None            # abi.EnvmapDesc of the scene's `envmap` emitter, if it has one
+        self.points = None            # (abi.PointDesc * n) of the scene's `point` emitters, if it has any (abi.Scene: msk_scene_ext)
 
 
 def _radiance_desc(radiance, fetch, scale_in=1.0):
@@ -596,6 +624,32 @@ def _radiance_desc(radiance, fetch, scale_in=1.0):
     col = rad / scale if scale != 0 else rad
     ce = fetch(tuple(float(x) for x in col))
     return ce, float(np.float32(np.float32(scale_in) * scale) * (np.float32(1.0) / np.float32(10568.0)))
+
+
+def _point_intensity(pt):
+    """The intensity of a point spec with its "scale" folded in (float32): an rgb triple, a scalar c (= D65 * c, what
+    <spectrum value="c"/> is inside an emitter) or a Regular (scale must then be 1)."""
+    inten, scale = pt.get("intensity", 1.0), np.float32(pt.get("scale", 1.0))
+    if isinstance(inten, Regular):
+        if scale != 1:
+            raise ValueError("point: a tabulated intensity takes no scale")
+        return inten
+    if np.isscalar(inten):
+        return float(np.float32(inten) * scale)
+    return tuple(float(x) for x in np.asarray(inten, np.float32) * scale)
+
+
+def _point_position(pt):
+    """emitters/point.cpp: `position`, or the translation of `to_world` (4x4, applied to the origin in fp32); not both"""
+    if "position" in pt and "to_world" in pt:
+        raise ValueError('point: only one of the parameters "position" and "to_world" can be specified at the same time!')
+    if "position" in pt:
+        return tuple(float(np.float32(x)) for x in pt["position"])
+    m = np.asarray(pt.get("to_world", np.eye(4)), np.float32).reshape(4, 4)
+    # Transform4f::apply_point on (0, 0, 0): the last column divided by w
+    w = m[3, 3]
+    col = m[:3, 3]
+    return tuple(float(x) for x in (col if w == 1 else (col / w).astype(np.float32)))
 
 
 def _env_to_world4(env):
@@ -654,7 +708,7 @@ def envmap_desc(env, fetch):
     return e, [texels, weights]
 
 
-def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=None, env=None, crop=None, extra_textures=()):
+def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=None, env=None, crop=None, extra_textures=(), points=()):
     """Scene -> msk_scene_desc, the step the `"path"` plugin's render() performs before calling
     the C ABI.  coeff_lookup(rgb)->(c0,c1,c2) overrides the spectral upsampling
     (tests pass the reference's own rgb2spec_fetch results); default = this package's rgb2spec.
@@ -663,6 +717,9 @@ def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=
     {"type": "envmap", "pixels": float32 [H, W, 3], "scale": 1.0, "to_world": rotation, "first": False} = an <emitter type="envmap">
     (envmap_desc above; the result's .envmap is its abi.EnvmapDesc).
     crop: None, or (offset_x, offset_y, width, height) = the film's crop_offset_x/_y, crop_width/_height (film.cpp:12-21).
+    points: [{"position": (x, y, z) | "to_world": 4x4, "intensity": rgb | c | Regular, "scale": 1.0, "first": False}] = top-level
+    <emitter type="point"> elements, placed like env: those with first=True before the shapes (behind a first env), the others after
+    them (behind env), each group in list order; the result's .points is their abi.PointDesc array.
     extra_textures: texture specs (as MeshSpec.bsdf["texture"]) appended to the scene's textures after those the BSDFs name:
     no surface shows them, Scene.eval_texture evaluates them."""
     from . import rgb2spec
@@ -687,8 +744,20 @@ def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=
             fs.env_texels, fs.env_weights = keep
             return abi.EmitterDesc(abi.MSK_EMITTER_ENVMAP, -1, (C.c_float * 3)(0.0, 0.0, float("inf")), _radiance_desc(None, fetch, env.get("scale", 1.0))[1], 0)
         return emitter_desc(abi.MSK_EMITTER_CONSTANT, -1, env.get("radiance"), env.get("scale", 1.0))
+    pd = []
+
+    def point_desc(pt):
+        pos = _point_position(pt)
+        inten = _point_intensity(pt)
+        pd.append(abi.PointDesc(len(ed), (C.c_float * 3)(*pos)))
+        if np.isscalar(inten):
+            return emitter_desc(abi.MSK_EMITTER_POINT, -1, None, inten)
+        return emitter_desc(abi.MSK_EMITTER_POINT, -1, inten)
     if env is not None and env.get("first"):
         ed.append(env_desc())
+    for pt in points:
+        if pt.get("first"):
+            ed.append(point_desc(pt))
     for i, m in enumerate(meshes):
         v, f = triangulate(m)
         bd.append(_bsdf_desc(m, fetch, len(bd), td, pool, texels))
@@ -703,6 +772,11 @@ def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=
         nf += len(f)
     if env is not None and not env.get("first"):
         ed.append(env_desc())
+    for pt in points:
+        if not pt.get("first"):
+            ed.append(point_desc(pt))
+    if pd:
+        fs.points = (abi.PointDesc * len(pd))(*pd)
     for tex in extra_textures:
         td.append(_texture_desc(tex, fetch, texels))
     verts = np.ascontiguousarray(np.concatenate(all_v + [np.zeros((0, 8), np.float32)]), np.float32).reshape(-1, 8)
