@@ -263,6 +263,7 @@ static inline CullBounds cull_bounds(const std::vector<float> &nodes, uint32_t r
 // surface area first, until four slots are filled or only leaves remain.
 struct Collapser {
     const std::vector<float> &n2;
+    explicit Collapser(const std::vector<float> &binary_nodes) : n2(binary_nodes) {}
     std::vector<float> out;
     int max_depth = 0;
     std::vector<uint32_t> out_q;        // the quantised twin (Built::nodes4q)
@@ -464,7 +465,7 @@ inline void Collapser::quantise_h(uint32_t me, const Slot *s, int ns, const uint
 static inline void collapse4(Built &b, bool optimal = true) {
     b.nodes4.clear(); b.nodes4q.clear(); b.nodes4h.clear(); b.root_ref4 = b.root_ref; b.max_depth4 = 0;
     if (b.root_ref & 0x80000000u) return;            // a single leaf: nothing to collapse
-    Collapser c{b.nodes, {}, 0};
+    Collapser c(b.nodes);
     if (optimal) c.plan(b.root_ref);
     b.root_ref4 = c.collapse(b.root_ref, 1);
     b.nodes4 = std::move(c.out);
@@ -480,7 +481,7 @@ struct Collapser8 {
     int max_depth = 0;
     bool ok = true;                      // false: a quantised box failed its containment check (extents beyond the exponent clamp)
     typedef Collapser::Slot Slot;
-    void children(uint32_t node, Slot *a, Slot *b) const { Collapser c{n2, {}, 0}; c.children(node, a, b); }
+    void children(uint32_t node, Slot *a, Slot *b) const { Collapser c(n2); c.children(node, a, b); }
     uint32_t collapse(uint32_t node, int depth) {
         max_depth = std::max(max_depth, depth);
         Slot s[8]; int ns = 2;

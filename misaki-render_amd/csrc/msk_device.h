@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "msk_layout.h"
 
 #define MSK_DEV __device__ __forceinline__
 
@@ -94,8 +95,7 @@ MSK_DEV bool any_nonzero(spec a) { return a.v[0] != 0.f || a.v[1] != 0.f || a.v[
 #define MSK_PI_F        3.14159274101257324f      /* float(3.14159265358979323846) */
 #define MSK_INV_FOUR_PI_F 0.0795774683356285095f   /* float(0.07957747154594766788) */
 #define MSK_INV_PI_F    0.318309873342514038f     /* float(0.31830988618379067154) */
-#define MSK_EPSILON_F   5.9604644775390625e-08f
-#define MSK_RAY_EPS_F   (MSK_EPSILON_F * 1500)
+/* MSK_EPSILON_F, MSK_RAY_EPS_F: msk_layout.h */
 #define MSK_SHADOW_EPS_F (MSK_RAY_EPS_F * 10)
 #define MSK_INF_F       __builtin_inff()
 

@@ -8,6 +8,7 @@
 #include "msk_serial.h"
 #include "msk_bvh.h"
 #include "msk_plan.h"
+#include "msk_scene_tables.h"
 #include "msk_envmap.h"
 #include "msk_lbvh.h"
 #define MSK_WATCHDOG_SYNC
@@ -22,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -71,13 +73,15 @@ static int fail_to(std::string *slot, int code, const char *fmt, ...) {
     *slot = buf;
     return code;
 }
+// what a failed runtime call becomes in the ABI: the one place that tells the two codes apart
+static int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? MSK_ERR_OOM : MSK_ERR_HIP; }
 #define HIP_TRY_SLOT(slot, expr)                                                                 \
     do { hipError_t e_ = (expr); if (e_ != hipSuccess)                                          \
-        return fail_to(slot, e_ == hipErrorOutOfMemory ? MSK_ERR_OOM : MSK_ERR_HIP, "%s failed: %s (%s:%d)", #expr, \
+        return fail_to(slot, hip_code(e_), "%s failed: %s (%s:%d)", #expr, \
                        hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 #define HIP_TRY(ctx, expr)                                                                       \
     do { hipError_t e_ = (expr); if (e_ != hipSuccess)                                          \
-        return fail(ctx, e_ == hipErrorOutOfMemory ? MSK_ERR_OOM : MSK_ERR_HIP, "%s failed: %s (%s:%d)", #expr, \
+        return fail(ctx, hip_code(e_), "%s failed: %s (%s:%d)", #expr, \
                     hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
 // a context the watchdog gave up on (msk_watchdog.h): nothing runs on it any more
@@ -97,10 +101,6 @@ struct DevBuf {
     void leak() { p = nullptr; bytes = 0; }        // a lost context: hipFree would wait for a kernel that never finishes; the memory goes with the process
 };
 
-// width of the tree for scenes that do not fit LDS: 4 (full-precision boxes) or 8 (quantised boxes); MSK_WIDE_BVH overrides, 0 = binary
-#ifndef MSK_WIDE_BVH_DEFAULT
-#define MSK_WIDE_BVH_DEFAULT 4
-#endif
 struct Workspace;
 struct msk_scene {
     msk_ctx *ctx = nullptr;
@@ -112,21 +112,12 @@ struct msk_scene {
     Workspace *ws = nullptr;           // render buffers, kept between calls (hipMalloc/hipFree of GBs costs milliseconds)
     DeviceScene dev;
     DevBuf nodes, nodes4, nodes4q, nodes8, tris, tris3, tri_bounds, tri_verts, tri_frames, tri_normals, tri_uvs, mesh_info, bsdfs, emitters, emitter_d65, emitter_grid, spectra, texels, cdf, cie;
-    bool lds_scene = false, lds_tables = false, all_diffuse = true;
-    bool has_dielectric = false;       // the scene holds a smooth `dielectric`: the instantiations with its delta lobes run (k_shade_gen_d, ...)
-    bool has_bitmap = false;           // the scene holds a `bitmap` texture (ABI v8): the instantiations with the texel lookup run (k_shade_gen_b, ...)
-    bool has_envmap = false;           // the scene's environment emitter is an image (MSK_EMITTER_ENVMAP): the instantiations with its lookup run (k_shade_gen_e, ...)
-    bool has_delta = false;            // the scene holds a `point` emitter or a smooth `conductor`: the instantiations with the delta light and the mirror run (k_shade_gen_p, ...)
+    mskplan::SceneFacts facts;         // what the scene holds, which tree the traversal kernels walk and where tree and tables live: decided once, at
+                                       // creation (msk_scene_tables.h, msk_plan.h), and all a render's launch plan needs to know of the scene
     std::vector<int32_t> emitter_types, bsdf_types;      // msk_gpu_point_sample / msk_gpu_conductor_sample check their index against these
     uint32_t n_textures = 0, tex_base = 0;      // msk_gpu_eval_texture: texture k's record sits at float4 tex_base + 3 k of `bsdfs`
-    bool has_regular = false;          // the scene holds tabulated spectra (ABI v7): the shading instantiations that evaluate them run
-    int trace_mode = 0;                // mskplan::TraceMode (msk_plan.h): which tree the traversal kernels walk, and where it lives
-    size_t trace_lds_bytes = 0, shade_lds_bytes = 0;
     int bvh_depth = 0;
     uint32_t n_tris = 0;
-    size_t tree_bytes = 0;             // node array the traversal walks
-    bool cull_ok = false;              // dev.cull_lo / cull_hi hold the root's bounds and a camera ray that misses them is a record of
-                                       // zeros: triangles, a tree with an inner root, no environment emitter (PassParams::cull)
 };
 
 static int ctx_sync(msk_ctx *ctx, hipStream_t stream, const char *what, double limit_scale = 1.0);     // (below: every wait of a render is timed)
@@ -234,449 +225,103 @@ extern "C" int msk_gpu_describe(const msk_ctx *ctx, char *buf, uint64_t buf_size
 }
 
 // ------------------------------------------------------------------------------------------
-// scene
+// scene: msk_scene_tables.h checks the descriptor and packs the tables, msk_plan.h reads the knobs and places tree and tables;
+// what is left here is the device side — upload, the device-built tree, DeviceScene, the two preparation kernels
 // ------------------------------------------------------------------------------------------
-static inline float h_dot(const float *a, const float *b) { return a[0] * b[0] + (a[1] * b[1] + a[2] * b[2]); }
-
-extern "C" int msk_gpu_scene_create(msk_ctx *ctx, const msk_scene_desc *d, msk_scene **out) { return msk_gpu_scene_create_env(ctx, d, nullptr, out); }
-extern "C" int msk_gpu_scene_create_env(msk_ctx *ctx, const msk_scene_desc *d, const msk_envmap_desc *env, msk_scene **out) {
-    const msk_scene_ext ext = {env, 0u, nullptr};
-    return msk_gpu_scene_create_ext(ctx, d, &ext, out);
-}
-extern "C" int msk_gpu_scene_create_ext(msk_ctx *ctx, const msk_scene_desc *d, const msk_scene_ext *ext, msk_scene **out) {
-    const msk_envmap_desc *env = ext ? ext->envmap : nullptr;
-    if (!ctx || !d || !out) return fail(ctx, MSK_ERR_INVALID_ARG, "msk_gpu_scene_create: NULL argument");
-    *out = nullptr;
-    MSK_REFUSE_LOST(ctx);
-    if (ctx->group) return group_scene_create(ctx, d, ext, out);
-    if (d->abi_version != MSK_ABI_VERSION)
-        return fail(ctx, MSK_ERR_INVALID_ARG, "msk_gpu_scene_create: abi_version %u != %u", d->abi_version, MSK_ABI_VERSION);
-    if (d->film.width <= 0 || d->film.height <= 0 || !(d->film.filter_radius > 0.f))
-        return fail(ctx, MSK_ERR_INVALID_ARG, "msk_gpu_scene_create: invalid film %dx%d radius %g", d->film.width,
-                    d->film.height, d->film.filter_radius);
-    {   // Film::set_crop_window (film.cpp:51-63); {0, 0} = the whole film
-        const int32_t cx = d->film.crop_offset[0], cy = d->film.crop_offset[1], cw = d->film.crop_size[0], ch = d->film.crop_size[1];
-        const bool whole = cw == 0 && ch == 0 && cx == 0 && cy == 0;
-        if (!whole && (cx < 0 || cy < 0 || cw <= 0 || ch <= 0 || (int64_t) cx + cw > d->film.width || (int64_t) cy + ch > d->film.height))
-            return fail(ctx, MSK_ERR_INVALID_ARG, "Invalid crop window specification! offset (%d, %d) + crop size (%d, %d) vs full size (%d, %d)",
-                        cx, cy, cw, ch, d->film.width, d->film.height);
-    }
-    if (!d->cie1931_xyz || !d->d65) return fail(ctx, MSK_ERR_INVALID_ARG, "msk_gpu_scene_create: spectral tables missing");
-    if ((d->n_faces && (!d->vertices || !d->faces)) || (d->n_meshes && !d->meshes))
-        return fail(ctx, MSK_ERR_INVALID_ARG, "msk_gpu_scene_create: geometry arrays missing");
-    if ((d->n_bsdfs && !d->bsdfs) || (d->n_emitters && !d->emitters))
-        return fail(ctx, MSK_ERR_INVALID_ARG, "msk_gpu_scene_create: bsdf / emitter arrays missing");
-    // leaf references pack first_tri << 5 | count into 31 bits (msk_bvh.h) and bit 31 of a hit's prim word is the shadow flag
-    if (d->n_faces >= (1u << 26))
-        return fail(ctx, MSK_ERR_UNSUPPORTED, "msk_gpu_scene_create: %u triangles, this back end addresses fewer than 2^26", d->n_faces);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-
-    // ---- validate + gather per-triangle data (operand shapes are checked here, on the host,
-    //      before any kernel can index with them)
-    std::vector<float> pos((size_t) d->n_faces * 9);
-    std::vector<float> tv((size_t) d->n_faces * 12), tn, tuv;
-    std::vector<int32_t> mesh_info((size_t) std::max(1u, d->n_meshes) * 4, 0);
-    bool any_normals = false, any_uvs = false;
-    for (uint32_t m = 0; m < d->n_meshes; ++m) {
-        const msk_mesh_desc &md = d->meshes[m];
-        if ((uint64_t) md.first_vertex + md.vertex_count > d->n_vertices || (uint64_t) md.first_face + md.face_count > d->n_faces)
-            return fail(ctx, MSK_ERR_INVALID_ARG, "mesh %u: vertex/face range exceeds the arrays", m);
-        if (md.bsdf_id < 0 || (uint32_t) md.bsdf_id >= d->n_bsdfs)
-            return fail(ctx, MSK_ERR_INVALID_ARG, "mesh %u: bsdf_id %d out of range", m, md.bsdf_id);
-        if (md.emitter_id >= (int32_t) d->n_emitters || md.emitter_id < -1)
-            return fail(ctx, MSK_ERR_INVALID_ARG, "mesh %u: emitter_id %d out of range", m, md.emitter_id);
-        // one mesh per area emitter, named from both sides (Shape::m_emitter / Emitter::m_shape, shape.cpp:27-37): a second
-        // mesh pointing at the same emitter would be lit with the first one's area pdf and CDF
-        if (md.emitter_id >= 0 && (!d->emitters || d->emitters[md.emitter_id].mesh_id != (int32_t) m))
-            return fail(ctx, MSK_ERR_INVALID_ARG, "mesh %u: emitter %d does not point back at it", m, md.emitter_id);
-        any_normals |= md.has_normals != 0; any_uvs |= md.has_texcoords != 0;
-    }
-    if (any_normals) tn.assign((size_t) d->n_faces * 12, 0.f);
-    if (any_uvs) tuv.assign((size_t) d->n_faces * 8, 0.f);
-    int rc_spec = MSK_OK;
-    std::vector<uint8_t> covered(d->n_faces, 0);
-    std::vector<float> mesh_area(d->n_meshes, 0.f);
-    std::vector<std::vector<float>> mesh_cdf(d->n_meshes);
-    for (uint32_t m = 0; m < d->n_meshes; ++m) {
-        const msk_mesh_desc &md = d->meshes[m];
-        mesh_info[m * 4 + 0] = md.bsdf_id; mesh_info[m * 4 + 1] = md.emitter_id;
-        mesh_info[m * 4 + 2] = (md.has_normals ? 1 : 0) | (md.has_texcoords ? 2 : 0);
-        mesh_info[m * 4 + 3] = (int32_t) md.first_face;
-        // mesh.cpp:39-48 area_distr_build + core/distribution.h:88-96 (fp32, started from 0)
-        float surface_area = 0.f, run = 0.f;
-        std::vector<float> &cdf = mesh_cdf[m];
-        cdf.push_back(0.f);
-        for (uint32_t f = 0; f < md.face_count; ++f) {
-            const uint32_t g = md.first_face + f;
-            if (covered[g]) return fail(ctx, MSK_ERR_INVALID_ARG, "face %u belongs to two meshes", g);
-            covered[g] = 1;
-            const uint32_t *fi = d->faces + (size_t) g * 3;
-            const float *v[3];
-            for (int k = 0; k < 3; ++k) {
-                if (fi[k] >= md.vertex_count) return fail(ctx, MSK_ERR_INVALID_ARG, "mesh %u face %u: vertex index %u out of range", m, f, fi[k]);
-                v[k] = d->vertices + (size_t) (md.first_vertex + fi[k]) * 8;
-                if (!(std::isfinite(v[k][0]) && std::isfinite(v[k][1]) && std::isfinite(v[k][2])))
-                    return fail(ctx, MSK_ERR_INVALID_ARG, "mesh %u vertex %u: non-finite position", m, fi[k]);
-                for (int c = 0; c < 3; ++c) { pos[(size_t) g * 9 + k * 3 + c] = v[k][c]; tv[(size_t) g * 12 + k * 4 + c] = v[k][c]; }
-                if (any_normals) for (int c = 0; c < 3; ++c) tn[(size_t) g * 12 + k * 4 + c] = v[k][3 + c];
-            }
-            uint32_t mb = m; std::memcpy(&tv[(size_t) g * 12 + 3], &mb, 4);
-            if (any_uvs) {
-                float *u = &tuv[(size_t) g * 8];
-                u[0] = v[0][6]; u[1] = v[0][7]; u[2] = v[1][6]; u[3] = v[1][7]; u[4] = v[2][6]; u[5] = v[2][7];
-            }
-            // mesh.h:54-61 face_area = 0.5 * |(p1-p0) x (p2-p0)|
-            const float a[3] = {v[1][0] - v[0][0], v[1][1] - v[0][1], v[1][2] - v[0][2]};
-            const float b[3] = {v[2][0] - v[0][0], v[2][1] - v[0][1], v[2][2] - v[0][2]};
-            const float cr[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
-            const float area = 0.5f * std::sqrt(h_dot(cr, cr));
-            surface_area += area;
-            run = (f == 0) ? area : run + area;
-            cdf.push_back(run);
-        }
-        if (md.face_count) { const float inv_sum = 1.f / cdf.back(); for (auto &c : cdf) c *= inv_sum; }
-        mesh_area[m] = surface_area;
-    }
-    for (uint32_t g = 0; g < d->n_faces; ++g)
-        if (!covered[g]) return fail(ctx, MSK_ERR_INVALID_ARG, "face %u belongs to no mesh", g);
-
-    // ---- tabulated (`regular`) spectra, ABI v7 (spectra/regular.cpp:27-70): validated here, before any kernel indexes with them
-    if ((d->n_regular_spectra && !d->regular_spectra) || (d->n_regular_values && !d->regular_values))
-        return fail(ctx, MSK_ERR_INVALID_ARG, "msk_gpu_scene_create: regular spectrum arrays missing");
-    if (d->n_regular_values >= (1u << 24))
-        return fail(ctx, MSK_ERR_UNSUPPORTED, "msk_gpu_scene_create: %u tabulated spectrum values, a spectrum record addresses fewer than 2^24", d->n_regular_values);
-    for (uint32_t k = 0; k < d->n_regular_spectra; ++k) {
-        const msk_regular_spectrum_desc &r = d->regular_spectra[k];
-        if (r.size < 2) return fail(ctx, MSK_ERR_INVALID_ARG, "regular spectrum %u: ContinuousDistribution: needs at least two entries!", k);     // regular.cpp:30-31
-        if (r.size > MSK_REGULAR_MAX) return fail(ctx, MSK_ERR_UNSUPPORTED, "regular spectrum %u: %u values, this back end takes at most %d", k, r.size, MSK_REGULAR_MAX);
-        if (!(r.lambda_min < r.lambda_max) || !std::isfinite(r.lambda_min) || !std::isfinite(r.lambda_max))
-            return fail(ctx, MSK_ERR_INVALID_ARG, "regular spectrum %u: ContinuousDistribution: invalid range!", k);                                // regular.cpp:33-34
-        if ((uint64_t) r.first_value + r.size > d->n_regular_values)
-            return fail(ctx, MSK_ERR_INVALID_ARG, "regular spectrum %u: values [%u, %u) exceed the %u in regular_values", k, r.first_value, r.first_value + r.size, d->n_regular_values);
-        bool mass = false;
-        for (uint32_t i = 0; i < r.size; ++i) {
-            const float v = d->regular_values[r.first_value + i];
-            if (!(v >= 0.f) || !std::isfinite(v)) return fail(ctx, MSK_ERR_INVALID_ARG, "regular spectrum %u: ContinuousDistribution: entries must be non-negative!", k);   // regular.cpp:59-60
-            mass |= v > 0.f;
-        }
-        if (!mass) return fail(ctx, MSK_ERR_INVALID_ARG, "regular spectrum %u: ContinuousDistribution: no probability mass found!", k);            // regular.cpp:73-74
-    }
-    // 1 / interval as RegularSpectrum keeps it: the interval in double, its reciprocal rounded to float (regular.cpp:42-43,66-70)
-    auto inv_interval = [&](const msk_regular_spectrum_desc &r) { return (float) (1.0 / (((double) r.lambda_max - (double) r.lambda_min) / (double) (r.size - 1))); };
-    bool any_regular = false;
-    // device form of an msk_spectrum_desc: {c0, c1, c2, scale} or {lambda_min, inv_interval, first | last << 24, -1} (msk_kernels.h: spectrum_eval)
-    auto spectrum_record = [&](const msk_spectrum_desc &sp, float *o, const char *what, uint32_t b) -> int {
-        if (sp.regular) {
-            if (sp.regular > d->n_regular_spectra) return fail(ctx, MSK_ERR_INVALID_ARG, "bsdf %u: %s names regular spectrum %u of %u", b, what, sp.regular, d->n_regular_spectra);
-            const msk_regular_spectrum_desc &r = d->regular_spectra[sp.regular - 1];
-            const uint32_t w = r.first_value | ((r.size - 2u) << 24);
-            o[0] = r.lambda_min; o[1] = inv_interval(r); std::memcpy(&o[2], &w, 4); o[3] = -1.f;
-            any_regular = true;
-            return MSK_OK;
-        }
-        if (!(sp.scale >= 0.f)) return fail(ctx, MSK_ERR_INVALID_ARG, "bsdf %u: the scale of %s must not be negative", b, what);
-        o[0] = sp.coeff[0]; o[1] = sp.coeff[1]; o[2] = sp.coeff[2]; o[3] = sp.scale;
-        return MSK_OK;
-    };
-    if (d->n_textures && !d->textures) return fail(ctx, MSK_ERR_INVALID_ARG, "msk_gpu_scene_create: texture array missing");
-    const uint32_t n_bsdf_f4 = std::max(1u, d->n_bsdfs) * MSK_BSDF_F4 + d->n_textures * 3;
-    std::vector<float> bsdfs((size_t) n_bsdf_f4 * 4, 0.f);
-    bool any_bitmap = false;
-    for (uint32_t t = 0; t < d->n_textures; ++t) {
-        const msk_texture_desc &td = d->textures[t];
-        if (td.type != MSK_TEXTURE_CHECKERBOARD && td.type != MSK_TEXTURE_BITMAP && td.type != MSK_TEXTURE_BITMAP_NEAREST)
-            return fail(ctx, MSK_ERR_UNSUPPORTED, "texture %u: type %d is not supported by this back end (checkerboard, bitmap)", t, td.type);
-        float *o = &bsdfs[((size_t) std::max(1u, d->n_bsdfs) * MSK_BSDF_F4 + (size_t) t * 3) * 4];
-        if (td.type != MSK_TEXTURE_CHECKERBOARD) {
-            if (td.width < 1 || td.height < 1)
-                return fail(ctx, MSK_ERR_INVALID_ARG, "texture %u: a bitmap of %u x %u texels (width and height must be at least 1)", t, td.width, td.height);
-            if ((uint64_t) td.first_texel + (uint64_t) td.width * td.height > d->n_texels)
-                return fail(ctx, MSK_ERR_INVALID_ARG, "texture %u: texels %u + %u x %u reach past the scene's n_texels %u", t, td.first_texel, td.width,
-                            td.height, d->n_texels);
-            if (!d->texels) return fail(ctx, MSK_ERR_INVALID_ARG, "texture %u: a bitmap, but the scene's texels array is missing", t);
-            const size_t n = (size_t) td.width * td.height * 3;
-            for (size_t k = 0; k < n; ++k)
-                if (std::isnan(d->texels[(size_t) td.first_texel * 3 + k]))
-                    return fail(ctx, MSK_ERR_INVALID_ARG, "texture %u: texel %zu holds a NaN coefficient", t, k / 3);
-            const uint32_t w[3] = {td.first_texel, td.width, td.height}, ty = (uint32_t) td.type;
-            std::memcpy(&o[0], w, 12); o[3] = td.to_uv[2];
-            std::memcpy(&o[4], &ty, 4); o[5] = 0.f; o[6] = 0.f; o[7] = td.to_uv[5];
-            o[8] = td.to_uv[0]; o[9] = td.to_uv[1]; o[10] = td.to_uv[3]; o[11] = td.to_uv[4];
-            any_bitmap = true;
-            continue;
-        }
-        o[0] = td.color0[0]; o[1] = td.color0[1]; o[2] = td.color0[2]; o[3] = td.to_uv[2];
-        o[4] = td.color1[0]; o[5] = td.color1[1]; o[6] = td.color1[2]; o[7] = td.to_uv[5];
-        o[8] = td.to_uv[0]; o[9] = td.to_uv[1]; o[10] = td.to_uv[3]; o[11] = td.to_uv[4];
-    }
-    bool all_diffuse = true, any_dielectric = false, any_delta = false;
-    for (uint32_t b = 0; b < d->n_bsdfs; ++b) {
-        const msk_bsdf_desc &bd = d->bsdfs[b];
-        if (bd.type != MSK_BSDF_DIFFUSE && bd.type != MSK_BSDF_ROUGHCONDUCTOR && bd.type != MSK_BSDF_ROUGHDIELECTRIC && bd.type != MSK_BSDF_DIELECTRIC &&
-            bd.type != MSK_BSDF_CONDUCTOR)
-            return fail(ctx, MSK_ERR_UNSUPPORTED,
-                        "bsdf %u: type %d is not supported by this back end (diffuse, roughconductor, roughdielectric, dielectric, conductor)", b, bd.type);
-        if (bd.back_bsdf >= (int32_t) d->n_bsdfs || bd.back_bsdf < -1)
-            return fail(ctx, MSK_ERR_INVALID_ARG, "bsdf %u: back_bsdf %d out of range", b, bd.back_bsdf);
-        if (bd.type != MSK_BSDF_DIFFUSE && !(bd.alpha_u >= 0.f && bd.alpha_v >= 0.f))
-            return fail(ctx, MSK_ERR_INVALID_ARG, "bsdf %u: negative roughness", b);
-        if ((bd.type == MSK_BSDF_ROUGHDIELECTRIC || bd.type == MSK_BSDF_DIELECTRIC) && !(bd.ior_eta > 0.f && bd.ior_inv_eta > 0.f))
-            return fail(ctx, MSK_ERR_INVALID_ARG, "bsdf %u: the relative index of refraction must be positive", b);
-        if (bd.type == MSK_BSDF_DIELECTRIC && bd.back_bsdf >= 0)                                         // twosided.cpp:33-35
-            return fail(ctx, MSK_ERR_INVALID_ARG, "bsdf %u: Only materials without a transmission component can be nested!", b);
-        if (bd.type == MSK_BSDF_DIELECTRIC) any_dielectric = true;
-        // Why this check exists: until the smooth conductor, type 4 was the first unassigned BSDF type, and tests/test_smooth_dielectric.py
-        // (an existing file, which a feature does not edit) creates a `dielectric` descriptor, overwrites its type with 4 and expects
-        // the refusal "type 4 is not supported".  A conductor has no relative index of refraction: both flatteners write 1 / 1 and a
-        // zero-filled descriptor carries 0 / 0.  A type-4 descriptor with any other index is a descriptor of another kind relabelled,
-        // and it keeps being refused with those words instead of being rendered as a mirror.
-        if (bd.type == MSK_BSDF_CONDUCTOR && !((bd.ior_eta == 1.f && bd.ior_inv_eta == 1.f) || (bd.ior_eta == 0.f && bd.ior_inv_eta == 0.f)))
-            return fail(ctx, MSK_ERR_INVALID_ARG, "bsdf %u: type %d is not supported for a descriptor with a relative index of refraction (ior_eta %g, ior_inv_eta %g): "
-                        "a conductor has none (1 / 1, or 0 / 0 = unset); its eta and k are spectra", b, bd.type, (double) bd.ior_eta, (double) bd.ior_inv_eta);
-        if (bd.type == MSK_BSDF_CONDUCTOR) any_delta = true;
-        if (bd.reflectance_texture > d->n_textures)
-            return fail(ctx, MSK_ERR_INVALID_ARG, "bsdf %u: reflectance_texture %u out of range", b, bd.reflectance_texture);
-        if (bd.type == MSK_BSDF_DIFFUSE && !bd.reflectance_regular && !(bd.reflectance_scale >= 0.f && bd.reflectance_scale < INFINITY))
-            return fail(ctx, MSK_ERR_INVALID_ARG, "bsdf %u: reflectance_scale must be finite and non-negative (1 for an srgb reflectance)", b);
-        if (bd.reflectance_texture && bd.type != MSK_BSDF_DIFFUSE)
-            return fail(ctx, MSK_ERR_UNSUPPORTED, "bsdf %u: only the diffuse reflectance can be textured", b);
-        if (bd.reflectance_regular && (bd.type != MSK_BSDF_DIFFUSE || bd.reflectance_texture))
-            return fail(ctx, MSK_ERR_INVALID_ARG, "bsdf %u: reflectance_regular names the reflectance of an untextured diffuse BSDF", b);
-        if (bd.type != MSK_BSDF_DIFFUSE || bd.back_bsdf >= 0 || bd.reflectance_texture || bd.reflectance_regular) all_diffuse = false;
-        // the device record, MSK_BSDF_F4 float4 (msk_kernels.h: BsdfRec): {type, back, r0, r1} {r2, au, av, sample_visible} eta k
-        // spec trans {ior_eta, ior_inv_eta, float4 offset of the texture record, reflectance_scale}
-        float *o = &bsdfs[(size_t) b * 4 * MSK_BSDF_F4];
-        std::memcpy(&o[0], &bd.type, 4); std::memcpy(&o[1], &bd.back_bsdf, 4);
-        msk_spectrum_desc refl;
-        refl.coeff[0] = bd.reflectance[0]; refl.coeff[1] = bd.reflectance[1]; refl.coeff[2] = bd.reflectance[2];
-        refl.scale = bd.type == MSK_BSDF_DIFFUSE ? bd.reflectance_scale : 0.f; refl.regular = bd.reflectance_regular;
-        float r4[4];
-        if ((rc_spec = spectrum_record(refl, r4, "reflectance", b))) return rc_spec;
-        o[2] = r4[0]; o[3] = r4[1]; o[4] = r4[2];
-        o[5] = bd.alpha_u; o[6] = bd.alpha_v; std::memcpy(&o[7], &bd.sample_visible, 4);
-        if ((rc_spec = spectrum_record(bd.eta, &o[8], "eta", b)) || (rc_spec = spectrum_record(bd.k, &o[12], "k", b)) ||
-            (rc_spec = spectrum_record(bd.specular_reflectance, &o[16], "specular_reflectance", b)) ||
-            (rc_spec = spectrum_record(bd.specular_transmittance, &o[20], "specular_transmittance", b))) return rc_spec;
-        o[24] = bd.ior_eta; o[25] = bd.ior_inv_eta;
-        const uint32_t tex_off = bd.reflectance_texture ? std::max(1u, d->n_bsdfs) * MSK_BSDF_F4 + (bd.reflectance_texture - 1) * 3 : 0u;
-        std::memcpy(&o[26], &tex_off, 4);
-        o[27] = r4[3];                                             // reflectance_scale, or -1 for a tabulated reflectance
-    }
-    std::vector<float> emitters((size_t) std::max(1u, d->n_emitters) * 8, 0.f), d65((size_t) std::max(1u, d->n_emitters) * 95, 0.f), cdf_all;
-    std::vector<float> emitter_grid((size_t) std::max(1u, d->n_emitters) * 4, 0.f);
-    int env_emitter = -1;
-    bool any_envmap = false;
-    for (uint32_t e = 0; e < d->n_emitters; ++e) {
-        const msk_emitter_desc &ed = d->emitters[e];
-        float *o = &emitters[e * 8];
-        o[0] = ed.radiance[0]; o[1] = ed.radiance[1]; o[2] = ed.radiance[2];
-        if (ed.type == MSK_EMITTER_CONSTANT || ed.type == MSK_EMITTER_ENVMAP) {
-            if (ed.type == MSK_EMITTER_ENVMAP) {
-                if (!env) return fail(ctx, MSK_ERR_INVALID_ARG, "emitter %u: an envmap emitter needs its image (msk_gpu_scene_create_env with an msk_envmap_desc)", e);
-                if (ed.radiance_regular) return fail(ctx, MSK_ERR_INVALID_ARG, "emitter %u: an envmap emitter has no tabulated radiance (radiance_regular must be 0)", e);
-                if (!(ed.d65_scale >= 0.f) || !std::isfinite(ed.d65_scale)) return fail(ctx, MSK_ERR_INVALID_ARG, "emitter %u: envmap: the scale must be finite and non-negative", e);
-                any_envmap = true;
-                o[0] = 0.f; o[1] = 0.f; o[2] = INFINITY;      // the emitter's own factor is its table alone: S = 1
-            }
-            if (env_emitter >= 0) return fail(ctx, MSK_ERR_INVALID_ARG, "Can only have one environment light");   // scene.cpp:38-39
-            if (ed.mesh_id != -1) return fail(ctx, MSK_ERR_INVALID_ARG, "emitter %u: an environment emitter has no mesh (mesh_id must be -1)", e);
-            env_emitter = (int) e;
-            o[3] = 0.f;
-            // (an envmap: word 1 = the float4 offset of its block in the texel pool, behind the bitmaps' texels — msk_kernels.h, EnvView)
-            // word 2 = 1 for an image, 0 for the `constant` sky: what the kernels that serve both read (env_is_image)
-            const uint32_t meta[4] = {0xffffffffu, ed.type == MSK_EMITTER_ENVMAP ? d->n_texels : 0u, ed.type == MSK_EMITTER_ENVMAP ? 1u : 0u, 0u};
-            std::memcpy(&o[4], meta, 16);
-        } else if (ed.type == MSK_EMITTER_AREA) {
-            if (ed.mesh_id < 0 || (uint32_t) ed.mesh_id >= d->n_meshes || d->meshes[ed.mesh_id].emitter_id != (int32_t) e)
-                return fail(ctx, MSK_ERR_INVALID_ARG, "emitter %u: mesh_id %d does not point back at it", e, ed.mesh_id);
-            const msk_mesh_desc &md = d->meshes[ed.mesh_id];
-            if (md.face_count == 0) return fail(ctx, MSK_ERR_INVALID_ARG, "emitter %u: its mesh has no faces", e);
-            o[3] = 1.f / mesh_area[ed.mesh_id];                               // mesh.cpp:129 ps.pdf
-            uint32_t meta[4] = {(uint32_t) ed.mesh_id, md.first_face, md.face_count, (uint32_t) cdf_all.size()};
-            std::memcpy(&o[4], meta, 16);
-            cdf_all.insert(cdf_all.end(), mesh_cdf[ed.mesh_id].begin(), mesh_cdf[ed.mesh_id].end());
-        } else if (ed.type == MSK_EMITTER_POINT) {
-            // point.cpp: the intensity in the radiance's place; the position behind a type marker (msk_kernels.h: MSK_EMITTER_MARK_POINT)
-            if (ed.mesh_id != -1) return fail(ctx, MSK_ERR_INVALID_ARG, "emitter %u: a point emitter has no mesh (mesh_id must be -1)", e);
-            const msk_point_desc *pd = nullptr;
-            for (uint32_t k = 0; ext && k < ext->n_points; ++k)
-                if (ext->points && ext->points[k].emitter == e) {
-                    if (pd) return fail(ctx, MSK_ERR_INVALID_ARG, "emitter %u: a point emitter with two positions (msk_point_desc %u is its second)", e, k);
-                    pd = &ext->points[k];
-                }
-            if (!pd) return fail(ctx, MSK_ERR_INVALID_ARG, "emitter %u: a point emitter needs its position (msk_gpu_scene_create_ext with an msk_point_desc)", e);
-            if (!std::isfinite(pd->position[0]) || !std::isfinite(pd->position[1]) || !std::isfinite(pd->position[2]))
-                return fail(ctx, MSK_ERR_INVALID_ARG, "emitter %u: a point emitter's position must be finite", e);
-            any_delta = true;
-            o[3] = 0.f;
-            const uint32_t mark = MSK_EMITTER_MARK_POINT;
-            std::memcpy(&o[4], &mark, 4); std::memcpy(&o[5], pd->position, 12);
-        } else {
-            return fail(ctx, MSK_ERR_UNSUPPORTED, "emitter %u: type %d is not supported (area, constant, envmap, point)", e, ed.type);
-        }
-        float *gr = &emitter_grid[(size_t) e * 4];
-        if (ed.radiance_regular) {          // a `regular` radiance: its own table on its own grid, no sigmoid factor (area.cpp:51-54, regular.cpp:148)
-            if (ed.radiance_regular > d->n_regular_spectra) return fail(ctx, MSK_ERR_INVALID_ARG, "emitter %u: radiance names regular spectrum %u of %u", e, ed.radiance_regular, d->n_regular_spectra);
-            const msk_regular_spectrum_desc &r = d->regular_spectra[ed.radiance_regular - 1];
-            for (uint32_t i = 0; i < r.size; ++i) d65[e * 95 + i] = d->regular_values[r.first_value + i];
-            const uint32_t last = r.size - 2u;
-            gr[0] = r.lambda_min; gr[1] = inv_interval(r); std::memcpy(&gr[2], &last, 4); gr[3] = 1.f;
-            o[0] = o[1] = 0.f; o[2] = INFINITY;
-            any_regular = true;
-        } else {
-            for (int i = 0; i < 95; ++i) d65[e * 95 + i] = d->d65[i] * ed.d65_scale;   // d65.cpp:41-42
-            const uint32_t last = 93u;
-            gr[0] = 360.f; gr[1] = (float) (1.0 / ((830.0 - 360.0) / 94.0)); std::memcpy(&gr[2], &last, 4); gr[3] = 0.f;
-        }
-    }
-    for (uint32_t k = 0; ext && k < ext->n_points; ++k) {
-        if (!ext->points) return fail(ctx, MSK_ERR_INVALID_ARG, "msk_scene_ext: n_points %u without points", ext->n_points);
-        const uint32_t pe = ext->points[k].emitter;
-        if (pe >= d->n_emitters) return fail(ctx, MSK_ERR_INVALID_ARG, "msk_point_desc %u: emitter %u out of range (the scene has %u)", k, pe, d->n_emitters);
-        if (d->emitters[pe].type != MSK_EMITTER_POINT)
-            return fail(ctx, MSK_ERR_INVALID_ARG, "msk_point_desc %u: emitter %u is of type %d, not a point emitter (type %d)", k, pe, d->emitters[pe].type, MSK_EMITTER_POINT);
-    }
-    // the image of the envmap emitter (msk_gpu.h: msk_envmap_desc; msk_envmap.h): validated here, before any kernel indexes with it
-    mskenv::Tables env_tables;
-    if (env && !any_envmap) return fail(ctx, MSK_ERR_INVALID_ARG, "envmap: an image was given, but the scene has no envmap emitter (type %d)", MSK_EMITTER_ENVMAP);
-    if (any_envmap) {
-        if (env->width < 1 || env->height < 1) return fail(ctx, MSK_ERR_INVALID_ARG, "envmap: an image of %u x %u texels (width and height must be at least 1)", env->width, env->height);
-        if ((uint64_t) env->width * env->height >= (1ull << 28)) return fail(ctx, MSK_ERR_UNSUPPORTED, "envmap: %u x %u texels, this back end takes fewer than 2^28", env->width, env->height);
-        if (!env->texels || !env->weights) return fail(ctx, MSK_ERR_INVALID_ARG, "envmap: texels / weights array missing");
-        const size_t n = (size_t) env->width * env->height;
-        for (size_t k = 0; k < n; ++k) {
-            const float *t = env->texels + k * 4;
-            if (!std::isfinite(t[3]) || t[3] < 0.f) return fail(ctx, MSK_ERR_INVALID_ARG, "envmap: texel %zu: the factor w must be finite and non-negative", k);
-            if (std::isnan(t[0]) || std::isnan(t[1]) || std::isnan(t[2])) return fail(ctx, MSK_ERR_INVALID_ARG, "envmap: texel %zu holds a NaN coefficient", k);
-        }
-        if (const char *msg = mskenv::check_weights(env->weights, env->width, env->height)) return fail(ctx, MSK_ERR_INVALID_ARG, "%s", msg);
-        if (!mskenv::is_rotation(env->to_world)) return fail(ctx, MSK_ERR_INVALID_ARG, "envmap: to_world must be a rotation");
-        if ((uint64_t) d->n_texels + 3u + n + ((uint64_t) env->height + 4u) / 4u + ((uint64_t) env->height * (env->width + 1u) + 3u) / 4u >= (1ull << 31))
-            return fail(ctx, MSK_ERR_UNSUPPORTED, "envmap: %u x %u texels do not fit the texel pool's 32-bit offsets", env->width, env->height);
-        env_tables = mskenv::build_tables(env->weights, env->width, env->height);
-    }
-    if (any_regular) all_diffuse = false;              // tabulated spectra are evaluated by the general shading variant only
-    std::vector<float> spectra_pool(d->regular_values, d->regular_values + d->n_regular_values);
-    if (spectra_pool.empty()) spectra_pool.push_back(0.f);
-    if (cdf_all.empty()) cdf_all.push_back(0.f);
-
-    // oracle D10: the triangle-bounds predicate's padding, computed exactly as the oracle does (0.5e-5 of the scene's scale =
-    // max(diagonal, largest coordinate magnitude)); node boxes are padded by twice that
-    float tri_pad, scene_lo[3] = {INFINITY, INFINITY, INFINITY}, scene_hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    {
-        float *lo = scene_lo, *hi = scene_hi;
-        for (uint32_t t = 0; t < d->n_faces; ++t)
-            for (int v = 0; v < 3; ++v)
-                for (int k = 0; k < 3; ++k) { const float q = pos[(size_t) t * 9 + v * 3 + k]; lo[k] = std::min(lo[k], q); hi[k] = std::max(hi[k], q); }
-        const float ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
-        const float diag = d->n_faces ? std::sqrt(ex * ex + (ey * ey + ez * ez)) : 1.f;
-        float amax = 0.f;
-        if (d->n_faces) amax = std::max(std::max(std::max(std::fabs(lo[0]), std::fabs(hi[0])), std::max(std::fabs(lo[1]), std::fabs(hi[1]))), std::max(std::fabs(lo[2]), std::fabs(hi[2])));
-        // (MSK_PAD_SCALE, read by the oracle too: the margin tests shrink the padding on both sides to show how far the rule is from
-        // failing — tree and brute force agree down to 1e-7 of the scale and part at 1e-8, tests/test_padding_margin.py.  A value that
-        // is not a number in [1e-7, 1e-3] is refused: zero, garbage or a stray setting would silently remove the padding on both
-        // sides of the parity tests at once.)
-        float pad_scale = 1e-5f;
-        if (const char *ps = getenv("MSK_PAD_SCALE")) {
-            char *end = nullptr;
-            const double v = strtod(ps, &end);
-            if (end == ps || *end != '\0' || !std::isfinite(v) || v < 1e-7 || v > 1e-3)
-                return fail(ctx, MSK_ERR_INVALID_ARG, "MSK_PAD_SCALE=\"%s\": the padding of the boxes must be a number in [1e-7, 1e-3] of the scene's scale "
-                            "(default 1e-5; the slab arithmetic needs a few 1e-7)", ps);
-            pad_scale = (float) v;
-        }
-        tri_pad = (0.5f * pad_scale) * std::max(diag, amax);
-    }
-    // MSK_BVH_BUILD=gpu: the tree is built on the device (msk_lbvh.hip, a linear BVH) once the vertices are uploaded — the
-    // option for scenes that change between renders; default: the host's binned-SAH builder (msk_bvh.h), the better tree
-    const char *build_env = getenv("MSK_BVH_BUILD");
-    const bool gpu_build = build_env && !strcmp(build_env, "gpu") && d->n_faces > 0;
-    mskbvh::Built bvh;
-    if (!gpu_build) bvh = mskbvh::build(pos.data(), d->n_faces, tri_pad);
-    // material class of every triangle into its leaf record's prim word (MSK_CLASS_SHIFT): the traversal hands it to the
-    // shading kernel with the hit, which sorts its paths by it
-    if (!all_diffuse && !gpu_build)
-        for (size_t k = 0; k < d->n_faces; ++k) {
-            uint32_t w, mesh;
-            std::memcpy(&w, &bvh.tris[k * 16 + 3], 4);
-            std::memcpy(&mesh, &tv[(size_t) w * 12 + 3], 4);
-            const int32_t b = mesh_info[(size_t) mesh * 4];
-            const uint32_t cls = (b >= 0 && (uint32_t) b < d->n_bsdfs) ? (uint32_t) d->bsdfs[b].type : 0u;      // MSK_BSDF_* = 0, 1, 2, 3 (and 4, the smooth conductor, with class 0)
-            w |= (cls & (MSK_N_CLASSES - 1u)) << MSK_CLASS_SHIFT;
-            std::memcpy(&bvh.tris[k * 16 + 3], &w, 4);
-        }
-
-    msk_scene *s = new msk_scene();
-    s->ctx = ctx; s->n_tris = d->n_faces; s->bvh_depth = bvh.max_depth; s->all_diffuse = all_diffuse; s->has_regular = any_regular; s->has_dielectric = any_dielectric; s->has_bitmap = any_bitmap; s->has_envmap = any_envmap; s->has_delta = any_delta;
-    for (uint32_t e2 = 0; e2 < d->n_emitters; ++e2) s->emitter_types.push_back(d->emitters[e2].type);
-    for (uint32_t b2 = 0; b2 < d->n_bsdfs; ++b2) s->bsdf_types.push_back(d->bsdfs[b2].type);
-    s->n_textures = d->n_textures; s->tex_base = std::max(1u, d->n_bsdfs) * MSK_BSDF_F4;
-    std::vector<float> cie(d->cie1931_xyz, d->cie1931_xyz + 3 * MSK_CIE_SAMPLES);
+// The tables, and the host-built tree (host_tree; nullptr = room for the device-built one instead).
+static int upload_tables(msk_scene *s, const mskscene::HostTables &t, const mskbvh::Built *host_tree, size_t n_faces) {
     hipError_t e = hipSuccess;
     auto up = [&](DevBuf &b, const std::vector<float> &v) { if (e == hipSuccess) e = b.upload(v); };
-    if (!gpu_build) { up(s->nodes, bvh.nodes); up(s->tris, bvh.tris); up(s->tri_bounds, bvh.bounds); }
-    up(s->tri_verts, tv); up(s->tri_normals, tn); up(s->tri_uvs, tuv);
-    up(s->bsdfs, bsdfs); up(s->emitters, emitters); up(s->emitter_d65, d65); up(s->cdf, cdf_all); up(s->cie, cie);
-    up(s->emitter_grid, emitter_grid); up(s->spectra, spectra_pool);
-    if (any_bitmap || any_envmap) {      // one float4 per texel: a lookup is one 16-byte load per texel
-        std::vector<float> tx4((size_t) d->n_texels * 4, 0.f);
-        if (d->texels) for (size_t k = 0; k < d->n_texels; ++k) { tx4[k * 4] = d->texels[k * 3]; tx4[k * 4 + 1] = d->texels[k * 3 + 1]; tx4[k * 4 + 2] = d->texels[k * 3 + 2]; }
-        if (any_envmap) {                // the envmap emitter's block behind them (msk_kernels.h, EnvView): header, texels, marginal, rows
-            const size_t n = (size_t) env->width * env->height;
-            float head[12] = {};
-            std::memcpy(&head[0], &env->width, 4); std::memcpy(&head[1], &env->height, 4);
-            std::memcpy(&head[2], env->to_world, 36);
-            tx4.insert(tx4.end(), head, head + 12);
-            tx4.insert(tx4.end(), env->texels, env->texels + n * 4);
-            tx4.insert(tx4.end(), env_tables.marg.begin(), env_tables.marg.end());
-            tx4.resize((tx4.size() + 3) & ~(size_t) 3, 0.f);
-            tx4.insert(tx4.end(), env_tables.cond.begin(), env_tables.cond.end());
-            tx4.resize((tx4.size() + 3) & ~(size_t) 3, 0.f);
-        }
-        up(s->texels, tx4);
-    }
-    if (e == hipSuccess) e = s->mesh_info.upload(mesh_info);
-    if (e == hipSuccess && gpu_build) {
-        const size_t nf = d->n_faces;
-        if ((e = s->nodes.alloc(nf * 64)) == hipSuccess && (e = s->tris.alloc(nf * 64)) == hipSuccess) e = s->tri_bounds.alloc(nf * 32);
-    }
-    if (e != hipSuccess) { delete s; return fail(ctx, e == hipErrorOutOfMemory ? MSK_ERR_OOM : MSK_ERR_HIP, "scene upload: %s", hipGetErrorString(e)); }
-    if (gpu_build) {
-        msklbvh::Input in;
-        in.tri_verts = s->tri_verts.as<float4>(); in.n_tris = d->n_faces;
-        for (int k = 0; k < 3; ++k) { in.lo[k] = scene_lo[k]; in.hi[k] = scene_hi[k]; }
-        in.box_pad = 2.f * tri_pad; in.tri_pad = tri_pad;
-        in.leaf_size = getenv("MSK_BVH_LEAF") ? (uint32_t) std::max(1, std::min(8, atoi(getenv("MSK_BVH_LEAF")))) : 2u;
-        in.mesh_info = s->mesh_info.as<int4>(); in.bsdfs = s->bsdfs.as<float4>(); in.n_bsdfs = d->n_bsdfs; in.bsdf_f4 = MSK_BSDF_F4;
-        in.class_shift = all_diffuse ? 0u : (uint32_t) MSK_CLASS_SHIFT;
-        msklbvh::Result res;
-        char msg[256] = "";
-        if (msklbvh::build(ctx->stream, in, s->nodes.as<float4>(), s->tris.as<float4>(), s->tri_bounds.as<float4>(), &res, msg, sizeof msg)) {
-            delete s;
-            return fail(ctx, MSK_ERR_HIP, "device BVH build: %s", msg);
-        }
-        // the node records back on the host: the size / depth bookkeeping below and the wide collapse read them
-        bvh.root_ref = res.root_ref; bvh.max_depth = res.depth; s->bvh_depth = res.depth;      // (k_path_serial sizes its stack by it)
-        bvh.nodes.resize((size_t) res.n_nodes * 16);
-        if (res.n_nodes) {
-            hipError_t ec = hipMemcpy(bvh.nodes.data(), s->nodes.p, (size_t) res.n_nodes * 64, hipMemcpyDeviceToHost);
-            if (ec != hipSuccess) { delete s; return fail(ctx, MSK_ERR_HIP, "device BVH build: %s", hipGetErrorString(ec)); }
-        }
-    }
+    if (host_tree) { up(s->nodes, host_tree->nodes); up(s->tris, host_tree->tris); up(s->tri_bounds, host_tree->bounds); }
+    up(s->tri_verts, t.tv); up(s->tri_normals, t.tn); up(s->tri_uvs, t.tuv);
+    up(s->bsdfs, t.bsdfs); up(s->emitters, t.emitters); up(s->emitter_d65, t.d65); up(s->cdf, t.cdf_all); up(s->cie, t.cie);
+    up(s->emitter_grid, t.emitter_grid); up(s->spectra, t.spectra_pool);
+    if (t.has_bitmap || t.has_envmap) up(s->texels, t.texels);
+    if (e == hipSuccess) e = s->mesh_info.upload(t.mesh_info);
+    if (e == hipSuccess && !host_tree)
+        if ((e = s->nodes.alloc(n_faces * 64)) == hipSuccess && (e = s->tris.alloc(n_faces * 64)) == hipSuccess) e = s->tri_bounds.alloc(n_faces * 32);
+    return e == hipSuccess ? MSK_OK : fail(s->ctx, hip_code(e), "scene upload: %s", hipGetErrorString(e));
+}
 
+// MSK_BVH_BUILD=gpu: a linear BVH from the uploaded vertices (msk_lbvh.hip).  The node records come back to the host: the
+// placement's bookkeeping and the wide collapse read them.
+static int device_build_tree(msk_scene *s, const mskscene::HostTables &t, const msk_scene_desc *d, const mskplan::SceneKnobs &knobs, mskbvh::Built *bvh) {
+    msk_ctx *ctx = s->ctx;
+    msklbvh::Input in;
+    in.tri_verts = s->tri_verts.as<float4>(); in.n_tris = d->n_faces;
+    for (int k = 0; k < 3; ++k) { in.lo[k] = t.scene_lo[k]; in.hi[k] = t.scene_hi[k]; }
+    in.box_pad = 2.f * t.tri_pad; in.tri_pad = t.tri_pad;
+    in.leaf_size = knobs.bvh_leaf;
+    in.mesh_info = s->mesh_info.as<int4>(); in.bsdfs = s->bsdfs.as<float4>(); in.n_bsdfs = d->n_bsdfs; in.bsdf_f4 = MSK_BSDF_F4;
+    in.class_shift = t.all_diffuse ? 0u : (uint32_t) MSK_CLASS_SHIFT;
+    msklbvh::Result res;
+    char msg[256] = "";
+    if (msklbvh::build(ctx->stream, in, s->nodes.as<float4>(), s->tris.as<float4>(), s->tri_bounds.as<float4>(), &res, msg, sizeof msg))
+        return fail(ctx, MSK_ERR_HIP, "device BVH build: %s", msg);
+    bvh->root_ref = res.root_ref; bvh->max_depth = res.depth;
+    bvh->nodes.resize((size_t) res.n_nodes * 16);
+    if (res.n_nodes) {
+        hipError_t ec = hipMemcpy(bvh->nodes.data(), s->nodes.p, (size_t) res.n_nodes * 64, hipMemcpyDeviceToHost);
+        if (ec != hipSuccess) return fail(ctx, MSK_ERR_HIP, "device BVH build: %s", hipGetErrorString(ec));
+    }
+    return MSK_OK;
+}
+
+// The form of the tree the placement chose, next to the binary one; for the 4-wide forms in HBM also the three-load triangle
+// records, packed on the device from `tris`.  (A failure here is reported as MSK_ERR_OOM whatever the runtime said, where
+// upload_tables tells MSK_ERR_HIP from MSK_ERR_OOM: kept as it always was.)
+static int upload_tree_form(msk_scene *s, const mskbvh::Built &bvh, int trace_mode, uint32_t n_faces) {
+    msk_ctx *ctx = s->ctx;
+    hipError_t e = hipSuccess;
+    switch (trace_mode) {
+    case mskplan::TRACE_WIDE8: e = s->nodes8.upload(bvh.nodes8); break;
+    case mskplan::TRACE_WIDE4_LDS: e = s->nodes4.upload(bvh.nodes4); break;
+    case mskplan::TRACE_WIDE4: case mskplan::TRACE_WIDE4_BYTE: case mskplan::TRACE_WIDE4_HALF:
+        // the traversal addresses nodes and triangle records through buffer resources with 32-bit byte offsets
+        if ((uint64_t) (bvh.nodes4.size() / 32) * 128u >= (1ull << 32) || (uint64_t) n_faces * MSK_TRI_REC_BYTES >= (1ull << 32))
+            return fail(ctx, MSK_ERR_UNSUPPORTED, "a tree of %zu 4-wide nodes exceeds the 4 GB a buffer resource addresses", bvh.nodes4.size() / 32);
+        e = s->nodes4.upload(bvh.nodes4);
+        if (e == hipSuccess && trace_mode != mskplan::TRACE_WIDE4) e = s->nodes4q.upload(trace_mode == mskplan::TRACE_WIDE4_HALF ? bvh.nodes4h : bvh.nodes4q);
+        if (e == hipSuccess) e = s->tris3.alloc(std::max<size_t>((size_t) n_faces * MSK_TRI_REC_BYTES, 16));
+        if (e == hipSuccess && n_faces)
+            hipLaunchKernelGGL(k_pack_tris3, dim3((n_faces + MSK_BLOCK - 1) / MSK_BLOCK), dim3(MSK_BLOCK), 0, ctx->stream,
+                               s->tris.as<float4>(), s->tri_bounds.as<float4>(), n_faces, s->tris3.as<float4>());
+        break;
+    default: break;                 // the binary tree: uploaded with the tables
+    }
+    return e == hipSuccess ? MSK_OK : fail(ctx, MSK_ERR_OOM, "scene upload: %s", hipGetErrorString(e));
+}
+
+// DeviceScene, whole: the uploaded tables, the tree as placed, the descriptor's camera and film.
+static void fill_device_scene(msk_scene *s, const mskscene::HostTables &t, const msk_scene_desc *d, const mskbvh::Built &bvh, uint32_t n_nodes,
+                              const mskbvh::CullBounds &cb, const mskplan::TreePlacement &tree) {
     DeviceScene &ds = s->dev;
     std::memset(&ds, 0, sizeof ds);
-    ds.nodes = s->nodes.as<float4>(); ds.tris = s->tris.as<float4>(); ds.tri_bounds = s->tri_bounds.as<float4>(); ds.tri_pad = tri_pad; ds.tri_verts = s->tri_verts.as<float4>();
-    ds.tri_normals = any_normals ? s->tri_normals.as<float4>() : nullptr;
-    ds.tri_uvs = any_uvs ? s->tri_uvs.as<float4>() : nullptr;
+    ds.nodes = s->nodes.as<float4>(); ds.tris = s->tris.as<float4>(); ds.tri_bounds = s->tri_bounds.as<float4>(); ds.tri_pad = t.tri_pad; ds.tri_verts = s->tri_verts.as<float4>();
+    ds.tri_normals = t.any_normals ? s->tri_normals.as<float4>() : nullptr;
+    ds.tri_uvs = t.any_uvs ? s->tri_uvs.as<float4>() : nullptr;
+    ds.tri_frames = s->tri_frames.as<float4>();
     ds.mesh_info = s->mesh_info.as<int4>(); ds.bsdfs = s->bsdfs.as<float4>(); ds.emitters = s->emitters.as<float4>();
     ds.emitter_d65 = s->emitter_d65.as<float>(); ds.cdf = s->cdf.as<float>(); ds.cie = s->cie.as<float>();
     ds.emitter_grid = s->emitter_grid.as<float4>(); ds.spectra = s->spectra.as<float>(); ds.n_spectra = d->n_regular_values;
-    ds.texels = (any_bitmap || any_envmap) ? s->texels.as<float4>() : nullptr;
-    ds.n_nodes = (uint32_t) (bvh.nodes.size() / 16); ds.n_tris = d->n_faces; ds.n_emitters = d->n_emitters;
-    ds.n_meshes = d->n_meshes; ds.n_bsdfs = d->n_bsdfs; ds.n_bsdf_f4 = n_bsdf_f4; ds.cdf_len = (uint32_t) cdf_all.size();
+    ds.texels = (t.has_bitmap || t.has_envmap) ? s->texels.as<float4>() : nullptr;
+    ds.n_nodes = n_nodes; ds.n_tris = d->n_faces; ds.n_emitters = d->n_emitters;
+    ds.n_meshes = d->n_meshes; ds.n_bsdfs = d->n_bsdfs; ds.n_bsdf_f4 = t.n_bsdf_f4; ds.cdf_len = (uint32_t) t.cdf_all.size();
     ds.root_ref = bvh.root_ref;
-    ds.stack_entries = (uint32_t) ((bvh.max_depth + 2 + 3) & ~3);
+    switch (tree.trace_mode) {
+    case mskplan::TRACE_WIDE8:
+        ds.nodes8 = s->nodes8.as<float4>(); ds.root_ref8 = bvh.root_ref8; ds.n_nodes8 = (uint32_t) (bvh.nodes8.size() / 32);
+        break;
+    case mskplan::TRACE_WIDE4: case mskplan::TRACE_WIDE4_BYTE: case mskplan::TRACE_WIDE4_HALF: case mskplan::TRACE_WIDE4_LDS:
+        ds.nodes4 = s->nodes4.as<float4>(); ds.root_ref4 = bvh.root_ref4; ds.n_nodes4 = (uint32_t) (bvh.nodes4.size() / 32);
+        if (tree.trace_mode == mskplan::TRACE_WIDE4_LDS) break;
+        if (tree.trace_mode != mskplan::TRACE_WIDE4) ds.nodes4q = s->nodes4q.as<float4>();
+        if (tree.trace_mode == mskplan::TRACE_WIDE4_HALF && !(ds.root_ref4 & MSK_LEAF_BIT)) ds.root_ref4 *= 80u;     // inner references of this form are byte offsets (msk_bvh.h: quantise_h)
+        ds.tris3 = s->tris3.as<float4>();
+        break;
+    default: break;
+    }
+    ds.stack_entries = tree.stack_entries; ds.stack_total = tree.stack_total;
     std::memcpy(ds.s2c, d->camera.sample_to_camera, 64); std::memcpy(ds.to_world, d->camera.to_world, 64);
     ds.near_clip = d->camera.near_clip; ds.far_clip = d->camera.far_clip;
     ds.width = d->film.width; ds.height = d->film.height;
@@ -687,127 +332,83 @@ extern "C" int msk_gpu_scene_create_ext(msk_ctx *ctx, const msk_scene_desc *d, c
     ds.filter_scale = float(MSK_FILTER_RESOLUTION) / d->film.filter_radius;           // rfilter.cpp:21
     ds.filter_border = (int) std::ceil(d->film.filter_radius - .5f);                  // rfilter.cpp:22
     std::memcpy(ds.lut, d->film.filter_lut, sizeof ds.lut);
-    // constant.cpp:21-28 set_scene: the sphere around Scene::bbox() (bbox.h:105-112), in fp32 exactly as the oracle does
-    ds.env_emitter = env_emitter; ds.env_radius = 0.f;
-    if (env_emitter >= 0) {
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (uint32_t v = 0; v < d->n_vertices; ++v)
-            for (int k = 0; k < 3; ++k) { const float q = d->vertices[(size_t) v * 8 + k]; lo[k] = std::min(lo[k], q); hi[k] = std::max(hi[k], q); }
-        float r[3];
-        for (int k = 0; k < 3; ++k) { const float c = (lo[k] + hi[k]) * .5f; r[k] = c - hi[k]; }
-        const float radius = std::sqrt(r[0] * r[0] + (r[1] * r[1] + r[2] * r[2]));
-        ds.env_radius = std::max(MSK_RAY_EPS_F, radius * (1.f + MSK_RAY_EPS_F));
-        s->all_diffuse = false;             // the environment terms live in the general shading variant
-    }
-    if (any_delta) s->all_diffuse = false;  // the delta light and the mirror live in instantiations of the general shading variant
-    // the bounds a camera ray must meet (msk_bvh.h: cull_bounds): the binary tree's root, host- or device-built, before any collapse.
-    // With an environment emitter a ray that leaves the scene carries radiance: nothing is culled
+    ds.env_emitter = t.env_emitter; ds.env_radius = t.env_radius;
+    // the bounds a camera ray must meet (msk_bvh.h: cull_bounds)
+    for (int k = 0; k < 3; ++k) { ds.cull_lo[k] = cb.lo[k]; ds.cull_hi[k] = cb.hi[k]; }
+}
+
+extern "C" int msk_gpu_scene_create(msk_ctx *ctx, const msk_scene_desc *d, msk_scene **out) { return msk_gpu_scene_create_env(ctx, d, nullptr, out); }
+extern "C" int msk_gpu_scene_create_env(msk_ctx *ctx, const msk_scene_desc *d, const msk_envmap_desc *env, msk_scene **out) {
+    const msk_scene_ext ext = {env, 0u, nullptr};
+    return msk_gpu_scene_create_ext(ctx, d, &ext, out);
+}
+extern "C" int msk_gpu_scene_create_ext(msk_ctx *ctx, const msk_scene_desc *d, const msk_scene_ext *ext, msk_scene **out) {
+    if (!ctx || !d || !out) return fail(ctx, MSK_ERR_INVALID_ARG, "msk_gpu_scene_create: NULL argument");
+    *out = nullptr;
+    MSK_REFUSE_LOST(ctx);
+    if (ctx->group) return group_scene_create(ctx, d, ext, out);
+    const mskplan::SceneKnobs knobs = mskplan::read_scene_knobs();
+    mskscene::HostTables t;
     {
-        const mskbvh::CullBounds cb = mskbvh::cull_bounds(bvh.nodes, bvh.root_ref, d->n_faces);
-        for (int k = 0; k < 3; ++k) { ds.cull_lo[k] = cb.lo[k]; ds.cull_hi[k] = cb.hi[k]; }
-        s->cull_ok = cb.on && env_emitter < 0;
+        std::string msg;
+        if (int rc = mskscene::pack(d, ext, knobs.pad_scale, &t, &msg)) return fail(ctx, rc, "%s", msg.c_str());
     }
-    // LDS plan of k_trace: per-lane stack + (when it fits) the whole BVH
-    const size_t stack_bytes = (size_t) ds.stack_entries * MSK_BLOCK * 4;
-    const size_t scene_bytes = (size_t) ds.n_nodes * 64 + (size_t) ds.n_tris * 96;
-    const size_t lds_cap = getenv("MSK_LDS_SCENE_KB") ? (size_t) atoi(getenv("MSK_LDS_SCENE_KB")) * 1024 : 48 * 1024;
-    s->lds_scene = scene_bytes <= lds_cap && stack_bytes + scene_bytes <= 64 * 1024;
-    s->trace_lds_bytes = stack_bytes + (s->lds_scene ? scene_bytes : 0);
-    s->trace_mode = s->lds_scene ? 0 : 1;
-    s->tree_bytes = bvh.nodes.size() * 4;
-    // (a tree whose boxes cannot be quantised conservatively — extents beyond the exponent range — keeps the 4-wide form)
-    if (!s->lds_scene && env_u32("MSK_WIDE_BVH", MSK_WIDE_BVH_DEFAULT) == 8 && !(bvh.root_ref & MSK_LEAF_BIT) && mskbvh::collapse8(bvh)) {
-        // the tree stays in HBM/L2: eight quantised child boxes per 128-byte line (msk_bvh.h: collapse8)
-        hipError_t e8 = s->nodes8.upload(bvh.nodes8);
-        if (e8 != hipSuccess) { delete s; return fail(ctx, MSK_ERR_OOM, "scene upload: %s", hipGetErrorString(e8)); }
-        ds.nodes8 = s->nodes8.as<float4>(); ds.root_ref8 = bvh.root_ref8; ds.n_nodes8 = (uint32_t) (bvh.nodes8.size() / 32);
-        ds.stack_entries = (uint32_t) ((7 * bvh.max_depth8 + 2 + 3) & ~3);     // up to seven pushes per level
-        s->trace_mode = 4;
-        s->tree_bytes = bvh.nodes8.size() * 4;
-    } else if (!s->lds_scene && env_u32("MSK_WIDE_BVH", MSK_WIDE_BVH_DEFAULT) && !(bvh.root_ref & MSK_LEAF_BIT)) {
-        // the tree stays in HBM/L2: walk it four children at a time, one 128-byte line per visit
-        mskbvh::collapse4(bvh, env_u32("MSK_COLLAPSE_OPTIMAL", 1) != 0);
-        // the traversal addresses nodes and triangle records through buffer resources with 32-bit byte offsets
-        if ((uint64_t) (bvh.nodes4.size() / 32) * 128u >= (1ull << 32) || (uint64_t) d->n_faces * MSK_TRI_REC_BYTES >= (1ull << 32)) {
-            delete s;
-            return fail(ctx, MSK_ERR_UNSUPPORTED, "a tree of %zu 4-wide nodes exceeds the 4 GB a buffer resource addresses", bvh.nodes4.size() / 32);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+    const bool gpu_build = knobs.gpu_build && d->n_faces > 0;
+    mskbvh::Built bvh;
+    if (!gpu_build) {
+        bvh = mskbvh::build(t.pos.data(), d->n_faces, t.tri_pad);
+        // (all_diffuse is the packer's final flag: an environment or point emitter clears it in a scene whose BSDFs are all plain
+        // diffuse — every class is then 0 and tagging changes no bit, here as in msk_lbvh.hip's class_shift branch)
+        if (!t.all_diffuse) mskscene::tag_classes(bvh, t, d);
+    }
+    std::unique_ptr<msk_scene> s(new msk_scene());
+    s->ctx = ctx; s->n_tris = d->n_faces;
+    s->emitter_types = std::move(t.emitter_types); s->bsdf_types = std::move(t.bsdf_types);
+    s->n_textures = t.n_textures; s->tex_base = t.tex_base;
+    if (int rc = upload_tables(s.get(), t, gpu_build ? nullptr : &bvh, d->n_faces)) return rc;
+    if (gpu_build) if (int rc = device_build_tree(s.get(), t, d, knobs, &bvh)) return rc;
+    s->bvh_depth = bvh.max_depth;                          // (k_path_serial sizes its stack by it)
+
+    // the camera cull's bounds: the binary tree's root, host- or device-built, before any collapse.  With an environment emitter
+    // a ray that leaves the scene carries radiance: nothing is culled
+    const mskbvh::CullBounds cb = mskbvh::cull_bounds(bvh.nodes, bvh.root_ref, d->n_faces);
+    mskplan::BinaryTree binary;
+    binary.n_nodes = (uint32_t) (bvh.nodes.size() / 16); binary.n_tris = d->n_faces; binary.max_depth = bvh.max_depth; binary.root_is_leaf = (bvh.root_ref & MSK_LEAF_BIT) != 0;
+    const mskplan::TreePlacement tree = mskplan::place_tree(binary, knobs, [&](int width) {
+        mskplan::WideTree w;
+        if (width == 8) { w.ok = mskbvh::collapse8(bvh); w.max_depth = bvh.max_depth8; w.n_nodes = (uint32_t) (bvh.nodes8.size() / 32); }
+        else {
+            mskbvh::collapse4(bvh, knobs.collapse_optimal);
+            w.ok = true; w.max_depth = bvh.max_depth4; w.n_nodes = (uint32_t) (bvh.nodes4.size() / 32); w.has_half = !bvh.nodes4h.empty(); w.has_byte = !bvh.nodes4q.empty();
         }
-        hipError_t e4 = s->nodes4.upload(bvh.nodes4);
-        if (e4 != hipSuccess) { delete s; return fail(ctx, MSK_ERR_OOM, "scene upload: %s", hipGetErrorString(e4)); }
-        ds.nodes4 = s->nodes4.as<float4>(); ds.root_ref4 = bvh.root_ref4; ds.n_nodes4 = (uint32_t) (bvh.nodes4.size() / 32);
-        ds.stack_entries = (uint32_t) ((3 * bvh.max_depth4 + 2 + 3) & ~3);     // up to three pushes per level
-        s->trace_mode = 2;
-        s->tree_bytes = bvh.nodes4.size() * 4;
-        // the walked form (MSK_QUANT_BVH): 2 (default since round 5) 80-byte nodes with half-float child boxes read by v_fma_mix_f32,
-        // 1 64-byte nodes with byte-quantised boxes (rounds 3-4), 0 the full-precision 128-byte ones; + three-load triangle
-        // records, packed on the device from `tris`.  Config-5 / config-3 class renders (round 5, same box): 124.7 / 159.5 ms
-        // with 2 against 126.9 / 168.3 with 1.
-        if (env_u32("MSK_QUANT_BVH", 2) == 2 && !bvh.nodes4h.empty()) {
-            hipError_t eq = s->nodes4q.upload(bvh.nodes4h);
-            if (eq != hipSuccess) { delete s; return fail(ctx, MSK_ERR_OOM, "scene upload: %s", hipGetErrorString(eq)); }
-            ds.nodes4q = s->nodes4q.as<float4>();
-            if (!(ds.root_ref4 & MSK_LEAF_BIT)) ds.root_ref4 *= 80u;     // inner references of this form are byte offsets (msk_bvh.h: quantise_h)
-            s->trace_mode = 6;
-            s->tree_bytes = bvh.nodes4h.size() * 4;
-        } else if (env_u32("MSK_QUANT_BVH", 2) && !bvh.nodes4q.empty()) {
-            hipError_t eq = s->nodes4q.upload(bvh.nodes4q);
-            if (eq != hipSuccess) { delete s; return fail(ctx, MSK_ERR_OOM, "scene upload: %s", hipGetErrorString(eq)); }
-            ds.nodes4q = s->nodes4q.as<float4>();
-            s->trace_mode = 5;
-            s->tree_bytes = bvh.nodes4q.size() * 4;
-        }
-        {
-            hipError_t et = s->tris3.alloc(std::max<size_t>((size_t) d->n_faces * MSK_TRI_REC_BYTES, 16));
-            if (et != hipSuccess) { delete s; return fail(ctx, MSK_ERR_OOM, "scene upload: %s", hipGetErrorString(et)); }
-            ds.tris3 = s->tris3.as<float4>();
-            if (d->n_faces) hipLaunchKernelGGL(k_pack_tris3, dim3((d->n_faces + MSK_BLOCK - 1) / MSK_BLOCK), dim3(MSK_BLOCK), 0, ctx->stream,
-                                               s->tris.as<float4>(), s->tri_bounds.as<float4>(), d->n_faces, s->tris3.as<float4>());
-        }
-    } else if (s->lds_scene && env_u32("MSK_WIDE_LDS", 0) && !(bvh.root_ref & MSK_LEAF_BIT)) {
-        // experiment knob, off by default: the 4-wide tree staged in LDS (half the dependent LDS round trips per ray).
-        // Measured on cbox: trace 12.45 vs 12.34 ms for the binary tree — no gain.
-        mskbvh::collapse4(bvh, env_u32("MSK_COLLAPSE_OPTIMAL", 1) != 0);
-        hipError_t e4 = s->nodes4.upload(bvh.nodes4);
-        if (e4 != hipSuccess) { delete s; return fail(ctx, MSK_ERR_OOM, "scene upload: %s", hipGetErrorString(e4)); }
-        ds.nodes4 = s->nodes4.as<float4>(); ds.root_ref4 = bvh.root_ref4; ds.n_nodes4 = (uint32_t) (bvh.nodes4.size() / 32);
-        ds.stack_entries = (uint32_t) ((3 * bvh.max_depth4 + 2 + 3) & ~3);
-        s->trace_lds_bytes = (size_t) ds.stack_entries * MSK_BLOCK * 4 + ((size_t) ds.n_nodes4 * 128 + (size_t) ds.n_tris * 96);
-        s->trace_mode = 3;
-    }
-    ds.stack_total = ds.stack_entries;
-    if (mskplan::tree_in_hbm(s->trace_mode)) {
-        // trees in HBM: only the first MSK_STACK_CAP entries of a lane's stack live in LDS, the rest in an HBM overflow
-        // array (LaneStack) — any tree depth works within a fixed 16 KB (+ 4 KB of node4_step scratch) of LDS per block, which
-        // leaves room for six blocks per CU.  (Measured: the cap does not change the trace time between 8 and 40 entries.)
-        ds.stack_entries = std::min(ds.stack_total, std::max(4u, env_u32("MSK_STACK_CAP", 16) & ~3u));
-        s->trace_lds_bytes = (size_t) ds.stack_entries * MSK_BLOCK * 4 + (size_t) MSK_BLOCK * 16;       // + four words per lane (node4_step)
-    }
-    // LDS plan of k_shade_gen: the small lookup tables (tri_verts, mesh/bsdf/emitter records, cdf, d65, cie)
-    const size_t table_bytes = ((size_t) ds.n_tris * 6 + ds.n_meshes + ds.n_bsdf_f4 + ds.n_emitters * 3 +
-                                (ds.n_emitters * 95 + 3) / 4 + (ds.cdf_len + 3) / 4 + 72 + (ds.n_spectra + 3) / 4) * 16;
-    s->lds_tables = table_bytes <= 40 * 1024;
-    // + the waves' done-queues (k_shade_gen: MSK_DONE_Q_F4 float4 per wave)
-    // (a scene whose per-triangle tables stay in HBM still stages the small ones: msk_kernels.h, small_tables_float4s — the same formula)
-    const size_t small_bytes = ((size_t) ds.n_meshes + ds.n_bsdf_f4 + ds.n_emitters * 3 + (ds.n_emitters * 95 + 3) / 4 + (ds.cdf_len + 3) / 4 + 72 + (ds.n_spectra + 3) / 4) * 16;
-    const size_t small_staged = small_bytes <= (size_t) MSK_SMALL_TABLES_KB * 1024 ? small_bytes : 0;
-    s->shade_lds_bytes = (s->lds_tables ? table_bytes : small_staged) + (size_t) (MSK_BLOCK / MSK_WAVE) * MSK_DONE_Q_F4 * 16;
-    if (s->trace_lds_bytes > ctx->prop.sharedMemPerBlock) {
-        delete s;
-        return fail(ctx, MSK_ERR_UNSUPPORTED, "BVH depth %d needs %zu B of traversal stack per block", bvh.max_depth, stack_bytes);
-    }
+        return w;
+    });
+    if (int rc = upload_tree_form(s.get(), bvh, tree.trace_mode, d->n_faces)) return rc;
+    mskplan::TableCounts counts;
+    counts.n_tris = d->n_faces; counts.n_meshes = d->n_meshes; counts.n_bsdf_f4 = t.n_bsdf_f4; counts.n_emitters = d->n_emitters;
+    counts.cdf_len = (uint32_t) t.cdf_all.size(); counts.n_spectra = d->n_regular_values;
+    const mskplan::TablePlacement tables = mskplan::place_tables(counts);
+    mskplan::SceneFacts &f = s->facts;
+    f.trace_mode = tree.trace_mode; f.lds_scene = tree.lds_scene; f.trace_lds_bytes = tree.trace_lds_bytes;
+    f.lds_tables = tables.lds_tables; f.shade_lds_bytes = tables.shade_lds_bytes;
+    f.all_diffuse = t.all_diffuse; f.has_regular = t.has_regular; f.has_dielectric = t.has_dielectric; f.has_bitmap = t.has_bitmap;
+    f.has_envmap = t.has_envmap; f.has_delta = t.has_delta;
+    f.cull_ok = cb.on && t.env_emitter < 0;
+    if (f.trace_lds_bytes > ctx->prop.sharedMemPerBlock)
+        return fail(ctx, MSK_ERR_UNSUPPORTED, "BVH depth %d needs %zu B of traversal stack per block", bvh.max_depth, tree.binary_stack_bytes);
+
     // per-triangle shading constants, computed on the device by the code the per-hit path used to run (k_tri_frames)
-    {
-        hipError_t ef = s->tri_frames.alloc(std::max<size_t>((size_t) ds.n_tris * 48, 16));
-        if (ef != hipSuccess) { delete s; return fail(ctx, MSK_ERR_OOM, "scene upload: %s", hipGetErrorString(ef)); }
-        ds.tri_frames = s->tri_frames.as<float4>();
-        if (ds.n_tris) {
-            hipLaunchKernelGGL(k_tri_frames, dim3((ds.n_tris + MSK_BLOCK - 1) / MSK_BLOCK), dim3(MSK_BLOCK), 0, ctx->stream, ds,
-                               s->tri_frames.as<float4>());
-            ef = hipStreamSynchronize(ctx->stream);
-            if (ef != hipSuccess) { delete s; return fail(ctx, MSK_ERR_HIP, "k_tri_frames: %s", hipGetErrorString(ef)); }
-        }
+    hipError_t ef = s->tri_frames.alloc(std::max<size_t>((size_t) d->n_faces * 48, 16));
+    if (ef != hipSuccess) return fail(ctx, MSK_ERR_OOM, "scene upload: %s", hipGetErrorString(ef));
+    fill_device_scene(s.get(), t, d, bvh, binary.n_nodes, cb, tree);
+    if (d->n_faces) {
+        hipLaunchKernelGGL(k_tri_frames, dim3((d->n_faces + MSK_BLOCK - 1) / MSK_BLOCK), dim3(MSK_BLOCK), 0, ctx->stream, s->dev, s->tri_frames.as<float4>());
+        ef = hipStreamSynchronize(ctx->stream);
+        if (ef != hipSuccess) return fail(ctx, MSK_ERR_HIP, "k_tri_frames: %s", hipGetErrorString(ef));
     }
-    *out = s;
+    *out = s.release();
     return MSK_OK;
 }
 
@@ -943,9 +544,6 @@ static int ctx_sync(msk_ctx *ctx, hipStream_t stream, const char *what, double l
 // t0 / t1: events that take the kernel's own start / end timestamps (hipExtLaunchKernelGGL: no extra packets in the queue,
 // unlike hipEventRecord, which cost 2 % of a bench step at three records per iteration), or nullptr
 // ------------------------------------------------------------------------------------------
-static_assert(mskplan::kWavesPerBlock == MSK_BLOCK / MSK_WAVE && mskplan::kDoneQueueBytes == (size_t) (MSK_BLOCK / MSK_WAVE) * MSK_DONE_Q_F4 * 16,
-              "msk_plan.h sizes the shading kernels' LDS with the constants of msk_kernels.h");
-
 // f(std::integral_constant<int, M>{}) with M = mode: the one place where a trace mode becomes a template argument
 template <typename F> static void with_trace_mode(int mode, F &&f) {
     switch (mode) {
@@ -1272,14 +870,6 @@ static PassParams pass_params(const msk_render_params *prm, uint32_t spp_owned, 
     return pp;
 }
 
-static mskplan::SceneFacts scene_facts(const msk_scene *sc) {
-    mskplan::SceneFacts f;
-    f.trace_mode = sc->trace_mode; f.lds_scene = sc->lds_scene; f.lds_tables = sc->lds_tables; f.all_diffuse = sc->all_diffuse;
-    f.has_regular = sc->has_regular; f.has_dielectric = sc->has_dielectric; f.has_bitmap = sc->has_bitmap; f.has_envmap = sc->has_envmap; f.has_delta = sc->has_delta; f.cull_ok = sc->cull_ok;
-    f.trace_lds_bytes = sc->trace_lds_bytes; f.shade_lds_bytes = sc->shade_lds_bytes;
-    return f;
-}
-
 // Renders the samples of `pix` (pass pixel table, host) into records; leaves records on device.
 static int run_wavefront(msk_scene *sc, hipStream_t stream, const msk_render_params *prm, const mskplan::RenderKnobs &knobs, uint32_t spp_owned,
                          const uint4 *d_pix, const uint32_t *d_pix_to_j, uint64_t n_pix, float4 *rec_a, float *rec_b, StateBufs &sb,
@@ -1290,7 +880,7 @@ static int run_wavefront(msk_scene *sc, hipStream_t stream, const msk_render_par
     if (int rc = reset_regions(sc, stream, sb, total, n_regions)) return rc;
     mskplan::CallFacts call;
     call.region_size = region_size; call.aov_groups = aov ? aov->n_groups : 0u; call.aov_rgb = aov_rgb != nullptr;
-    const mskplan::LaunchPlan plan = mskplan::make_launch_plan(scene_facts(sc), call, knobs);
+    const mskplan::LaunchPlan plan = mskplan::make_launch_plan(sc->facts, call, knobs);
     const PassParams pp0 = pass_params(prm, spp_owned, d_pix, d_pix_to_j, rec_a, rec_b, sb, region_size, n_regions, plan, aov, aov_rgb, packed);
     const Wavefront wf{sc, sb, plan, knobs, aov, region_size, stats != nullptr, ctx->timing_phase++, mskwd::Waiter{mskwd::wait_mode_from_env(), ctx->hub}};
     const mskwd::Limits wd_limits = mskwd::limits_from_env();
@@ -1454,10 +1044,10 @@ static int render_serial(msk_scene *sc, const msk_render_params *prm, float *d_f
         sp.blocks = ws.blocks.as<BlockInfo>(); sp.n_blocks = (uint32_t) owned.size();
         sp.block_buf = ws.block_buf.as<float>(); sp.buf_stride = buf_stride;
         sp.stack_ovf = ovf.as<uint32_t>(); sp.counters = counters.as<unsigned long long>(); sp.per_wave = per_wave ? 1u : 0u;
-        if (sc->has_delta) hipLaunchKernelGGL(k_path_serial_p, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
-        else if (sc->has_envmap) hipLaunchKernelGGL(k_path_serial_e, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
-        else if (sc->has_bitmap) hipLaunchKernelGGL(k_path_serial_b, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
-        else if (sc->has_dielectric) hipLaunchKernelGGL(k_path_serial_d, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
+        if (sc->facts.has_delta) hipLaunchKernelGGL(k_path_serial_p, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
+        else if (sc->facts.has_envmap) hipLaunchKernelGGL(k_path_serial_e, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
+        else if (sc->facts.has_bitmap) hipLaunchKernelGGL(k_path_serial_b, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
+        else if (sc->facts.has_dielectric) hipLaunchKernelGGL(k_path_serial_d, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
         else hipLaunchKernelGGL(k_path_serial, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
     }
     FilmOut fo;
@@ -1520,7 +1110,7 @@ static int render_impl(msk_scene *sc, const msk_render_params *prm, float *d_fil
     uint32_t region_size, n_regions;
     uint64_t all_samples = 0;
     for (auto &b : owned) all_samples += (uint64_t) b.size_x * b.size_y * spp_owned;
-    mskplan::pool_shape(sc->trace_mode, all_samples, knobs, &region_size, &n_regions);
+    mskplan::pool_shape(sc->facts.trace_mode, all_samples, knobs, &region_size, &n_regions);
     const size_t n_slots = (size_t) region_size * n_regions;
     const size_t state_bytes = 2 * n_slots * 144 + 4096;                              // two halves per region (StateBufs::alloc)
     const size_t held = ws.rec_a.bytes + ws.rec_b.bytes + ws.sb.id.bytes * 144 / 8;     // reusable: counts as free
@@ -1823,7 +1413,7 @@ extern "C" int msk_gpu_sample_pixels(msk_scene *scene, const msk_render_params *
     const uint64_t n_rec = n_pixels * p.spp;
     const mskplan::RenderKnobs knobs = mskplan::read_render_knobs();
     uint32_t region_size, n_regions;
-    mskplan::pool_shape(scene->trace_mode, n_rec, knobs, &region_size, &n_regions);
+    mskplan::pool_shape(scene->facts.trace_mode, n_rec, knobs, &region_size, &n_regions);
     StateBufs sb; DevBuf d_pix, d_inv, ra, rb, ox, op;
     HIP_TRY(ctx, sb.alloc((size_t) region_size * n_regions, n_regions));
     HIP_TRY(ctx, d_pix.upload(pix)); HIP_TRY(ctx, d_inv.upload(inv)); HIP_TRY(ctx, ra.alloc(n_rec * 16)); HIP_TRY(ctx, rb.alloc(n_rec * 4));
@@ -1861,8 +1451,8 @@ static int trace_batch(msk_scene *scene, uint64_t n, const float *rays, float *o
     DevBuf d_ovf;
     if (scene->dev.stack_total > scene->dev.stack_entries)
         HIP_TRY(ctx, d_ovf.alloc((size_t) (scene->dev.stack_total - scene->dev.stack_entries) * grid * MSK_BLOCK * 4));
-    with_trace_mode(scene->trace_mode, [&](auto m) {
-        hipLaunchKernelGGL(k_trace_batch<decltype(m)::value>, dim3(grid), dim3(MSK_BLOCK), scene->trace_lds_bytes, ctx->stream, scene->dev,
+    with_trace_mode(scene->facts.trace_mode, [&](auto m) {
+        hipLaunchKernelGGL(k_trace_batch<decltype(m)::value>, dim3(grid), dim3(MSK_BLOCK), scene->facts.trace_lds_bytes, ctx->stream, scene->dev,
                            d_rays.as<float4>(), n, oh, oa, d_ovf.as<uint32_t>());
     });
     HIP_TRY(ctx, hipGetLastError());
@@ -1901,7 +1491,7 @@ static int env_probe(msk_scene *scene, const char *who, uint32_t sample, uint64_
                      float *out_uv, float *out_pdf) {
     msk_ctx *ctx = scene->ctx;
     MSK_REFUSE_LOST(ctx);
-    if (!scene->has_envmap) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: the scene has no envmap emitter", who);
+    if (!scene->facts.has_envmap) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: the scene has no envmap emitter", who);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (n == 0) return MSK_OK;
     const size_t in_f = sample ? 2 : 3;
@@ -1938,7 +1528,7 @@ extern "C" int msk_gpu_env_sample(msk_scene *scene, uint64_t n, const float *u, 
 static int delta_probe(msk_scene *scene, const char *who, uint32_t conductor, uint32_t index, uint64_t n, const float *in, const float *wavelengths, float *out_a, float *out_b) {
     msk_ctx *ctx = scene->ctx;
     MSK_REFUSE_LOST(ctx);
-    if (!scene->has_delta) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: the scene holds neither a point emitter nor a conductor", who);
+    if (!scene->facts.has_delta) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: the scene holds neither a point emitter nor a conductor", who);
     if (conductor) {
         if (index >= scene->bsdf_types.size() || scene->bsdf_types[index] != MSK_BSDF_CONDUCTOR) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: bsdf %u is not a conductor of this scene", who, index);
     } else if (index >= scene->emitter_types.size() || scene->emitter_types[index] != MSK_EMITTER_POINT) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: emitter %u is not a point emitter of this scene", who, index);

@@ -21,24 +21,20 @@
 // records in exactly the order ImageBlock::put / Film::put accumulate them
 // (imageblock.cpp:55-114, 133-173), so the film is bit-identical to the scalar CPU order.
 #pragma once
+#include "msk_layout.h"
 #include "msk_device.h"
 #include <type_traits>
 #include "../../include/msk_gpu.h"
 
 namespace msk {
 
-#define MSK_WAVE 64
-#define MSK_BSDF_F4 7   /* float4 per BSDF record (built from msk_bsdf_desc by msk_gpu_scene_create) */
-#define MSK_BLOCK 256
-#define MSK_LEAF_BIT 0x80000000u  /* child ref: leaf = BIT | first_tri << 5 | count ; inner = node index */
+// (MSK_WAVE, MSK_BLOCK, MSK_BSDF_F4, MSK_LEAF_BIT, MSK_CLASS_SHIFT, MSK_N_CLASSES: msk_layout.h, which host code reads too)
 #define MSK_NO_PRIM 0xffffffffu
 // The prim word of a triangle record / hit record: bits 0..25 the scene-global triangle index (msk_gpu_scene_create rejects
 // scenes of 2^26 triangles and more), bits 27..28 the MATERIAL CLASS of the triangle's BSDF (0 diffuse, 1 rough conductor,
 // 2 rough dielectric, 3 smooth dielectric; a miss reads 3 too and shares the last place of the sort with it), written into the leaf records at scene creation so that the traversal kernels deliver
 // it with the hit for free.  k_shade_gen sorts a region's paths by it (material-sorted shading, shade_region).
 #define MSK_PRIM_ID 0x03ffffffu
-#define MSK_CLASS_SHIFT 27
-#define MSK_N_CLASSES 4
 #define MSK_DEPTH_SHIFT 20                 /* id.y: 20 bits of owned sample index (msk_gpu_render rejects more than 2^20 owned samples per pixel and call), */
 #define MSK_SI_MASK 0xfffffu               /* 12 bits of depth: a path that reaches bounce 4094 is cut (Russian roulette makes that a 1e-89 event) */
 #define MSK_MAX_DEPTH 4094u
@@ -1423,7 +1419,7 @@ struct SceneTablesE : SceneTablesB {};
 // only into the instantiations that carry this type (k_shade_gen_p, k_wavefront_p, k_wavefront_h_p, k_path_serial_p).  In them the
 // environment emitter, if any, is the image OR the `constant` sky: the emitter's record says which (env_is_image).
 struct SceneTablesP : SceneTablesE {};
-#define MSK_EMITTER_MARK_POINT 0xfffffffeu      /* word 0 of a point emitter's second float4 (an environment emitter's: 0xffffffff) */
+// (MSK_EMITTER_MARK_POINT, word 0 of a point emitter's second float4: msk_layout.h)
 template <class TB> struct tb_traits { static constexpr bool regular = false, dielectric = false, bitmap = false, envmap = false, delta = false; };
 template <> struct tb_traits<SceneTablesR> { static constexpr bool regular = true, dielectric = false, bitmap = false, envmap = false, delta = false; };
 template <> struct tb_traits<SceneTablesD> { static constexpr bool regular = true, dielectric = true, bitmap = false, envmap = false, delta = false; };
@@ -1436,9 +1432,7 @@ MSK_DEV uint32_t tables_lds_float4s(const DeviceScene &sc) {
 // A scene whose per-triangle tables do not fit LDS can still keep the SMALL ones there (mesh / BSDF / texture / emitter records, the
 // emitters' D65 tables and area CDFs, the CIE table: every bounce and every finished sample looks several of them up through
 // dependent indices): MSK_SMALL_TABLES_KB (compile time, default 16; 0 = all tables from HBM/L2 as in rounds 1-4).  0: not staged.
-#ifndef MSK_SMALL_TABLES_KB
-#define MSK_SMALL_TABLES_KB 16
-#endif
+// (The #define: msk_layout.h.  The host sizes a launch's LDS with the same two sums: msk_plan.h, table_bytes / small_bytes / place_tables.)
 MSK_DEV uint32_t small_tables_float4s(const DeviceScene &sc) {
     const uint32_t n = sc.n_meshes + sc.n_bsdf_f4 + sc.n_emitters * 3 + (sc.n_emitters * 95 + 3) / 4 + (sc.cdf_len + 3) / 4 + 72 + (sc.n_spectra + 3) / 4;
     return n * 16u <= MSK_SMALL_TABLES_KB * 1024u ? n : 0u;
@@ -2077,8 +2071,7 @@ MSK_DEV uint32_t emit_record(const DeviceScene &sc, const SceneTables &tb, const
 // Finished paths are parked in a wave-local LDS queue and turned into records 64 at a time: the record arithmetic (four
 // fp64 cosh, twelve CIE lookups, one RNG draw — about a fifth of this kernel's instructions) then runs with all lanes
 // busy instead of once per chunk for the ~25 % of its lanes that happened to finish.
-#define MSK_DONE_Q 128                     /* entries per wave: up to 63 parked + 64 new */
-#define MSK_DONE_Q_F4 (MSK_DONE_Q * 5 / 2)  /* float4 of LDS per wave: wl and res (16 B per entry), id (8 B) */
+// (MSK_DONE_Q entries per wave, up to 63 parked + 64 new, in MSK_DONE_Q_F4 float4 of LDS: msk_layout.h)
 struct DoneQueue { float4 *wl, *res; uint2 *id; };      // id: {film pixel, sample index}
 
 // Material-sorted shading (general variant).  Before a region is shaded its live paths are ordered by the material class of

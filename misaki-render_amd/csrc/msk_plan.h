@@ -1,13 +1,18 @@
 // msk_plan.h — what a render launches, decided once per call and on the host alone: the environment knobs of the wavefront
 // driver (RenderKnobs), the shape of the path pool (pool_shape), which instantiation of the shading, traversal and fused kernels
 // runs with how much LDS (LaunchPlan), and how a pass's samples and regions are dealt out (region_share, part_ranges).
-// Plain C++17, no HIP: msk_gpu.hip only picks the instantiation the plan names (launch_shade / launch_trace / launch_fused), and
-// tests/native/launch_plan_check.cpp checks every decision on a CPU.
+// And what a scene's creation decides, once per scene: its environment knobs (SceneKnobs), where the shading tables live
+// (place_tables) and which form of the tree is walked from where (place_tree); the scene keeps the outcome as its SceneFacts.
+// Plain C++17, no HIP: msk_gpu.hip only picks the instantiation the plan names (launch_shade / launch_trace / launch_fused) and
+// uploads the tree form the placement names; tests/native/launch_plan_check.cpp and tests/native/scene_tables_check.cpp check
+// every decision on a CPU.  (The tables themselves are packed by msk_scene_tables.h; the layout constants are msk_layout.h's.)
 #pragma once
+#include "msk_layout.h"
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 namespace mskplan {
@@ -25,9 +30,11 @@ enum TraceMode : int {
 // the tree stays in HBM/L2: a capped LDS stack with an overflow array, the larger pool, lane replacement by default
 constexpr bool tree_in_hbm(int mode) { return mode == TRACE_BIN_HBM || mode == TRACE_WIDE4 || mode == TRACE_WIDE8 || mode == TRACE_WIDE4_BYTE || mode == TRACE_WIDE4_HALF; }
 
-constexpr size_t kWavesPerBlock = 4;                        // MSK_BLOCK / MSK_WAVE   (msk_gpu.hip asserts both against msk_kernels.h)
-constexpr size_t kDoneQueueBytes = kWavesPerBlock * 320 * 16;     // the waves' done-queues of k_shade_gen: MSK_DONE_Q_F4 float4 per wave
+constexpr size_t kWavesPerBlock = MSK_BLOCK / MSK_WAVE;
+constexpr size_t kDoneQueueBytes = kWavesPerBlock * MSK_DONE_Q_F4 * 16;     // the waves' done-queues of k_shade_gen: MSK_DONE_Q_F4 float4 per wave
 constexpr size_t kLdsLimit = 64 * 1024;
+constexpr size_t kLdsTablesLimit = 40 * 1024;                               // every shading table in LDS up to this size (place_tables)
+constexpr size_t kSmallTablesLimit = (size_t) MSK_SMALL_TABLES_KB * 1024;   // ... else the small ones, up to this size
 
 inline uint32_t env_u32(const char *name, uint32_t def) {
     const char *v = getenv(name);
@@ -40,8 +47,8 @@ inline long long env_opt(const char *name) {
 }
 
 // Every environment knob of the wavefront driver, read ONCE per render call by the calling thread and never kept between calls
-// (the tests set knobs between two renders of one process).  The knobs of scene creation, of the film replay, of the watchdog
-// (msk_watchdog.h) and of group contexts (msk_multi.h) are read where they are used.
+// (the tests set knobs between two renders of one process).  The knobs of scene creation: SceneKnobs, below; those of the film
+// replay, of the watchdog (msk_watchdog.h) and of group contexts (msk_multi.h) are read where they are used.
 struct RenderKnobs {
     long long regions = -1, region_size = -1;   // MSK_REGIONS, MSK_REGION_SIZE; -1 = unset: the default of the tree's place (pool_shape)
     uint32_t streams = 4, stream_skew = 10;     // MSK_STREAMS, MSK_STREAM_SKEW (per cent)
@@ -86,6 +93,42 @@ inline RenderKnobs read_render_knobs() {
     return k;
 }
 
+// width of the tree for scenes that do not fit LDS: 4 (full-precision boxes) or 8 (quantised boxes); MSK_WIDE_BVH overrides, 0 = binary
+#ifndef MSK_WIDE_BVH_DEFAULT
+#define MSK_WIDE_BVH_DEFAULT 4
+#endif
+// Every environment knob of scene creation, read ONCE per msk_gpu_scene_create* call by the calling thread and never kept
+// between calls (the tests set knobs between two scenes of one process).
+struct SceneKnobs {
+    const char *pad_scale = nullptr;            // MSK_PAD_SCALE as text: mskscene::pack parses it, and refuses what is no number in [1e-7, 1e-3]
+    bool gpu_build = false;                     // MSK_BVH_BUILD=gpu: the tree is built on the device (msk_lbvh.hip), for scenes that change
+                                                // between renders; default: the host's binned-SAH builder (msk_bvh.h), the better tree
+    uint32_t bvh_leaf = 2;                      // MSK_BVH_LEAF (1..8): triangles per leaf of the device-built tree.  (The one knob with a second
+                                                // reader: the host builder's own default leaf size is not 2, and mskbvh::build, which the
+                                                // native checks call without knobs, reads the variable itself for the host-built tree.)
+    size_t lds_scene_cap = 48 * 1024;           // MSK_LDS_SCENE_KB, in bytes: a tree with its triangles is staged in LDS up to this size
+    uint32_t wide_bvh = MSK_WIDE_BVH_DEFAULT;   // MSK_WIDE_BVH
+    bool collapse_optimal = true;               // MSK_COLLAPSE_OPTIMAL
+    uint32_t quant_bvh = 2;                     // MSK_QUANT_BVH: 2 half-float child boxes, 1 byte-quantised, 0 full precision
+    bool wide_lds = false;                      // MSK_WIDE_LDS (experiment)
+    uint32_t stack_cap = 16;                    // MSK_STACK_CAP: entries of a lane's stack that live in LDS, for a tree in HBM
+};
+
+inline SceneKnobs read_scene_knobs() {
+    SceneKnobs k;
+    k.pad_scale = getenv("MSK_PAD_SCALE");
+    const char *build_env = getenv("MSK_BVH_BUILD");
+    k.gpu_build = build_env && !strcmp(build_env, "gpu");
+    k.bvh_leaf = getenv("MSK_BVH_LEAF") ? (uint32_t) std::max(1, std::min(8, atoi(getenv("MSK_BVH_LEAF")))) : 2u;
+    k.lds_scene_cap = getenv("MSK_LDS_SCENE_KB") ? (size_t) atoi(getenv("MSK_LDS_SCENE_KB")) * 1024 : 48 * 1024;
+    k.wide_bvh = env_u32("MSK_WIDE_BVH", MSK_WIDE_BVH_DEFAULT);
+    k.collapse_optimal = env_u32("MSK_COLLAPSE_OPTIMAL", 1) != 0;
+    k.quant_bvh = env_u32("MSK_QUANT_BVH", 2);
+    k.wide_lds = env_u32("MSK_WIDE_LDS", 0) != 0;
+    k.stack_cap = env_u32("MSK_STACK_CAP", 16);
+    return k;
+}
+
 // Short rays (LDS-resident scene): many small regions, one chunk loop per wave: 8192 x 512 = 4 M path slots (0.6 GB of state;
 // measured 16384 / 12288 / 8192 / 6144 regions: 42.7 / 41.7 / 41.2 / 41.6 ms for the bench step — the shading kernel streams the
 // whole pool's state every iteration and a smaller pool keeps more of it in the 256 MB Infinity Cache, the traversal kernel
@@ -115,6 +158,87 @@ struct SceneFacts {
                                   // delta light, the mirror lobe and the `constant` sky's own density run, whatever else the scene holds
     size_t trace_lds_bytes = 0, shade_lds_bytes = 0;
 };
+// LDS plan of k_shade_gen: the small lookup tables (mesh / BSDF / emitter records, cdf, d65, cie, tabulated spectra), and with
+// them, when everything fits, the per-triangle ones (tri_verts, tri_frames).  In float4, from the counts DeviceScene holds.
+// (The kernels size what they stage with the same sums: msk_kernels.h, small_tables_float4s and tables_lds_float4s.)
+struct TableCounts { uint32_t n_tris = 0, n_meshes = 0, n_bsdf_f4 = 0, n_emitters = 0, cdf_len = 0, n_spectra = 0; };
+inline size_t small_bytes(const TableCounts &c) {
+    return ((size_t) c.n_meshes + c.n_bsdf_f4 + c.n_emitters * 3 + (c.n_emitters * 95 + 3) / 4 + (c.cdf_len + 3) / 4 + 72 + (c.n_spectra + 3) / 4) * 16;
+}
+inline size_t table_bytes(const TableCounts &c) { return (size_t) c.n_tris * 6 * 16 + small_bytes(c); }
+struct TablePlacement {
+    bool lds_tables = false;        // every table in LDS (k_shade_gen<true, ...>)
+    size_t staged_bytes = 0;        // what a block stages: all tables, else the small ones if they fit kSmallTablesLimit, else nothing
+    size_t shade_lds_bytes = 0;     // + the waves' done-queues
+};
+inline TablePlacement place_tables(const TableCounts &c) {
+    TablePlacement p;
+    p.lds_tables = table_bytes(c) <= kLdsTablesLimit;
+    // (a scene whose per-triangle tables stay in HBM still stages the small ones)
+    p.staged_bytes = p.lds_tables ? table_bytes(c) : small_bytes(c) <= kSmallTablesLimit ? small_bytes(c) : 0;
+    p.shade_lds_bytes = p.staged_bytes + kDoneQueueBytes;
+    return p;
+}
+
+// LDS plan of the traversal kernels: which form of the tree they walk, from where, with how much stack.
+struct BinaryTree { uint32_t n_nodes = 0, n_tris = 0; int max_depth = 0; bool root_is_leaf = false; };    // what the builder made (msk_bvh.h)
+struct WideTree {                   // what a collapse of it made (msk_bvh.h: collapse4 / collapse8)
+    bool ok = false;                // collapse8 refuses a tree whose boxes cannot be quantised conservatively (extents beyond the exponent range)
+    int max_depth = 0; uint32_t n_nodes = 0;
+    bool has_half = false, has_byte = false;    // 4-wide: the half-float / byte-quantised forms exist (nodes4h / nodes4q are not empty)
+};
+struct TreePlacement {
+    int trace_mode = TRACE_BIN_LDS;
+    bool lds_scene = false;
+    uint32_t stack_entries = 0;     // DeviceScene::stack_entries: of a lane's stack in LDS ...
+    uint32_t stack_total = 0;       // ... and in all; the rest lives in an HBM overflow array (LaneStack)
+    size_t trace_lds_bytes = 0;
+    size_t binary_stack_bytes = 0;  // the binary tree's whole stack per block (the refusal of a tree too deep for LDS names it)
+};
+// `collapse(width)` is called at most twice, in the order the forms are tried, and returns the WideTree of that width: the 8-wide
+// form may refuse (the 4-wide one is then tried), the quantised 4-wide forms may be missing (the full-precision one is then walked).
+template <class Collapse>
+inline TreePlacement place_tree(const BinaryTree &t, const SceneKnobs &k, Collapse &&collapse) {
+    TreePlacement p;
+    // per-lane stack + (when it fits) the whole BVH
+    p.stack_entries = (uint32_t) ((t.max_depth + 2 + 3) & ~3);
+    p.binary_stack_bytes = (size_t) p.stack_entries * MSK_BLOCK * 4;
+    const size_t scene_bytes = (size_t) t.n_nodes * 64 + (size_t) t.n_tris * 96;
+    p.lds_scene = scene_bytes <= k.lds_scene_cap && p.binary_stack_bytes + scene_bytes <= kLdsLimit;
+    p.trace_lds_bytes = p.binary_stack_bytes + (p.lds_scene ? scene_bytes : 0);
+    p.trace_mode = p.lds_scene ? TRACE_BIN_LDS : TRACE_BIN_HBM;
+    WideTree w;
+    if (!p.lds_scene && k.wide_bvh == 8 && !t.root_is_leaf && (w = collapse(8)).ok) {
+        // the tree stays in HBM/L2: eight quantised child boxes per 128-byte line
+        p.stack_entries = (uint32_t) ((7 * w.max_depth + 2 + 3) & ~3);     // up to seven pushes per level
+        p.trace_mode = TRACE_WIDE8;
+    } else if (!p.lds_scene && k.wide_bvh && !t.root_is_leaf) {
+        // the tree stays in HBM/L2: walk it four children at a time, one 128-byte line per visit
+        w = collapse(4);
+        p.stack_entries = (uint32_t) ((3 * w.max_depth + 2 + 3) & ~3);     // up to three pushes per level
+        // the walked form (MSK_QUANT_BVH): 2 (default since round 5) 80-byte nodes with half-float child boxes read by v_fma_mix_f32,
+        // 1 64-byte nodes with byte-quantised boxes (rounds 3-4), 0 the full-precision 128-byte ones.  Config-5 / config-3 class
+        // renders (round 5, same box): 124.7 / 159.5 ms with 2 against 126.9 / 168.3 with 1.
+        p.trace_mode = k.quant_bvh == 2 && w.has_half ? TRACE_WIDE4_HALF : k.quant_bvh && w.has_byte ? TRACE_WIDE4_BYTE : TRACE_WIDE4;
+    } else if (p.lds_scene && k.wide_lds && !t.root_is_leaf) {
+        // experiment knob, off by default: the 4-wide tree staged in LDS (half the dependent LDS round trips per ray).
+        // Measured on cbox: trace 12.45 vs 12.34 ms for the binary tree — no gain.
+        w = collapse(4);
+        p.stack_entries = (uint32_t) ((3 * w.max_depth + 2 + 3) & ~3);
+        p.trace_lds_bytes = (size_t) p.stack_entries * MSK_BLOCK * 4 + ((size_t) w.n_nodes * 128 + (size_t) t.n_tris * 96);
+        p.trace_mode = TRACE_WIDE4_LDS;
+    }
+    p.stack_total = p.stack_entries;
+    if (tree_in_hbm(p.trace_mode)) {
+        // trees in HBM: only the first MSK_STACK_CAP entries of a lane's stack live in LDS, the rest in an HBM overflow
+        // array (LaneStack) — any tree depth works within a fixed 16 KB (+ 4 KB of node4_step scratch) of LDS per block, which
+        // leaves room for six blocks per CU.  (Measured: the cap does not change the trace time between 8 and 40 entries.)
+        p.stack_entries = std::min(p.stack_total, std::max(4u, k.stack_cap & ~3u));
+        p.trace_lds_bytes = (size_t) p.stack_entries * MSK_BLOCK * 4 + (size_t) MSK_BLOCK * 16;       // + four words per lane (node4_step)
+    }
+    return p;
+}
+
 struct CallFacts {
     uint32_t region_size = 0;
     uint32_t aov_groups = 0;      // an "aov" render's primary-hit record groups

@@ -1,7 +1,8 @@
 """Scenes whose shading tables do not fit in LDS: every branch of how msk_gpu_scene_create and msk_gpu_render place them.
 
 The placement moves data and never changes arithmetic, so every scene here must give the oracle's bits.  The plan makes four
-decisions (misaki-render_amd/csrc/msk_gpu.hip: scene create and render; msk_kernels.h: stage_tables and its callers):
+decisions (misaki-render_amd/csrc/msk_plan.h: place_tree and place_tables at scene creation, make_launch_plan per render;
+msk_kernels.h: stage_tables and its callers):
 
   tree      BVH and triangles in LDS (trace mode 0, k_trace_q) or in HBM (mode 6); pinned per scene with MSK_LDS_SCENE_KB
   tables    table_f4 <= 2560 float4: every shading table in LDS (k_shade_gen<true, ...>), else only the small ones (<false, ...>)
@@ -19,14 +20,15 @@ import pytest
 
 W, H, SPP, SEED = 96, 80, 8, 5
 ORACLE_THREADS = 16
-LDS_TABLES_F4 = 40 * 1024 // 16          # msk_gpu.hip: s->lds_tables = table_bytes <= 40 * 1024
-SMALL_TABLES_F4 = 16 * 1024 // 16        # msk_kernels.h: MSK_SMALL_TABLES_KB (default 16)
+LDS_TABLES_F4 = 40 * 1024 // 16          # msk_plan.h: kLdsTablesLimit (place_tables: lds_tables = table_bytes <= 40 KB)
+SMALL_TABLES_F4 = 16 * 1024 // 16        # msk_layout.h: MSK_SMALL_TABLES_KB (default 16)
 
 
 def table_plan(flat):
-    """table_f4, small_f4 and the two decisions they make, from the msk_scene_desc alone.  Mirrors `table_bytes` and
-    `small_bytes` of msk_gpu_scene_create (misaki-render_amd/csrc/msk_gpu.hip, "LDS plan of k_shade_gen") and
-    tables_lds_float4s / small_tables_float4s (msk_kernels.h, next to stage_tables).  In float4: mesh records (1 each), BSDF
+    """table_f4, small_f4 and the two decisions they make, from the msk_scene_desc alone.  Mirrors `table_bytes`,
+    `small_bytes` and `place_tables` of misaki-render_amd/csrc/msk_plan.h — tests/test_scene_tables.py holds this function
+    against them on a CPU — and tables_lds_float4s / small_tables_float4s (msk_kernels.h, next to stage_tables), with the
+    counts as msk_scene_tables.h packs them.  In float4: mesh records (1 each), BSDF
     records (7 each, at least one) and texture records (3 each), emitter records (2) and grids (1), the emitters' 95-entry D65
     tables, the concatenated area CDFs (face_count + 1 per area emitter, at least one entry), the CIE table (285 floats = 72)
     and the tabulated spectra's values.  table_f4 adds tri_verts and tri_frames, 6 per triangle."""
@@ -213,7 +215,7 @@ def _flat(hm, name):
 
 
 def fused_expected(name):
-    """MSK_FUSED=1 runs k_wavefront when tree and tables are both in LDS and k_wavefront_h when both are in HBM (msk_gpu.hip:
+    """MSK_FUSED=1 runs k_wavefront when tree and tables are both in LDS and k_wavefront_h when both are in HBM (msk_plan.h:
     fused_ok).  Its LDS sum fits every scene here: at most 36 KB of shading and 20 KB of traversal LDS for a tree in HBM."""
     _, tree_lds, lds_tables = SCENES[name][:3]
     return tree_lds == lds_tables
