@@ -533,6 +533,31 @@ int  msk_gpu_env_sample(msk_scene *scene, uint64_t n, const float *u, float *out
 int  msk_gpu_point_sample(msk_scene *scene, uint32_t emitter, uint64_t n, const float *ref_points, const float *wavelengths, float *out_d_dist, float *out_value);
 int  msk_gpu_conductor_sample(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *cos_theta_i, const float *wavelengths, float *out_value);
 
+/* ---- the "direct" integrator ----------------------------------------------- */
+/*
+ * Direct illumination only (integrators/direct.cpp): per camera sample one primary ray, `light_samples` next-event samples and
+ * `bsdf_samples` BSDF samples at the primary hit, combined by the power heuristic over the sample COUNTS:
+ *   w_l = (N p_l)^2 / ((N p_l)^2 + (M p_b)^2),  w_b = (M p_b)^2 / ((M p_b)^2 + (N p_e)^2),  terms divided by N and M.
+ * Random pairs of a sample (counter_pair of its key): 0-2 as "path" (film position, wavelengths, aperture), 3 + i light sample i,
+ * 3 + N + 2 j / + 1 the lobe choice (.x) and the direction of BSDF sample j; additions in the order emission, light samples,
+ * BSDF samples.  With (1, 1) the result is, bit for bit, msk_gpu_render at max_depth = 2 — except for a `constant` sky in a scene
+ * of the older kernel families, which counts here with the density of the ray's own direction always.
+ * light_samples and bsdf_samples are each in [0, 4096] and not both 0 (MSK_ERR_INVALID_ARG otherwise).
+ * msk_render_params: rr_depth and max_depth are ignored; spp, seed, hide_emitters, block_size and the shard selectors mean what
+ * they mean for msk_gpu_render.  MSK_RNG_PCG_BLOCK and group contexts: MSK_ERR_UNSUPPORTED (shard over processes with
+ * sample_first / sample_stride).  msk_stats: samples, segments, shadow_rays, invalid_samples, passes, ms_total, ms_resolve;
+ * iterations = kernel launches of k_direct; the wavefront-only fields are 0.
+ * msk_gpu_sample_pixels_direct: msk_gpu_sample_pixels for this integrator; unlike it, it HONOURS sample_first / sample_stride:
+ * out_xyz / out_pos hold, per listed pixel, the call's owned samples s = sample_first + k * sample_stride < spp, in order.
+ */
+typedef struct msk_direct_params { uint32_t light_samples, bsdf_samples; } msk_direct_params;
+int  msk_gpu_render_direct(msk_scene *scene, const msk_render_params *params, const msk_direct_params *direct,
+                           float *film_xyzaw, msk_stats *stats);
+int  msk_gpu_render_direct_device(msk_scene *scene, const msk_render_params *params, const msk_direct_params *direct,
+                                  float *d_film_xyzaw, void *hip_stream, msk_stats *stats);
+int  msk_gpu_sample_pixels_direct(msk_scene *scene, const msk_render_params *params, const msk_direct_params *direct,
+                                  uint64_t n_pixels, const int32_t *pixels, float *out_xyz, float *out_pos);
+
 /* device + build information for logs: fills a NUL-terminated string */
 int  msk_gpu_describe(const msk_ctx *ctx, char *buf, uint64_t buf_size);
 

@@ -108,6 +108,11 @@ class RenderParams(C.Structure):
                 ("sample_first", C.c_uint32), ("sample_stride", C.c_uint32)]
 
 
+class DirectParams(C.Structure):
+    """msk_direct_params: the "direct" integrator's sample counts per camera sample (each 0 .. 4096, not both 0)."""
+    _fields_ = [("light_samples", C.c_uint32), ("bsdf_samples", C.c_uint32)]
+
+
 class Stats(C.Structure):
     _fields_ = [("samples", C.c_uint64), ("segments", C.c_uint64), ("shadow_rays", C.c_uint64),
                 ("iterations", C.c_uint32), ("passes", C.c_uint32), ("ms_total", C.c_float),
@@ -144,7 +149,8 @@ EXPORTS = ["msk_gpu_init", "msk_gpu_shutdown", "msk_gpu_last_error", "msk_gpu_sc
            "msk_gpu_scene_destroy", "msk_gpu_render", "msk_gpu_render_device", "msk_gpu_trace_closest",
            "msk_gpu_trace_any", "msk_gpu_sample_pixels", "msk_gpu_describe", "msk_gpu_render_aov", "msk_gpu_aov_channels",
            "msk_gpu_eval_texture", "msk_gpu_scene_create_env", "msk_gpu_env_eval", "msk_gpu_env_sample",
-           "msk_gpu_scene_create_ext", "msk_gpu_point_sample", "msk_gpu_conductor_sample"]
+           "msk_gpu_scene_create_ext", "msk_gpu_point_sample", "msk_gpu_conductor_sample",
+           "msk_gpu_render_direct", "msk_gpu_render_direct_device", "msk_gpu_sample_pixels_direct"]
 
 # integrators/aov.cpp:21-28
 MSK_AOV_DEPTH, MSK_AOV_POSITION, MSK_AOV_UV, MSK_AOV_GEO_NORMAL, MSK_AOV_SH_NORMAL, MSK_AOV_PATH_RGBA = range(6)
@@ -203,6 +209,12 @@ def load_library(path=None):
     lib.msk_gpu_point_sample.restype = C.c_int
     lib.msk_gpu_conductor_sample.argtypes = [vp, C.c_uint32, u64, vp, vp, vp]
     lib.msk_gpu_conductor_sample.restype = C.c_int
+    lib.msk_gpu_render_direct.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(DirectParams), vp, C.POINTER(Stats)]
+    lib.msk_gpu_render_direct.restype = C.c_int
+    lib.msk_gpu_render_direct_device.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(DirectParams), vp, vp, C.POINTER(Stats)]
+    lib.msk_gpu_render_direct_device.restype = C.c_int
+    lib.msk_gpu_sample_pixels_direct.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(DirectParams), u64, vp, vp, vp]
+    lib.msk_gpu_sample_pixels_direct.restype = C.c_int
     lib.msk_gpu_describe.argtypes = [vp, C.c_char_p, u64]
     lib.msk_gpu_describe.restype = C.c_int
     if path is None:
@@ -330,6 +342,35 @@ class Scene:
         pos = np.empty((n, params.spp, 2), np.float32)
         self.ctx.check(self.ctx.lib.msk_gpu_sample_pixels(self.handle, C.byref(params), n, _ptr(pixels),
                                                            _ptr(xyz), _ptr(pos)))
+        return xyz, pos
+
+    def render_direct(self, params, light_samples=1, bsdf_samples=1, out=None):
+        """The "direct" integrator (msk_gpu_render_direct): -> (film float32[H,W,5], Stats).  rr_depth / max_depth of params are ignored."""
+        film = out if out is not None else np.empty((self.height, self.width, 5), np.float32)
+        if not (isinstance(film, np.ndarray) and film.dtype == np.float32 and film.flags.c_contiguous and film.shape == (self.height, self.width, 5)):
+            raise ValueError(f"out must be a C-contiguous float32 array of shape {(self.height, self.width, 5)}")
+        st, dp = Stats(), DirectParams(light_samples, bsdf_samples)
+        self.ctx.check(self.ctx.lib.msk_gpu_render_direct(self.handle, C.byref(params), C.byref(dp), _ptr(film), C.byref(st)))
+        return film, st
+
+    def render_direct_device(self, params, device_ptr, light_samples=1, bsdf_samples=1, stream=None):
+        st, dp = Stats(), DirectParams(light_samples, bsdf_samples)
+        self.ctx.check(self.ctx.lib.msk_gpu_render_direct_device(self.handle, C.byref(params), C.byref(dp), C.c_void_p(device_ptr),
+                                                                  C.c_void_p(stream or 0), C.byref(st)))
+        return st
+
+    def sample_pixels_direct(self, params, pixels, light_samples=1, bsdf_samples=1):
+        """msk_gpu_sample_pixels_direct: per listed pixel the samples this call OWNS (s = sample_first + k sample_stride < spp), in
+        order -> (xyz float32[n, owned, 3], pos float32[n, owned, 2])."""
+        pixels = np.ascontiguousarray(pixels, np.int32).reshape(-1, 2)
+        n = pixels.shape[0]
+        stride = params.sample_stride or 1
+        owned = (params.spp - params.sample_first + stride - 1) // stride if params.sample_first < params.spp else 0
+        xyz = np.empty((n, owned, 3), np.float32)
+        pos = np.empty((n, owned, 2), np.float32)
+        dp = DirectParams(light_samples, bsdf_samples)
+        self.ctx.check(self.ctx.lib.msk_gpu_sample_pixels_direct(self.handle, C.byref(params), C.byref(dp), n, _ptr(pixels),
+                                                                  _ptr(xyz), _ptr(pos)))
         return xyz, pos
 
     def eval_texture(self, texture, uv, wavelengths):

@@ -6,6 +6,7 @@
 // resolve.  Everything per-sample runs in the kernels of msk_kernels.h.
 #include "msk_kernels.h"
 #include "msk_serial.h"
+#include "msk_direct.h"
 #include "msk_bvh.h"
 #include "msk_plan.h"
 #include "msk_scene_tables.h"
@@ -484,6 +485,7 @@ struct Workspace {
     ~Workspace() { if (host_film) (void) hipHostFree(host_film); }
     uint32_t n_bands = 0;
     DevBuf aov_rec[MSK_MAX_AOV_GROUPS + 1], aov_block_buf[MSK_MAX_AOV_GROUPS + 1];   // [n_groups] = the nested path's RGB
+    DevBuf direct_counters, direct_ovf;      // the "direct" integrator's counters and stack overflow (run_direct)
 };
 
 // what msk_gpu_render_aov asked for, in record groups of three channels (see AovParams)
@@ -932,6 +934,57 @@ static int run_wavefront(msk_scene *sc, hipStream_t stream, const msk_render_par
     return MSK_OK;
 }
 
+// The "direct" integrator's pass: the records of `pix` by k_direct (msk_direct.h), cut into launches of a bounded number of rays
+// (mskplan::make_direct_plan); every few launches the host waits through the watchdog's timed wait.  Leaves records on the device.
+static int run_direct(msk_scene *sc, hipStream_t stream, const msk_render_params *prm, const msk_direct_params *dp, uint32_t spp_owned,
+                      const uint4 *d_pix, const uint32_t *d_pix_to_j, uint64_t n_pix, float4 *rec_a, float *rec_b, msk_stats *stats, bool packed) {
+    msk_ctx *ctx = sc->ctx;
+    const uint64_t total = n_pix * spp_owned;
+    if (total == 0) return MSK_OK;
+    const mskplan::DirectPlan plan = mskplan::make_direct_plan(sc->facts, sc->dev.stack_entries, sc->dev.stack_total, sc->bvh_depth,
+                                                               dp->light_samples, dp->bsdf_samples, total);
+    if (!sc->ws) sc->ws = new Workspace();
+    Workspace &ws = *sc->ws;
+    StateBufs none;                                      // no path state: the regions' pointer of PassParams stays null
+    const PassParams pp = pass_params(prm, spp_owned, d_pix, d_pix_to_j, rec_a, rec_b, none, 0u, 0u, mskplan::LaunchPlan{}, nullptr, nullptr, packed);
+    PathState st;
+    std::memset(&st, 0, sizeof st);
+    DeviceScene ds = sc->dev;
+    ds.stack_entries = plan.stack_entries;
+    const size_t counter_bytes = (size_t) MSK_DIRECT_COUNTER_LINES * 8 * sizeof(unsigned long long);
+    HIP_TRY(ctx, ws.direct_counters.reserve(counter_bytes));
+    HIP_TRY(ctx, hipMemsetAsync(ws.direct_counters.p, 0, counter_bytes, stream));
+    const uint32_t grid_max = plan.grid_blocks(std::min<uint64_t>(total, plan.records_per_launch));
+    if (plan.ovf_entries) HIP_TRY(ctx, ws.direct_ovf.reserve((size_t) plan.ovf_entries * grid_max * MSK_BLOCK * 4));
+    DirectArgs da;
+    da.n_light = dp->light_samples; da.n_bsdf = dp->bsdf_samples;
+    da.per_wave = plan.records_per_wave; da.tables_mode = plan.tables_mode; da.stack_f4 = plan.stack_f4;
+    da.stack_ovf = plan.ovf_entries ? ws.direct_ovf.as<uint32_t>() : nullptr;
+    da.counters = ws.direct_counters.as<unsigned long long>();
+    uint32_t n_launches = 0;
+    for (uint64_t first = 0; first < total; first += plan.records_per_launch) {
+        da.rec_first = first; da.rec_count = std::min<uint64_t>(plan.records_per_launch, total - first);
+        const dim3 grid(plan.grid_blocks(da.rec_count)), block(MSK_BLOCK);
+        if (plan.form == mskplan::TRACE_BIN_LDS) hipLaunchKernelGGL(k_direct<0>, grid, block, plan.lds_bytes, stream, ds, st, pp, da);
+        else if (plan.form == mskplan::TRACE_WIDE4_HALF) hipLaunchKernelGGL(k_direct<6>, grid, block, plan.lds_bytes, stream, ds, st, pp, da);
+        else hipLaunchKernelGGL(k_direct<1>, grid, block, plan.lds_bytes, stream, ds, st, pp, da);
+        HIP_TRY(ctx, hipGetLastError());
+        // (a launch is bounded work — DirectPlan::records_per_launch — so a group of eight is what one timed wait covers)
+        if (++n_launches % 8u == 0u)
+            if (int rc = ctx_sync(ctx, stream, "a group of k_direct launches")) return rc;
+    }
+    std::vector<unsigned long long> h((size_t) MSK_DIRECT_COUNTER_LINES * 8, 0ull);
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), ws.direct_counters.p, counter_bytes, hipMemcpyDeviceToHost, stream));
+    if (int rc = ctx_sync(ctx, stream, "the last k_direct launches of a pass")) return rc;
+    if (stats) {
+        for (uint32_t l = 0; l < MSK_DIRECT_COUNTER_LINES; ++l) {
+            stats->samples += h[l * 8]; stats->segments += h[l * 8 + 1]; stats->shadow_rays += h[l * 8 + 2]; stats->invalid_samples += h[l * 8 + 3];
+        }
+        stats->iterations += n_launches;
+    }
+    return MSK_OK;
+}
+
 // samples per pixel this call renders: s = sample_first + k * sample_stride < spp.  64-bit: spp - first + stride - 1 wraps in
 // 32 bits (spp 0xFFFFFFFF, stride 4095 owns 1048833 samples; a 32-bit sum would give 0 and render nothing)
 static unsigned long long owned_spp(const msk_render_params *p) {
@@ -1070,13 +1123,14 @@ static int render_serial(msk_scene *sc, const msk_render_params *prm, float *d_f
 }
 
 static int render_impl(msk_scene *sc, const msk_render_params *prm, float *d_film, hipStream_t user_stream, msk_stats *stats,
-                       const AovPlan *aov = nullptr) {
+                       const AovPlan *aov = nullptr, const msk_direct_params *direct = nullptr) {
     msk_ctx *ctx = sc->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int border = sc->dev.filter_border;
     int rc = check_params(ctx, prm, std::max(4, 2 * border));
     if (rc) return rc;
     if (prm->rng_mode == MSK_RNG_PCG_BLOCK) {
+        if (direct) return fail(ctx, MSK_ERR_UNSUPPORTED, "MSK_RNG_PCG_BLOCK is not supported by the \"direct\" integrator (it uses MSK_RNG_COUNTER)");
         if (aov) return fail(ctx, MSK_ERR_UNSUPPORTED, "MSK_RNG_PCG_BLOCK renders the \"path\" integrator only (the \"aov\" integrator uses MSK_RNG_COUNTER)");
         if (stats) std::memset(stats, 0, sizeof *stats);
         return render_serial(sc, prm, d_film, user_stream ? user_stream : ctx->stream, stats);
@@ -1148,7 +1202,7 @@ static int render_impl(msk_scene *sc, const msk_render_params *prm, float *d_fil
         HIP_TRY(ctx, d_blocks.upload(owned)); HIP_TRY(ctx, d_block_of.upload(ob.block_of)); HIP_TRY(ctx, d_spiral.upload(ob.spiral_id));
     }
     StateBufs &sb = ws.sb;
-    if (!owned.empty()) HIP_TRY(ctx, sb.alloc(n_slots, n_regions));
+    if (!owned.empty() && !direct) HIP_TRY(ctx, sb.alloc(n_slots, n_regions));      // (the "direct" integrator keeps no path state)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_resolve;
     DevBuf &d_pix = ws.pix, &d_rec_a = ws.rec_a, &d_rec_b = ws.rec_b;
     for (auto &ps : passes) {
@@ -1196,6 +1250,9 @@ static int render_impl(msk_scene *sc, const msk_render_params *prm, float *d_fil
             }
             if (aov->rgba) { HIP_TRY(ctx, ws.aov_rec[MSK_MAX_AOV_GROUPS].reserve(n_rec * 16)); aov_rgb = ws.aov_rec[MSK_MAX_AOV_GROUPS].as<float4>(); }
         }
+        if (direct) rc = run_direct(sc, stream, prm, direct, spp_owned, d_pix.as<uint4>(), ws.pix_inv.as<uint32_t>(), n_pix, d_rec_a.as<float4>(),
+                                    d_rec_b.as<float>(), stats, packed);
+        else
         rc = run_wavefront(sc, stream, prm, knobs, spp_owned, d_pix.as<uint4>(), ws.pix_inv.as<uint32_t>(), n_pix, d_rec_a.as<float4>(),
                            d_rec_b.as<float>(), sb, region_size, n_regions, stats, ev, aov ? &ap : nullptr, aov_rgb, packed);
         if (rc) return rc;
@@ -1369,21 +1426,16 @@ extern "C" int msk_gpu_render_aov(msk_scene *scene, const msk_render_params *par
     return MSK_OK;
 }
 
-extern "C" int msk_gpu_sample_pixels(msk_scene *scene, const msk_render_params *prm, uint64_t n_pixels, const int32_t *pixels,
-                                     float *out_xyz, float *out_pos) {
-    if (!scene || !pixels || !out_xyz) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_sample_pixels: NULL argument");
-    MSK_REFUSE_LOST(scene->ctx);
-    if (scene->ctx->group) {             // sub-stage entry points of a group run on its first member
-        const int rc = msk_gpu_sample_pixels(scene->parts[0], prm, n_pixels, pixels, out_xyz, out_pos);
-        return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK;
-    }
+// msk_gpu_sample_pixels, and with `direct` msk_gpu_sample_pixels_direct (which honours the sample selectors: msk_gpu.h)
+static int sample_pixels_impl(msk_scene *scene, const msk_render_params *prm, uint64_t n_pixels, const int32_t *pixels,
+                              float *out_xyz, float *out_pos, const msk_direct_params *direct) {
     msk_ctx *ctx = scene->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = check_params(ctx, prm, 1);
     if (rc) return rc;
     // every sample 0 .. spp-1 of a listed pixel is rendered (the selectors are ignored below): all of them count against the
     // path state's 20 bits of sample index
-    if (prm->spp > (1u << MSK_DEPTH_SHIFT))
+    if (!direct && prm->spp > (1u << MSK_DEPTH_SHIFT))
         return fail(ctx, MSK_ERR_UNSUPPORTED, "msk_gpu_sample_pixels: spp %u, at most %u (every sample of a pixel is rendered)",
                     prm->spp, 1u << MSK_DEPTH_SHIFT);
     if (prm->rng_mode != MSK_RNG_COUNTER)
@@ -1409,32 +1461,105 @@ extern "C" int msk_gpu_sample_pixels(msk_scene *scene, const msk_render_params *
     if (n_pixels == 0) return MSK_OK;
     const uint64_t n_listed = n_pixels;
     n_pixels = pix.size();
-    msk_render_params p = *prm; p.sample_first = 0; p.sample_stride = 1;
-    const uint64_t n_rec = n_pixels * p.spp;
+    msk_render_params p = *prm;
+    if (!direct) { p.sample_first = 0; p.sample_stride = 1; }
+    const uint32_t spp_out = direct ? (uint32_t) owned_spp(&p) : p.spp;       // samples per listed pixel in the output
+    if (spp_out == 0) return MSK_OK;
+    const uint64_t n_rec = n_pixels * spp_out;
     const mskplan::RenderKnobs knobs = mskplan::read_render_knobs();
-    uint32_t region_size, n_regions;
-    mskplan::pool_shape(scene->facts.trace_mode, n_rec, knobs, &region_size, &n_regions);
+    uint32_t region_size = 0, n_regions = 0;
     StateBufs sb; DevBuf d_pix, d_inv, ra, rb, ox, op;
-    HIP_TRY(ctx, sb.alloc((size_t) region_size * n_regions, n_regions));
+    if (!direct) {
+        mskplan::pool_shape(scene->facts.trace_mode, n_rec, knobs, &region_size, &n_regions);
+        HIP_TRY(ctx, sb.alloc((size_t) region_size * n_regions, n_regions));
+    }
     HIP_TRY(ctx, d_pix.upload(pix)); HIP_TRY(ctx, d_inv.upload(inv)); HIP_TRY(ctx, ra.alloc(n_rec * 16)); HIP_TRY(ctx, rb.alloc(n_rec * 4));
     HIP_TRY(ctx, ox.alloc(n_rec * 12)); HIP_TRY(ctx, op.alloc(n_rec * 8));
     EventPool ev{ctx, 0};
     // a lost context (the watchdog gave up): the local buffers are dropped without hipFree, which would wait for the device
     auto sb_leak = [&]() { if (ctx->lost) { sb.leak(); for (DevBuf *b : {&d_pix, &d_inv, &ra, &rb, &ox, &op}) b->leak(); } };
+    if (direct) rc = run_direct(scene, ctx->stream, &p, direct, spp_out, d_pix.as<uint4>(), d_inv.as<uint32_t>(), n_pixels, ra.as<float4>(), rb.as<float>(), nullptr, false);
+    else
     rc = run_wavefront(scene, ctx->stream, &p, knobs, p.spp, d_pix.as<uint4>(), d_inv.as<uint32_t>(), n_pixels, ra.as<float4>(), rb.as<float>(), sb,
                        region_size, n_regions, nullptr, ev);
     if (rc) { sb_leak(); return rc; }
     hipLaunchKernelGGL(k_export_records, dim3((uint32_t) ((n_rec + 255) / 256)), dim3(256), 0, ctx->stream, ra.as<float4>(),
-                       rb.as<float>(), n_pixels, p.spp, ox.as<float>(), op.as<float>());
+                       rb.as<float>(), n_pixels, spp_out, ox.as<float>(), op.as<float>());
     if ((rc = ctx_sync(ctx, ctx->stream, "k_export_records"))) { sb_leak(); return rc; }
     std::vector<float> hx((size_t) n_rec * 3), hp(out_pos ? (size_t) n_rec * 2 : 0);
     HIP_TRY(ctx, hipMemcpy(hx.data(), ox.p, n_rec * 12, hipMemcpyDeviceToHost));
     if (out_pos) HIP_TRY(ctx, hipMemcpy(hp.data(), op.p, n_rec * 8, hipMemcpyDeviceToHost));
     for (uint64_t i = 0; i < n_listed; ++i) {
-        std::memcpy(out_xyz + i * p.spp * 3, hx.data() + (size_t) place[i] * p.spp * 3, (size_t) p.spp * 12);
-        if (out_pos) std::memcpy(out_pos + i * p.spp * 2, hp.data() + (size_t) place[i] * p.spp * 2, (size_t) p.spp * 8);
+        std::memcpy(out_xyz + i * spp_out * 3, hx.data() + (size_t) place[i] * spp_out * 3, (size_t) spp_out * 12);
+        if (out_pos) std::memcpy(out_pos + i * spp_out * 2, hp.data() + (size_t) place[i] * spp_out * 2, (size_t) spp_out * 8);
     }
     return MSK_OK;
+}
+
+extern "C" int msk_gpu_sample_pixels(msk_scene *scene, const msk_render_params *prm, uint64_t n_pixels, const int32_t *pixels,
+                                     float *out_xyz, float *out_pos) {
+    if (!scene || !pixels || !out_xyz) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_sample_pixels: NULL argument");
+    MSK_REFUSE_LOST(scene->ctx);
+    if (scene->ctx->group) {             // sub-stage entry points of a group run on its first member
+        const int rc = msk_gpu_sample_pixels(scene->parts[0], prm, n_pixels, pixels, out_xyz, out_pos);
+        return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK;
+    }
+    return sample_pixels_impl(scene, prm, n_pixels, pixels, out_xyz, out_pos, nullptr);
+}
+
+// ---- the "direct" integrator (msk_gpu.h: msk_direct_params; msk_direct.h) ----------------------------------------------------------
+// What the three calls refuse before anything runs, and the parameters they render with: rr_depth and max_depth are ignored.
+static int check_direct(msk_scene *scene, const msk_render_params *prm, const msk_direct_params *d, const char *who, msk_render_params *out) {
+    msk_ctx *ctx = scene->ctx;
+    if (!prm || !d) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: NULL argument", who);
+    if (ctx->group)
+        return fail(ctx, MSK_ERR_UNSUPPORTED, "%s: group contexts (msk_gpu_init with n > 1) are not supported by the \"direct\" integrator; "
+                    "run one process per GPU and shard the samples with sample_first / sample_stride", who);
+    if (prm->rng_mode == MSK_RNG_PCG_BLOCK)
+        return fail(ctx, MSK_ERR_UNSUPPORTED, "%s: MSK_RNG_PCG_BLOCK is not supported by the \"direct\" integrator (it uses MSK_RNG_COUNTER)", who);
+    if (d->light_samples > mskplan::kDirectMaxSamples)
+        return fail(ctx, MSK_ERR_INVALID_ARG, "%s: \"light_samples\" is %u, at most %u", who, d->light_samples, mskplan::kDirectMaxSamples);
+    if (d->bsdf_samples > mskplan::kDirectMaxSamples)
+        return fail(ctx, MSK_ERR_INVALID_ARG, "%s: \"bsdf_samples\" is %u, at most %u", who, d->bsdf_samples, mskplan::kDirectMaxSamples);
+    if (d->light_samples == 0 && d->bsdf_samples == 0)
+        return fail(ctx, MSK_ERR_INVALID_ARG, "%s: \"light_samples\" and \"bsdf_samples\" must not both be 0", who);
+    *out = *prm;
+    out->rr_depth = 5; out->max_depth = -1;
+    return MSK_OK;
+}
+
+extern "C" int msk_gpu_render_direct_device(msk_scene *scene, const msk_render_params *params, const msk_direct_params *direct,
+                                            float *d_film_xyzaw, void *hip_stream, msk_stats *stats) {
+    if (!scene || !d_film_xyzaw) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_render_direct_device: NULL argument");
+    MSK_REFUSE_LOST(scene->ctx);
+    msk_render_params p;
+    if (int rc = check_direct(scene, params, direct, "msk_gpu_render_direct_device", &p)) return rc;
+    return render_impl(scene, &p, d_film_xyzaw, (hipStream_t) hip_stream, stats, nullptr, direct);
+}
+
+extern "C" int msk_gpu_render_direct(msk_scene *scene, const msk_render_params *params, const msk_direct_params *direct,
+                                     float *film_xyzaw, msk_stats *stats) {
+    if (!scene || !film_xyzaw) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_render_direct: NULL argument");
+    MSK_REFUSE_LOST(scene->ctx);
+    msk_render_params p;
+    if (int rc = check_direct(scene, params, direct, "msk_gpu_render_direct", &p)) return rc;
+    msk_ctx *ctx = scene->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!scene->ws) scene->ws = new Workspace();
+    DevBuf &film = scene->ws->film;
+    const size_t bytes = (size_t) scene->dev.crop_w * scene->dev.crop_h * 5 * 4;
+    HIP_TRY(ctx, film.reserve(bytes));
+    if (int rc = render_impl(scene, &p, film.as<float>(), nullptr, stats, nullptr, direct)) return rc;
+    return film_to_host(ctx, ctx->stream, film.p, film_xyzaw, bytes, &scene->ws->host_film, &scene->ws->host_film_bytes);
+}
+
+extern "C" int msk_gpu_sample_pixels_direct(msk_scene *scene, const msk_render_params *params, const msk_direct_params *direct,
+                                            uint64_t n_pixels, const int32_t *pixels, float *out_xyz, float *out_pos) {
+    if (!scene || !pixels || !out_xyz) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_sample_pixels_direct: NULL argument");
+    MSK_REFUSE_LOST(scene->ctx);
+    msk_render_params p;
+    if (int rc = check_direct(scene, params, direct, "msk_gpu_sample_pixels_direct", &p)) return rc;
+    return sample_pixels_impl(scene, &p, n_pixels, pixels, out_xyz, out_pos, direct);
 }
 
 static int trace_batch(msk_scene *scene, uint64_t n, const float *rays, float *out_hit, uint8_t *out_any) {

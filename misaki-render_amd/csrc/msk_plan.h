@@ -351,6 +351,68 @@ inline LaunchPlan make_launch_plan(const SceneFacts &sc, const CallFacts &call, 
     return p;
 }
 
+// ---- the "direct" integrator (msk_direct.h: k_direct<form>) -------------------------------------------------------------------------
+// One lane owns one camera sample through its 1 + N + M rays, a wave owns `records_per_wave` consecutive records of the pass, a
+// launch `records_per_launch` of them.  The form follows the scene's tree: the binary tree staged in LDS beside the shading tables,
+// the half-float 4-wide tree in HBM (the default for a tree that stays there), or — every other trace mode — the binary tree in
+// HBM, which every scene has (as k_path_serial walks it).  The tables a block stages are the scene's own placement (all of them,
+// the small ones, or none) unless they do not fit beside the tree and the stacks: then they are read from HBM / L2.
+constexpr uint32_t kDirectMaxSamples = 4096;                       // light_samples and bsdf_samples, each
+constexpr uint64_t kDirectRaysPerLaunch = 1ull << 26;              // a launch traces about this many rays ...
+constexpr uint64_t kDirectMinWaves = 2048;                         // ... but is never cut below two waves per SIMD of 256 CUs
+constexpr uint32_t kDirectWavesPerLaunch = 8192;                   // records_per_wave aims at this many waves per launch,
+constexpr uint32_t kDirectMaxRecordsPerWave = 1024;                // within [MSK_WAVE, this]
+struct DirectPlan {
+    int form = TRACE_BIN_LDS;          // k_direct's MODE: TRACE_BIN_LDS, TRACE_WIDE4_HALF or TRACE_BIN_HBM
+    uint32_t tables_mode = 0;          // what a block stages: 0 nothing, 1 the small tables, 2 all tables
+    uint32_t stack_f4 = 0;             // float4 offset of the traversal stacks in the block's LDS (behind the staged tables)
+    uint32_t stack_entries = 0;        // of a lane's stack in LDS ...
+    uint32_t ovf_entries = 0;          // ... and in the HBM overflow array (LaneStack)
+    size_t lds_bytes = 0;
+    uint32_t rays_per_sample = 0;      // 1 + N + M: the most a sample can trace
+    uint32_t records_per_wave = MSK_WAVE;
+    uint64_t records_per_launch = 0;   // a multiple of records_per_wave
+    uint64_t n_launches = 0;           // of a pass of `pass_records` records
+    uint32_t grid_blocks(uint64_t records) const {
+        const uint64_t waves = (records + records_per_wave - 1) / records_per_wave;
+        return (uint32_t) ((waves + kWavesPerBlock - 1) / kWavesPerBlock);
+    }
+};
+// dev_stack_entries / dev_stack_total: DeviceScene's, of the tree the scene's trace mode walks; bvh_depth: the binary tree's
+inline DirectPlan make_direct_plan(const SceneFacts &sc, uint32_t dev_stack_entries, uint32_t dev_stack_total, int bvh_depth,
+                                   uint32_t light_samples, uint32_t bsdf_samples, uint64_t pass_records) {
+    DirectPlan p;
+    size_t staged = sc.shade_lds_bytes >= kDoneQueueBytes ? sc.shade_lds_bytes - kDoneQueueBytes : 0;
+    size_t trace_bytes;
+    if (sc.trace_mode == TRACE_BIN_LDS) {
+        p.form = TRACE_BIN_LDS;
+        p.stack_entries = dev_stack_entries; p.ovf_entries = 0;
+        trace_bytes = sc.trace_lds_bytes;                                       // the whole stack + tree + triangles
+    } else {
+        uint32_t total = dev_stack_total;
+        p.form = TRACE_WIDE4_HALF; p.stack_entries = dev_stack_entries;
+        if (sc.trace_mode != TRACE_WIDE4_HALF) {                                // the binary tree in HBM: depth + 2 entries
+            p.form = TRACE_BIN_HBM;
+            total = (uint32_t) bvh_depth + 2u;
+            p.stack_entries = std::max(4u, std::min(dev_stack_entries, (total + 3u) & ~3u));
+        }
+        p.ovf_entries = total > p.stack_entries ? total - p.stack_entries : 0u;
+        trace_bytes = (size_t) p.stack_entries * MSK_BLOCK * 4 + (size_t) MSK_BLOCK * 16;      // + four words per lane (node4h_step)
+    }
+    if (staged + trace_bytes > kLdsLimit) staged = 0;
+    p.tables_mode = staged == 0 ? 0u : sc.lds_tables ? 2u : 1u;
+    p.stack_f4 = (uint32_t) (staged / 16);
+    p.lds_bytes = staged + trace_bytes;
+    p.rays_per_sample = 1u + light_samples + bsdf_samples;
+    uint64_t per_launch = std::max<uint64_t>(kDirectRaysPerLaunch / p.rays_per_sample, kDirectMinWaves * MSK_WAVE);
+    per_launch = std::min(per_launch, std::max<uint64_t>(pass_records, 1));
+    const uint64_t per_wave = ((per_launch + kDirectWavesPerLaunch - 1) / kDirectWavesPerLaunch + MSK_WAVE - 1) / MSK_WAVE * MSK_WAVE;
+    p.records_per_wave = (uint32_t) std::min<uint64_t>(kDirectMaxRecordsPerWave, std::max<uint64_t>(MSK_WAVE, per_wave));
+    p.records_per_launch = (per_launch + p.records_per_wave - 1) / p.records_per_wave * p.records_per_wave;
+    p.n_launches = (pass_records + p.records_per_launch - 1) / p.records_per_launch;
+    return p;
+}
+
 // The static, interleaved partition of a pass's samples over the regions (RegionCtl): chunks of 64 samples dealt round robin,
 // the last chunk partial.  The regions' initial records and what a part of the pool expects to finish both come from here.
 inline unsigned long long region_share(unsigned long long total, uint32_t n_regions, uint32_t r) {

@@ -9,6 +9,7 @@ void path_fill_params(const Integrator *integ, const Sensor *sensor, msk_render_
 bool path_last_stats(const Integrator *integ, msk_stats &st);
 std::vector<std::string> integrator_aov_names(const Integrator *integ);
 std::vector<int32_t> integrator_aov_types(const Integrator *integ);
+bool integrator_direct_params(const Integrator *integ, msk_direct_params &d);
 }
 using namespace misaki;
 
@@ -121,6 +122,12 @@ int msk_host_aov_types(msk_host_scene *h, int32_t *out, size_t cap) {
         std::copy(t.begin(), t.end(), out);
         return (int) t.size();
     } catch (const std::exception &e) { return fail(e); }
+}
+
+// the sample counts of the scene's "direct" integrator: 1 and *out filled, 0 when the integrator is another one
+int msk_host_direct_params(msk_host_scene *h, msk_direct_params *out) {
+    try { return integrator_direct_params(h->scene->integrator(), *out) ? 1 : 0; }
+    catch (const std::exception &e) { return fail(e); }
 }
 
 int msk_host_film_size(msk_host_scene *h, int *w, int *hgt, int *spp) {

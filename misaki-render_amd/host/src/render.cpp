@@ -1114,6 +1114,38 @@ static std::vector<int> parse_gpu_devices(const std::string &list, int single) {
     return ids;
 }
 
+// What the render() of "path" and of "direct" share (integrator.cpp:31-80 with the per-sample work on the MI355X): flatten the
+// scene, make the context on first use, create the device scene, run the integrator's own call into a block of the film's crop
+// window, put it, log.  fill(params) sets the integrator's msk_render_params; call(scene, params, film, stats) is its C-ABI call.
+template <class Fill, class Call>
+static msk_stats render_on_gpu(Scene *scene, Sensor *sensor, std::vector<int> &devices, msk_ctx *&ctx, Fill &&fill, Call &&call) {
+    ref<Film> film = sensor->film();
+    const Vector2i size = film->size();
+    film->prepare({"X", "Y", "Z", "A", "W"});
+    Log(Info, "Starting render job ({}x{}, {} sample)", size.x, size.y, sensor->sampler()->sample_count());
+    auto t0 = std::chrono::steady_clock::now();
+    FlatScene flat;
+    flatten_scene(scene, sensor, flat);
+    fill(flat.params);
+    if (!ctx && msk_gpu_init(devices.data(), (int) devices.size(), &ctx) != MSK_OK) Throw("{}", msk_gpu_last_error(nullptr));
+    msk_scene *gs = nullptr;
+    if (msk_gpu_scene_create_ext(ctx, &flat.desc, flat.ext_ptr(), &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(ctx));
+    ref<ImageBlock> whole = new ImageBlock(film->crop_size(), 5);        // the crop window (the whole film by default), as the storage holds it
+    whole->set_offset(film->crop_offset());
+    msk_stats st;
+    const int rc = call(gs, flat.params, whole->data().data(), &st);
+    msk_gpu_scene_destroy(gs);
+    if (rc != MSK_OK) Throw("{}", msk_gpu_last_error(ctx));
+    film->put(whole);
+    // ImageBlock::put logs every such sample as it arrives (imageblock.cpp:57-81); the samples are splatted on the device, so
+    // the plugin reports how many there were
+    if (st.invalid_samples) Log(Warn, "Invalid sample value: {} of {} samples were negative or not finite", st.invalid_samples, st.samples);
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    Log(Info, "Rendering finished. (took {}s, device {} ms, {} Msamples/s)", secs, st.ms_total,
+        st.ms_total > 0 ? st.samples / (st.ms_total * 1e3) : 0.0);
+    return st;
+}
+
 // =========================================================================== the "path" integrator
 // integrators/path.cpp:19-21,133-140 — same plugin name and properties; render() runs on the MI355X.
 class PathTracer final : public MonteCarloIntegrator {
@@ -1150,31 +1182,8 @@ public:
     }
 
     bool render(Scene *scene, Sensor *sensor) override {           // integrator.cpp:31-80
-        ref<Film> film = sensor->film();
-        const Vector2i size = film->size();
-        film->prepare({"X", "Y", "Z", "A", "W"});
-        Log(Info, "Starting render job ({}x{}, {} sample)", size.x, size.y, sensor->sampler()->sample_count());
-        auto t0 = std::chrono::steady_clock::now();
-        FlatScene flat;
-        flatten_scene(scene, sensor, flat);
-        fill_params(sensor, flat.params);
-        if (!m_ctx && msk_gpu_init(m_devices.data(), (int) m_devices.size(), &m_ctx) != MSK_OK) Throw("{}", msk_gpu_last_error(nullptr));
-        msk_scene *gs = nullptr;
-        if (msk_gpu_scene_create_ext(m_ctx, &flat.desc, flat.ext_ptr(), &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(m_ctx));
-        ref<ImageBlock> whole = new ImageBlock(film->crop_size(), 5);        // the crop window (the whole film by default), as the storage holds it
-        whole->set_offset(film->crop_offset());
-        msk_stats st;
-        const int rc = msk_gpu_render(gs, &flat.params, whole->data().data(), &st);
-        msk_gpu_scene_destroy(gs);
-        if (rc != MSK_OK) Throw("{}", msk_gpu_last_error(m_ctx));
-        film->put(whole);
-        m_last_stats = st;
-        // ImageBlock::put logs every such sample as it arrives (imageblock.cpp:57-81); the samples are splatted on the device, so
-        // the plugin reports how many there were
-        if (st.invalid_samples) Log(Warn, "Invalid sample value: {} of {} samples were negative or not finite", st.invalid_samples, st.samples);
-        const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        Log(Info, "Rendering finished. (took {}s, device {} ms, {} Msamples/s)", secs, st.ms_total,
-            st.ms_total > 0 ? st.samples / (st.ms_total * 1e3) : 0.0);
+        m_last_stats = render_on_gpu(scene, sensor, m_devices, m_ctx, [&](msk_render_params &p) { fill_params(sensor, p); },
+                                     [](msk_scene *gs, const msk_render_params &p, float *film, msk_stats *st) { return msk_gpu_render(gs, &p, film, st); });
         return true;
     }
     const msk_stats &last_stats() const { return m_last_stats; }
@@ -1189,6 +1198,56 @@ private:
 };
 MSK_IMPLEMENT_CLASS(PathTracer, MonteCarloIntegrator)
 MSK_REGISTER_INSTANCE(PathTracer, "path")
+
+// =========================================================================== the "direct" integrator
+// integrators/direct.cpp — same plugin name and properties (light_samples, bsdf_samples); render() runs k_direct on the MI355X
+// (include/msk_gpu.h: msk_direct_params has the semantics, DESIGN.md section 9 the departures from direct.cpp).
+class DirectIntegrator final : public SamplingIntegrator {
+public:
+    DirectIntegrator(const Properties &props) : SamplingIntegrator(props) {
+        m_device = props.int_("gpu_device", 0);
+        m_devices = parse_gpu_devices(props.string("gpu_devices", ""), m_device);
+        if (m_devices.size() > 1)
+            Throw("\"gpu_devices\": the \"direct\" integrator renders on one device (got {}); run one process per GPU and shard the samples", m_devices.size());
+        m_honor = props.bool_("honor_properties", false);
+        const int n = props.int_("light_samples", 1), m = props.int_("bsdf_samples", 1);
+        if (n < 0) Throw("\"light_samples\" must be >= 0 (got {})", n);
+        if (m < 0) Throw("\"bsdf_samples\" must be >= 0 (got {})", m);
+        if (n > 4096) Throw("\"light_samples\" must be at most 4096 (got {})", n);
+        if (m > 4096) Throw("\"bsdf_samples\" must be at most 4096 (got {})", m);
+        if (n == 0 && m == 0) Throw("\"light_samples\" and \"bsdf_samples\" must not both be 0");
+        m_direct.light_samples = (uint32_t) n; m_direct.bsdf_samples = (uint32_t) m;
+    }
+    ~DirectIntegrator() { if (m_ctx) msk_gpu_shutdown(m_ctx); }
+
+    void fill_params(const Sensor *sensor, msk_render_params &p) const {
+        std::memset(&p, 0, sizeof p);
+        p.spp = (uint32_t) sensor->sampler()->sample_count();
+        p.seed = sensor->sampler()->base_seed();
+        p.rng_mode = MSK_RNG_COUNTER;
+        p.rr_depth = 5; p.max_depth = -1;                          // (ignored by msk_gpu_render_direct)
+        p.hide_emitters = m_honor ? (m_hide_emitters ? 1 : 0) : 0; // the plugin convention of "path"
+        p.block_size = (int32_t) m_block_size;
+        p.block_first = 0; p.block_stride = 1; p.sample_first = 0; p.sample_stride = 1;
+    }
+    bool render(Scene *scene, Sensor *sensor) override {
+        m_last_stats = render_on_gpu(scene, sensor, m_devices, m_ctx, [&](msk_render_params &p) { fill_params(sensor, p); },
+                                     [&](msk_scene *gs, const msk_render_params &p, float *film, msk_stats *st) { return msk_gpu_render_direct(gs, &p, &m_direct, film, st); });
+        return true;
+    }
+    const msk_stats &last_stats() const { return m_last_stats; }
+    const msk_direct_params &direct_params() const { return m_direct; }
+    MSK_DECLARE_CLASS()
+private:
+    int m_device = 0;
+    std::vector<int> m_devices;
+    bool m_honor = false;
+    msk_direct_params m_direct{1, 1};
+    msk_ctx *m_ctx = nullptr;
+    msk_stats m_last_stats{};
+};
+MSK_IMPLEMENT_CLASS(DirectIntegrator, SamplingIntegrator)
+MSK_REGISTER_INSTANCE(DirectIntegrator, "direct")
 
 // integrators/aov.cpp:19-144 — same plugin name, "aovs" string and nested-integrator convention; render() runs the
 // primary-hit channels and the nested path integrator on the MI355X in one job.
@@ -1291,13 +1350,21 @@ std::vector<std::string> integrator_aov_names(const Integrator *integ) {
 // used by capi.cpp
 void path_fill_params(const Integrator *integ, const Sensor *sensor, msk_render_params &p) {
     if (auto *av = dynamic_cast<const AOVIntegrator *>(integ)) { av->fill_params(sensor, p); return; }
+    if (auto *di = dynamic_cast<const DirectIntegrator *>(integ)) { di->fill_params(sensor, p); return; }
     auto *pt = dynamic_cast<const PathTracer *>(integ);
-    if (!pt) Throw("the scene's integrator is not a GPU integrator (\"path\" or \"aov\")");
+    if (!pt) Throw("the scene's integrator is not a GPU integrator (\"path\", \"direct\" or \"aov\")");
     pt->fill_params(sensor, p);
+}
+// the sample counts of a "direct" integrator; false for any other
+bool integrator_direct_params(const Integrator *integ, msk_direct_params &d) {
+    auto *di = dynamic_cast<const DirectIntegrator *>(integ);
+    if (di) d = di->direct_params();
+    return di != nullptr;
 }
 bool path_last_stats(const Integrator *integ, msk_stats &st) {
     if (auto *pt = dynamic_cast<const PathTracer *>(integ)) { st = pt->last_stats(); return true; }
     if (auto *av = dynamic_cast<const AOVIntegrator *>(integ)) { st = av->last_stats(); return true; }
+    if (auto *di = dynamic_cast<const DirectIntegrator *>(integ)) { st = di->last_stats(); return true; }
     return false;
 }
 

@@ -35,6 +35,7 @@ def load():
         lib.msk_host_film_crop.argtypes = [vp, C.POINTER(C.c_int * 4)]
         lib.msk_host_aov_names.argtypes = [vp, C.c_char_p, C.c_size_t]
         lib.msk_host_aov_types.argtypes = [vp, vp, C.c_size_t]
+        lib.msk_host_direct_params.argtypes = [vp, C.POINTER(abi.DirectParams)]
         lib.msk_host_srgb_model_fetch.argtypes = [vp, vp]
         lib.msk_host_rgb2spec_build.argtypes = [C.c_int, C.c_char_p, C.c_int]
         lib.msk_host_srgb_model_source.argtypes = [C.c_char_p, C.c_size_t]
@@ -105,6 +106,14 @@ class HostScene:
         if n < 0:
             _check(n)
         return [int(x) for x in buf[:n]]
+
+    def direct_params(self):
+        """(light_samples, bsdf_samples) of the scene's "direct" integrator, or None when the integrator is another one."""
+        d = abi.DirectParams()
+        rc = self.lib.msk_host_direct_params(self.h, C.byref(d))
+        if rc < 0:
+            _check(rc)
+        return (int(d.light_samples), int(d.bsdf_samples)) if rc == 1 else None
 
     def render(self, develop_to=None):
         """scene->integrator()->render(scene, sensor) on the GPU -> (film[H,W,5+C], image[H,W,4+C], Stats), H x W the film's crop window;

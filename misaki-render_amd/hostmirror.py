@@ -303,15 +303,57 @@ def _bsdf_xml(m, v3, directory=None):
     return ['        ' + b for b in inner]
 
 
+DIRECT_MAX_SAMPLES = 4096
+
+
+def direct_integrator(props=None):
+    """The constructor of the host library's `"direct"` plugin (host/src/render.cpp: DirectIntegrator), property for property and
+    refusal for refusal (the same words): props -> {"light_samples", "bsdf_samples", "gpu_device", "honor_properties",
+    "block_size", "hide_emitters"} with the plugin's defaults filled in (a property the plugin does not read is ignored, as the
+    plugin ignores it).  Raises ValueError where the plugin throws."""
+    props = dict(props or {})
+    devices = [t for t in str(props.get("gpu_devices", "")).replace(",", " ").split() if t]
+    if len(devices) > 1:
+        raise ValueError('"gpu_devices": the "direct" integrator renders on one device (got %d); run one process per GPU and shard the samples' % len(devices))
+    n, m = int(props.get("light_samples", 1)), int(props.get("bsdf_samples", 1))
+    if n < 0:
+        raise ValueError('"light_samples" must be >= 0 (got %d)' % n)
+    if m < 0:
+        raise ValueError('"bsdf_samples" must be >= 0 (got %d)' % m)
+    if n > DIRECT_MAX_SAMPLES:
+        raise ValueError('"light_samples" must be at most 4096 (got %d)' % n)
+    if m > DIRECT_MAX_SAMPLES:
+        raise ValueError('"bsdf_samples" must be at most 4096 (got %d)' % m)
+    if n == 0 and m == 0:
+        raise ValueError('"light_samples" and "bsdf_samples" must not both be 0')
+    as_bool = lambda v: v if isinstance(v, bool) else str(v).lower() == "true"
+    return {"light_samples": n, "bsdf_samples": m, "gpu_device": int(devices[0]) if devices else int(props.get("gpu_device", 0)),
+            "honor_properties": as_bool(props.get("honor_properties", False)), "block_size": int(props.get("block_size", 32)),
+            "hide_emitters": as_bool(props.get("hide_emitters", False))}
+
+
+def read_integrator(xml_path):
+    """The <integrator> element of a scene XML -> (plugin name, its properties as the plugin's constructor settles them).  "direct"
+    goes through direct_integrator (and its refusals); any other integrator's properties are returned as written."""
+    import xml.etree.ElementTree as ET
+    node = ET.parse(str(xml_path)).getroot().find("integrator")
+    if node is None:
+        raise ValueError("the scene has no integrator")
+    conv = {"integer": int, "boolean": lambda v: v.lower() == "true", "string": str, "float": float}
+    props = {c.get("name"): conv[c.tag](c.get("value")) for c in node if c.tag in conv}
+    kind = node.get("type")
+    return kind, (direct_integrator(props) if kind == "direct" else props)
+
+
 def write_scene_xml(meshes, directory, width, height, spp, camera=None, integrator_props=None, film_type="hdrfilm",
-                    filename="scene.xml", env=None, film_props=None, points=()):
+                    filename="scene.xml", env=None, film_props=None, points=(), integrator_type="path"):
     """Writes <directory>/meshes/*.obj and a Mitsuba-style scene XML the C++ host (and the reference's
     loader) understands; same structure as results/Figure_1_Pathtrace/scene.xml, $-parameters for spp/size."""
     camera = camera or CBOX_CAMERA
     os.makedirs(os.path.join(directory, "meshes"), exist_ok=True)
     v3 = lambda v: ", ".join("%.9g" % float(x) for x in v)
     out = ['<scene>', '    <default name="spp" value="%d"/>' % spp, '    <default name="width" value="%d"/>' % width,
-           '    <default name="height" value="%d"/>' % height, '    <integrator type="path">']
+           '    <default name="height" value="%d"/>' % height, '    <integrator type="%s">' % integrator_type]
     for k, val in (integrator_props or {}).items():
         tag = "boolean" if isinstance(val, bool) else "string" if isinstance(val, str) else "integer"
         out.append('        <%s name="%s" value="%s"/>' % (tag, k, str(val).lower()))
