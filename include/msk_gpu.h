@@ -305,6 +305,54 @@ typedef struct msk_scene_ext {
     const msk_point_desc *points;
 } msk_scene_ext;
 
+/*
+ * The `mask` BSDF (bsdfs/mask.cpp): an opacity cutout with a null lobe, as a decoration of ONE entry of msk_scene_desc.bsdfs (at most
+ * one msk_mask_desc per entry).  Let a be the opacity at the hit's uv, a scalar in [0, 1], and X the nested BSDF: the entry itself
+ * with its back_bsdf flip.  The opacity read is always that of the entry the mesh names, taken before the twosided flip.
+ * Everything below is fp32, one operation at a time, IEEE division, no contraction.
+ *
+ * Opacity.  filter 0: the constant `opacity`.  filter 1 / 2: an image of width x height scalars (row-major, `values`), looked up as
+ * MSK_TEXTURE_BITMAP_NEAREST / MSK_TEXTURE_BITMAP look their texels up, word for word (msk_texture_desc: to_uv, repeat wrap, the
+ * bilinear v = a0 + t (a1 - a0) on the values), the scalar standing where S(texel, l) stands.  An image of equal values is therefore
+ * the constant, to the bit.  A value (or the constant) outside [0, 1] or not finite is refused at scene creation.
+ *
+ * sample(sample1, u): the lobe is picked by u.x (mask.cpp:43-44), not by sample1.  u.x < a: u.x = u.x / a, then X.sample(sample1, u)
+ * with pdf = a * pdf_X and X's value.  Otherwise the null lobe: the continuation ray has the incoming ray's own world direction, bit
+ * for bit (no frame round trip: interpolated shading frames are not orthonormal), pdf = 1 - a, value 1, eta = 1, and the lobe is
+ * delta.  The null lobe is taken on either face: it does not see the cos_i <= 0 failure of a one-sided X.  a = 0 never samples X;
+ * a = 1 never samples the null lobe, and there u.x / 1 and 1 * pdf are exact: the decorated entry is X to the bit.
+ * eval = a * eval_X, pdf = a * pdf_X.
+ *
+ * Integrator ("path").  The next-event sample is taken iff X has a smooth lobe (path.cpp:56: flags, not the sampled lobe).  "The
+ * last bounce was delta" (emitter density 0, MIS weight 1) holds when the null lobe was taken or X is delta.  Shadow rays are
+ * unchanged: as in the reference (scene.cpp:91-95) a masked surface is opaque to them, and light through a cutout arrives by the
+ * BSDF sample alone, with weight mis_weight(1 - a, 0) = 1.  A null bounce counts a depth and takes Russian roulette like any other;
+ * the random numbers of a bounce are every BSDF's.  `scattered` (path.cpp:31,73) is false at the camera and true after any non-null
+ * sample; under hide_emitters an emitter reached while it is still false adds nothing — the environment (path.cpp:92-93) and,
+ * unlike path.cpp:82-88, an area emitter too.  A `constant` sky counts with the density of the ray's own direction, as in every
+ * scene that runs the kernels of msk_point_desc.
+ * Not kept from mask.cpp as written (departures 6-8): mask.cpp:47,53,68 multiplies the nested value by the
+ * opacity AND returns the nested pdf unscaled (the nested lobe then carries a^2); the opacity is a scalar (the hosts reduce a colour
+ * to 0.212671 r + 0.715160 g + 0.072169 b); the area emitter behind a cutout under hide_emitters.
+ * "aov" renders see a masked surface as a surface: the primary-hit channels are those of the first hit, whatever its opacity.
+ * The "direct" integrator refuses a scene that holds a mask (MSK_ERR_UNSUPPORTED): a cutout would be a black hole in it.
+ */
+typedef struct msk_mask_desc {
+    uint32_t bsdf;           /* index into msk_scene_desc.bsdfs: the decorated entry                 */
+    float    opacity;        /* filter 0: the constant, in [0, 1]                                    */
+    int32_t  filter;         /* 0 constant, 1 nearest, 2 bilinear                                    */
+    float    to_uv[6];       /* filter 1 / 2: row-major 2 x 3, as msk_texture_desc::to_uv            */
+    uint32_t width, height;  /* filter 1 / 2: at least 1 x 1                                         */
+    const float *values;     /* filter 1 / 2: width * height scalars in [0, 1], row 0 first          */
+} msk_mask_desc;
+
+/* msk_scene_ext is passed by pointer without a size and cannot grow in place: what a scene holds beyond it wraps it. */
+typedef struct msk_scene_masks {
+    msk_scene_ext ext;       /* the envmap emitter's image and the point emitters' positions, as above */
+    uint32_t n_masks;        /* may be 0, masks then unused                                            */
+    const msk_mask_desc *masks;
+} msk_scene_masks;
+
 /* PerspectiveCamera (sensors/perspective.cpp:8-42); matrices are row-major 4x4. */
 typedef struct msk_camera_desc {
     float sample_to_camera[16];  /* m_sample_to_camera, sample space in PIXELS */
@@ -450,6 +498,12 @@ int  msk_gpu_scene_create_env(msk_ctx *ctx, const msk_scene_desc *desc, const ms
    without its msk_point_desc, with two of them, an msk_point_desc whose emitter is of another type (or out of range), a position
    that is not finite, a point emitter whose mesh_id is not -1.  A group context passes the extension to every member. */
 int  msk_gpu_scene_create_ext(msk_ctx *ctx, const msk_scene_desc *desc, const msk_scene_ext *ext, msk_scene **out_scene);
+/* The same with everything msk_scene_masks holds: msk_gpu_scene_create_ext(c, d, e, o) is msk_gpu_scene_create_masks(c, d, &{*e, 0, NULL}, o)
+   and em == NULL is no extension at all.  MSK_ERR_INVALID_ARG, with a message that names the mask: an msk_mask_desc whose bsdf is
+   out of range, two of them on one entry, a constant or a value outside [0, 1] or not finite, a filter outside 0..2, an image of
+   zero width or height (or without values).  A scene that holds a mask runs kernels of its own (k_shade_gen_m, ...), whatever else
+   it holds.  A group context passes the extension to every member. */
+int  msk_gpu_scene_create_masks(msk_ctx *ctx, const msk_scene_desc *desc, const msk_scene_masks *em, msk_scene **out_scene);
 void msk_gpu_scene_destroy(msk_scene *scene);
 
 /* ---- the hot path --------------------------------------------------------- */
@@ -532,6 +586,19 @@ int  msk_gpu_env_sample(msk_scene *scene, uint64_t n, const float *u, float *out
  */
 int  msk_gpu_point_sample(msk_scene *scene, uint32_t emitter, uint64_t n, const float *ref_points, const float *wavelengths, float *out_d_dist, float *out_value);
 int  msk_gpu_conductor_sample(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *cos_theta_i, const float *wavelengths, float *out_value);
+
+/*
+ * The decorated BSDF entry `bsdf` of a scene that holds a mask (msk_mask_desc; an entry without one has the constant opacity 1), at n
+ * points, through the device functions the shading kernels call.  uv n * 2, wi n * 3 (local frame, either face), wavelengths n * 4.
+ * msk_gpu_mask_sample: sample1_u n * 3 = {sample1, u.x, u.y}; out_wo_pdf n * 4 = {wo.x, wo.y, wo.z, pdf} (the null lobe: wo = -wi,
+ * the local form of "the ray's own direction"), out_value n * 4, out_flags n * 4 = {eta, delta (1 / 0), null lobe (1 / 0), a
+ * direction was produced (1 / 0)}.  msk_gpu_mask_eval: wo n * 3; out_a_pdf n * 2 = {a, pdf}, out_value n * 4 = eval.
+ * Host pointers; MSK_ERR_INVALID_ARG for a scene without a mask or an entry out of range.
+ */
+int  msk_gpu_mask_sample(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *sample1_u, const float *wavelengths,
+                         float *out_wo_pdf, float *out_value, float *out_flags);
+int  msk_gpu_mask_eval(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *wo, const float *wavelengths,
+                       float *out_a_pdf, float *out_value);
 
 /* ---- the "direct" integrator ----------------------------------------------- */
 /*

@@ -75,6 +75,16 @@ class SceneExt(C.Structure):
     _fields_ = [("envmap", C.POINTER(EnvmapDesc)), ("n_points", C.c_uint32), ("points", C.POINTER(PointDesc))]
 
 
+class MaskDesc(C.Structure):
+    """msk_mask_desc: the `mask` decoration of one BSDF entry.  filter 0: the constant `opacity`; 1 / 2: a nearest / bilinear image"""
+    _fields_ = [("bsdf", C.c_uint32), ("opacity", C.c_float), ("filter", C.c_int32), ("to_uv", C.c_float * 6),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("values", C.POINTER(C.c_float))]      # width * height scalars in [0, 1]
+
+
+class SceneMasks(C.Structure):
+    _fields_ = [("ext", SceneExt), ("n_masks", C.c_uint32), ("masks", C.POINTER(MaskDesc))]
+
+
 class CameraDesc(C.Structure):
     _fields_ = [("sample_to_camera", C.c_float * 16), ("to_world", C.c_float * 16),
                 ("near_clip", C.c_float), ("far_clip", C.c_float)]
@@ -150,6 +160,7 @@ EXPORTS = ["msk_gpu_init", "msk_gpu_shutdown", "msk_gpu_last_error", "msk_gpu_sc
            "msk_gpu_trace_any", "msk_gpu_sample_pixels", "msk_gpu_describe", "msk_gpu_render_aov", "msk_gpu_aov_channels",
            "msk_gpu_eval_texture", "msk_gpu_scene_create_env", "msk_gpu_env_eval", "msk_gpu_env_sample",
            "msk_gpu_scene_create_ext", "msk_gpu_point_sample", "msk_gpu_conductor_sample",
+           "msk_gpu_scene_create_masks", "msk_gpu_mask_sample", "msk_gpu_mask_eval",
            "msk_gpu_render_direct", "msk_gpu_render_direct_device", "msk_gpu_sample_pixels_direct"]
 
 # integrators/aov.cpp:21-28
@@ -209,6 +220,12 @@ def load_library(path=None):
     lib.msk_gpu_point_sample.restype = C.c_int
     lib.msk_gpu_conductor_sample.argtypes = [vp, C.c_uint32, u64, vp, vp, vp]
     lib.msk_gpu_conductor_sample.restype = C.c_int
+    lib.msk_gpu_scene_create_masks.argtypes = [vp, C.POINTER(SceneDesc), C.POINTER(SceneMasks), C.POINTER(vp)]
+    lib.msk_gpu_scene_create_masks.restype = C.c_int
+    lib.msk_gpu_mask_sample.argtypes = [vp, C.c_uint32, u64, vp, vp, vp, vp, vp, vp, vp]
+    lib.msk_gpu_mask_sample.restype = C.c_int
+    lib.msk_gpu_mask_eval.argtypes = [vp, C.c_uint32, u64, vp, vp, vp, vp, vp, vp]
+    lib.msk_gpu_mask_eval.restype = C.c_int
     lib.msk_gpu_render_direct.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(DirectParams), vp, C.POINTER(Stats)]
     lib.msk_gpu_render_direct.restype = C.c_int
     lib.msk_gpu_render_direct_device.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(DirectParams), vp, vp, C.POINTER(Stats)]
@@ -267,11 +284,13 @@ class Context:
 class Scene:
     """msk_scene: geometry + BVH + light tables resident in HBM."""
 
-    def __init__(self, ctx, flat, envmap=None, points=None):
+    def __init__(self, ctx, flat, envmap=None, points=None, masks=None):
         """flat: hostmirror.FlatScene (keeps the numpy arrays the desc points into alive).  envmap: the EnvmapDesc of the scene's
         MSK_EMITTER_ENVMAP emitter; by default the one the flattener made (flat.envmap), if any.  points: the PointDesc array of
         its MSK_EMITTER_POINT emitters (a ctypes array or a list); by default flat.points.  A scene with points is created
-        through msk_gpu_scene_create_ext, one with an image alone through _create_env, any other through msk_gpu_scene_create."""
+        through msk_gpu_scene_create_ext, one with an image alone through _create_env, any other through msk_gpu_scene_create.
+        masks: the MaskDesc array of its `mask` BSDFs (a ctypes array or a list); by default flat.masks.  A scene with masks is
+        created through msk_gpu_scene_create_masks."""
         self.ctx, self.flat = ctx, flat
         self.handle = C.c_void_p()
         self.envmap = envmap if envmap is not None else getattr(flat, "envmap", None)
@@ -279,7 +298,15 @@ class Scene:
         if pts is not None and not isinstance(pts, C.Array):
             pts = (PointDesc * max(1, len(pts)))(*pts) if len(pts) else None
         self.points = pts if (pts is not None and len(pts)) else None
-        if self.points is not None:
+        mk = masks if masks is not None else getattr(flat, "masks", None)
+        if mk is not None and not isinstance(mk, C.Array):
+            mk = (MaskDesc * max(1, len(mk)))(*mk) if len(mk) else None
+        self.masks = mk if (mk is not None and len(mk)) else None
+        if self.masks is not None:
+            ext = SceneExt(C.pointer(self.envmap) if self.envmap is not None else None, len(self.points) if self.points is not None else 0, self.points)
+            self.em = SceneMasks(ext, len(self.masks), self.masks)
+            ctx.check(ctx.lib.msk_gpu_scene_create_masks(ctx.handle, C.byref(flat.desc), C.byref(self.em), C.byref(self.handle)))
+        elif self.points is not None:
             self.ext = SceneExt(C.pointer(self.envmap) if self.envmap is not None else None, len(self.points), self.points)
             ctx.check(ctx.lib.msk_gpu_scene_create_ext(ctx.handle, C.byref(flat.desc), C.byref(self.ext), C.byref(self.handle)))
         elif self.envmap is not None:
@@ -424,6 +451,33 @@ class Scene:
         val = np.empty((len(c), 4), np.float32)
         self.ctx.check(self.ctx.lib.msk_gpu_conductor_sample(self.handle, int(bsdf), len(c), _ptr(c), _ptr(wl), _ptr(val)))
         return val
+
+    def mask_sample(self, bsdf, uv, wi, sample1_u, wavelengths):
+        """sample() of the decorated BSDF entry `bsdf` of a scene that holds a mask: uv float32[n, 2], wi float32[n, 3] (local),
+        sample1_u float32[n, 3] = {sample1, u.x, u.y}, wavelengths float32[n, 4] -> ({wo, pdf} float32[n, 4], value float32[n, 4],
+        {eta, delta, null lobe, ok} float32[n, 4])."""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
+        su = np.ascontiguousarray(sample1_u, np.float32).reshape(-1, 3)
+        wl = np.ascontiguousarray(wavelengths, np.float32).reshape(-1, 4)
+        if not (len(uv) == len(wi) == len(su) == len(wl)):
+            raise ValueError("uv, wi, sample1_u and wavelengths must name the same number of points")
+        a, b, c = (np.empty((len(uv), 4), np.float32) for _ in range(3))
+        self.ctx.check(self.ctx.lib.msk_gpu_mask_sample(self.handle, int(bsdf), len(uv), _ptr(uv), _ptr(wi), _ptr(su), _ptr(wl), _ptr(a), _ptr(b), _ptr(c)))
+        return a, b, c
+
+    def mask_eval(self, bsdf, uv, wi, wo, wavelengths):
+        """The opacity, eval() and pdf() of the decorated BSDF entry `bsdf`: uv float32[n, 2], wi / wo float32[n, 3] (local),
+        wavelengths float32[n, 4] -> ({a, pdf} float32[n, 2], eval float32[n, 4])."""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
+        wo = np.ascontiguousarray(wo, np.float32).reshape(-1, 3)
+        wl = np.ascontiguousarray(wavelengths, np.float32).reshape(-1, 4)
+        if not (len(uv) == len(wi) == len(wo) == len(wl)):
+            raise ValueError("uv, wi, wo and wavelengths must name the same number of points")
+        a, v = np.empty((len(uv), 2), np.float32), np.empty((len(uv), 4), np.float32)
+        self.ctx.check(self.ctx.lib.msk_gpu_mask_eval(self.handle, int(bsdf), len(uv), _ptr(uv), _ptr(wi), _ptr(wo), _ptr(wl), _ptr(a), _ptr(v)))
+        return a, v
 
     def close(self):
         if self.handle:

@@ -237,7 +237,7 @@ static int upload_tables(msk_scene *s, const mskscene::HostTables &t, const mskb
     up(s->tri_verts, t.tv); up(s->tri_normals, t.tn); up(s->tri_uvs, t.tuv);
     up(s->bsdfs, t.bsdfs); up(s->emitters, t.emitters); up(s->emitter_d65, t.d65); up(s->cdf, t.cdf_all); up(s->cie, t.cie);
     up(s->emitter_grid, t.emitter_grid); up(s->spectra, t.spectra_pool);
-    if (t.has_bitmap || t.has_envmap) up(s->texels, t.texels);
+    if (t.has_bitmap || t.has_envmap || t.has_mask_image) up(s->texels, t.texels);
     if (e == hipSuccess) e = s->mesh_info.upload(t.mesh_info);
     if (e == hipSuccess && !host_tree)
         if ((e = s->nodes.alloc(n_faces * 64)) == hipSuccess && (e = s->tris.alloc(n_faces * 64)) == hipSuccess) e = s->tri_bounds.alloc(n_faces * 32);
@@ -305,7 +305,7 @@ static void fill_device_scene(msk_scene *s, const mskscene::HostTables &t, const
     ds.mesh_info = s->mesh_info.as<int4>(); ds.bsdfs = s->bsdfs.as<float4>(); ds.emitters = s->emitters.as<float4>();
     ds.emitter_d65 = s->emitter_d65.as<float>(); ds.cdf = s->cdf.as<float>(); ds.cie = s->cie.as<float>();
     ds.emitter_grid = s->emitter_grid.as<float4>(); ds.spectra = s->spectra.as<float>(); ds.n_spectra = d->n_regular_values;
-    ds.texels = (t.has_bitmap || t.has_envmap) ? s->texels.as<float4>() : nullptr;
+    ds.texels = (t.has_bitmap || t.has_envmap || t.has_mask_image) ? s->texels.as<float4>() : nullptr;
     ds.n_nodes = n_nodes; ds.n_tris = d->n_faces; ds.n_emitters = d->n_emitters;
     ds.n_meshes = d->n_meshes; ds.n_bsdfs = d->n_bsdfs; ds.n_bsdf_f4 = t.n_bsdf_f4; ds.cdf_len = (uint32_t) t.cdf_all.size();
     ds.root_ref = bvh.root_ref;
@@ -344,15 +344,21 @@ extern "C" int msk_gpu_scene_create_env(msk_ctx *ctx, const msk_scene_desc *d, c
     return msk_gpu_scene_create_ext(ctx, d, &ext, out);
 }
 extern "C" int msk_gpu_scene_create_ext(msk_ctx *ctx, const msk_scene_desc *d, const msk_scene_ext *ext, msk_scene **out) {
+    msk_scene_masks em = {{nullptr, 0u, nullptr}, 0u, nullptr};
+    if (ext) em.ext = *ext;
+    return msk_gpu_scene_create_masks(ctx, d, &em, out);
+}
+extern "C" int msk_gpu_scene_create_masks(msk_ctx *ctx, const msk_scene_desc *d, const msk_scene_masks *em, msk_scene **out) {
+    const msk_scene_ext *ext = em ? &em->ext : nullptr;
     if (!ctx || !d || !out) return fail(ctx, MSK_ERR_INVALID_ARG, "msk_gpu_scene_create: NULL argument");
     *out = nullptr;
     MSK_REFUSE_LOST(ctx);
-    if (ctx->group) return group_scene_create(ctx, d, ext, out);
+    if (ctx->group) return group_scene_create(ctx, d, em, out);
     const mskplan::SceneKnobs knobs = mskplan::read_scene_knobs();
     mskscene::HostTables t;
     {
         std::string msg;
-        if (int rc = mskscene::pack(d, ext, knobs.pad_scale, &t, &msg)) return fail(ctx, rc, "%s", msg.c_str());
+        if (int rc = mskscene::pack(d, ext, knobs.pad_scale, &t, &msg, em ? em->n_masks : 0u, em ? em->masks : nullptr)) return fail(ctx, rc, "%s", msg.c_str());
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
@@ -395,7 +401,7 @@ extern "C" int msk_gpu_scene_create_ext(msk_ctx *ctx, const msk_scene_desc *d, c
     f.trace_mode = tree.trace_mode; f.lds_scene = tree.lds_scene; f.trace_lds_bytes = tree.trace_lds_bytes;
     f.lds_tables = tables.lds_tables; f.shade_lds_bytes = tables.shade_lds_bytes;
     f.all_diffuse = t.all_diffuse; f.has_regular = t.has_regular; f.has_dielectric = t.has_dielectric; f.has_bitmap = t.has_bitmap;
-    f.has_envmap = t.has_envmap; f.has_delta = t.has_delta;
+    f.has_envmap = t.has_envmap; f.has_delta = t.has_delta; f.has_mask = t.has_mask;
     f.cull_ok = cb.on && t.env_emitter < 0;
     if (f.trace_lds_bytes > ctx->prop.sharedMemPerBlock)
         return fail(ctx, MSK_ERR_UNSUPPORTED, "BVH depth %d needs %zu B of traversal stack per block", bvh.max_depth, tree.binary_stack_bytes);
@@ -587,6 +593,7 @@ static void launch_shade_t(const msk_scene *sc, const mskplan::LaunchPlan &plan,
     case mskplan::SHADE_BITMAP: MSK_SHADE(k_shade_gen_b<LDS_TABLES>); break;
     case mskplan::SHADE_ENVMAP: MSK_SHADE(k_shade_gen_e<LDS_TABLES>); break;
     case mskplan::SHADE_DELTA: MSK_SHADE(k_shade_gen_p<LDS_TABLES>); break;
+    case mskplan::SHADE_MASK: MSK_SHADE(k_shade_gen_m<LDS_TABLES>); break;
     }
 #undef MSK_SHADE
 }
@@ -608,6 +615,7 @@ static void launch_fused(const msk_scene *sc, const mskplan::LaunchPlan &plan, d
     case mskplan::SHADE_BITMAP: MSK_FUSED(k_wavefront_h_b); break;
     case mskplan::SHADE_ENVMAP: MSK_FUSED(k_wavefront_h_e); break;
     case mskplan::SHADE_DELTA: MSK_FUSED(k_wavefront_h_p); break;
+    case mskplan::SHADE_MASK: MSK_FUSED(k_wavefront_h_m); break;
     }
     else switch (plan.shade_kind) {                   // everything in LDS (trace mode 0)
     case mskplan::SHADE_DIELECTRIC: MSK_FUSED(k_wavefront_d); break;
@@ -617,6 +625,7 @@ static void launch_fused(const msk_scene *sc, const mskplan::LaunchPlan &plan, d
     case mskplan::SHADE_BITMAP: MSK_FUSED(k_wavefront_b); break;
     case mskplan::SHADE_ENVMAP: MSK_FUSED(k_wavefront_e); break;
     case mskplan::SHADE_DELTA: MSK_FUSED(k_wavefront_p); break;
+    case mskplan::SHADE_MASK: MSK_FUSED(k_wavefront_m); break;
     }
 #undef MSK_FUSED
 }
@@ -1097,7 +1106,8 @@ static int render_serial(msk_scene *sc, const msk_render_params *prm, float *d_f
         sp.blocks = ws.blocks.as<BlockInfo>(); sp.n_blocks = (uint32_t) owned.size();
         sp.block_buf = ws.block_buf.as<float>(); sp.buf_stride = buf_stride;
         sp.stack_ovf = ovf.as<uint32_t>(); sp.counters = counters.as<unsigned long long>(); sp.per_wave = per_wave ? 1u : 0u;
-        if (sc->facts.has_delta) hipLaunchKernelGGL(k_path_serial_p, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
+        if (sc->facts.has_mask) hipLaunchKernelGGL(k_path_serial_m, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
+        else if (sc->facts.has_delta) hipLaunchKernelGGL(k_path_serial_p, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
         else if (sc->facts.has_envmap) hipLaunchKernelGGL(k_path_serial_e, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
         else if (sc->facts.has_bitmap) hipLaunchKernelGGL(k_path_serial_b, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
         else if (sc->facts.has_dielectric) hipLaunchKernelGGL(k_path_serial_d, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
@@ -1515,6 +1525,9 @@ static int check_direct(msk_scene *scene, const msk_render_params *prm, const ms
     if (ctx->group)
         return fail(ctx, MSK_ERR_UNSUPPORTED, "%s: group contexts (msk_gpu_init with n > 1) are not supported by the \"direct\" integrator; "
                     "run one process per GPU and shard the samples with sample_first / sample_stride", who);
+    if (scene->facts.has_mask)
+        return fail(ctx, MSK_ERR_UNSUPPORTED, "%s: the scene holds a `mask` BSDF, which the \"direct\" integrator does not support "
+                    "(a cutout would be a black hole in a one-bounce integrator; use \"path\")", who);
     if (prm->rng_mode == MSK_RNG_PCG_BLOCK)
         return fail(ctx, MSK_ERR_UNSUPPORTED, "%s: MSK_RNG_PCG_BLOCK is not supported by the \"direct\" integrator (it uses MSK_RNG_COUNTER)", who);
     if (d->light_samples > mskplan::kDirectMaxSamples)
@@ -1682,6 +1695,51 @@ extern "C" int msk_gpu_conductor_sample(msk_scene *scene, uint32_t bsdf, uint64_
     if (!scene || (n && (!cos_theta_i || !wavelengths || !out_value))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_conductor_sample: NULL argument");
     if (scene->ctx->group) { const int rc = delta_probe(scene->parts[0], "msk_gpu_conductor_sample", 1, bsdf, n, cos_theta_i, wavelengths, nullptr, out_value); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
     return delta_probe(scene, "msk_gpu_conductor_sample", 1, bsdf, n, cos_theta_i, wavelengths, nullptr, out_value);
+}
+
+// msk_gpu_mask_sample (eval == 0: in_b = {sample1, u.x, u.y}, three outputs) / msk_gpu_mask_eval (in_b = wo; out_a = n * 2 {a, pdf})
+static int mask_probe(msk_scene *scene, const char *who, uint32_t eval, uint32_t bsdf, uint64_t n, const float *uv, const float *in_a, const float *in_b,
+                      const float *wavelengths, float *out_a, float *out_b, float *out_c) {
+    msk_ctx *ctx = scene->ctx;
+    MSK_REFUSE_LOST(ctx);
+    if (!scene->facts.has_mask) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: the scene holds no mask", who);
+    if (bsdf >= scene->bsdf_types.size()) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: bsdf %u out of range (the scene has %zu)", who, bsdf, scene->bsdf_types.size());
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n == 0) return MSK_OK;
+    DevBuf d_uv, d_a, d_b, d_wl, o_a, o_b, o_c;
+    HIP_TRY(ctx, d_uv.alloc(n * 8)); HIP_TRY(ctx, d_a.alloc(n * 12)); HIP_TRY(ctx, d_b.alloc(n * 12)); HIP_TRY(ctx, d_wl.alloc(n * 16));
+    HIP_TRY(ctx, o_a.alloc(n * 16)); HIP_TRY(ctx, o_b.alloc(n * 16)); HIP_TRY(ctx, o_c.alloc(n * 16));
+    HIP_TRY(ctx, hipMemcpy(d_uv.p, uv, n * 8, hipMemcpyHostToDevice)); HIP_TRY(ctx, hipMemcpy(d_a.p, in_a, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(d_b.p, in_b, n * 12, hipMemcpyHostToDevice)); HIP_TRY(ctx, hipMemcpy(d_wl.p, wavelengths, n * 16, hipMemcpyHostToDevice));
+    const uint32_t grid = (uint32_t) std::min<uint64_t>((n + MSK_BLOCK - 1) / MSK_BLOCK, 4096);
+    hipLaunchKernelGGL(k_mask_probe, dim3(grid), dim3(MSK_BLOCK), 0, ctx->stream, scene->dev, eval, bsdf, n, d_uv.as<float>(), d_a.as<float>(), d_b.as<float>(),
+                       d_wl.as<float4>(), o_a.as<float4>(), o_b.as<float4>(), o_c.as<float4>());
+    HIP_TRY(ctx, hipGetLastError());
+    if (int rcw = ctx_sync(ctx, ctx->stream, "k_mask_probe")) { for (DevBuf *b : {&d_uv, &d_a, &d_b, &d_wl, &o_a, &o_b, &o_c}) b->leak(); return rcw; }
+    if (eval) {
+        std::vector<float> tmp(n * 4);
+        HIP_TRY(ctx, hipMemcpy(tmp.data(), o_a.p, n * 16, hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < n; ++i) { out_a[i * 2] = tmp[i * 4]; out_a[i * 2 + 1] = tmp[i * 4 + 1]; }
+    } else {
+        HIP_TRY(ctx, hipMemcpy(out_a, o_a.p, n * 16, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out_c, o_c.p, n * 16, hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(ctx, hipMemcpy(out_b, o_b.p, n * 16, hipMemcpyDeviceToHost));
+    return MSK_OK;
+}
+extern "C" int msk_gpu_mask_sample(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *sample1_u, const float *wavelengths,
+                                   float *out_wo_pdf, float *out_value, float *out_flags) {
+    if (!scene || (n && (!uv || !wi || !sample1_u || !wavelengths || !out_wo_pdf || !out_value || !out_flags)))
+        return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_mask_sample: NULL argument");
+    if (scene->ctx->group) { const int rc = mask_probe(scene->parts[0], "msk_gpu_mask_sample", 0, bsdf, n, uv, wi, sample1_u, wavelengths, out_wo_pdf, out_value, out_flags); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
+    return mask_probe(scene, "msk_gpu_mask_sample", 0, bsdf, n, uv, wi, sample1_u, wavelengths, out_wo_pdf, out_value, out_flags);
+}
+extern "C" int msk_gpu_mask_eval(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *wo, const float *wavelengths,
+                                 float *out_a_pdf, float *out_value) {
+    if (!scene || (n && (!uv || !wi || !wo || !wavelengths || !out_a_pdf || !out_value)))
+        return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_mask_eval: NULL argument");
+    if (scene->ctx->group) { const int rc = mask_probe(scene->parts[0], "msk_gpu_mask_eval", 1, bsdf, n, uv, wi, wo, wavelengths, out_a_pdf, out_value, nullptr); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
+    return mask_probe(scene, "msk_gpu_mask_eval", 1, bsdf, n, uv, wi, wo, wavelengths, out_a_pdf, out_value, nullptr);
 }
 
 extern "C" int msk_gpu_trace_closest(msk_scene *scene, uint64_t n, const float *rays, float *out_hit) {

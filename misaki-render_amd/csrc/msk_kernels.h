@@ -1419,13 +1419,19 @@ struct SceneTablesE : SceneTablesB {};
 // only into the instantiations that carry this type (k_shade_gen_p, k_wavefront_p, k_wavefront_h_p, k_path_serial_p).  In them the
 // environment emitter, if any, is the image OR the `constant` sky: the emitter's record says which (env_is_image).
 struct SceneTablesP : SceneTablesE {};
+// ... and of a scene that holds a `mask` (msk_gpu.h: msk_mask_desc), whatever else it holds: the opacity lookup, the null lobe, the
+// per-sample delta mark and the `scattered` bit of the path state are compiled only into the instantiations that carry this type
+// (k_shade_gen_m, k_wavefront_m, k_wavefront_h_m, k_path_serial_m, k_mask_probe).  They carry everything SceneTablesP does, the
+// `constant` sky's own density included.
+struct SceneTablesM : SceneTablesP {};
 // (MSK_EMITTER_MARK_POINT, word 0 of a point emitter's second float4: msk_layout.h)
-template <class TB> struct tb_traits { static constexpr bool regular = false, dielectric = false, bitmap = false, envmap = false, delta = false; };
-template <> struct tb_traits<SceneTablesR> { static constexpr bool regular = true, dielectric = false, bitmap = false, envmap = false, delta = false; };
-template <> struct tb_traits<SceneTablesD> { static constexpr bool regular = true, dielectric = true, bitmap = false, envmap = false, delta = false; };
-template <> struct tb_traits<SceneTablesB> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = false, delta = false; };
-template <> struct tb_traits<SceneTablesE> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = true, delta = false; };
-template <> struct tb_traits<SceneTablesP> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = true, delta = true; };
+template <class TB> struct tb_traits { static constexpr bool regular = false, dielectric = false, bitmap = false, envmap = false, delta = false, mask = false; };
+template <> struct tb_traits<SceneTablesR> { static constexpr bool regular = true, dielectric = false, bitmap = false, envmap = false, delta = false, mask = false; };
+template <> struct tb_traits<SceneTablesD> { static constexpr bool regular = true, dielectric = true, bitmap = false, envmap = false, delta = false, mask = false; };
+template <> struct tb_traits<SceneTablesB> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = false, delta = false, mask = false; };
+template <> struct tb_traits<SceneTablesE> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = true, delta = false, mask = false; };
+template <> struct tb_traits<SceneTablesP> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = true, delta = true, mask = false; };
+template <> struct tb_traits<SceneTablesM> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = true, delta = true, mask = true; };
 MSK_DEV uint32_t tables_lds_float4s(const DeviceScene &sc) {
     return sc.n_tris * 6 + sc.n_meshes + sc.n_bsdf_f4 + sc.n_emitters * 3 + (sc.n_emitters * 95 + 3) / 4 + (sc.cdf_len + 3) / 4 + 72 + (sc.n_spectra + 3) / 4;
 }
@@ -1637,6 +1643,43 @@ MSK_DEV spec reflectance_eval(const TB &tb, f3 c, float scale, uint32_t tex, UV 
         scale = 1.f;
     }
     return spectrum_eval(tb, make_float4(c.x, c.y, c.z, scale), wl);
+}
+
+// The `mask` decorator (msk_gpu.h: msk_mask_desc).  In a scene that holds a mask every BSDF entry has a mask record, three float4 at
+// the END of the BSDF table (entry b: float4 n_bsdf_f4 - 3 n_bsdfs + 3 b): {first value (index into `texels` read as floats), W, H
+// (uint bits), m02} {filter (uint bits: 0 constant, 1 nearest, 2 bilinear), opacity, 0, m12} {m00 m01 m10 m11}; an entry without a
+// mask: the constant 1, for which the decorated BSDF is the nested one to the bit.  The image lookup is the bitmap texture's
+// (reflectance_eval), the scalar where S(texel, l) stands.  Only the SceneTablesM instantiations call these.
+MSK_DEV uint32_t mask_record(const DeviceScene &sc, int bsdf) { return sc.n_bsdf_f4 - 3u * sc.n_bsdfs + 3u * (uint32_t) bsdf; }
+template <class TB, class UV>
+MSK_DEV float mask_opacity(const TB &tb, uint32_t rec, UV uv_of) {
+    const float4 t0 = tb.bsdfs[rec], t1 = tb.bsdfs[rec + 1];
+    const uint32_t filter = __float_as_uint(t1.x);
+    if (filter == 0u) return t1.y;
+    const float4 m = tb.bsdfs[rec + 2];
+    const f2 uv = uv_of();
+    const float x = m.x * uv.x + (m.y * uv.y + t0.w * 1.f), y = m.z * uv.x + (m.w * uv.y + t1.w * 1.f);
+    const float fu = x - floorf(x), fv = y - floorf(y);
+    const uint32_t W = __float_as_uint(t0.y), H = __float_as_uint(t0.z);
+    const float *tx = (const float *) tb.texels + __float_as_uint(t0.x);
+    if (filter == 1u) {
+        uint32_t i = (uint32_t) (int) (fu * (float) W), j = (uint32_t) (int) (fv * (float) H);
+        i = i < W - 1u ? i : W - 1u; j = j < H - 1u ? j : H - 1u;
+        return tx[(size_t) j * W + i];
+    }
+    uint32_t i0, i1, j0, j1; float wx, wy;
+    bitmap_axis(fu, W, &i0, &i1, &wx);
+    bitmap_axis(fv, H, &j0, &j1, &wy);
+    const float k00 = tx[(size_t) j0 * W + i0], k10 = tx[(size_t) j0 * W + i1];
+    const float k01 = tx[(size_t) j1 * W + i0], k11 = tx[(size_t) j1 * W + i1];
+    const float a = k00 + (k10 - k00) * wx;
+    const float b = k01 + (k11 - k01) * wx;
+    return a + (b - a) * wy;
+}
+// The lobe choice of mask.cpp:43-44 by u.x: true = the nested BSDF is sampled with u.x / a (one IEEE division), false = the null lobe
+MSK_DEV bool mask_pick_nested(float a, f2 *u) {
+    if (u->x < a) { u->x = u->x / a; return true; }
+    return false;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2197,6 +2240,11 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
         // the sign of eta (> 0) says that the bounce which made this ray sampled a delta lobe (BSDFFlags::Delta, path.cpp:104-106)
         const bool delta_in = tb_traits<TB>::dielectric && cur.aux.x < 0.f;
         if (tb_traits<TB>::dielectric) eta = fabsf(eta);
+        // the sign of the last next-event density (>= 0) says that the path has scattered: a non-null lobe was sampled (path.cpp:31,73)
+        bool scattered = tb_traits<TB>::mask && (__float_as_uint(cur.aux.y) >> 31) != 0u;
+        if (tb_traits<TB>::mask) nee_pdf = fabsf(nee_pdf);
+        // under hide_emitters an emitter reached before the path has scattered adds nothing (path.cpp:92-93; DESIGN.md section 9, departure 8)
+        const bool hidden_in = tb_traits<TB>::mask && pp.hide_emitters && !scattered;
         bool delta_out = false;
         uint32_t depth = id.y >> MSK_DEPTH_SHIFT;
         const uint32_t s_own = id.y & MSK_SI_MASK;
@@ -2223,7 +2271,7 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
                     float pdf = env_pdf(ev, uv, sin_t);
                     if (n_em != 1) pdf = pdf * (1.f / n_em);
                     if (delta_in) pdf = 0.f;
-                    res = res + thr * le * mis_weight(bs_pdf, pdf);
+                    if (!hidden_in) res = res + thr * le * mis_weight(bs_pdf, pdf);
                 }
             } else
             if (tb_traits<TB>::delta) {
@@ -2236,7 +2284,7 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
                         float pdf = MSK_INV_FOUR_PI_F;
                         if (n_em != 1) pdf = pdf * (1.f / n_em);
                         if (delta_in) pdf = 0.f;
-                        res = res + thr * le * mis_weight(bs_pdf, pdf);
+                        if (!hidden_in) res = res + thr * le * mis_weight(bs_pdf, pdf);
                     }
                 }
             } else
@@ -2280,7 +2328,7 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
                     pdf *= (dp != 0.f) ? (si.t * si.t) / dp : 0.f;
                     if (n_em != 1) pdf = pdf * (1.f / n_em);
                     if (delta_in) pdf = 0.f;
-                    res = res + thr * value * mis_weight(bs_pdf, pdf);
+                    if (!hidden_in) res = res + thr * value * mis_weight(bs_pdf, pdf);
                 }
                 // ---- Russian roulette (path.cpp:116-122)
                 if ((int) depth >= pp.rr_depth) {
@@ -2304,6 +2352,9 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
                     const uint32_t tex = __float_as_uint(bs.ior.z);
                     refl = reflectance_eval(tb, mk3(bs.a.z, bs.a.w, bs.b.x), bs.ior.w, tex, [&]() { return hit_uv(tb, hit); }, wl);
                 }
+                // the opacity of the entry the mesh names, at the hit's uv (msk_gpu.h, msk_mask_desc)
+                float opacity = 1.f;
+                if (tb_traits<TB>::mask) opacity = mask_opacity(tb, mask_record(sc, si.bsdf_id), [&]() { return hit_uv(tb, hit); });
                 // ---- next-event estimation (path.cpp:56-67, scene.cpp:68-103): not at a BSDF without a smooth lobe
                 delta_out = bsdf_is_delta<TB>(bs);
                 if (n_em > 0 && !delta_out) {
@@ -2390,6 +2441,7 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
                         if (flipped) wo.z = -wo.z;
                         spec bsdf_val; float bsdf_pdf;
                         bsdf_eval_pdf<DIFFUSE_ONLY>(tb, bs, wi_s, wo, wl, refl, &bsdf_val, &bsdf_pdf);
+                        if (tb_traits<TB>::mask) { bsdf_val = bsdf_val * opacity; bsdf_pdf = opacity * bsdf_pdf; }      // eval = a eval_X, pdf = a pdf_X
                         const float w = (tb_traits<TB>::delta && point) ? 1.f : mis_weight(pdf, bsdf_pdf);
                         contrib = thr * emitter_val * bsdf_val * w;
                         if (any_nonzero(contrib)) {
@@ -2400,10 +2452,19 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
                 }
                 // ---- BSDF sampling (path.cpp:71-80)
                 {
-                    const f2 u2 = counter_pair(key, pb + 2);
+                    f2 u2 = counter_pair(key, pb + 2);
                     f3 wo_l; bool ok; float bs_eta;
                     const float sample1 = DIFFUSE_ONLY ? 0.f : counter_pair(key, pb + 1).x;
-                    const spec bsdf_val = bsdf_sample<DIFFUSE_ONLY>(tb, bs, wi_s, sample1, u2, wl, refl, &wo_l, &bs_pdf, &bs_eta, &ok);
+                    // a mask picks its lobe by u.x (mask.cpp:43-44): the nested BSDF with u.x / a, density a pdf_X, or the null lobe
+                    const bool null_lobe = tb_traits<TB>::mask && !mask_pick_nested(opacity, &u2);
+                    spec bsdf_val;
+                    if (tb_traits<TB>::mask && null_lobe) {
+                        bsdf_val = splat(1.f); bs_pdf = 1.f - opacity; bs_eta = 1.f; ok = true; wo_l = mk3(0.f, 0.f, 0.f);
+                        delta_out = true;                                  // "the last bounce was delta"
+                    } else {
+                        bsdf_val = bsdf_sample<DIFFUSE_ONLY>(tb, bs, wi_s, sample1, u2, wl, refl, &wo_l, &bs_pdf, &bs_eta, &ok);
+                        if (tb_traits<TB>::mask) { bs_pdf = opacity * bs_pdf; scattered = true; }
+                    }
                     if (!ok) {
                         // failed sample: zero direction, the reference's ray misses and the loop ends (path.cpp:89-97) — but the
                         // NEE term of this bounce was added before the sample (path.cpp:60-66).  diffuse / roughconductor fail
@@ -2418,7 +2479,8 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
                         }
                     } else {
                         if (flipped) wo_l.z = -wo_l.z;
-                        const f3 wo = si.sh.to_world(wo_l);
+                        f3 wo = si.sh.to_world(wo_l);
+                        if (tb_traits<TB>::mask && null_lobe) wo = rd;     // the incoming ray's own direction, bit for bit: no frame round trip
                         thr = thr * bsdf_val;                              // path.cpp:99
                         eta *= bs_eta;                                     // path.cpp:100
                         // A path whose throughput is now zero can only add zeros from here on; it lives one more
@@ -2469,6 +2531,7 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
             st4<1>(st.wl + o, to4(wl)); st4<1>(st.thr + o, to4(thr)); st4<1>(st.res + o, to4(res));
             st4<4>(st.ray_o + o, new_o); st4<4>(st.ray_d + o, new_d);
             if (has_shadow) { st4<4>(st.sh + o, new_sh); st4<1>(st.contrib + o, to4(contrib)); }
+            if (tb_traits<TB>::mask) nee_pdf = xor_sign(fabsf(nee_pdf), scattered ? 0x80000000u : 0u);
             if (!DIFFUSE_ONLY) st.aux[o] = make_float2(delta_out ? -eta : eta, nee_pdf);
         }
         cur_s += (uint32_t) __popcll(m_s); cur_n += (uint32_t) __popcll(m_n);
@@ -2628,14 +2691,14 @@ MSK_DEV DoneQueue done_queue(float4 *base) {
 
 // the table type of an instantiation: plain, with tabulated spectra, with the smooth dielectric (which includes them), with bitmap
 // textures (which includes both)
-template <bool REGULAR, bool DIELECTRIC, bool BITMAP = false, bool ENVMAP = false, bool DELTA = false>
-using tables_of = typename std::conditional<DELTA, SceneTablesP, typename std::conditional<ENVMAP, SceneTablesE, typename std::conditional<BITMAP, SceneTablesB, typename std::conditional<DIELECTRIC, SceneTablesD,
-                                            typename std::conditional<REGULAR, SceneTablesR, SceneTables>::type>::type>::type>::type>::type;
+template <bool REGULAR, bool DIELECTRIC, bool BITMAP = false, bool ENVMAP = false, bool DELTA = false, bool MASK = false>
+using tables_of = typename std::conditional<MASK, SceneTablesM, typename std::conditional<DELTA, SceneTablesP, typename std::conditional<ENVMAP, SceneTablesE, typename std::conditional<BITMAP, SceneTablesB, typename std::conditional<DIELECTRIC, SceneTablesD,
+                                            typename std::conditional<REGULAR, SceneTablesR, SceneTables>::type>::type>::type>::type>::type>::type;
 
-template <bool LDS_TABLES, bool DIFFUSE_ONLY, bool REGULAR = false, bool DIELECTRIC = false, bool BITMAP = false, bool ENVMAP = false, bool DELTA = false>
+template <bool LDS_TABLES, bool DIFFUSE_ONLY, bool REGULAR = false, bool DIELECTRIC = false, bool BITMAP = false, bool ENVMAP = false, bool DELTA = false, bool MASK = false>
 MSK_DEV void shade_gen_body(const DeviceScene &sc, const PathState &st, const PassParams &pp) {
     extern __shared__ float4 lds_dyn[];
-    tables_of<REGULAR, DIELECTRIC, BITMAP, ENVMAP, DELTA> tb;
+    tables_of<REGULAR, DIELECTRIC, BITMAP, ENVMAP, DELTA, MASK> tb;
     static_cast<SceneTables &>(tb) = stage_tables<LDS_TABLES>(sc, lds_dyn);
     const uint32_t lwave = (blockIdx.x * MSK_BLOCK + threadIdx.x) / MSK_WAVE;
     const uint32_t queue_f4 = LDS_TABLES ? tables_lds_float4s(sc) : small_tables_float4s(sc);   // after the staged tables
@@ -2688,6 +2751,11 @@ k_shade_gen_e(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_
 template <bool LDS_TABLES>
 __global__ void __launch_bounds__(MSK_BLOCK)
 k_shade_gen_p(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_TABLES, false, true, true, true, true, true>(sc, st, pp); }
+// ... and the two that scenes with a `mask` run, and only they (SceneTablesM), whatever else they hold.  Not held at a wave count by
+// attribute either: they carry everything k_shade_gen_p does
+template <bool LDS_TABLES>
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_shade_gen_m(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_TABLES, false, true, true, true, true, true, true>(sc, st, pp); }
 // The diffuse-only variants fit four waves per SIMD (128 VGPRs, no scratch); left alone, the allocator spends 24 more registers
 // on the explicit fp64 fma chains of det_sincos and lands at three.
 #ifndef MSK_NO_SHADE4
@@ -2789,6 +2857,14 @@ k_wavefront_p(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, u
     constexpr bool CULL = false;      // (as k_wavefront_d)
     MSK_WAVEFRONT_BODY
 }
+// the one scenes with a `mask` run (see k_shade_gen_m)
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_wavefront_m(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
+    typedef SceneTablesM TB;
+    constexpr bool DIFFUSE_ONLY = false;
+    constexpr bool CULL = false;      // (as k_wavefront_d)
+    MSK_WAVEFRONT_BODY
+}
 #undef MSK_WAVEFRONT_BODY
 
 // k_wavefront_h (round 6): the same device-side loop for scenes whose TREE STAYS IN HBM / L2 (trace mode 6: the 4-wide tree with
@@ -2873,6 +2949,13 @@ k_wavefront_h_p(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters,
     constexpr bool DIFFUSE_ONLY = false;
     MSK_WAVEFRONT_H_BODY
 }
+// the one scenes with a `mask` run (see k_shade_gen_m)
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_wavefront_h_m(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
+    typedef SceneTablesM TB;
+    constexpr bool DIFFUSE_ONLY = false;
+    MSK_WAVEFRONT_H_BODY
+}
 #undef MSK_WAVEFRONT_H_BODY
 
 // msk_gpu_eval_texture: the value of the texture whose record sits at float4 offset `rec` of the BSDF table, at n given uv and
@@ -2936,6 +3019,53 @@ k_delta_probe(DeviceScene sc, uint32_t conductor, uint32_t index, uint64_t n, co
             float4 a = make_float4(d.x, d.y, d.z, dist);
             if (dist == 0.f) { v = splat(0.f); a = make_float4(0.f, 0.f, 0.f, 0.f); }
             out_a[i] = a; out_b[i] = make_float4(v.v[0], v.v[1], v.v[2], v.v[3]);
+        }
+    }
+}
+
+// msk_gpu_mask_sample (eval == 0) / msk_gpu_mask_eval (eval == 1) of BSDF entry `bsdf`, through the functions the shading kernels
+// call, in the order they call them: the opacity of the entry at uv, the twosided flip, then the lobe.  One point per thread.
+// sample: in_a = wi (n * 3, local), in_b = {sample1, u.x, u.y} (n * 3); out_a = {wo.x, wo.y, wo.z, pdf}, out_b = value,
+// out_c = {eta, delta (1 / 0), null (1 / 0), ok (1 / 0)}; the null lobe has wo = -wi (the caller's frame; the renderer keeps the
+// ray's world direction).  eval: in_b = wo (n * 3); out_a = {a, pdf, 0, 0}, out_b = eval.
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_mask_probe(DeviceScene sc, uint32_t eval, uint32_t bsdf, uint64_t n, const float *uv, const float *in_a, const float *in_b, const float4 *wl,
+             float4 *out_a, float4 *out_b, float4 *out_c) {
+    SceneTablesM tb;
+    static_cast<SceneTables &>(tb) = stage_tables<false>(sc, nullptr);
+    for (uint64_t i = (uint64_t) blockIdx.x * MSK_BLOCK + threadIdx.x; i < n; i += (uint64_t) gridDim.x * MSK_BLOCK) {
+        const spec w = from4(wl[i]);
+        f2 t; t.x = uv[i * 2]; t.y = uv[i * 2 + 1];
+        const float a = mask_opacity(tb, mask_record(sc, (int) bsdf), [&]() { return t; });
+        BsdfRec bs = load_bsdf(tb, (int) bsdf);
+        f3 wi = mk3(in_a[i * 3], in_a[i * 3 + 1], in_a[i * 3 + 2]);
+        bool flipped = false;
+        const int back = __float_as_int(bs.a.y);
+        if (back >= 0 && wi.z < 0.f) { wi.z = -wi.z; flipped = true; if (back != (int) bsdf) bs = load_bsdf(tb, back); }
+        spec refl = splat(0.f);
+        if (__float_as_int(bs.a.x) == 0) refl = reflectance_eval(tb, mk3(bs.a.z, bs.a.w, bs.b.x), bs.ior.w, __float_as_uint(bs.ior.z), [&]() { return t; }, w);
+        if (eval) {
+            f3 wo = mk3(in_b[i * 3], in_b[i * 3 + 1], in_b[i * 3 + 2]);
+            if (flipped) wo.z = -wo.z;
+            spec v; float pdf;
+            bsdf_eval_pdf<false>(tb, bs, wi, wo, w, refl, &v, &pdf);
+            v = v * a; pdf = a * pdf;
+            out_a[i] = make_float4(a, pdf, 0.f, 0.f); out_b[i] = to4(v);
+        } else {
+            f2 u; u.x = in_b[i * 3 + 1]; u.y = in_b[i * 3 + 2];
+            f3 wo; float pdf, eta; bool ok; spec v;
+            bool delta = bsdf_is_delta<SceneTablesM>(bs);
+            const bool null_lobe = !mask_pick_nested(a, &u);
+            if (null_lobe) {
+                v = splat(1.f); pdf = 1.f - a; eta = 1.f; ok = true; delta = true;
+                wo = mk3(-in_a[i * 3], -in_a[i * 3 + 1], -in_a[i * 3 + 2]);
+            } else {
+                v = bsdf_sample<false>(tb, bs, wi, in_b[i * 3], u, w, refl, &wo, &pdf, &eta, &ok);
+                pdf = a * pdf;
+                if (flipped) wo.z = -wo.z;
+            }
+            out_a[i] = make_float4(wo.x, wo.y, wo.z, pdf); out_b[i] = to4(v);
+            out_c[i] = make_float4(eta, delta ? 1.f : 0.f, null_lobe ? 1.f : 0.f, ok ? 1.f : 0.f);
         }
     }
 }

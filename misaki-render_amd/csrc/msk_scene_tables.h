@@ -19,6 +19,8 @@
 #include <string>
 #include <vector>
 
+#include "msk_mask_tables.h"
+
 namespace mskscene {
 
 struct HostTables {
@@ -38,6 +40,10 @@ struct HostTables {
     uint32_t n_textures = 0, tex_base = 0;  // msk_gpu_eval_texture: texture k's record sits at float4 tex_base + 3 k of `bsdfs`
     // the scene's flags (mskplan::SceneFacts), final when pack() returns
     bool all_diffuse = true, has_regular = false, has_dielectric = false, has_bitmap = false, has_envmap = false, has_delta = false;
+    // a `mask` (msk_mask_tables.h): every BSDF entry then has a mask record at the end of `bsdfs`, from float4 mask_base on;
+    // has_mask_image: an opacity is an image, whose values lie behind everything else in `texels`.  Set by pack_masks()
+    bool has_mask = false, has_mask_image = false;
+    uint32_t mask_base = 0;
 };
 
 static inline float h_dot(const float *a, const float *b) { return a[0] * b[0] + (a[1] * b[1] + a[2] * b[2]); }
@@ -61,14 +67,18 @@ struct Packer : HostTables {
     std::vector<float> mesh_area;
     std::vector<std::vector<float>> mesh_cdf;
     mskenv::Tables env_tables;
+    uint32_t n_masks;
+    const msk_mask_desc *masks;
+    std::vector<float> mask_values;         // the mask images' values, in the order of `masks`
 
-    Packer(const msk_scene_desc *d_, const msk_scene_ext *ext_, const char *pad_scale_text_, std::string *msg_)
-        : d(d_), ext(ext_), env(ext_ ? ext_->envmap : nullptr), pad_scale_text(pad_scale_text_), msg(msg_) {}
+    Packer(const msk_scene_desc *d_, const msk_scene_ext *ext_, const char *pad_scale_text_, std::string *msg_, uint32_t n_masks_ = 0,
+           const msk_mask_desc *masks_ = nullptr)
+        : d(d_), ext(ext_), env(ext_ ? ext_->envmap : nullptr), pad_scale_text(pad_scale_text_), msg(msg_), n_masks(n_masks_), masks(masks_) {}
 
     int run() {
         int rc;
         if ((rc = check_header()) || (rc = pack_meshes()) || (rc = check_regular_spectra()) || (rc = pack_textures()) || (rc = pack_bsdfs()) ||
-            (rc = pack_emitters()) || (rc = pack_envmap())) return rc;
+            (rc = pack_masks()) || (rc = pack_emitters()) || (rc = pack_envmap())) return rc;
         if (has_regular) all_diffuse = false;              // tabulated spectra are evaluated by the general shading variant only
         spectra_pool.assign(d->regular_values, d->regular_values + d->n_regular_values);
         if (spectra_pool.empty()) spectra_pool.push_back(0.f);
@@ -81,8 +91,12 @@ struct Packer : HostTables {
         pack_texels();
         pack_env_radius();
         if (has_delta) all_diffuse = false;  // the delta light and the mirror live in instantiations of the general shading variant
+        if (has_mask) all_diffuse = false;   // ... and the null lobe
         return MSK_OK;
     }
+
+    // the mask records, behind the texture records in `bsdfs` (msk_mask_tables.h).  A scene without masks gets none: its tables are what they were.
+    int pack_masks() { return pack_mask_records(d, n_masks, masks, bsdfs, n_bsdf_f4, has_mask, has_mask_image, mask_base, mask_values, msg); }
 
     int check_header() {
         if (d->abi_version != MSK_ABI_VERSION)
@@ -440,7 +454,7 @@ struct Packer : HostTables {
 
     // one float4 per texel: a lookup is one 16-byte load per texel
     void pack_texels() {
-        if (!(has_bitmap || has_envmap)) return;
+        if (!(has_bitmap || has_envmap || has_mask_image)) return;
         std::vector<float> &tx4 = texels;
         tx4.assign((size_t) d->n_texels * 4, 0.f);
         if (d->texels) for (size_t k = 0; k < d->n_texels; ++k) { tx4[k * 4] = d->texels[k * 3]; tx4[k * 4 + 1] = d->texels[k * 3 + 1]; tx4[k * 4 + 2] = d->texels[k * 3 + 2]; }
@@ -456,6 +470,7 @@ struct Packer : HostTables {
             tx4.insert(tx4.end(), env_tables.cond.begin(), env_tables.cond.end());
             tx4.resize((tx4.size() + 3) & ~(size_t) 3, 0.f);
         }
+        if (has_mask_image) place_mask_values(d->n_bsdfs, mask_base, bsdfs, mask_values, tx4);      // the mask images' values behind them (msk_mask_tables.h)
     }
 
     // constant.cpp:21-28 set_scene: the sphere around Scene::bbox() (bbox.h:105-112), in fp32 exactly as the oracle does
@@ -474,8 +489,10 @@ struct Packer : HostTables {
 
 // Fills *out from the descriptor; pad_scale_text = MSK_PAD_SCALE as the environment holds it (mskplan::SceneKnobs), or nullptr.
 // MSK_OK, or the code of the first refusal with its text in *msg (*out is then untouched).
-inline int pack(const msk_scene_desc *d, const msk_scene_ext *ext, const char *pad_scale_text, HostTables *out, std::string *msg) {
-    Packer p(d, ext, pad_scale_text, msg);
+// n_masks / masks: what msk_scene_masks holds beyond msk_scene_ext (none: the tables are those of the scene without the argument).
+inline int pack(const msk_scene_desc *d, const msk_scene_ext *ext, const char *pad_scale_text, HostTables *out, std::string *msg, uint32_t n_masks = 0,
+                const msk_mask_desc *masks = nullptr) {
+    Packer p(d, ext, pad_scale_text, msg, n_masks, masks);
     const int rc = p.run();
     if (rc == MSK_OK) *out = std::move(static_cast<HostTables &>(p));
     return rc;

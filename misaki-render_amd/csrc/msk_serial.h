@@ -92,5 +92,11 @@ k_path_serial_p(DeviceScene sc, SerialParams prm) {
     typedef SceneTablesP TB;
 #include "msk_serial_body.inc"
 }
+// ... and SceneTablesM for a scene that holds a `mask` (whatever else it holds)
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_path_serial_m(DeviceScene sc, SerialParams prm) {
+    typedef SceneTablesM TB;
+#include "msk_serial_body.inc"
+}
 
 }  // namespace msk

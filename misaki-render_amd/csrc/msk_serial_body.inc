@@ -1,4 +1,4 @@
-// msk_serial_body.inc — the body of k_path_serial / k_path_serial_d / k_path_serial_b / k_path_serial_e / k_path_serial_p (msk_serial.h), included once into each: `TB` is the
+// msk_serial_body.inc — the body of k_path_serial / k_path_serial_d / k_path_serial_b / k_path_serial_e / k_path_serial_p / k_path_serial_m (msk_serial.h), included once into each: `TB` is the
 // kernel's table type, `sc` and `prm` its arguments.  Written once and stamped, not shared through a function, so that
 // k_path_serial compiles from the token stream it always had.
     extern __shared__ float4 lds_dyn[];
@@ -58,6 +58,7 @@
                 // ---- PathTracer::sample (path.cpp:23-125), the scalar loop
                 spec thr = splat(1.f), res = splat(0.f);
                 float eta = 1.f;
+                bool scattered = false;                                                // path.cpp:31,73 (read only where tb_traits<TB>::mask)
                 ++n_segments;
                 float4 hit = closest(ro, rd, sc.near_clip * inv_z, sc.far_clip * inv_z);
                 for (int depth = 1; depth <= prm.max_depth || prm.max_depth < 0; ++depth) {
@@ -84,6 +85,8 @@
                         const uint32_t tex = __float_as_uint(bs.ior.z);
                         refl = reflectance_eval(tb, mk3(bs.a.z, bs.a.w, bs.b.x), bs.ior.w, tex, [&]() { return hit_uv(tb, hit); }, wl);
                     }
+                    float opacity = 1.f;                                               // of the entry the mesh names (msk_gpu.h, msk_mask_desc)
+                    if (tb_traits<TB>::mask) opacity = mask_opacity(tb, mask_record(sc, si.bsdf_id), [&]() { return hit_uv(tb, hit); });
                     const float tmin = (1.f + max_abs(si.p)) * MSK_RAY_EPS_F;          // interaction.h:40-44
                     // ---- next-event estimation (path.cpp:56-67, scene.cpp:68-103); the draw is made whatever the scene holds —
                     // but not at a BSDF without a smooth lobe (a `dielectric`), where path.cpp:56 skips the sample and its next2d()
@@ -165,6 +168,7 @@
                                 if (flipped) wo.z = -wo.z;
                                 spec bsdf_val; float bsdf_pdf;
                                 bsdf_eval_pdf<false>(tb, bs, wi_s, wo, wl, refl, &bsdf_val, &bsdf_pdf);
+                                if (tb_traits<TB>::mask) { bsdf_val = bsdf_val * opacity; bsdf_pdf = opacity * bsdf_pdf; }
                                 const float w = (tb_traits<TB>::delta && point) ? 1.f : mis_weight(pdf, bsdf_pdf);     // a delta light: weight 1
                                 const spec contrib = thr * emitter_val * bsdf_val * w;
                                 if (any_nonzero(contrib)) {                            // scene.cpp:91-95: an occluded sample adds nothing
@@ -181,9 +185,17 @@
                     const float sample1 = rng.next_float();
                     f2 u2; u2.x = rng.next_float(); u2.y = rng.next_float();
                     f3 wo_l; bool ok; float bs_pdf, bs_eta;
-                    const spec bsdf_val = bsdf_sample<false>(tb, bs, wi_s, sample1, u2, wl, refl, &wo_l, &bs_pdf, &bs_eta, &ok);
+                    // a mask picks its lobe by u.x (mask.cpp:43-44): the nested BSDF with u.x / a, or the null lobe along the ray's own direction
+                    const bool null_lobe = tb_traits<TB>::mask && !mask_pick_nested(opacity, &u2);
+                    spec bsdf_val;
+                    if (tb_traits<TB>::mask && null_lobe) { bsdf_val = splat(1.f); bs_pdf = 1.f - opacity; bs_eta = 1.f; ok = true; wo_l = mk3(0.f, 0.f, 0.f); }
+                    else {
+                        bsdf_val = bsdf_sample<false>(tb, bs, wi_s, sample1, u2, wl, refl, &wo_l, &bs_pdf, &bs_eta, &ok);
+                        if (tb_traits<TB>::mask) { bs_pdf = opacity * bs_pdf; scattered = true; }
+                    }
+                    const bool hidden = tb_traits<TB>::mask && prm.hide_emitters && !scattered;      // path.cpp:92-93; DESIGN.md section 9, departure 8
                     f3 wo = mk3(0.f, 0.f, 0.f);
-                    if (ok) { if (flipped) wo_l.z = -wo_l.z; wo = si.sh.to_world(wo_l); ++n_segments; }
+                    if (ok) { if (flipped) wo_l.z = -wo_l.z; wo = si.sh.to_world(wo_l); if (tb_traits<TB>::mask && null_lobe) wo = rd; ++n_segments; }
                     // the sampled ray (a failed sample's zero direction finds nothing: path.cpp:89-97)
                     ro = si.p; rd = wo;
                     const float4 hit_b = ok ? closest(ro, rd, tmin, MSK_INF_F) : make_float4(MSK_INF_F, 0.f, 0.f, __uint_as_float(MSK_PRIM_ID));
@@ -223,8 +235,8 @@
                     }
                     thr = thr * bsdf_val;                                              // path.cpp:99 (a failed sample: weight 0, pdf 0, eta 1)
                     eta *= bs_eta;                                                     // path.cpp:100
-                    if (delta) emitter_pdf = 0.f;                                      // path.cpp:104-106: BSDFFlags::Delta
-                    if (hit_emitter) res = res + thr * value * mis_weight(bs_pdf, emitter_pdf);
+                    if (delta || (tb_traits<TB>::mask && null_lobe)) emitter_pdf = 0.f;                                      // path.cpp:104-106: BSDFFlags::Delta
+                    if (hit_emitter && !hidden) res = res + thr * value * mis_weight(bs_pdf, emitter_pdf);
                     hit = hit_b;
                     if (depth + 1 >= prm.rr_depth) {                                   // path.cpp:116-122
                         const float q = fmin_std(max4(thr) * eta * eta, 0.95f);

@@ -29,6 +29,11 @@ public:
     // plugins whose value varies with si.uv describe themselves as an msk_texture_desc instead (a bitmap adds its texels to
     // the scene's pool, tables.texels)
     virtual bool flatten_texture(msk_texture_desc &out, FlatTables &tables) const { (void) out; (void) tables; return false; }
+    // an image plugin read as a SCALAR image (the `mask` BSDF's opacity, include/msk_gpu.h at msk_mask_desc): size, filter
+    // (1 nearest, 2 bilinear), to_uv and one value per texel (opacity_scalar of its r, g, b)
+    virtual bool flatten_scalar_image(msk_mask_desc &out, std::vector<float> &values) const { (void) out; (void) values; return false; }
+    // an <rgb> (the `srgb` plugin): the colour it was made from, for a parameter that wants the colour itself (the `mask` BSDF's opacity)
+    virtual bool flatten_rgb(float rgb[3]) const { (void) rgb; return false; }
     virtual float mean() const { return 0.f; }
     static ref<Texture> D65(float scale);
     MSK_DECLARE_CLASS()
@@ -134,6 +139,10 @@ public:
     virtual bool flatten(msk_bsdf_desc &out, FlatTables &tables) const { (void) out; (void) tables; return false; }
     virtual const BSDF *nested(int side) const { (void) side; return nullptr; }   // twosided: the BSDF of side 0 / 1
     virtual bool has_transmission() const { return false; }                        // BSDFFlags::Transmission, as far as twosided.cpp:33-35 asks
+    // `mask` (bsdfs/mask.cpp): the decoration of the entry the nested BSDF flattens to; `values` receives an image's values
+    // (flatten_scene points `out` at them and fills out.bsdf)
+    virtual bool is_mask() const { return false; }
+    virtual bool flatten_mask(msk_mask_desc &out, std::vector<float> &values) const { (void) out; (void) values; return false; }
     std::string id() const override { return m_id; }
     MSK_DECLARE_CLASS()
 protected:
@@ -289,6 +298,11 @@ struct FlatScene {
     std::vector<msk_point_desc> points;
     msk_scene_ext ext = {nullptr, 0, nullptr};
     const msk_scene_ext *ext_ptr() const { return &ext; }
+    // the scene's `mask` BSDFs with their images' values, and the extension that holds them too (msk_gpu_scene_create_masks)
+    std::vector<msk_mask_desc> masks;
+    std::vector<std::vector<float>> mask_values;
+    msk_scene_masks em = {{nullptr, 0, nullptr}, 0, nullptr};
+    const msk_scene_masks *masks_ptr() const { return &em; }
 };
 void flatten_scene(const Scene *scene, const Sensor *sensor, FlatScene &out);
 

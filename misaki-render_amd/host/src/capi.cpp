@@ -73,6 +73,14 @@ int msk_host_points(msk_host_scene *h, msk_point_desc *points, size_t cap) {
     return (int) n;
 }
 
+// the flattened scene's `mask` BSDFs (after msk_host_flatten): returns their number and, when `masks` is not NULL, copies up to
+// `cap` of them (their `values` point into the handle)
+int msk_host_masks(msk_host_scene *h, msk_mask_desc *masks, size_t cap) {
+    const size_t n = h->flat.masks.size();
+    if (masks) std::memcpy(masks, h->flat.masks.data(), std::min(n, cap) * sizeof(msk_mask_desc));
+    return (int) n;
+}
+
 // scene->integrator()->render(scene, sensor) followed by HDRFilm::image(); optionally develop() to a file
 int msk_host_render(msk_host_scene *h, float *film_xyzaw, float *rgba, const char *develop_to, msk_stats *stats) {
     try {

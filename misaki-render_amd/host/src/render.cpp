@@ -180,11 +180,12 @@ MSK_REGISTER_INSTANCE(Scene, "scene")      // <scene> is instantiated like any p
 // spectra/srgb.cpp:13-23
 class SRGBReflectanceSpectrum final : public Texture {
 public:
-    SRGBReflectanceSpectrum(const Properties &props) : Texture(props) { m_value = srgb_model_fetch(props.color("color")); }
+    SRGBReflectanceSpectrum(const Properties &props) : Texture(props) { m_rgb = props.color("color"); m_value = srgb_model_fetch(m_rgb); }
     bool flatten(Flat &out) const override { out.coeff[0] = m_value.r; out.coeff[1] = m_value.g; out.coeff[2] = m_value.b; out.uses_d65 = false; return true; }
+    bool flatten_rgb(float rgb[3]) const override { rgb[0] = m_rgb.r; rgb[1] = m_rgb.g; rgb[2] = m_rgb.b; return true; }
     MSK_DECLARE_CLASS()
 private:
-    Color3 m_value;
+    Color3 m_value, m_rgb;
 };
 MSK_IMPLEMENT_CLASS(SRGBReflectanceSpectrum, Texture)
 MSK_REGISTER_INSTANCE(SRGBReflectanceSpectrum, "srgb")
@@ -326,6 +327,13 @@ private:
 MSK_IMPLEMENT_CLASS(CheckerboardTexture, Texture)
 MSK_REGISTER_INSTANCE(CheckerboardTexture, "checkerboard")
 
+// What a coloured opacity is reduced to (include/msk_gpu.h at msk_mask_desc, DESIGN.md section 9 departure 7): a grey is its value,
+// any other colour 0.212671 r + 0.715160 g + 0.072169 b, fp32, left to right
+static float opacity_scalar(float r, float g, float b) {
+    if (r == g && g == b) return r;
+    return (0.212671f * r + 0.715160f * g) + 0.072169f * b;
+}
+
 // The `bitmap` texture: an image file as the diffuse reflectance (the reference's textures/bitmap.cpp is RGB-typed and not built;
 // this is its lookup in spectral form, include/msk_gpu.h at msk_texture_desc).  Properties: filename (through the file resolver),
 // filter_type "bilinear" (default) | "nearest", to_uv, wrap_mode "repeat" only, raw (default false: PGM / PPM samples are sRGB
@@ -357,6 +365,14 @@ public:
             if (it == seen.end()) it = seen.emplace(rgb, srgb_model_fetch(Color3{rgb[0], rgb[1], rgb[2]})).first;
             tables.texels.push_back(it->second.r); tables.texels.push_back(it->second.g); tables.texels.push_back(it->second.b);
         }
+        return true;
+    }
+    bool flatten_scalar_image(msk_mask_desc &out, std::vector<float> &values) const override {
+        out.filter = m_nearest ? 1 : 2;
+        out.width = (uint32_t) m_width; out.height = (uint32_t) m_height;
+        for (int r = 0; r < 2; ++r) for (int c = 0; c < 3; ++c) out.to_uv[r * 3 + c] = (float) m_to_uv.matrix().m[r][c];
+        values.resize((size_t) m_width * m_height);
+        for (size_t k = 0; k < values.size(); ++k) values[k] = opacity_scalar(m_rgb[k * 3], m_rgb[k * 3 + 1], m_rgb[k * 3 + 2]);
         return true;
     }
     float mean() const override {
@@ -683,6 +699,7 @@ public:
     TwoSidedBRDF(const Properties &props) : BSDF(props) {
         auto bsdfs = props.objects();
         for (auto &kv : bsdfs) if (!dynamic_cast<BSDF *>(kv.second.get())) Throw("twosided: nested object \"{}\" is not a BSDF", kv.first);
+        for (auto &kv : bsdfs) if (static_cast<BSDF *>(kv.second.get())->is_mask()) Throw("mask: a \"twosided\" BSDF cannot hold a mask; write mask(twosided(X))");
         if (!bsdfs.empty()) m_brdf[0] = static_cast<BSDF *>(bsdfs[0].second.get());
         if (bsdfs.size() == 2) m_brdf[1] = static_cast<BSDF *>(bsdfs[1].second.get());
         else if (bsdfs.size() > 2) Throw("At most two nested BSDFs can be specified!");
@@ -699,6 +716,56 @@ private:
 };
 MSK_IMPLEMENT_CLASS(TwoSidedBRDF, BSDF)
 MSK_REGISTER_INSTANCE(TwoSidedBRDF, "twosided")
+
+// bsdfs/mask.cpp: an opacity cutout with a null lobe over exactly one nested BSDF (include/msk_gpu.h at msk_mask_desc).  `opacity`:
+// a float (default 0.5), an <rgb> or a constant spectrum (a colour is reduced to a scalar: opacity_scalar), or a nested `bitmap`
+// texture named "opacity" (filter_type and to_uv as for a reflectance).  mask(twosided(X)) is allowed; twosided(mask(..)) and
+// mask(mask(..)) are refused.
+class MaskBSDF final : public BSDF {
+public:
+    MaskBSDF(const Properties &props) : BSDF(props) {
+        std::memset(&m_desc, 0, sizeof m_desc);
+        m_desc.opacity = 0.5f;
+        for (auto &kv : props.objects()) {
+            if (BSDF *b = dynamic_cast<BSDF *>(kv.second.get())) {
+                if (m_nested) Throw("mask: exactly one nested BSDF is required");
+                m_nested = b;
+            } else if (kv.first != "opacity")
+                Throw("mask: nested object \"{}\" is neither a BSDF nor the texture \"opacity\"", kv.first);
+        }
+        if (!m_nested) Throw("mask: exactly one nested BSDF is required");
+        if (m_nested->is_mask()) Throw("mask: a mask cannot be nested in a mask");
+        if (props.has_property("opacity")) {
+            if (props.type("opacity") == Properties::Type::Object) {
+                ref<Texture> t = props.texture("opacity");
+                Texture::Flat f;
+                float rgb[3];
+                if (t->flatten_scalar_image(m_desc, m_values)) {
+                    m_desc.opacity = 0.f;                                // (an image: the constant is unused and written as 0)
+                } else if (t->flatten_rgb(rgb)) {                        // <rgb name="opacity" .../>
+                    m_desc.opacity = opacity_scalar(rgb[0], rgb[1], rgb[2]);
+                } else if (t->flatten(f) && !f.uses_d65 && !f.regular && f.coeff[0] == 0.f && f.coeff[1] == 0.f && std::isinf(f.coeff[2])) {
+                    m_desc.opacity = f.scale;                            // <spectrum value="c"/>: the `uniform` plugin
+                } else Throw("mask: \"opacity\" must be a float, a colour or a bitmap texture");
+            } else if (props.type("opacity") == Properties::Type::Color) {
+                const Color3 c = props.color("opacity");
+                m_desc.opacity = opacity_scalar(c.r, c.g, c.b);
+            } else m_desc.opacity = props.float_("opacity", 0.5f);
+        }
+    }
+    bool is_mask() const override { return true; }
+    const BSDF *nested(int i) const override { return m_nested->nested(i); }
+    bool has_transmission() const override { return true; }              // the null lobe
+    bool flatten(msk_bsdf_desc &out, FlatTables &tables) const override { return m_nested->flatten(out, tables); }
+    bool flatten_mask(msk_mask_desc &out, std::vector<float> &values) const override { out = m_desc; values = m_values; return true; }
+    MSK_DECLARE_CLASS()
+private:
+    ref<BSDF> m_nested;
+    msk_mask_desc m_desc;
+    std::vector<float> m_values;
+};
+MSK_IMPLEMENT_CLASS(MaskBSDF, BSDF)
+MSK_REGISTER_INSTANCE(MaskBSDF, "mask")
 
 // emitters/area.cpp:13-18
 class AreaLight final : public Emitter {
@@ -1023,7 +1090,7 @@ MSK_REGISTER_INSTANCE(OBJMesh, "obj")
 void flatten_scene(const Scene *scene, const Sensor *sensor, FlatScene &out) {
     out.meshes.clear(); out.bsdfs.clear(); out.emitters.clear(); out.textures.clear(); out.vertices.clear(); out.faces.clear();
     out.regular.clear(); out.regular_values.clear(); out.texels.clear();
-    out.has_envmap = false; out.env_texels.clear(); out.env_weights.clear(); out.points.clear();
+    out.has_envmap = false; out.env_texels.clear(); out.env_weights.clear(); out.points.clear(); out.masks.clear(); out.mask_values.clear();
     FlatTables tables{out.textures, out.regular, out.regular_values, out.texels};
     // Scene::m_emitters order (scene.cpp:27-41) decides which emitter sample_emitter_direct picks (scene.cpp:80-84)
     std::map<const Emitter *, int> emitter_index;
@@ -1066,6 +1133,13 @@ void flatten_scene(const Scene *scene, const Sensor *sensor, FlatScene &out) {
             }
         }
         out.bsdfs.push_back(bd);
+        if (shape->bsdf()->is_mask()) {                              // the decoration of the entry just made (msk_mask_desc)
+            msk_mask_desc kd;
+            out.mask_values.emplace_back();
+            if (!shape->bsdf()->flatten_mask(kd, out.mask_values.back())) Throw("BSDF \"{}\" of shape {} has no mask to flatten", shape->bsdf()->clazz()->name(), i);
+            kd.bsdf = (uint32_t) out.bsdfs.size() - 1;
+            out.masks.push_back(kd);
+        }
         int eid = -1;
         if (shape->is_emitter()) {
             eid = emitter_index.at(shape->emitter());
@@ -1099,6 +1173,8 @@ void flatten_scene(const Scene *scene, const Sensor *sensor, FlatScene &out) {
     d.n_texels = (uint32_t) (out.texels.size() / 3); d.texels = out.texels.empty() ? nullptr : out.texels.data();
     if (out.has_envmap) { out.envmap.texels = out.env_texels.data(); out.envmap.weights = out.env_weights.data(); }
     out.ext.envmap = out.envmap_ptr(); out.ext.n_points = (uint32_t) out.points.size(); out.ext.points = out.points.empty() ? nullptr : out.points.data();
+    for (size_t k = 0; k < out.masks.size(); ++k) out.masks[k].values = out.masks[k].filter ? out.mask_values[k].data() : nullptr;
+    out.em.ext = out.ext; out.em.n_masks = (uint32_t) out.masks.size(); out.em.masks = out.masks.empty() ? nullptr : out.masks.data();
 }
 
 // "0,1,2" -> {0,1,2}; empty -> {single}
@@ -1129,7 +1205,7 @@ static msk_stats render_on_gpu(Scene *scene, Sensor *sensor, std::vector<int> &d
     fill(flat.params);
     if (!ctx && msk_gpu_init(devices.data(), (int) devices.size(), &ctx) != MSK_OK) Throw("{}", msk_gpu_last_error(nullptr));
     msk_scene *gs = nullptr;
-    if (msk_gpu_scene_create_ext(ctx, &flat.desc, flat.ext_ptr(), &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(ctx));
+    if (msk_gpu_scene_create_masks(ctx, &flat.desc, flat.masks_ptr(), &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(ctx));
     ref<ImageBlock> whole = new ImageBlock(film->crop_size(), 5);        // the crop window (the whole film by default), as the storage holds it
     whole->set_offset(film->crop_offset());
     msk_stats st;
@@ -1311,7 +1387,7 @@ public:
         fill_params(sensor, flat.params);
         if (!m_ctx && msk_gpu_init(m_devices.data(), (int) m_devices.size(), &m_ctx) != MSK_OK) Throw("{}", msk_gpu_last_error(nullptr));
         msk_scene *gs = nullptr;
-        if (msk_gpu_scene_create_ext(m_ctx, &flat.desc, flat.ext_ptr(), &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(m_ctx));
+        if (msk_gpu_scene_create_masks(m_ctx, &flat.desc, flat.masks_ptr(), &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(m_ctx));
         ref<ImageBlock> whole = new ImageBlock(film->crop_size(), channels.size());   // the crop window, as the storage holds it (as in "path")
         whole->set_offset(film->crop_offset());
         msk_stats st;

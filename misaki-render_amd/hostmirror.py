@@ -14,6 +14,7 @@ Python callers (tests, bench.py, smoke) can build the flattened `msk_scene_desc`
 The C++ host library (misaki-render_amd/host/) provides the same through the reference's
 plugin/Properties/XML interface; this module is the scripting-side equivalent.
 """
+import copy
 import ctypes as C
 import json
 import math
@@ -185,7 +186,9 @@ class MeshSpec:
         {"type": "diffuse", "twosided": bool, "texture": {"type": "checkerboard", "color0": rgb, "color1": rgb,
          "scale": (sx, sy) | "matrix": 16 floats (the to_uv 4x4, row-major)}} (texture absent = `reflectance`), or the texture
         {"type": "bitmap", "pixels": float32 [H, W, 3] linear RGB (row 0 = texel row 0 = the image's top row),
-         "filter": "bilinear" (default) | "nearest", "scale" | "matrix" (default: identity)}.
+         "filter": "bilinear" (default) | "nearest", "scale" | "matrix" (default: identity)}; or any of them under a mask,
+        {"type": "mask", "opacity": 0.5 (default) | rgb (reduced to its luminance) | a bitmap texture as above with pixels
+         float32 [H, W] or [H, W, 3], "bsdf": {...}} (bsdfs/mask.cpp; the nested BSDF may be "twosided", the mask itself may not).
         texcoords: None, or per face a tuple of (u, v) per corner as written in the OBJ `vt` lines (the loader stores 1 - v)."""
         self.name, self.faces, self.reflectance, self.radiance = name, faces, reflectance, radiance
         self.translate, self.normals, self.bsdf, self.texcoords = translate, normals, bsdf, texcoords
@@ -238,6 +241,70 @@ def write_pfm(path, pixels, little_endian=True):
         fh.write(a[::-1].astype("<f4" if little_endian else ">f4").tobytes())
 
 
+MASK_TWOSIDED = 'mask: a "twosided" BSDF cannot hold a mask; write mask(twosided(X))'
+MASK_NESTED = "mask: a mask cannot be nested in a mask"
+MASK_CHILDREN = "mask: exactly one nested BSDF is required"
+MASK_UNKNOWN = 'mask: nested object "%s" is neither a BSDF nor the texture "opacity"'
+
+
+def _mask_nested(spec):
+    """The nested BSDF spec of {"type": "mask", "opacity": ..., "bsdf": {...}}, after the refusals both flatteners word alike."""
+    if spec.get("twosided"):
+        raise ValueError(MASK_TWOSIDED)
+    for key, value in spec.items():
+        if key not in ("type", "opacity", "bsdf", "twosided") and isinstance(value, dict):
+            raise ValueError(MASK_UNKNOWN % key)
+    nested = spec.get("bsdf")
+    if not isinstance(nested, dict):
+        raise ValueError(MASK_CHILDREN)
+    if nested.get("type") == "mask":
+        raise ValueError(MASK_NESTED)
+    return nested
+
+
+def luminance32(rgb):
+    """What both flatteners reduce a coloured opacity to: a grey is its value, any other colour 0.212671 r + 0.715160 g + 0.072169 b
+    in fp32, left to right"""
+    rgb = np.asarray(rgb, np.float32)
+    r, g, b = rgb[..., 0], rgb[..., 1], rgb[..., 2]
+    lum = (np.float32(0.212671) * r + np.float32(0.715160) * g) + np.float32(0.072169) * b
+    return np.where((r == g) & (g == b), r, lum).astype(np.float32)
+
+
+def _mask_desc(spec, index, keep):
+    """msk_mask_desc of a mask spec on BSDF entry `index` (msk_gpu.h); an image's values are appended to `keep`"""
+    k = abi.MaskDesc()
+    k.bsdf = index
+    op = spec.get("opacity", 0.5)
+    if isinstance(op, dict):
+        if op.get("type") != "bitmap":
+            raise ValueError('mask: "opacity" must be a float, a colour or a bitmap texture')
+        px = np.asarray(op["pixels"], np.float32)
+        if px.ndim == 3 and px.shape[2] == 3:
+            px = luminance32(px)
+        if px.ndim != 2 or px.shape[0] < 1 or px.shape[1] < 1:
+            raise ValueError("mask: opacity pixels must be float32 [H, W] or [H, W, 3]")
+        filt = op.get("filter", "bilinear")
+        if filt not in ("bilinear", "nearest"):
+            raise ValueError("bitmap filter %r (bilinear or nearest)" % (filt,))
+        vals = np.ascontiguousarray(px, np.float32)
+        keep.append(vals)
+        k.filter = 2 if filt == "bilinear" else 1
+        k.height, k.width = vals.shape
+        k.values = vals.ctypes.data_as(C.POINTER(C.c_float))
+        if "scale" in op:
+            m4 = np.diag([op["scale"][0], op["scale"][1], 1.0, 1.0]).astype(np.float32)
+        elif "matrix" in op:
+            m4 = np.asarray(op["matrix"], np.float32).reshape(4, 4)
+        else:
+            m4 = np.eye(4, dtype=np.float32)
+        k.to_uv[:] = [float(x) for x in (m4[0, 0], m4[0, 1], m4[0, 2], m4[1, 0], m4[1, 1], m4[1, 2])]
+    else:
+        k.filter = 0
+        k.opacity = float(op) if np.isscalar(op) else float(luminance32(op))
+    return k
+
+
 def _to_uv_xml(tex):
     if "scale" in tex:
         return ['    <transform name="to_uv">', '        <scale x="%.9g" y="%.9g"/>' % tuple(tex["scale"]), '    </transform>']
@@ -251,6 +318,23 @@ def _bsdf_xml(m, v3, directory=None):
     """The <bsdf> element of one shape (reference plugin parameter names); a bitmap texture's pixels go to
     <directory>/textures/<shape>.pfm."""
     spec = m.bsdf
+    if spec is not None and spec.get("type") == "mask":        # bsdfs/mask.cpp: the opacity and exactly one nested BSDF
+        nested = _mask_nested(spec)
+        inner_mesh = copy.copy(m)
+        inner_mesh.bsdf = nested
+        op = spec.get("opacity", 0.5)
+        if isinstance(op, dict):
+            os.makedirs(os.path.join(directory, "textures"), exist_ok=True)
+            write_pfm(os.path.join(directory, "textures", m.name + "_opacity.pfm"), np.asarray(op["pixels"], np.float32))
+            op_xml = ['<texture name="opacity" type="bitmap">', '    <string name="filename" value="textures/%s_opacity.pfm"/>' % m.name] + \
+                     (['    <string name="filter_type" value="%s"/>' % op["filter"]] if "filter" in op else []) + _to_uv_xml(op) + ['</texture>']
+        elif np.isscalar(op):
+            op_xml = ['<float name="opacity" value="%.9g"/>' % float(np.float32(op))]
+        else:
+            op_xml = ['<rgb name="opacity" value="%s"/>' % v3(op)]
+        inner = [b[8:] for b in _bsdf_xml(inner_mesh, v3, directory)]
+        body = (op_xml if "opacity" in spec else []) + inner
+        return ['        ' + b for b in ['<bsdf type="mask">'] + ['    ' + b for b in body] + ['</bsdf>']]
     refl_xml = '<spectrum name="reflectance" value="%s"/>' % m.reflectance.text if isinstance(m.reflectance, Regular) else \
                '<spectrum name="reflectance" value="%.9g"/>' % float(m.reflectance) if np.isscalar(m.reflectance) else \
                '<rgb name="reflectance" value="%s"/>' % v3(m.reflectance)
@@ -654,6 +738,7 @@ class FlatScene:
         self.keep = []
         self.envmap = None            # abi.EnvmapDesc of the scene's `envmap` emitter, if it has one
         self.points = None            # (abi.PointDesc * n) of the scene's `point` emitters, if it has any (abi.Scene: msk_scene_ext)
+        self.masks = None             # (abi.MaskDesc * n) of the scene's `mask` BSDFs, if it has any (abi.Scene: msk_scene_masks)
 
 
 def _radiance_desc(radiance, fetch, scale_in=1.0):
@@ -786,7 +871,7 @@ def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=
             fs.env_texels, fs.env_weights = keep
             return abi.EmitterDesc(abi.MSK_EMITTER_ENVMAP, -1, (C.c_float * 3)(0.0, 0.0, float("inf")), _radiance_desc(None, fetch, env.get("scale", 1.0))[1], 0)
         return emitter_desc(abi.MSK_EMITTER_CONSTANT, -1, env.get("radiance"), env.get("scale", 1.0))
-    pd = []
+    pd, kd = [], []
 
     def point_desc(pt):
         pos = _point_position(pt)
@@ -802,6 +887,11 @@ def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=
             ed.append(point_desc(pt))
     for i, m in enumerate(meshes):
         v, f = triangulate(m)
+        if m.bsdf is not None and m.bsdf.get("type") == "mask":      # a mask decorates the entry of its nested BSDF
+            inner_mesh = copy.copy(m)
+            inner_mesh.bsdf = _mask_nested(m.bsdf)
+            kd.append(_mask_desc(m.bsdf, len(bd), fs.keep))
+            m = inner_mesh
         bd.append(_bsdf_desc(m, fetch, len(bd), td, pool, texels))
         eid = -1
         if m.radiance is not None:
@@ -819,6 +909,8 @@ def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=
             ed.append(point_desc(pt))
     if pd:
         fs.points = (abi.PointDesc * len(pd))(*pd)
+    if kd:
+        fs.masks = (abi.MaskDesc * len(kd))(*kd)
     for tex in extra_textures:
         td.append(_texture_desc(tex, fetch, texels))
     verts = np.ascontiguousarray(np.concatenate(all_v + [np.zeros((0, 8), np.float32)]), np.float32).reshape(-1, 8)
