@@ -75,6 +75,19 @@
  *            (tools/fuzz_parity.py): a shadow ray lying in the plane of a sliver emitter
  *            triangle produced a numerical "hit" 40 units outside the triangle that one
  *            tree reported and another culled.
+ *   The features merged after the glass twin are restated from the text of include/msk_gpu.h (msk_texture_desc,
+ *   msk_envmap_desc, msk_point_desc, MSK_BSDF_CONDUCTOR, msk_mask_desc) and from the tests' fp32 restatements (envmap_ref.py, delta_ref.py, bitmap_ref.py, mask_ref.py), not from the device's
+ *   code; their departures from the reference as written are DESIGN.md section 9, (1)-(8):
+ *   D11 (1)  envmap: a piecewise-constant distribution over the texels (per-row tables and a marginal, built in double and
+ *            stored as float), not core/distribution.h's Distribution2D.
+ *   D12 (2)  envmap hit by a BSDF sample: L(ray direction) and pdf(ray direction) / n_emitters, not path.cpp's stale records.
+ *   D13 (3)  envmap and bitmap texels are spectra ({c0, c1, c2, w} / three coefficients); spectral VALUES are interpolated.
+ *   D14 (4)  a point light's next-event term has weight 1, not mis_weight(1, bsdf_pdf).
+ *   D15 (5)  in a scene that holds a point emitter, a `conductor` entry or a mask (the facts the launch plan reads) a
+ *            `constant` sky hit by a BSDF sample counts with (1 / 4 pi) / n_emitters; every other scene keeps D9's stale record.
+ *   D16 (6)  mask: the nested lobe has X's value and the density a pdf_X (mask.cpp multiplies the value AND keeps the pdf).
+ *   D17 (7)  mask: the opacity is a scalar.
+ *   D18 (8)  mask: under hide_emitters an AREA emitter reached while `scattered` is false adds nothing.
  */
 #include "oracle_math.h"
 #include "msk_gpu.h"
@@ -128,6 +141,17 @@ struct Scene {
     float tri_pad = 0.f;                   // D10: half the BVH padding, see intersect_triangle
     int env = -1;                          // Scene::m_environment as an index into emitters
     float env_radius = 0.f;                // ConstantBackgroundEmitter::m_bsphere.radius after set_scene
+    std::vector<float> texels;             // msk_scene_desc.texels: 3 coefficients per texel (bitmap textures)
+    // msk_envmap_desc: the image, its rotation and the tables built from the host's weights (cumulative(), in double stored as float)
+    struct Envmap { uint32_t W = 0, H = 0; std::vector<float> texels, marg; std::vector<std::vector<float>> cond; float R[9]; };
+    Envmap envmap;
+    bool env_is_image = false;
+    std::vector<V3> point_pos;             // msk_point_desc.position per emitter (MSK_EMITTER_POINT entries only)
+    // msk_mask_desc per BSDF entry (filter < 0: the entry has no mask)
+    struct Mask { int filter = -1; float opacity = 1.f; float to_uv[6]; uint32_t W = 0, H = 0; std::vector<float> values; };
+    std::vector<Mask> masks;
+    bool any_mask = false;
+    bool own_density_sky = false;          // D15: a point emitter, a `conductor` entry or a mask is in the scene
 
     std::vector<BVHNode> nodes;
     std::vector<uint32_t> tri_order;
@@ -220,8 +244,107 @@ static int build_node(Scene &sc, int first, int count, float pad) {
     return idx;
 }
 
-static Scene *scene_from_desc(const msk_scene_desc *d) {
+// msk_gpu.h at msk_envmap_desc: "The library builds, in double and stored as float, ... a cumulative table": entry k = the sum of
+// the first k weights over the total, the last entry 1; a row of zero weight is 0 .. 0 1 (tests/envmap_ref.py: cumulative)
+static std::vector<float> cumulative(const std::vector<double> &w) {
+    std::vector<float> out(w.size() + 1, 0.f);
+    double total = 0.0;
+    for (double x : w) total += x;
+    if (total > 0.0) { double run = 0.0; for (size_t k = 0; k < w.size(); ++k) { run += w[k]; out[k + 1] = (float) (run / total); } }
+    out[w.size()] = 1.f;
+    return out;
+}
+// msk_gpu.h: "must be a rotation: |R R^T - 1| <= 1e-4 per entry and det > 0, anything else is refused"
+static bool is_rotation(const float *r) {
+    for (int i = 0; i < 9; ++i) if (!std::isfinite(r[i])) return false;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double s = 0.0;
+            for (int k = 0; k < 3; ++k) s += (double) r[i * 3 + k] * (double) r[j * 3 + k];
+            if (std::fabs(s - (i == j ? 1.0 : 0.0)) > 1e-4) return false;
+        }
+    const double det = (double) r[0] * ((double) r[4] * r[8] - (double) r[5] * r[7]) - (double) r[1] * ((double) r[3] * r[8] - (double) r[5] * r[6]) +
+                       (double) r[2] * ((double) r[3] * r[7] - (double) r[4] * r[6]);
+    return det > 0.0;
+}
+// What a scene holds beyond msk_scene_desc; false = something the library refuses at scene creation (msk_gpu.h at
+// msk_gpu_scene_create_env / _ext / _masks)
+static bool scene_extensions(Scene *sc, const msk_scene_desc *d, const msk_scene_masks *em) {
+    const msk_envmap_desc *env = em ? em->ext.envmap : nullptr;
+    uint32_t n_env = 0, n_image = 0;
+    for (uint32_t e = 0; e < d->n_emitters; ++e) {
+        const int32_t t = d->emitters[e].type;
+        if (t == MSK_EMITTER_CONSTANT || t == MSK_EMITTER_ENVMAP) ++n_env;
+        if (t == MSK_EMITTER_ENVMAP) ++n_image;
+        if (t == MSK_EMITTER_POINT && d->emitters[e].mesh_id != -1) return false;
+    }
+    if (n_env > 1 || (n_image != 0) != (env != nullptr)) return false;
+    if (env) {
+        if (env->width == 0 || env->height == 0 || !env->texels || !env->weights || !is_rotation(env->to_world)) return false;
+        Scene::Envmap &m = sc->envmap;
+        m.W = env->width; m.H = env->height;
+        const size_t n = (size_t) m.W * m.H;
+        m.texels.assign(env->texels, env->texels + n * 4);
+        std::memcpy(m.R, env->to_world, sizeof(m.R));
+        bool any = false;
+        for (size_t k = 0; k < n; ++k) {
+            if (!(std::isfinite(env->weights[k]) && env->weights[k] >= 0.f) || !(std::isfinite(m.texels[k * 4 + 3]) && m.texels[k * 4 + 3] >= 0.f)) return false;
+            any |= env->weights[k] > 0.f;
+        }
+        if (!any) return false;
+        std::vector<double> rows(m.H), row(m.W);
+        m.cond.resize(m.H);
+        for (uint32_t j = 0; j < m.H; ++j) {
+            double sum = 0.0;
+            for (uint32_t i = 0; i < m.W; ++i) { row[i] = (double) env->weights[(size_t) j * m.W + i]; sum += row[i]; }      // (row sums added left to right)
+            rows[j] = sum;
+            m.cond[j] = cumulative(row);
+        }
+        m.marg = cumulative(rows);
+        sc->env_is_image = true;
+    }
+    // exactly one msk_point_desc per MSK_EMITTER_POINT emitter, in any order
+    sc->point_pos.assign(d->n_emitters, mk3(0.f, 0.f, 0.f));
+    std::vector<int> seen(d->n_emitters, 0);
+    const uint32_t n_points = em ? em->ext.n_points : 0u;
+    for (uint32_t k = 0; k < n_points; ++k) {
+        const msk_point_desc &p = em->ext.points[k];
+        if (p.emitter >= d->n_emitters || d->emitters[p.emitter].type != MSK_EMITTER_POINT || seen[p.emitter]++) return false;
+        if (!(std::isfinite(p.position[0]) && std::isfinite(p.position[1]) && std::isfinite(p.position[2]))) return false;
+        sc->point_pos[p.emitter] = mk3(p.position[0], p.position[1], p.position[2]);
+    }
+    bool any_point = false;
+    for (uint32_t e = 0; e < d->n_emitters; ++e)
+        if (d->emitters[e].type == MSK_EMITTER_POINT) { any_point = true; if (!seen[e]) return false; }
+    // at most one msk_mask_desc per entry
+    sc->masks.assign(d->n_bsdfs, Scene::Mask());
+    const uint32_t n_masks = em ? em->n_masks : 0u;
+    for (uint32_t k = 0; k < n_masks; ++k) {
+        const msk_mask_desc &md = em->masks[k];
+        if (md.bsdf >= d->n_bsdfs || sc->masks[md.bsdf].filter >= 0 || md.filter < 0 || md.filter > 2) return false;
+        Scene::Mask &m = sc->masks[md.bsdf];
+        m.filter = md.filter; m.opacity = md.opacity;
+        std::memcpy(m.to_uv, md.to_uv, sizeof(m.to_uv));
+        if (md.filter == 0) {
+            if (!(std::isfinite(md.opacity) && md.opacity >= 0.f && md.opacity <= 1.f)) return false;
+        } else {
+            if (md.width == 0 || md.height == 0 || !md.values) return false;
+            m.W = md.width; m.H = md.height;
+            m.values.assign(md.values, md.values + (size_t) m.W * m.H);
+            for (float v : m.values) if (!(std::isfinite(v) && v >= 0.f && v <= 1.f)) return false;
+        }
+        sc->any_mask = true;
+    }
+    bool any_conductor = false;
+    for (uint32_t b = 0; b < d->n_bsdfs; ++b) any_conductor |= d->bsdfs[b].type == MSK_BSDF_CONDUCTOR;
+    sc->own_density_sky = any_point || any_conductor || sc->any_mask;                    // D15
+    return true;
+}
+
+static Scene *scene_from_desc(const msk_scene_desc *d, const msk_scene_masks *em = nullptr) {
     Scene *sc = new Scene();
+    if (!scene_extensions(sc, d, em)) { delete sc; return nullptr; }
+    if (d->n_texels) sc->texels.assign(d->texels, d->texels + (size_t) d->n_texels * 3);
     sc->meshes.assign(d->meshes, d->meshes + d->n_meshes);
     sc->bsdfs.assign(d->bsdfs, d->bsdfs + d->n_bsdfs);
     sc->emitters.assign(d->emitters, d->emitters + d->n_emitters);
@@ -270,7 +393,7 @@ static Scene *scene_from_desc(const msk_scene_desc *d) {
     }
     // scene.cpp:35-41 m_environment; constant.cpp:21-28 set_scene: sphere around Scene::bbox() (bbox.h:105-112)
     for (uint32_t e = 0; e < d->n_emitters; ++e)
-        if (sc->emitters[e].type == MSK_EMITTER_CONSTANT) sc->env = (int) e;
+        if (sc->emitters[e].type == MSK_EMITTER_CONSTANT || sc->emitters[e].type == MSK_EMITTER_ENVMAP) sc->env = (int) e;
     if (sc->env >= 0) {
         V3 pmin = mk3(kInf, kInf, kInf), pmax = mk3(-kInf, -kInf, -kInf);
         for (uint32_t v = 0; v < d->n_vertices; ++v) {
@@ -312,7 +435,7 @@ struct Ray { V3 o, d; float mint, maxt; };
 struct Hit { float t, u, v; uint32_t prim; bool valid; };
 
 // How far the two oracle-side rules are from a plain Moeller-Trumbore / first-found intersector: per-thread
-// tallies, summed into g_isect by isect_flush() (the render workers and the ray batches call it), read and cleared through
+// tallies, summed into g_isect by isect_flush() (the render workers and the ray batches call it through tallies_flush()), read and cleared through
 // msk_oracle_isect_counters().  [0] closest-hit rays  [1] any-hit rays  [2] triangle tests Moeller-Trumbore accepts
 // [3] of those, rejected by the D10 bounds predicate  [4] closest-hit rays that met a D10-rejected hit NEARER than the hit
 // they report (or report none): the rays whose answer D10 can have changed, as this tree's traversal meets them
@@ -322,6 +445,23 @@ static std::atomic<uint64_t> g_isect[8];
 struct IsectTally { uint64_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0}; float rej_t = kInf; bool rej = false; };
 static thread_local IsectTally tl_isect;
 static void isect_flush() { for (int i = 0; i < 8; ++i) { g_isect[i].fetch_add(tl_isect.v[i], std::memory_order_relaxed); tl_isect.v[i] = 0; } }
+
+// Named path events (msk_oracle_path_tallies, read and clear like the intersection tallies): which branches of the path loop a
+// render reached, so that a parity scene can be shown to exercise what it is meant to exercise.
+enum PathTally { kTallyNullLobe, kTallyEmitterAfterNull, kTallyEmitterAfterDelta, kTallyEnvmapMissSmooth, kTallyPointUnoccluded, kTallyPointOccluded,
+                 kTallySkyOwnDensity, kTallyAreaHidden, kTallyRRAfterNull, kTallyTexelWrap, kTallyPoleClamp,
+                 kTallyShadowNonzero,      // next-event samples whose unoccluded term is not zero: the shadow rays the device traces
+                 kTallyDeadSample,         // BSDF samples that failed or left a zero throughput: where the device's segment count may differ by one
+                 kTallySegmentDropped,     // a sample with a lobe whose throughput is zero and no shadow ray pending: the wavefront kernels end the path, no ray
+                 kTallySegmentExtra,       // a failed sample with a shadow ray pending: the wavefront kernels keep the slot one more sweep, one (zero) ray
+                 kTallyCount };
+static std::atomic<uint64_t> g_path[kTallyCount];
+struct PathTallies { uint64_t v[kTallyCount] = {}; };
+static thread_local PathTallies tl_path;
+static inline void tally(PathTally t) { tl_path.v[t] += 1; }
+static void path_flush() { for (int i = 0; i < kTallyCount; ++i) { g_path[i].fetch_add(tl_path.v[i], std::memory_order_relaxed); tl_path.v[i] = 0; } }
+// what a render worker or a ray batch calls when it ends: this thread's intersection AND path tallies into the totals
+static void tallies_flush() { isect_flush(); path_flush(); }
 
 static inline float xor_sign(float a, uint32_t sgn) {
     uint32_t b; std::memcpy(&b, &a, 4); b ^= sgn; std::memcpy(&a, &b, 4); return a;
@@ -581,17 +721,122 @@ static Ray camera_ray(const Scene &sc, float wavelength_sample, V2 pos, S4 *wl, 
 // ===========================================================================
 // a9/a10  emitter sampling
 // ===========================================================================
-struct DirectSample { V3 p, n, d; float dist, pdf; int emitter; };
+// ---------------------------------------------------------------------------
+// the `envmap` emitter (msk_gpu.h at msk_envmap_desc; D11-D13), fp32, one operation at a time
+// ---------------------------------------------------------------------------
+static const float kEnvEps2 = 3.5527136788005009e-15f;              // eps^2, eps = 2^-24
+static const float kOneBelow = 1.f - 5.9604644775390625e-08f;       // 1 - 2^-24
+// direction -> (u, v) and sin theta: dl = R^T d
+static V2 env_dir_to_uv(const Scene::Envmap &m, V3 d, float *sin_theta) {
+    const float *r = m.R;
+    const float lx = r[0] * d.x + (r[3] * d.y + r[6] * d.z), ly = r[1] * d.x + (r[4] * d.y + r[7] * d.z), lz = r[2] * d.x + (r[5] * d.y + r[8] * d.z);
+    const float s2 = lx * lx + lz * lz;
+    float u = det_atan2(lx, -lz) / kTwoPi;
+    u = u - std::floor(u);
+    if (!(u < 1.f)) u = 0.f;
+    const float v = det_atan2(std::sqrt(s2), ly) / kPi;
+    *sin_theta = std::sqrt(s2 < kEnvEps2 ? kEnvEps2 : s2);
+    return V2{u, v};
+}
+static S4 env_texel(const Scene::Envmap &m, int j, int i, S4 wl) {
+    const float *t = &m.texels[((size_t) j * m.W + (size_t) i) * 4];
+    return srgb_model_eval(t, wl) * t[3];
+}
+// L(u, v, l) = T_e(l) * bilerp(w_k S(coeff_k, l)): u wraps, v clamps at the poles
+static S4 env_radiance(const Scene &sc, V2 uv, S4 wl) {
+    const Scene::Envmap &m = sc.envmap;
+    const int W = (int) m.W, H = (int) m.H;
+    const float px = uv.x * (float) W - 0.5f;
+    const float fi = std::floor(px), tx = px - fi;
+    int i0 = (int) fi;
+    if (i0 < 0) i0 = W - 1;
+    if (i0 >= W) i0 = 0;
+    const int i1 = i0 + 1 >= W ? 0 : i0 + 1;
+    const float py = uv.y * (float) H - 0.5f;
+    const float fj = std::floor(py), ty = py - fj;
+    const int j = (int) fj;
+    const int j0 = std::min(std::max(j, 0), H - 1), j1 = std::min(std::max(j + 1, 0), H - 1);
+    if (j < 0 || j + 1 > H - 1) tally(kTallyPoleClamp);
+    const S4 s00 = env_texel(m, j0, i0, wl), s10 = env_texel(m, j0, i1, wl), s01 = env_texel(m, j1, i0, wl), s11 = env_texel(m, j1, i1, wl);
+    const S4 a = s00 + (s10 - s00) * tx, b = s01 + (s11 - s01) * tx;
+    const S4 r = a + (b - a) * ty;
+    return regular_eval(sc.emitter_table[sc.env], wl) * r;
+}
+static float env_pdf_cell(const Scene::Envmap &m, int i, int j, float sin_theta) {
+    const float pr = m.marg[j + 1] - m.marg[j], pc = m.cond[j][i + 1] - m.cond[j][i];
+    const float p = ((pr * pc) * (float) m.W) * (float) m.H;
+    return p / (kTwoPiSqr * sin_theta);
+}
+// pdf(direction) from the uv of env_dir_to_uv: i = min((int) (u W), W - 1), j likewise
+static float env_pdf(const Scene::Envmap &m, V2 uv, float sin_theta) {
+    const int i = std::min((int) (uv.x * (float) m.W), (int) m.W - 1), j = std::min((int) (uv.y * (float) m.H), (int) m.H - 1);
+    return env_pdf_cell(m, i, j, sin_theta);
+}
+// core/distribution.h:106-116 on a table of n + 1 entries: upper bound, clamp, the reused fraction kept below 1
+static int env_search(const std::vector<float> &cdf, int n, float u, float *frac) {
+    const int k = std::min(std::max((int) (std::upper_bound(cdf.begin(), cdf.begin() + n + 1, u) - cdf.begin()) - 1, 0), n - 1);
+    const float f = (u - cdf[k]) / (cdf[k + 1] - cdf[k]);
+    *frac = kOneBelow < f ? kOneBelow : f;
+    return k;
+}
+static V3 env_sample(const Scene::Envmap &m, V2 u2, V2 *uv, float *pdf) {
+    float dv, du;
+    const int j = env_search(m.marg, (int) m.H, u2.y, &dv);
+    const int i = env_search(m.cond[j], (int) m.W, u2.x, &du);
+    const float u = ((float) i + du) / (float) m.W, v = ((float) j + dv) / (float) m.H;
+    float st, ct, sp, cp;
+    det_sincos(kPi * v, &st, &ct);
+    det_sincos(kTwoPi * u, &sp, &cp);
+    const float lx = sp * st, ly = ct, lz = -(cp * st);
+    const float s2 = lx * lx + lz * lz;
+    const float sin_theta = std::sqrt(s2 < kEnvEps2 ? kEnvEps2 : s2);
+    const float *r = m.R;
+    *uv = V2{u, v};
+    *pdf = env_pdf_cell(m, i, j, sin_theta);
+    return mk3(r[0] * lx + (r[1] * ly + r[2] * lz), r[3] * lx + (r[4] * ly + r[5] * lz), r[6] * lx + (r[7] * ly + r[8] * lz));
+}
+
+struct DirectSample { V3 p, n, d; float dist, pdf; int emitter; bool point = false; };
 
 // core/distribution.h:106-116 Distribution1D::sample / sample_reuse
 static uint32_t distr_sample(const std::vector<float> &cdf, float u) {
     auto it = std::upper_bound(cdf.begin(), cdf.end(), u);
     return (uint32_t) std::min(std::max((int) std::distance(cdf.begin(), it) - 1, 0), (int) cdf.size() - 2);
 }
+// msk_gpu.h at msk_point_desc: d = position - p; dist = sqrt(d.x d.x + (d.y d.y + d.z d.z)); inv = 1 / dist; d = d * inv; pdf = 1;
+// value(l) = (I(l) * inv) * inv.  dist == 0 gives pdf = 0 and no contribution.
+static S4 point_sample(V3 position, V3 p, S4 intensity, V3 *d_out, float *dist_out, float *pdf) {
+    const V3 d = position - p;
+    const float dist = std::sqrt(d.x * d.x + (d.y * d.y + d.z * d.z));
+    *dist_out = dist;
+    if (dist == 0.f) { *d_out = mk3(0.f, 0.f, 0.f); *pdf = 0.f; return s4(0.f); }
+    const float inv = 1.f / dist;
+    *d_out = d * inv;
+    *pdf = 1.f;
+    return (intensity * inv) * inv;
+}
 // mesh.cpp:103-133 sample_position + shape.cpp:64-78 sample_direct + area.cpp:32-45
 static DirectSample emitter_sample_direct(const Scene &sc, int e, const Interaction &ref, V2 sample,
                                           S4 wl, S4 *spec) {
     const msk_emitter_desc &em = sc.emitters[e];
+    if (em.type == MSK_EMITTER_POINT) {
+        DirectSample ds;
+        *spec = point_sample(sc.point_pos[e], ref.p, emitter_radiance(sc, e, wl), &ds.d, &ds.dist, &ds.pdf);
+        ds.p = sc.point_pos[e]; ds.n = -ds.d; ds.emitter = e; ds.point = true;
+        return ds;
+    }
+    if (em.type == MSK_EMITTER_ENVMAP) {
+        // msk_gpu.h at msk_envmap_desc: next-event value = L(uv) / pdf_omega, dist = 2 * env_radius; pdf 0 gives no contribution
+        DirectSample ds;
+        V2 uv;
+        ds.d = env_sample(sc.envmap, sample, &uv, &ds.pdf);
+        ds.dist = 2.f * sc.env_radius;
+        ds.p = ref.p + ds.d * ds.dist;
+        ds.n = -ds.d;
+        ds.emitter = e;
+        *spec = ds.pdf != 0.f ? env_radiance(sc, uv, wl) / ds.pdf : s4(0.f);
+        return ds;
+    }
     if (em.type == MSK_EMITTER_CONSTANT) {
         // constant.cpp:53-72.  D8: the reference evaluates the radiance on a default-constructed interaction
         // (uninitialised wavelengths); the wavelengths of the reference point are used, as area.cpp:35-36 does.
@@ -643,7 +888,7 @@ static DirectSample emitter_sample_direct(const Scene &sc, int e, const Interact
 }
 // scene.cpp:68-103
 static DirectSample sample_emitter_direct(const Scene &sc, const Interaction &ref, V2 sample, S4 wl,
-                                          S4 *spec, uint64_t *shadow_rays) {
+                                          S4 *spec, uint64_t *shadow_rays, S4 *unoccluded = nullptr, bool *occluded_out = nullptr) {
     DirectSample ds; ds.pdf = 0; ds.emitter = -1;
     size_t n = sc.emitters.size();
     if (n == 0) { *spec = s4(0.f); return ds; }
@@ -664,6 +909,8 @@ static DirectSample sample_emitter_direct(const Scene &sc, const Interaction &re
         if (g_trace_path)
             std::printf("  shadow ray o %.9g %.9g %.9g tmin %.9g d %.9g %.9g %.9g tmax %.9g occluded %d\n", ray.o.x, ray.o.y, ray.o.z, ray.mint,
                         ray.d.x, ray.d.y, ray.d.z, ray.maxt, (int) occluded);
+        if (unoccluded) *unoccluded = *spec;             // (tallies only)
+        if (occluded_out) *occluded_out = occluded;
         if (occluded) *spec = s4(0.f);
     }
     return ds;
@@ -707,7 +954,8 @@ static float mis_weight(float pdf_a, float pdf_b) {
 // ===========================================================================
 struct BSDFSampleRec { V3 wo; float pdf, eta; uint32_t sampled_type; };   // render/bsdf.h:60-80
 enum : uint32_t { kDiffuseReflection = 1u, kGlossyReflection = 2u, kGlossyTransmission = 4u, kDeltaReflection = 8u, kDeltaTransmission = 16u,
-                  kDelta = kDeltaReflection | kDeltaTransmission };   // BSDFFlags::Delta: what path.cpp:104 asks of sampled_type
+                  kDelta = kDeltaReflection | kDeltaTransmission,       // BSDFFlags::Delta: what path.cpp:104 asks of sampled_type
+                  kNull = 32u };                                        // a mask's null lobe (BSDFFlags::Null)
 
 static S4 spectrum_eval(const Scene &sc, const msk_spectrum_desc &sp, S4 wl) {
     if (sp.regular) return regular_eval(sc.regular[sp.regular - 1], wl);          // RegularSpectrum::eval (regular.cpp:148)
@@ -860,7 +1108,64 @@ static S4 dielectric_sample(const Scene &sc, const msk_bsdf_desc &b, V3 wi, V2 s
     return spectrum_eval(sc, b.specular_transmittance, wl) * eta_ti * eta_ti;           // :57-58,61,67-70
 }
 // BSDFFlags::Smooth of bsdf->flags() (path.cpp:56): every BSDF here but `dielectric`, whose two components are delta (dielectric.cpp:21-23)
-static bool bsdf_has_smooth_lobe(const msk_bsdf_desc &b) { return b.type != MSK_BSDF_DIELECTRIC; }
+// and `conductor`, one delta reflection lobe (msk_gpu.h at MSK_BSDF_CONDUCTOR: "no next-event sample is taken at such a hit")
+static bool bsdf_has_smooth_lobe(const msk_bsdf_desc &b) { return b.type != MSK_BSDF_DIELECTRIC && b.type != MSK_BSDF_CONDUCTOR; }
+// msk_gpu.h at MSK_BSDF_CONDUCTOR: cos_i <= 0 fails (no direction); otherwise wo = (-wi.x, -wi.y, wi.z), pdf = 1, eta = 1,
+// value(l) = specular_reflectance(l) * fresnel_conductor(cos_i, eta(l), k(l)), one product
+static S4 conductor_sample(const Scene &sc, const msk_bsdf_desc &b, V3 wi, S4 wl, BSDFSampleRec *bs) {
+    const float cos_i = wi.z;
+    if (!(cos_i > 0.f)) return s4(0.f);
+    bs->wo = mk3(-wi.x, -wi.y, wi.z);
+    bs->pdf = 1.f;
+    bs->eta = 1.f;
+    bs->sampled_type = kDeltaReflection;
+    return spectrum_eval(sc, b.specular_reflectance, wl) * fresnel_conductor4(cos_i, spectrum_eval(sc, b.eta, wl), spectrum_eval(sc, b.k, wl));
+}
+
+// msk_gpu.h at msk_texture_desc: uv' = to_uv (u, v, 1), each row a0 + (a1 + a2); f = x - floor(x) (repeat; can be exactly 1)
+static V2 texture_frac_uv(const float *to_uv, V2 uv) {
+    const float x = to_uv[0] * uv.x + (to_uv[1] * uv.y + to_uv[2] * 1.f);
+    const float y = to_uv[3] * uv.x + (to_uv[4] * uv.y + to_uv[5] * 1.f);
+    return V2{x - std::floor(x), y - std::floor(y)};
+}
+static int nearest_axis(float f, int n) { return std::min((int) (f * (float) n), n - 1); }
+// bilinear: px = f n - 0.5; i0 = floor(px); t = px - i0; i0 < 0 -> n - 1; i0 >= n -> 0; i1 = i0 + 1, i1 >= n -> 0
+static void bilinear_axis(float f, int n, int *i0, int *i1, float *t, bool *wrapped) {
+    const float p = f * (float) n - 0.5f;
+    const float fl = std::floor(p);
+    *t = p - fl;
+    int a = (int) fl;
+    if (a < 0) { a = n - 1; *wrapped = true; }
+    if (a >= n) { a = 0; *wrapped = true; }
+    int b = a + 1;
+    if (b >= n) { b = 0; *wrapped = true; }
+    *i0 = a; *i1 = b;
+}
+// the lookup of MSK_TEXTURE_BITMAP / _NEAREST over any texel function: what a bitmap's reflectance and a mask's opacity share,
+// "word for word"; value = a + ty (b - a) with a = s00 + tx (s10 - s00), b = s01 + tx (s11 - s01)
+template <typename T, typename Texel> static T image_lookup(const float *to_uv, int W, int H, bool bilinear, V2 uv, Texel texel) {
+    const V2 f = texture_frac_uv(to_uv, uv);
+    if (!bilinear) return texel(nearest_axis(f.y, H), nearest_axis(f.x, W));
+    int i0, i1, j0, j1; float tx, ty; bool wrapped = false;
+    bilinear_axis(f.x, W, &i0, &i1, &tx, &wrapped);
+    bilinear_axis(f.y, H, &j0, &j1, &ty, &wrapped);
+    if (wrapped) tally(kTallyTexelWrap);
+    const T s00 = texel(j0, i0), s10 = texel(j0, i1), s01 = texel(j1, i0), s11 = texel(j1, i1);
+    const T a = s00 + (s10 - s00) * tx, b = s01 + (s11 - s01) * tx;
+    return a + (b - a) * ty;
+}
+static S4 bitmap_eval(const Scene &sc, const msk_texture_desc &t, V2 uv, S4 wl) {
+    const float *pool = sc.texels.data() + (size_t) t.first_texel * 3;
+    return image_lookup<S4>(t.to_uv, (int) t.width, (int) t.height, t.type == MSK_TEXTURE_BITMAP, uv,
+                            [&](int j, int i) { return srgb_model_eval(pool + ((size_t) j * t.width + (size_t) i) * 3, wl); });
+}
+// msk_gpu.h at msk_mask_desc: the opacity of entry `bsdf_id` at uv; 1 for an entry without a mask
+static float mask_opacity(const Scene &sc, int bsdf_id, V2 uv) {
+    if (sc.masks.empty() || sc.masks[bsdf_id].filter < 0) return 1.f;
+    const Scene::Mask &m = sc.masks[bsdf_id];
+    if (m.filter == 0) return m.opacity;
+    return image_lookup<float>(m.to_uv, (int) m.W, (int) m.H, m.filter == 2, uv, [&](int j, int i) { return m.values[(size_t) j * m.W + (size_t) i]; });
+}
 
 // textures/checkerboard.cpp:24-33: which of the two colours the texture shows at uv.  The 3x3 product of
 // Transform3f::transform_affine_point (core/transform.h:41-48) is Eigen's coefficient-based one: each row is
@@ -873,13 +1178,16 @@ static const float *checkerboard_lookup(const msk_texture_desc &t, V2 uv) {
 }
 // SmoothDiffuse::m_reflectance->eval(si) (diffuse.cpp:31,44): the coefficients of the spectrum the reflectance
 // texture shows at the hit
-struct Reflectance { const float *coeff; float scale; uint32_t regular; };
+struct Reflectance { const float *coeff; float scale; uint32_t regular; const msk_texture_desc *bitmap = nullptr; V2 uv = V2{0.f, 0.f}; };
 static Reflectance reflectance_at(const Scene &sc, const msk_bsdf_desc &b, V2 uv) {
     if (b.reflectance_regular) return {b.reflectance, 1.f, b.reflectance_regular};
     if (b.reflectance_texture == 0) return {b.reflectance, b.reflectance_scale, 0u};
-    return {checkerboard_lookup(sc.textures[b.reflectance_texture - 1], uv), 1.f, 0u};
+    const msk_texture_desc &t = sc.textures[b.reflectance_texture - 1];
+    if (t.type == MSK_TEXTURE_BITMAP || t.type == MSK_TEXTURE_BITMAP_NEAREST) return {b.reflectance, 1.f, 0u, &t, uv};   // a spectrum, not coefficients
+    return {checkerboard_lookup(t, uv), 1.f, 0u};
 }
 static S4 reflectance_eval(const Scene &sc, Reflectance r, S4 wl) {
+    if (r.bitmap) return bitmap_eval(sc, *r.bitmap, r.uv, wl);
     if (r.regular) return regular_eval(sc.regular[r.regular - 1], wl);
     return srgb_model_eval(r.coeff, wl) * r.scale;
 }
@@ -897,6 +1205,7 @@ static void bsdf_eval_pdf(const Scene &sc, const msk_bsdf_desc &b, Reflectance r
     }
     if (b.type == MSK_BSDF_ROUGHDIELECTRIC) { roughdielectric_eval_pdf(sc, b, wi, wo, wl, val, pdf); return; }
     if (b.type == MSK_BSDF_DIELECTRIC) return;                         // dielectric.cpp:74-82: eval and pdf are zero
+    if (b.type == MSK_BSDF_CONDUCTOR) return;                          // msk_gpu.h at MSK_BSDF_CONDUCTOR: eval and pdf are zero
     const float au = clamp_alpha(b.alpha_u), av = clamp_alpha(b.alpha_v);
     // roughconductor.cpp:82-98 eval
     if (cos_i > 0.f && cos_o > 0.f) {
@@ -920,6 +1229,7 @@ static S4 bsdf_sample(const Scene &sc, const msk_bsdf_desc &b, Reflectance refl,
     bs->wo = mk3(0, 0, 0); bs->pdf = 0.f; bs->eta = 1.f; bs->sampled_type = 0;       // render/bsdf.h:75-77
     if (b.type == MSK_BSDF_ROUGHDIELECTRIC) return roughdielectric_sample(sc, b, wi, sample1, sample, wl, bs);
     if (b.type == MSK_BSDF_DIELECTRIC) return dielectric_sample(sc, b, wi, sample, wl, bs);
+    if (b.type == MSK_BSDF_CONDUCTOR) return conductor_sample(sc, b, wi, wl, bs);
     float cos_i = wi.z;
     if (cos_i <= 0.f) return s4(0.f);
     if (b.type == MSK_BSDF_DIFFUSE) {                                  // diffuse.cpp:18-33
@@ -950,6 +1260,13 @@ static const msk_bsdf_desc *bsdf_side(const Scene &sc, const msk_bsdf_desc &b, V
 
 struct Counters { uint64_t samples = 0, segments = 0, shadow_rays = 0, invalid = 0; };
 
+// what a ray that leaves the scene in direction d sees: the constant sky's radiance, or the image's L(d) (msk_gpu.h at msk_envmap_desc)
+static S4 environment_radiance(const Scene &sc, V3 d, S4 wl) {
+    if (!sc.env_is_image) return emitter_radiance(sc, sc.env, wl);
+    float sin_theta;
+    return env_radiance(sc, env_dir_to_uv(sc.envmap, d, &sin_theta), wl);
+}
+
 // ===========================================================================
 // a5  PathTracer::sample (integrators/path.cpp:23-125) with a11 diffuse BSDF
 //     (bsdfs/diffuse.cpp:18-57) inlined where the reference makes virtual calls
@@ -966,7 +1283,7 @@ static S4 path_sample(const Scene &sc, Sampler &sampler, Ray ray, S4 wl, const m
     for (int depth = 1; depth <= max_depth || max_depth < 0; depth++) {
         if (!si.valid()) {                                         // path.cpp:34-41
             if (depth == 1 && (!hide_emitter || scattered) && sc.env >= 0)
-                result = result + throughput * emitter_radiance(sc, sc.env, wl);
+                result = result + throughput * environment_radiance(sc, ray.d, wl);
             break;
         }
         int emitter = sc.meshes[si.mesh].emitter_id;
@@ -974,14 +1291,21 @@ static S4 path_sample(const Scene &sc, Sampler &sampler, Ray ray, S4 wl, const m
             result = result + throughput * emitter_eval(sc, emitter, si, wl);
         if (depth >= max_depth && max_depth > 0) break;
         const uint32_t base = 3 + 3 * (uint32_t) (depth - 1);
-        const msk_bsdf_desc &bsdf = sc.bsdfs[sc.meshes[si.mesh].bsdf_id];
+        const int bsdf_id = sc.meshes[si.mesh].bsdf_id;
+        const msk_bsdf_desc &bsdf = sc.bsdfs[bsdf_id];
+        // msk_gpu.h at msk_mask_desc: the opacity of the entry the mesh names, before the twosided flip; in a scene that holds a
+        // mask every entry has one (1 without a mask, where u.x / 1 and 1 * pdf are exact)
+        const bool masked = sc.any_mask;
+        const float opacity = masked ? mask_opacity(sc, bsdf_id, si.uv) : 1.f;
         // ---- direct illumination (path.cpp:56-67): only for a BSDF with a Smooth lobe.  Without one the sample is not drawn
         // (MSK_RNG_PCG_BLOCK: no next2d(); MSK_RNG_COUNTER: the pair base + 0 stays unused) and `ds` stays default-constructed
         DirectSample ds; ds.pdf = 0; ds.emitter = -1;
+        bool has_shadow = false;               // (tallies only) this bounce's next-event term is not zero: the device traces its shadow ray
         if (bsdf_has_smooth_lobe(bsdf)) {
             V2 u; sampler.pair(base + 0, &u.x, &u.y);
-            S4 emitter_val;
-            ds = sample_emitter_direct(sc, si, u, wl, &emitter_val, &cnt.shadow_rays);
+            S4 emitter_val, unoccluded = s4(0.f);
+            bool occluded = false;
+            ds = sample_emitter_direct(sc, si, u, wl, &emitter_val, &cnt.shadow_rays, &unoccluded, &occluded);
             if (ds.pdf != 0.f) {
                 V3 wo = si.sh.to_local(ds.d), wi_s = si.wi;
                 bool flipped;
@@ -989,7 +1313,14 @@ static S4 path_sample(const Scene &sc, Sampler &sampler, Ray ray, S4 wl, const m
                 if (flipped) wo.z *= -1.f;
                 S4 bsdf_val; float bsdf_pdf;
                 bsdf_eval_pdf(sc, *bb, reflectance_at(sc, *bb, si.uv), wi_s, wo, wl, &bsdf_val, &bsdf_pdf);
-                float weight = mis_weight(ds.pdf, bsdf_pdf);
+                if (masked) { bsdf_val = bsdf_val * opacity; bsdf_pdf = opacity * bsdf_pdf; }      // eval = a eval_X, pdf = a pdf_X
+                // D14: a delta emitter cannot be reached by a BSDF sample: weight 1
+                float weight = ds.point ? 1.f : mis_weight(ds.pdf, bsdf_pdf);
+                {
+                    const S4 term = throughput * unoccluded * bsdf_val * weight;
+                    if (term.v[0] != 0.f || term.v[1] != 0.f || term.v[2] != 0.f || term.v[3] != 0.f) { has_shadow = true; tally(kTallyShadowNonzero); }
+                    if (ds.point) tally(occluded ? kTallyPointOccluded : kTallyPointUnoccluded);
+                }
                 if (g_trace_path)
                     std::printf("  d%d NEE: ds.pdf %.9g bsdf_pdf %.9g w %.9g emitter_val %.9g bsdf_val %.9g %.9g %.9g %.9g thr %.9g wo_local %.9g %.9g %.9g wi %.9g %.9g %.9g\n", depth, ds.pdf,
                                 bsdf_pdf, weight, emitter_val.v[0], bsdf_val.v[0], bsdf_val.v[1], bsdf_val.v[2], bsdf_val.v[3], throughput.v[0], wo.x, wo.y, wo.z, wi_s.x, wi_s.y, wi_s.z);
@@ -1001,17 +1332,38 @@ static S4 path_sample(const Scene &sc, Sampler &sampler, Ray ray, S4 wl, const m
         V2 u2; sampler.pair(base + 2, &u2.x, &u2.y);
         BSDFSampleRec bs;
         S4 bsdf_val;
-        {
+        // mask.cpp:43-44: the lobe is picked by u.x; u.x < a: X with u.x / a, else the null lobe (pdf = 1 - a, value 1, eta = 1, delta)
+        bool null_lobe = false;
+        if (masked) { null_lobe = !(u2.x < opacity); if (!null_lobe) u2.x = u2.x / opacity; }
+        if (null_lobe) {
+            bs.wo = mk3(0.f, 0.f, 0.f); bs.pdf = 1.f - opacity; bs.eta = 1.f; bs.sampled_type = kNull;
+            bsdf_val = s4(1.f);
+            tally(kTallyNullLobe);
+        } else {
             V3 wi_s = si.wi; bool flipped;
             const msk_bsdf_desc *bb = bsdf_side(sc, bsdf, &wi_s, &flipped);
             bsdf_val = bsdf_sample(sc, *bb, reflectance_at(sc, *bb, si.uv), wi_s, sample1, u2, wl, &bs);
             if (flipped) bs.wo.z *= -1.f;
+            if (masked) bs.pdf = opacity * bs.pdf;                 // D16: pdf = a pdf_X, the value stays X's
         }
         const V3 bs_wo = bs.wo; const float bs_pdf = bs.pdf, bs_eta = bs.eta;
         const uint32_t sampled_type = bs.sampled_type;
-        scattered |= true;   // path.cpp:73: sampled_type (0 on failure) != Null is always true
-        V3 wo = si.sh.to_world(bs_wo);
-        bool hit_emitter = false;
+        {   // (tallies only) where the device's segment count parts from `if (sampled_type) ++cnt.segments` below
+            const S4 next = throughput * bsdf_val;
+            const bool dead = !(next.v[0] != 0.f || next.v[1] != 0.f || next.v[2] != 0.f || next.v[3] != 0.f);
+            if (!sampled_type || dead) tally(kTallyDeadSample);
+            if (sampled_type && dead && !has_shadow) tally(kTallySegmentDropped);
+            if (!sampled_type && has_shadow) tally(kTallySegmentExtra);
+        }
+        // path.cpp:73: sampled_type (0 on failure) != Null is true for every sample but a mask's null lobe
+        if (!null_lobe) scattered = true;
+        // D18: under hide_emitters an emitter of any kind reached while `scattered` is false adds nothing (only a mask's null lobe
+        // leaves it false after a bounce).  "Adds nothing", not path.cpp:92-93's `break`: a null bounce takes Russian roulette like
+        // any other (msk_gpu.h at msk_mask_desc), so MSK_RNG_PCG_BLOCK draws that number before the path ends on the miss.
+        const bool hidden = hide_emitter && !scattered;
+        // the null lobe: the incoming ray's own world direction, bit for bit (no frame round trip)
+        V3 wo = null_lobe ? ray.d : si.sh.to_world(bs_wo);
+        bool hit_emitter = false, env_hit = false;
         S4 value = s4(0.f);
         ray = Ray{si.p, wo, (1.f + max_abs(si.p)) * kRayEpsilon, kInf};   // interaction.h:40-44
         if (sampled_type) ++cnt.segments;     // statistics only: the zero-direction ray of a failed sample is not counted
@@ -1021,13 +1373,12 @@ static S4 path_sample(const Scene &sc, Sampler &sampler, Ray ray, S4 wl, const m
             if (em >= 0) {
                 value = emitter_eval(sc, em, si_bsdf, wl);
                 // records.cpp:7-14 set_query
-                ds.p = si_bsdf.p; ds.n = si_bsdf.sh.n; ds.emitter = em; ds.d = ray.d; ds.dist = si_bsdf.t;
+                ds.p = si_bsdf.p; ds.n = si_bsdf.sh.n; ds.emitter = em; ds.d = ray.d; ds.dist = si_bsdf.t; ds.point = false;
                 hit_emitter = true;
             }
         } else if (sc.env >= 0) {                                  // path.cpp:90-95
-            if (hide_emitter && !scattered) break;
-            value = emitter_radiance(sc, sc.env, wl);
-            hit_emitter = true;            // `ds` is NOT re-queried: the MIS weight below uses the NEE sample's record
+            value = environment_radiance(sc, ray.d, wl);
+            hit_emitter = env_hit = true;  // `ds` is NOT re-queried: D9's MIS weight below uses the NEE sample's record (but D12, D15)
         } else {
             break;                                                 // path.cpp:96-97
         }
@@ -1038,14 +1389,33 @@ static S4 path_sample(const Scene &sc, Sampler &sampler, Ray ray, S4 wl, const m
                         throughput.v[0], throughput.v[1], throughput.v[2], throughput.v[3], (int) si_bsdf.valid(), si_bsdf.t, (int) hit_emitter);
         eta *= bs_eta;
         if (hit_emitter) {
-            // path.cpp:104-106: a delta lobe has no emitter pdf (and after one `ds` may hold no emitter at all)
-            float emitter_pdf = !(sampled_type & kDelta) ? pdf_emitter_direct(sc, ds) : 0.f;
-            result = result + throughput * value * mis_weight(bs_pdf, emitter_pdf);
+            // path.cpp:104-106: a delta lobe has no emitter pdf (and after one `ds` may hold no emitter at all); "the last bounce
+            // was delta" holds when the null lobe was taken or X is delta (msk_gpu.h at msk_mask_desc)
+            const bool delta = (sampled_type & (kDelta | kNull)) != 0u || !bsdf_has_smooth_lobe(bsdf);
+            const size_t n_em = sc.emitters.size();
+            float emitter_pdf = 0.f;
+            if (delta) emitter_pdf = 0.f;
+            else if (env_hit && sc.env_is_image) {                 // D12: the density of the ray's own direction
+                float sin_theta;
+                const V2 uv = env_dir_to_uv(sc.envmap, ray.d, &sin_theta);
+                emitter_pdf = env_pdf(sc.envmap, uv, sin_theta);
+                if (n_em != 1) emitter_pdf = emitter_pdf * (1.f / n_em);
+            } else if (env_hit && sc.own_density_sky) {            // D15
+                emitter_pdf = kInvFourPi;
+                if (n_em != 1) emitter_pdf = emitter_pdf * (1.f / n_em);
+                tally(kTallySkyOwnDensity);
+            } else emitter_pdf = pdf_emitter_direct(sc, ds);
+            const float weight = mis_weight(bs_pdf, emitter_pdf);
+            if (null_lobe) tally(kTallyEmitterAfterNull);
+            if (sampled_type & kDelta) tally(kTallyEmitterAfterDelta);
+            if (env_hit && sc.env_is_image && !delta && weight > 0.f && weight < 1.f) tally(kTallyEnvmapMissSmooth);
+            if (hidden) { if (!env_hit) tally(kTallyAreaHidden); }
+            else result = result + throughput * value * weight;
         }
         si = si_bsdf;
         if (depth + 1 >= rr_depth) {                               // path.cpp:116-122
             float q = std::min(max4(throughput) * eta * eta, 0.95f);
-            if (sampler.single(base + 1, 1) >= q) break;
+            if (sampler.single(base + 1, 1) >= q) { if (null_lobe) tally(kTallyRRAfterNull); break; }
             throughput = throughput / q;
         }
     }
@@ -1246,7 +1616,7 @@ static void render(const Scene &sc, const msk_render_params &prm, float *film, C
         }
         std::lock_guard<std::mutex> g(mtx);
         total->samples += cnt.samples; total->segments += cnt.segments; total->shadow_rays += cnt.shadow_rays; total->invalid += cnt.invalid;
-        isect_flush();
+        tallies_flush();
     };
     std::vector<std::thread> pool;
     for (int i = 0; i < std::max(1, n_threads); ++i) pool.emplace_back(worker);
@@ -1267,17 +1637,110 @@ template <typename F> static void for_rays(uint64_t n, F body) {
     unsigned nt = std::thread::hardware_concurrency();
     if (const char *e = getenv("MSK_ORACLE_THREADS")) nt = (unsigned) atoi(e);
     nt = std::max(1u, std::min(nt, 64u));
-    if (n < 4096 || nt == 1) { for (uint64_t i = 0; i < n; ++i) body(i); orc::isect_flush(); return; }
+    if (n < 4096 || nt == 1) { for (uint64_t i = 0; i < n; ++i) body(i); orc::tallies_flush(); return; }
     std::vector<std::thread> pool;
     std::atomic<uint64_t> next{0};
     for (unsigned t = 0; t < nt; ++t)
-        pool.emplace_back([&]() { for (;;) { const uint64_t b = next.fetch_add(256); if (b >= n) break; for (uint64_t i = b; i < std::min(n, b + 256); ++i) body(i); } orc::isect_flush(); });
+        pool.emplace_back([&]() { for (;;) { const uint64_t b = next.fetch_add(256); if (b >= n) break; for (uint64_t i = b; i < std::min(n, b + 256); ++i) body(i); } orc::tallies_flush(); });
     for (auto &t : pool) t.join();
 }
 using namespace orc;
 extern "C" {
 
-void *msk_oracle_scene_create(const msk_scene_desc *d) { return scene_from_desc(d); }
+// the ABI's own structs; NULL for what the library refuses at scene creation (scene_extensions)
+void *msk_oracle_scene_create_masks(const msk_scene_desc *d, const msk_scene_masks *em) { return scene_from_desc(d, em); }
+void *msk_oracle_scene_create(const msk_scene_desc *d) { return msk_oracle_scene_create_masks(d, nullptr); }
+// reads and clears the path tallies (see PathTally): out receives msk_oracle_path_tally_count() values
+int msk_oracle_path_tally_count() { return (int) kTallyCount; }
+void msk_oracle_path_tallies(uint64_t *out) { path_flush(); for (int i = 0; i < kTallyCount; ++i) out[i] = g_path[i].exchange(0); }
+
+// ---- known-answer hooks of the features restated from include/msk_gpu.h (shaped like msk_oracle_bsdf_sample2) ----
+static S4 load4(const float *p) { S4 r; for (int i = 0; i < 4; ++i) r.v[i] = p[i]; return r; }
+static void store4(float *p, S4 v) { for (int i = 0; i < 4; ++i) p[i] = v.v[i]; }
+// texture `texture` (1-based) of the scene at uv, four wavelengths: what a diffuse BSDF's reflectance is there (scale 1)
+void msk_oracle_eval_texture(void *s, uint32_t texture, const float *uv2, const float *wl4, float *out4) {
+    const Scene &sc = *(Scene *) s;
+    msk_bsdf_desc b{}; b.reflectance_texture = texture; b.reflectance_scale = 1.f;
+    store4(out4, reflectance_eval(sc, reflectance_at(sc, b, V2{uv2[0], uv2[1]}), load4(wl4)));
+}
+int msk_oracle_env_eval(void *s, const float *dir3, const float *wl4, float *out_radiance4, float *out_pdf) {
+    const Scene &sc = *(Scene *) s;
+    if (!sc.env_is_image) return -1;
+    float sin_theta;
+    const V2 uv = env_dir_to_uv(sc.envmap, mk3(dir3[0], dir3[1], dir3[2]), &sin_theta);
+    store4(out_radiance4, env_radiance(sc, uv, load4(wl4)));
+    *out_pdf = env_pdf(sc.envmap, uv, sin_theta);
+    return 0;
+}
+int msk_oracle_env_sample(void *s, const float *u2, float *out_dir3, float *out_uv2, float *out_pdf) {
+    const Scene &sc = *(Scene *) s;
+    if (!sc.env_is_image) return -1;
+    V2 uv;
+    const V3 d = env_sample(sc.envmap, V2{u2[0], u2[1]}, &uv, out_pdf);
+    out_dir3[0] = d.x; out_dir3[1] = d.y; out_dir3[2] = d.z; out_uv2[0] = uv.x; out_uv2[1] = uv.y;
+    return 0;
+}
+// the next-event sample of point emitter `emitter` from p: out_d_dist4 = {d, dist}, out_value4 (without the light-selection factor)
+int msk_oracle_point_sample(void *s, uint32_t emitter, const float *p3, const float *wl4, float *out_d_dist4, float *out_value4) {
+    const Scene &sc = *(Scene *) s;
+    if (emitter >= sc.emitters.size() || sc.emitters[emitter].type != MSK_EMITTER_POINT) return -1;
+    V3 d; float dist, pdf;
+    const S4 v = point_sample(sc.point_pos[emitter], mk3(p3[0], p3[1], p3[2]), emitter_radiance(sc, (int) emitter, load4(wl4)), &d, &dist, &pdf);
+    out_d_dist4[0] = d.x; out_d_dist4[1] = d.y; out_d_dist4[2] = d.z; out_d_dist4[3] = dist;
+    store4(out_value4, v);
+    return 0;
+}
+// the delta lobe's value of conductor `bsdf` for cos_theta_i (zeros for cos_i <= 0)
+int msk_oracle_conductor_sample(void *s, uint32_t bsdf, float cos_theta_i, const float *wl4, float *out_value4) {
+    const Scene &sc = *(Scene *) s;
+    if (bsdf >= sc.bsdfs.size() || sc.bsdfs[bsdf].type != MSK_BSDF_CONDUCTOR) return -1;
+    BSDFSampleRec bs; bs.wo = mk3(0, 0, 0); bs.pdf = 0.f; bs.eta = 1.f; bs.sampled_type = 0;
+    const float st = std::sqrt(std::max(0.f, 1.f - cos_theta_i * cos_theta_i));
+    store4(out_value4, conductor_sample(sc, sc.bsdfs[bsdf], mk3(st, 0.f, cos_theta_i), load4(wl4), &bs));
+    return 0;
+}
+// sample() / eval() of the decorated entry `bsdf` (an entry without a mask: opacity 1) as msk_gpu_mask_sample / _mask_eval give them:
+// out_wo_pdf4 = {wo, pdf} (the null lobe: wo = -wi), out_flags4 = {eta, delta, null lobe, a direction was produced}
+int msk_oracle_mask_sample(void *s, uint32_t bsdf, const float *uv2, const float *wi3, const float *sample1_u3, const float *wl4,
+                           float *out_wo_pdf4, float *out_value4, float *out_flags4) {
+    const Scene &sc = *(Scene *) s;
+    if (bsdf >= sc.bsdfs.size()) return -1;
+    const V2 uv{uv2[0], uv2[1]};
+    const float a = mask_opacity(sc, (int) bsdf, uv);
+    V3 wi = mk3(wi3[0], wi3[1], wi3[2]);
+    V2 u{sample1_u3[1], sample1_u3[2]};
+    const S4 wl = load4(wl4);
+    BSDFSampleRec bs; S4 value;
+    const bool null_lobe = !(u.x < a);
+    if (null_lobe) {
+        bs.wo = -wi; bs.pdf = 1.f - a; bs.eta = 1.f; bs.sampled_type = kNull; value = s4(1.f);
+    } else {
+        u.x = u.x / a;
+        bool flipped; const msk_bsdf_desc *bb = bsdf_side(sc, sc.bsdfs[bsdf], &wi, &flipped);
+        value = bsdf_sample(sc, *bb, reflectance_at(sc, *bb, uv), wi, sample1_u3[0], u, wl, &bs);
+        if (flipped) bs.wo.z *= -1.f;
+        bs.pdf = a * bs.pdf;
+    }
+    out_wo_pdf4[0] = bs.wo.x; out_wo_pdf4[1] = bs.wo.y; out_wo_pdf4[2] = bs.wo.z; out_wo_pdf4[3] = bs.pdf;
+    store4(out_value4, value);
+    out_flags4[0] = bs.eta; out_flags4[1] = (null_lobe || !bsdf_has_smooth_lobe(sc.bsdfs[bsdf])) ? 1.f : 0.f;
+    out_flags4[2] = null_lobe ? 1.f : 0.f; out_flags4[3] = bs.sampled_type ? 1.f : 0.f;
+    return 0;
+}
+int msk_oracle_mask_eval(void *s, uint32_t bsdf, const float *uv2, const float *wi3, const float *wo3, const float *wl4, float *out_a_pdf2, float *out_value4) {
+    const Scene &sc = *(Scene *) s;
+    if (bsdf >= sc.bsdfs.size()) return -1;
+    const V2 uv{uv2[0], uv2[1]};
+    const float a = mask_opacity(sc, (int) bsdf, uv);
+    V3 wi = mk3(wi3[0], wi3[1], wi3[2]), wo = mk3(wo3[0], wo3[1], wo3[2]);
+    bool flipped; const msk_bsdf_desc *bb = bsdf_side(sc, sc.bsdfs[bsdf], &wi, &flipped);
+    if (flipped) wo.z *= -1.f;
+    S4 v; float pdf;
+    bsdf_eval_pdf(sc, *bb, reflectance_at(sc, *bb, uv), wi, wo, load4(wl4), &v, &pdf);
+    out_a_pdf2[0] = a; out_a_pdf2[1] = a * pdf;
+    store4(out_value4, v * a);
+    return 0;
+}
 void msk_oracle_scene_destroy(void *s) { delete (Scene *) s; }
 void msk_oracle_set_bvh(void *s, int on) { ((Scene *) s)->use_bvh = on; }
 void msk_oracle_set_libm(int on) { g_use_libm = on; }

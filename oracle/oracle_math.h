@@ -234,6 +234,15 @@ static inline float det_tan(float phi) {
     const double sy = det_sin_poly(y), cy = det_cos_poly(y);
     return (float) ((k & 1) ? -cy / sy : sy / cy);
 }
+// msk_gpu.h at msk_envmap_desc: atan2 from det_atan on an fp32 quotient; pi, 2 pi and 2 pi^2 are the fp32 constants
+static const float kTwoPi = 2.f * kPi;
+static const float kTwoPiSqr = 2.f * (kPi * kPi);
+static inline float det_atan2(float y, float x) {
+    if (x == 0.f) return y > 0.f ? kPi * 0.5f : y < 0.f ? -(kPi * 0.5f) : 0.f;
+    const float r = det_atan(y / x);
+    if (x < 0.f) return y >= 0.f ? r + kPi : r - kPi;
+    return r;
+}
 
 // ---------------------------------------------------------------------------
 // PCG32 — core/mathutils.h:85-143

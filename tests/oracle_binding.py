@@ -20,7 +20,18 @@ class Oracle:
         vp = C.c_void_p
         lib.msk_oracle_scene_create.restype = vp
         lib.msk_oracle_scene_create.argtypes = [C.POINTER(abi.SceneDesc)]
+        lib.msk_oracle_scene_create_masks.restype = vp
+        lib.msk_oracle_scene_create_masks.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(abi.SceneMasks)]
         lib.msk_oracle_scene_destroy.argtypes = [vp]
+        lib.msk_oracle_path_tally_count.restype = C.c_int
+        lib.msk_oracle_path_tallies.argtypes = [vp]
+        lib.msk_oracle_eval_texture.argtypes = [vp, C.c_uint32, vp, vp, vp]
+        lib.msk_oracle_env_eval.argtypes = [vp, vp, vp, vp, vp]
+        lib.msk_oracle_env_sample.argtypes = [vp, vp, vp, vp, vp]
+        lib.msk_oracle_point_sample.argtypes = [vp, C.c_uint32, vp, vp, vp, vp]
+        lib.msk_oracle_conductor_sample.argtypes = [vp, C.c_uint32, C.c_float, vp, vp]
+        lib.msk_oracle_mask_sample.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
+        lib.msk_oracle_mask_eval.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
         lib.msk_oracle_set_bvh.argtypes = [vp, C.c_int]
         lib.msk_oracle_render.argtypes = [vp, C.POINTER(abi.RenderParams), vp, C.POINTER(abi.Stats), C.c_int]
         lib.msk_oracle_render_aov.argtypes = [vp, C.POINTER(abi.RenderParams), vp, C.c_uint32, vp, C.POINTER(abi.Stats), C.c_int]
@@ -49,8 +60,9 @@ class Oracle:
         lib.msk_oracle_bsdf_sample2.argtypes = [C.POINTER(abi.BsdfDesc), C.c_int, C.c_int, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp]
 
     # ---- scene-level
-    def scene(self, flat):
-        return OracleScene(self, flat)
+    def scene(self, flat, **ext):
+        """ext: envmap / points / masks in place of flat's own, as abi.Scene takes them"""
+        return OracleScene(self, flat, **ext)
 
     # ---- known-answer hooks
     def pcg32(self, initstate, initseq, n):
@@ -147,6 +159,22 @@ class Oracle:
                  "closest_rays_tie_decided", "equal_t_pairs")
         return dict(zip(names, [int(x) for x in a]))
 
+    PATH_TALLIES = ("null_lobe", "emitter_after_null", "emitter_after_delta", "envmap_miss_after_smooth", "point_unoccluded", "point_occluded",
+                    "sky_own_density", "area_emitter_hidden", "rr_after_null", "texel_wrap", "envmap_pole_clamp", "shadow_rays_nonzero", "dead_samples",
+                    "segments_dropped", "segments_extra")
+
+    def path_tallies(self):
+        """Reads and clears the oracle's path tallies (oracle.cpp: PathTally) -> dict.  Beside the named path events: the next-event
+        samples whose unoccluded term is not zero (the shadow rays the device traces) and the BSDF samples that failed or left a
+        zero throughput (where the device's segment count may differ from the oracle's by one each); of those, the samples with a lobe,
+        a zero throughput and no shadow ray pending (`segments_dropped`: the wavefront kernels end the path without a ray the oracle
+        counts) and the failed samples with one pending (`segments_extra`: they keep the slot for one more, zero, ray)."""
+        n = self.lib.msk_oracle_path_tally_count()
+        assert n == len(self.PATH_TALLIES)
+        a = (C.c_uint64 * n)()
+        self.lib.msk_oracle_path_tallies(a)
+        return dict(zip(self.PATH_TALLIES, [int(x) for x in a]))
+
     def gaussian_filter(self, stddev):
         r, sf = C.c_float(), C.c_float()
         b = C.c_int()
@@ -181,10 +209,81 @@ class Oracle:
         return o
 
 
+def _rows(fn, *arrays):
+    """calls a per-point hook for every row of the float32 input arrays; fn(k) makes the call for row k"""
+    for k in range(len(arrays[0])):
+        fn(k)
+
+
+def _row(a, k):
+    return C.c_void_p(a.ctypes.data + a.strides[0] * k)
+
+
 class OracleScene:
-    def __init__(self, orc, flat):
+    def __init__(self, orc, flat, envmap=None, points=None, masks=None):
+        """flat's envmap, points and masks are passed exactly as abi.Scene passes them (msk_scene_masks); a scene the library
+        refuses at creation raises ValueError"""
         self.orc, self.flat, self.abi = orc, flat, orc.abi
-        self.h = orc.lib.msk_oracle_scene_create(C.byref(flat.desc))
+        abi = orc.abi
+        self.envmap = envmap if envmap is not None else getattr(flat, "envmap", None)
+        pts = points if points is not None else getattr(flat, "points", None)
+        if pts is not None and not isinstance(pts, C.Array):
+            pts = (abi.PointDesc * max(1, len(pts)))(*pts) if len(pts) else None
+        self.points = pts if (pts is not None and len(pts)) else None
+        mk = masks if masks is not None else getattr(flat, "masks", None)
+        if mk is not None and not isinstance(mk, C.Array):
+            mk = (abi.MaskDesc * max(1, len(mk)))(*mk) if len(mk) else None
+        self.masks = mk if (mk is not None and len(mk)) else None
+        ext = abi.SceneExt(C.pointer(self.envmap) if self.envmap is not None else None, len(self.points) if self.points is not None else 0, self.points)
+        self.em = abi.SceneMasks(ext, len(self.masks) if self.masks is not None else 0, self.masks)
+        self.h = orc.lib.msk_oracle_scene_create_masks(C.byref(flat.desc), C.byref(self.em))
+        if not self.h:
+            raise ValueError("the oracle refuses this scene (as the library does at scene creation)")
+
+    # ---- the hooks of the features restated from include/msk_gpu.h, shaped like the device's probes (abi.Scene)
+    def eval_texture(self, texture, uv, wavelengths):
+        uv, wl = np.ascontiguousarray(uv, np.float32).reshape(-1, 2), np.ascontiguousarray(wavelengths, np.float32).reshape(-1, 4)
+        out = np.empty((len(uv), 4), np.float32)
+        _rows(lambda k: self.orc.lib.msk_oracle_eval_texture(self.h, int(texture), _row(uv, k), _row(wl, k), _row(out, k)), uv)
+        return out
+
+    def env_eval(self, dirs, wavelengths):
+        d, wl = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3), np.ascontiguousarray(wavelengths, np.float32).reshape(-1, 4)
+        rad, pdf = np.empty((len(d), 4), np.float32), np.empty(len(d), np.float32)
+        _rows(lambda k: self.orc.lib.msk_oracle_env_eval(self.h, _row(d, k), _row(wl, k), _row(rad, k), _row(pdf, k)), d)
+        return rad, pdf
+
+    def env_sample(self, u):
+        u = np.ascontiguousarray(u, np.float32).reshape(-1, 2)
+        d, uv, pdf = np.empty((len(u), 3), np.float32), np.empty((len(u), 2), np.float32), np.empty(len(u), np.float32)
+        _rows(lambda k: self.orc.lib.msk_oracle_env_sample(self.h, _row(u, k), _row(d, k), _row(uv, k), _row(pdf, k)), u)
+        return d, uv, pdf
+
+    def point_sample(self, emitter, ref_points, wavelengths):
+        p, wl = np.ascontiguousarray(ref_points, np.float32).reshape(-1, 3), np.ascontiguousarray(wavelengths, np.float32).reshape(-1, 4)
+        dd, val = np.empty((len(p), 4), np.float32), np.empty((len(p), 4), np.float32)
+        _rows(lambda k: self.orc.lib.msk_oracle_point_sample(self.h, int(emitter), _row(p, k), _row(wl, k), _row(dd, k), _row(val, k)), p)
+        return dd, val
+
+    def conductor_sample(self, bsdf, cos_theta_i, wavelengths):
+        c, wl = np.ascontiguousarray(cos_theta_i, np.float32).reshape(-1), np.ascontiguousarray(wavelengths, np.float32).reshape(-1, 4)
+        val = np.empty((len(c), 4), np.float32)
+        _rows(lambda k: self.orc.lib.msk_oracle_conductor_sample(self.h, int(bsdf), C.c_float(float(c[k])), _row(wl, k), _row(val, k)), c)
+        return val
+
+    def mask_sample(self, bsdf, uv, wi, sample1_u, wavelengths):
+        uv, wi = np.ascontiguousarray(uv, np.float32).reshape(-1, 2), np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
+        su, wl = np.ascontiguousarray(sample1_u, np.float32).reshape(-1, 3), np.ascontiguousarray(wavelengths, np.float32).reshape(-1, 4)
+        a, b, c = (np.empty((len(uv), 4), np.float32) for _ in range(3))
+        _rows(lambda k: self.orc.lib.msk_oracle_mask_sample(self.h, int(bsdf), _row(uv, k), _row(wi, k), _row(su, k), _row(wl, k), _row(a, k), _row(b, k), _row(c, k)), uv)
+        return a, b, c
+
+    def mask_eval(self, bsdf, uv, wi, wo, wavelengths):
+        uv, wi = np.ascontiguousarray(uv, np.float32).reshape(-1, 2), np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
+        wo, wl = np.ascontiguousarray(wo, np.float32).reshape(-1, 3), np.ascontiguousarray(wavelengths, np.float32).reshape(-1, 4)
+        a, v = np.empty((len(uv), 2), np.float32), np.empty((len(uv), 4), np.float32)
+        _rows(lambda k: self.orc.lib.msk_oracle_mask_eval(self.h, int(bsdf), _row(uv, k), _row(wi, k), _row(wo, k), _row(wl, k), _row(a, k), _row(v, k)), uv)
+        return a, v
 
     def set_bvh(self, on):
         self.orc.lib.msk_oracle_set_bvh(self.h, int(on))

@@ -3,8 +3,8 @@
 The reference's textures/bitmap.cpp is RGB-typed and not built, so nothing runnable pins its lookup.  Two things do here:
 tests/bitmap_ref.py, a float32 restatement of the semantics written in include/msk_gpu.h (at msk_texture_desc), and the
 oracle wherever a bitmap degenerates to something the oracle already renders — an image of equal texels is a constant
-reflectance, a nearest-filtered 2x2 image is a checkerboard.  The oracle itself never sees a bitmap (it reads any texture
-as a checkerboard)."""
+reflectance, a nearest-filtered 2x2 image is a checkerboard.  In this file the oracle never sees a bitmap; its own restatement
+of the lookup, and the device against it on bitmap floors, are in tests/test_widened_oracle_parity.py."""
 import ctypes as C
 import importlib
 import math
@@ -283,10 +283,9 @@ def probe_points(rng, w, h, n=4096):
 PROBE_IMAGES = ["1x1", "2x2", "3x5", "5x3", "16x16", "black", "white"]
 
 
-@pytest.fixture(scope="module")
-def probe_scene(gpu_ctx, hostmirror, abi):
+def probe_flat(hostmirror):
     """ONE scene that holds every texture of the probe tests (no surface shows them): images x filters x to_uv, then the
-    checkerboards and the 2x2 nearest images of tests 7 and 8."""
+    checkerboards and the 2x2 nearest images of tests 7 and 8.  -> (flat, images, index of (image, filter, to_uv) -> texture)"""
     rng = np.random.RandomState(21)
     images = {}
     for name in PROBE_IMAGES:
@@ -307,7 +306,12 @@ def probe_scene(gpu_ctx, hostmirror, abi):
         specs.append(bitmap(checker_pixels(), "nearest", **uvspec))
         index[("checker2x2", uvn)] = len(specs) + 1
     meshes = floor_meshes(hostmirror, bitmap(images["2x2"]), n=8)
-    flat = hostmirror.flatten(meshes, 16, 16, extra_textures=specs)
+    return hostmirror.flatten(meshes, 16, 16, extra_textures=specs), images, index
+
+
+@pytest.fixture(scope="module")
+def probe_scene(gpu_ctx, hostmirror, abi):
+    flat, images, index = probe_flat(hostmirror)
     scene = abi.Scene(gpu_ctx, flat)
     yield scene, flat, images, index
     scene.close()

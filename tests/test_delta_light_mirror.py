@@ -369,9 +369,9 @@ def conductor_probe_meshes(hm):
     return [plane(hm, {"type": "conductor"}, name="c0"), plane(hm, GOLD, name="c1"), plane(hm, dict(GOLD_RGB, twosided=True), name="c2")]
 
 
-@pytest.mark.gpu
-def test_probes_equal_the_restatement_bit_for_bit(gpu_ctx, hostmirror, oracle, abi):
-    """(5) msk_gpu_point_sample and msk_gpu_conductor_sample run the device functions the shading kernels call; no case excluded"""
+def probe_inputs():
+    """-> (the first point light's position, reference points float32[4096, 3]: around it, along 13 directions at distances
+    2^-10 .. 2^10 and the position itself; wavelengths float32[4096, 4]; cos_theta_i float32[4096] over [-1, 1] with the edges)"""
     rng = np.random.RandomState(23)
     pos = np.array([0.75, 2.5, -1.25], F)
     dirs = [(1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1), (1, 1, 0), (1, -1, 1), (-1, 1, 1), (1, 1, 1), (-1, -1, -1), (0, 1, -1), (3, -2, 1)]
@@ -380,15 +380,30 @@ def test_probes_equal_the_restatement_bit_for_bit(gpu_ctx, hostmirror, oracle, a
     assert p.shape == (4096, 3) and np.array_equal(p[-1], pos)
     wl = rng.uniform(360, 830, (4096, 4)).astype(F)
     cos = np.concatenate([np.linspace(-1, 1, 4089), [0.0, 2.0 ** -20, -2.0 ** -20, 1.0, -1.0, 2.0 ** -12, 0.5]]).astype(F)
+    return pos, p, wl, cos
+
+
+PROBE_POINT_2 = (5.0, 1.0, 1.0)
+
+
+def probe_flat(hostmirror, pos):
+    """the probes' scene: three conductor planes, a lamp (emitter 0) and two point lights (emitters 1 and 2)"""
     lamp = hostmirror.MeshSpec("lamp", [tuple(LAMP)], hostmirror.LUMINAIRE, radiance=(40, 30, 20))
-    pts = [point_spec(tuple(pos), INTENSITY), point_spec((5.0, 1.0, 1.0), 3.0)]
-    flat = hostmirror.flatten(conductor_probe_meshes(hostmirror) + [lamp], 16, 16, camera=CAM, points=pts)
+    pts = [point_spec(tuple(pos), INTENSITY), point_spec(PROBE_POINT_2, 3.0)]
+    return hostmirror.flatten(conductor_probe_meshes(hostmirror) + [lamp], 16, 16, camera=CAM, points=pts)
+
+
+@pytest.mark.gpu
+def test_probes_equal_the_restatement_bit_for_bit(gpu_ctx, hostmirror, oracle, abi):
+    """(5) msk_gpu_point_sample and msk_gpu_conductor_sample run the device functions the shading kernels call; no case excluded"""
+    pos, p, wl, cos = probe_inputs()
+    flat = probe_flat(hostmirror, pos)
     d = flat.desc
     assert [d.emitters[i].type for i in range(3)] == [0, 3, 3]
     _, d65 = hostmirror.cie_tables()
     g = abi.Scene(gpu_ctx, flat)
     try:
-        for e, position in ((1, pos), (2, np.array([5.0, 1.0, 1.0], F))):
+        for e, position in ((1, pos), (2, np.array(PROBE_POINT_2, F))):
             gd, gv = g.point_sample(e, p, wl)
             ed = d.emitters[e]
             inten = D.intensity32(oracle, ed.radiance[:], (d65 * F(ed.d65_scale)).astype(F), wl)

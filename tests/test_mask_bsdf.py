@@ -1,6 +1,7 @@
 """The `mask` BSDF (include/msk_gpu.h at msk_mask_desc; DESIGN.md section 9, departures 6-8): an opacity cutout with a null lobe.
 
-The oracle has no mask, so the device is held in three ways: to the fp32 restatement (mask_ref.py) bit for bit through the probes,
+In this file the oracle sees no mask (its restatement of the mask, and the device against it bit for bit, are in
+test_widened_oracle_parity.py); here the device is held in three ways: to the fp32 restatement (mask_ref.py) bit for bit through the probes,
 to the oracle where it can follow (a = 1 is the nested BSDF, to the bit), and to float64 closed forms.
 
 CPU: the restatement checks itself; the packer, its refusals and the launch plan as a stand-alone native program (also under
