@@ -607,7 +607,15 @@ int  msk_gpu_mask_eval(msk_scene *scene, uint32_t bsdf, uint64_t n, const float 
  *   w_l = (N p_l)^2 / ((N p_l)^2 + (M p_b)^2),  w_b = (M p_b)^2 / ((M p_b)^2 + (N p_e)^2),  terms divided by N and M.
  * Random pairs of a sample (counter_pair of its key): 0-2 as "path" (film position, wavelengths, aperture), 3 + i light sample i,
  * 3 + N + 2 j / + 1 the lobe choice (.x) and the direction of BSDF sample j; additions in the order emission, light samples,
- * BSDF samples.  With (1, 1) the result is, bit for bit, msk_gpu_render at max_depth = 2 — except for a `constant` sky in a scene
+ * BSDF samples.  The fp32 operations of a term, in order (each its own rounded operation, per wavelength; N and M as floats):
+ *   weight(n_a, p_a, n_b, p_b):  a = n_a * p_a;  b = n_b * p_b;  a = a * a;  b = b * b;  a > 0 ? a / (a + b) : 0
+ *   light sample i:  t = emitter_val * bsdf_val;  t = t * w_l;  w_l = weight(N, p_l, M, p_b), or 1 for a point light;
+ *                    a shadow ray is traced (and counted) iff t is not zero at every wavelength; unoccluded: t = t / N; result += t
+ *   BSDF sample j:   traced (and counted as a segment) iff the sample succeeded and bsdf_val is not zero at every wavelength;
+ *                    reaching an emitter or an environment:  t = bsdf_val * value;  t = t * w_b;  w_b = weight(M, p_b, N, p_e);
+ *                    t = t / M;  result += t
+ * p_l and p_e carry the light-selection factor 1 / n_emitters; emitter_val is the radiance over p_l (a point light: I / d^2 times
+ * n_emitters).  With (1, 1) the result is, bit for bit, msk_gpu_render at max_depth = 2 — except for a `constant` sky in a scene
  * of the older kernel families, which counts here with the density of the ray's own direction always.
  * light_samples and bsdf_samples are each in [0, 4096] and not both 0 (MSK_ERR_INVALID_ARG otherwise).
  * msk_render_params: rr_depth and max_depth are ignored; spp, seed, hide_emitters, block_size and the shard selectors mean what

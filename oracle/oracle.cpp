@@ -460,8 +460,24 @@ struct PathTallies { uint64_t v[kTallyCount] = {}; };
 static thread_local PathTallies tl_path;
 static inline void tally(PathTally t) { tl_path.v[t] += 1; }
 static void path_flush() { for (int i = 0; i < kTallyCount; ++i) { g_path[i].fetch_add(tl_path.v[i], std::memory_order_relaxed); tl_path.v[i] = 0; } }
-// what a render worker or a ray batch calls when it ends: this thread's intersection AND path tallies into the totals
-static void tallies_flush() { isect_flush(); path_flush(); }
+// Named events of the `direct` integrator (msk_oracle_direct_tallies; the path tallies' mechanism): which branches of direct_sample a
+// render reached
+enum DirectTally { kDirPrimaryMissEnv, kDirPrimaryEmitterSeen, kDirPrimaryEmitterHidden, kDirTwosidedFlipped, kDirLightSkippedDelta,
+                   kDirLightAreaVisible, kDirLightAreaOccluded, kDirLightAreaBack,      // Back: pdf = 0, the sampled point faces away
+                   kDirLightConstantSky, kDirLightImage, kDirLightPointVisible, kDirLightPointOccluded,
+                   kDirLightLastEmitter,      // the selection took the last emitter of several
+                   kDirBsdfNotTraced,         // the sample failed or its value is zero at every wavelength
+                   kDirBsdfEmitterFrontMis,   // an area emitter's front with 0 < w_b < 1
+                   kDirBsdfEmitterBack, kDirBsdfNonEmitter, kDirBsdfMissImage, kDirBsdfMissConstant, kDirBsdfMissNothing,
+                   kDirBsdfEmitterAfterDelta, // an emitter or environment after a delta lobe: p_e = 0, weight exactly 1
+                   kDirTallyCount };
+static std::atomic<uint64_t> g_direct[kDirTallyCount];
+struct DirectTallies { uint64_t v[kDirTallyCount] = {}; };
+static thread_local DirectTallies tl_direct;
+static inline void tally(DirectTally t) { tl_direct.v[t] += 1; }
+static void direct_flush() { for (int i = 0; i < kDirTallyCount; ++i) { g_direct[i].fetch_add(tl_direct.v[i], std::memory_order_relaxed); tl_direct.v[i] = 0; } }
+// what a render worker or a ray batch calls when it ends: this thread's intersection, path AND direct tallies into the totals
+static void tallies_flush() { isect_flush(); path_flush(); direct_flush(); }
 
 static inline float xor_sign(float a, uint32_t sgn) {
     uint32_t b; std::memcpy(&b, &a, 4); b ^= sgn; std::memcpy(&a, &b, 4); return a;
@@ -681,11 +697,14 @@ struct Sampler {
     uint64_t key = 0;   // MSK_RNG_COUNTER
     // dimension pairs: 0 = film position, 1 = (wavelength, -), 2 = aperture,
     // 3+3(k-1)+{0: NEE, 1: (bsdf sample1, rr), 2: bsdf direction}, k = depth
+    std::vector<uint32_t> *log = nullptr;   // (msk_oracle_direct_terms) every pair index drawn from, in order
     void pair(uint32_t idx, float *a, float *b) {
+        if (log) log->push_back(idx);
         if (mode == MSK_RNG_COUNTER) counter_pair(key, idx, a, b);
         else { *a = rng.next_float32(); *b = rng.next_float32(); }
     }
     float single(uint32_t idx, int lo) {
+        if (log) log->push_back(idx);
         if (mode == MSK_RNG_COUNTER) { float a, b; counter_pair(key, idx, &a, &b); return lo ? b : a; }
         return rng.next_float32();
     }
@@ -1423,6 +1442,167 @@ static S4 path_sample(const Scene &sc, Sampler &sampler, Ray ray, S4 wl, const m
 }
 
 // ===========================================================================
+// The `direct` integrator: include/msk_gpu.h at msk_direct_params, DESIGN.md section 9.  One primary ray, N light samples and M
+// BSDF samples at its hit; the fp32 operation order of a term is the header's.  rr_depth and max_depth are not read.
+// ===========================================================================
+static inline bool any_nonzero(S4 v) { return v.v[0] != 0.f || v.v[1] != 0.f || v.v[2] != 0.f || v.v[3] != 0.f; }
+// the power heuristic over the sample counts
+static float direct_weight(float n_a, float p_a, float n_b, float p_b) {
+    float a = n_a * p_a, b = n_b * p_b;
+    a = a * a; b = b * b;
+    return a > 0.f ? a / (a + b) : 0.f;
+}
+// what msk_oracle_direct_terms reports of one camera sample: every factor of every term, before the weights and the counts
+struct DirectLightTerm { uint32_t pair = 0; int emitter = -1; float p_l = 0.f, p_b = 0.f; bool point = false, shadow = false, occluded = false; S4 prod; };
+struct DirectBsdfTerm { uint32_t pair_lobe = 0, pair_dir = 0; float p_b = 0.f, p_e = 0.f; bool traced = false, reached = false, escaped = false; S4 prod; };
+struct DirectTerms { bool hit = false; S4 emission; std::vector<DirectLightTerm> light; std::vector<DirectBsdfTerm> bsdf; };
+
+static S4 direct_sample(const Scene &sc, Sampler &sampler, Ray ray, S4 wl, const msk_render_params &prm, uint32_t N, uint32_t M,
+                        Counters &cnt, DirectTerms *terms = nullptr) {
+    const bool hide_emitter = prm.hide_emitters != 0;
+    const float fN = (float) N, fM = (float) M;
+    const size_t n_em = sc.emitters.size();
+    S4 result = s4(0.f);
+    ++cnt.segments;
+    const Interaction si = compute_interaction(sc, ray, closest_hit(sc, ray));
+    if (terms) { terms->hit = si.valid(); terms->emission = s4(0.f); }
+    // ---- emission: the environment behind a primary miss, the front of an emitter at the primary hit; hide_emitters removes both
+    if (!si.valid()) {
+        if (!hide_emitter && sc.env >= 0) {
+            const S4 e = environment_radiance(sc, ray.d, wl);
+            if (terms) terms->emission = e;
+            result = result + e;
+            tally(kDirPrimaryMissEnv);
+        }
+        return result;
+    }
+    const int emitter = sc.meshes[si.mesh].emitter_id;
+    if (emitter >= 0) {
+        if (!hide_emitter) {
+            const S4 e = emitter_eval(sc, emitter, si, wl);
+            if (terms) terms->emission = e;
+            result = result + e;
+            tally(kDirPrimaryEmitterSeen);
+        } else tally(kDirPrimaryEmitterHidden);
+    }
+    const msk_bsdf_desc &bsdf = sc.bsdfs[sc.meshes[si.mesh].bsdf_id];
+    V3 wi_s = si.wi;
+    bool flipped;
+    const msk_bsdf_desc *bb = bsdf_side(sc, bsdf, &wi_s, &flipped);
+    if (flipped) tally(kDirTwosidedFlipped);
+    const Reflectance refl = reflectance_at(sc, *bb, si.uv);
+    const bool smooth = bsdf_has_smooth_lobe(bsdf);
+    // ---- light samples: pair 3 + i; none at a BSDF without a smooth lobe, none without an emitter
+    if (!smooth && N > 0 && n_em > 0) tally(kDirLightSkippedDelta);
+    if (smooth && n_em > 0)
+        for (uint32_t i = 0; i < N; ++i) {
+            V2 u; sampler.pair(3u + i, &u.x, &u.y);
+            DirectLightTerm lt;
+            if (terms) lt.pair = sampler.log ? sampler.log->back() : 3u + i;
+            S4 emitter_val, unoccluded = s4(0.f);
+            bool occluded = false;
+            uint64_t traced_by_block = 0;       // (the building block counts a ray per non-zero density; this integrator counts by the term)
+            const DirectSample ds = sample_emitter_direct(sc, si, u, wl, &emitter_val, &traced_by_block, &unoccluded, &occluded);
+            lt.emitter = ds.emitter; lt.p_l = ds.pdf; lt.point = ds.point; lt.prod = s4(0.f);
+            if (ds.emitter >= 0 && n_em > 1 && (size_t) ds.emitter == n_em - 1) tally(kDirLightLastEmitter);
+            const int etype = ds.emitter >= 0 ? (int) sc.emitters[ds.emitter].type : -1;
+            if (etype == MSK_EMITTER_CONSTANT) tally(kDirLightConstantSky);
+            if (etype == MSK_EMITTER_ENVMAP) tally(kDirLightImage);
+            if (etype == MSK_EMITTER_AREA && ds.pdf == 0.f) tally(kDirLightAreaBack);
+            if (ds.pdf != 0.f) {
+                V3 wo = si.sh.to_local(ds.d);
+                if (flipped) wo.z *= -1.f;
+                S4 bsdf_val; float bsdf_pdf;
+                bsdf_eval_pdf(sc, *bb, refl, wi_s, wo, wl, &bsdf_val, &bsdf_pdf);
+                const float w_l = ds.point ? 1.f : direct_weight(fN, ds.pdf, fM, bsdf_pdf);      // a delta light: weight 1
+                const S4 prod = unoccluded * bsdf_val;
+                S4 term = prod * w_l;
+                lt.p_b = bsdf_pdf; lt.prod = prod;
+                if (any_nonzero(term)) {                                  // the shadow ray: an occluded sample adds nothing
+                    ++cnt.shadow_rays;
+                    lt.shadow = true; lt.occluded = occluded;
+                    if (ds.point) tally(occluded ? kDirLightPointOccluded : kDirLightPointVisible);
+                    if (etype == MSK_EMITTER_AREA) tally(occluded ? kDirLightAreaOccluded : kDirLightAreaVisible);
+                    if (!occluded) {
+                        term = term / fN;
+                        result = result + term;
+                    }
+                }
+            }
+            if (terms) terms->light.push_back(lt);
+        }
+    // ---- BSDF samples: pair 3 + N + 2 j the lobe choice (.x), the next pair the direction
+    for (uint32_t j = 0; j < M; ++j) {
+        const uint32_t base = 3u + N + 2u * j;
+        DirectBsdfTerm bt;
+        const float sample1 = sampler.single(base, 0);
+        if (terms) bt.pair_lobe = sampler.log ? sampler.log->back() : base;
+        V2 u2; sampler.pair(base + 1u, &u2.x, &u2.y);
+        if (terms) bt.pair_dir = sampler.log ? sampler.log->back() : base + 1u;
+        BSDFSampleRec bs;
+        const S4 bsdf_val = bsdf_sample(sc, *bb, refl, wi_s, sample1, u2, wl, &bs);
+        if (flipped) bs.wo.z *= -1.f;
+        bt.p_b = bs.pdf; bt.prod = s4(0.f);
+        if (bs.sampled_type && any_nonzero(bsdf_val)) {
+            ++cnt.segments;
+            bt.traced = true;
+            const Ray r2{si.p, si.sh.to_world(bs.wo), (1.f + max_abs(si.p)) * kRayEpsilon, kInf};
+            const Interaction sb = compute_interaction(sc, r2, closest_hit(sc, r2));
+            const bool delta = (bs.sampled_type & kDelta) != 0u || !smooth;
+            S4 value = s4(0.f);
+            float p_e = 0.f;
+            bool reached = false;
+            bt.escaped = !sb.valid();
+            if (sb.valid()) {
+                const int em = sc.meshes[sb.mesh].emitter_id;
+                if (em >= 0) {
+                    value = emitter_eval(sc, em, sb, wl);
+                    DirectSample q;                                       // records.cpp:7-14 set_query
+                    q.p = sb.p; q.n = sb.sh.n; q.emitter = em; q.d = r2.d; q.dist = sb.t; q.pdf = 0.f;
+                    p_e = pdf_emitter_direct(sc, q);
+                    reached = true;
+                    if (!(sb.wi.z > 0.f)) tally(kDirBsdfEmitterBack);
+                } else tally(kDirBsdfNonEmitter);
+            } else if (sc.env >= 0 && sc.env_is_image) {                  // value and density of the ray's own direction
+                float sin_theta;
+                const V2 uv = env_dir_to_uv(sc.envmap, r2.d, &sin_theta);
+                value = env_radiance(sc, uv, wl);
+                p_e = env_pdf(sc.envmap, uv, sin_theta);
+                if (n_em != 1) p_e = p_e * (1.f / n_em);
+                reached = true;
+                tally(kDirBsdfMissImage);
+            } else if (sc.env >= 0) {                                     // the `constant` sky: its own density, always
+                value = emitter_radiance(sc, sc.env, wl);
+                p_e = kInvFourPi;
+                if (n_em != 1) p_e = p_e * (1.f / n_em);
+                reached = true;
+                tally(kDirBsdfMissConstant);
+            } else tally(kDirBsdfMissNothing);
+            if (delta) p_e = 0.f;
+            if (reached) {
+                const float w_b = direct_weight(fM, bs.pdf, fN, p_e);
+                const S4 prod = bsdf_val * value;
+                S4 term = prod * w_b;
+                term = term / fM;
+                result = result + term;
+                bt.reached = true; bt.p_e = p_e; bt.prod = prod;
+                if (delta) tally(kDirBsdfEmitterAfterDelta);
+                else if (sb.valid() && sb.wi.z > 0.f && w_b > 0.f && w_b < 1.f) tally(kDirBsdfEmitterFrontMis);
+            }
+        } else tally(kDirBsdfNotTraced);
+        if (terms) terms->bsdf.push_back(bt);
+    }
+    return result;
+}
+// what the library refuses of a `direct` call (msk_gpu.h): 0 when it is taken
+static int direct_refusal(const Scene &sc, const msk_render_params &prm, const msk_direct_params &dp) {
+    if (sc.any_mask) return MSK_ERR_UNSUPPORTED;
+    if (prm.rng_mode != MSK_RNG_COUNTER) return MSK_ERR_UNSUPPORTED;
+    if (dp.light_samples > 4096u || dp.bsdf_samples > 4096u || (dp.light_samples == 0u && dp.bsdf_samples == 0u)) return MSK_ERR_INVALID_ARG;
+    return 0;
+}
+
+// ===========================================================================
 // a14/a15  ImageBlock (imageblock.cpp:9-173) and a1 BlockGenerator (:176-247)
 // ===========================================================================
 struct ImageBlock {
@@ -1525,7 +1705,9 @@ struct AovSpec {
 };
 // integrators/aov.cpp:87-144 (aov == nullptr: the plain "path" integrator); aovs receives spec.channels floats
 static void render_sample(const Scene &sc, Sampler &sampler, V2 pos, const msk_render_params &prm,
-                          Counters &cnt, V2 *position_sample, float xyz[3], const AovSpec *aov = nullptr, float *aovs = nullptr) {
+                          Counters &cnt, V2 *position_sample, float xyz[3], const AovSpec *aov = nullptr, float *aovs = nullptr,
+                          const msk_direct_params *direct = nullptr, DirectTerms *terms = nullptr, S4 *out_wl = nullptr, S4 *out_weight = nullptr,
+                          S4 *out_spectral = nullptr) {
     float jx, jy; sampler.pair(0, &jx, &jy);
     *position_sample = V2{pos.x + jx, pos.y + jy};
     float wavelength_sample = sampler.single(1, 0);
@@ -1534,7 +1716,12 @@ static void render_sample(const Scene &sc, Sampler &sampler, V2 pos, const msk_r
     Ray ray = camera_ray(sc, wavelength_sample, *position_sample, &wl, &ray_weight);
     ++cnt.samples;
     S4 result;
-    if (!aov) {
+    if (out_wl) *out_wl = wl;
+    if (out_weight) *out_weight = ray_weight;
+    if (direct) {                                                  // the "direct" integrator in place of "path"
+        result = direct_sample(sc, sampler, ray, wl, prm, direct->light_samples, direct->bsdf_samples, cnt, terms);
+        if (out_spectral) *out_spectral = result;
+    } else if (!aov) {
         result = path_sample(sc, sampler, ray, wl, prm, cnt);
     } else {
         result = s4(0.f);                                          // aov.cpp:91 leaves it uninitialised without a nested integrator
@@ -1566,7 +1753,7 @@ static void render_sample(const Scene &sc, Sampler &sampler, V2 pos, const msk_r
 
 // a1/a2  SamplingIntegrator::render + render_block (integrator.cpp:31-101)
 static void render(const Scene &sc, const msk_render_params &prm, float *film, Counters *total, int n_threads,
-                   const AovSpec *aov = nullptr) {
+                   const AovSpec *aov = nullptr, const msk_direct_params *direct = nullptr) {
     const int n_ch = 5 + (aov ? aov->channels : 0);
     const int W = sc.film.width, H = sc.film.height;
     // film.cpp:12-21: the crop window; the block schedule and the sensor stay those of the full film (integrator.cpp:45)
@@ -1606,7 +1793,7 @@ static void render(const Scene &sc, const msk_render_params &prm, float *film, C
                         if (prm.rng_mode == MSK_RNG_COUNTER)
                             sampler.key = counter_key(prm.seed, (uint32_t) ((y + bd.off_y) * W + (x + bd.off_x)), s);
                         V2 ps;
-                        render_sample(sc, sampler, pos, prm, cnt, &ps, v.data(), aov, v.data() + 5);
+                        render_sample(sc, sampler, pos, prm, cnt, &ps, v.data(), aov, v.data() + 5, direct);
                         v[3] = 1.f; v[4] = 1.f;                    // integrator.cpp:119-123
                         blk.put(ps, v.data());
                     }
@@ -1794,6 +1981,85 @@ int msk_oracle_sample_pixels(void *s, const msk_render_params *prm, uint64_t n_p
     }
     return 0;
 }
+
+// ---- the "direct" integrator (msk_gpu.h at msk_direct_params).  Non-zero where the library refuses: a scene that holds a mask,
+// MSK_RNG_PCG_BLOCK, a count above 4096, both counts 0
+int msk_oracle_render_direct(void *s, const msk_render_params *prm, const msk_direct_params *direct, float *film, msk_stats *stats, int n_threads) {
+    const Scene &sc = *(Scene *) s;
+    if (int rc = direct_refusal(sc, *prm, *direct)) return rc;
+    Counters c;
+    auto t0 = std::chrono::steady_clock::now();
+    render(sc, *prm, film, &c, n_threads, nullptr, direct);
+    auto t1 = std::chrono::steady_clock::now();
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->samples = c.samples; stats->segments = c.segments; stats->shadow_rays = c.shadow_rays; stats->invalid_samples = c.invalid;
+        stats->ms_total = std::chrono::duration<float, std::milli>(t1 - t0).count();
+    }
+    return 0;
+}
+// like msk_gpu_sample_pixels_direct it honours sample_first / sample_stride: per listed pixel the owned samples, in order
+int msk_oracle_sample_pixels_direct(void *s, const msk_render_params *prm, const msk_direct_params *direct, uint64_t n_pixels, const int32_t *pixels,
+                                    float *out_xyz, float *out_pos) {
+    const Scene &sc = *(Scene *) s;
+    if (int rc = direct_refusal(sc, *prm, *direct)) return rc;
+    const uint32_t stride = prm->sample_stride ? prm->sample_stride : 1;
+    Counters cnt;
+    size_t o = 0;
+    for (uint64_t i = 0; i < n_pixels; ++i) {
+        const int x = pixels[2 * i], y = pixels[2 * i + 1];
+        for (uint64_t sidx = prm->sample_first; sidx < prm->spp; sidx += stride, ++o) {
+            Sampler sampler; sampler.mode = MSK_RNG_COUNTER;
+            sampler.key = counter_key(prm->seed, (uint32_t) (y * sc.film.width + x), (uint32_t) sidx);
+            V2 ps; float xyz[3];
+            render_sample(sc, sampler, V2{(float) x, (float) y}, *prm, cnt, &ps, xyz, nullptr, nullptr, direct);
+            out_xyz[o * 3 + 0] = xyz[0]; out_xyz[o * 3 + 1] = xyz[1]; out_xyz[o * 3 + 2] = xyz[2];
+            if (out_pos) { out_pos[o * 2] = ps.x; out_pos[o * 2 + 1] = ps.y; }
+        }
+    }
+    tallies_flush();
+    return 0;
+}
+// Every factor of camera sample `sample` of pixel (px, py), before the weights and the counts are applied:
+//   out_head 16 floats: the four wavelengths, the ray weight, the emission term, the spectral result (before the ray weight and spectrum_to_xyz)
+//   out_counts 4 ints: primary hit (1 / 0), light samples drawn, BSDF samples drawn, pairs drawn in all
+//   out_light_i  N x 5: {pair, emitter, point, shadow ray traced, occluded};  out_light_f  N x 6: {p_l, p_b, emitter_val * bsdf_val at 4 wavelengths}
+//   out_bsdf_i   M x 5: {pair of the lobe choice, pair of the direction, traced, reached an emitter or environment, left the scene};  out_bsdf_f  M x 6: {p_b, p_e, bsdf_val * value at 4}
+//   out_draws 3 + N + 2 M ints: every pair index the sample drew from, in order
+int msk_oracle_direct_terms(void *s, const msk_render_params *prm, const msk_direct_params *direct, int32_t px, int32_t py, uint32_t sample,
+                            float *out_head, int32_t *out_counts, int32_t *out_light_i, float *out_light_f, int32_t *out_bsdf_i, float *out_bsdf_f,
+                            int32_t *out_draws) {
+    const Scene &sc = *(Scene *) s;
+    if (int rc = direct_refusal(sc, *prm, *direct)) return rc;
+    std::vector<uint32_t> log;
+    Sampler sampler; sampler.mode = MSK_RNG_COUNTER; sampler.log = &log;
+    sampler.key = counter_key(prm->seed, (uint32_t) (py * sc.film.width + px), sample);
+    Counters cnt;
+    DirectTerms t;
+    V2 ps; float xyz[3];
+    S4 wl, weight, spectral;
+    render_sample(sc, sampler, V2{(float) px, (float) py}, *prm, cnt, &ps, xyz, nullptr, nullptr, direct, &t, &wl, &weight, &spectral);
+    store4(out_head, wl); store4(out_head + 4, weight); store4(out_head + 8, t.emission); store4(out_head + 12, spectral);
+    out_counts[0] = t.hit ? 1 : 0; out_counts[1] = (int32_t) t.light.size(); out_counts[2] = (int32_t) t.bsdf.size(); out_counts[3] = (int32_t) log.size();
+    for (size_t i = 0; i < t.light.size(); ++i) {
+        const DirectLightTerm &l = t.light[i];
+        int32_t *oi = out_light_i + 5 * i; float *of = out_light_f + 6 * i;
+        oi[0] = (int32_t) l.pair; oi[1] = l.emitter; oi[2] = l.point; oi[3] = l.shadow; oi[4] = l.occluded;
+        of[0] = l.p_l; of[1] = l.p_b; store4(of + 2, l.prod);
+    }
+    for (size_t j = 0; j < t.bsdf.size(); ++j) {
+        const DirectBsdfTerm &b = t.bsdf[j];
+        int32_t *oi = out_bsdf_i + 5 * j; float *of = out_bsdf_f + 6 * j;
+        oi[0] = (int32_t) b.pair_lobe; oi[1] = (int32_t) b.pair_dir; oi[2] = b.traced; oi[3] = b.reached; oi[4] = b.escaped;
+        of[0] = b.p_b; of[1] = b.p_e; store4(of + 2, b.prod);
+    }
+    for (size_t k = 0; k < log.size(); ++k) out_draws[k] = (int32_t) log[k];
+    tallies_flush();
+    return 0;
+}
+// reads and clears the direct tallies (see DirectTally): out receives msk_oracle_direct_tally_count() values
+int msk_oracle_direct_tally_count() { return (int) kDirTallyCount; }
+void msk_oracle_direct_tallies(uint64_t *out) { direct_flush(); for (int i = 0; i < kDirTallyCount; ++i) out[i] = g_direct[i].exchange(0); }
 
 int msk_oracle_trace_closest(void *s, uint64_t n, const float *rays, float *out_hit) {
     const Scene &sc = *(Scene *) s;

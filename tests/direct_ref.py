@@ -39,6 +39,44 @@ def weight(na, pa, nb, pb):
     return np.where(a > 0, a / np.where(a + b > 0, a + b, 1.0), 0.0)
 
 
+def weight_f32(na, pa, nb, pb):
+    """the same weight in fp32, one rounded operation at a time, in the order include/msk_gpu.h pins:
+    a = na * pa; b = nb * pb; a = a * a; b = b * b; a > 0 ? a / (a + b) : 0"""
+    f = np.float32
+    with np.errstate(all="ignore"):
+        a, b = f(f(na) * f(pa)), f(f(nb) * f(pb))
+        a, b = f(a * a), f(b * b)
+        return f(a / f(a + b)) if a > 0 else f(0)
+
+
+def recombine_f32(terms, n_light, n_bsdf):
+    """the spectral result of one camera sample from the factors msk_oracle_direct_terms reports, in numpy fp32, one operation at
+    a time in the header's order: emission, then the light samples, then the BSDF samples; a light term is (prod * w_l) / N where its
+    shadow ray was traced and found nothing, a BSDF term (prod * w_b) / M where the ray reached an emitter or an environment.
+    -> (float32[4], the shadow flags this restatement derives for the light samples)"""
+    f = np.float32
+    fn, fm = f(n_light), f(n_bsdf)
+    shadows = []
+    with np.errstate(all="ignore"):
+        res = (np.zeros(4, f) + terms["emission"]).astype(f)
+        for lt in terms["light"]:
+            if lt["p_l"] == 0:
+                shadows.append(False)
+                continue
+            w = f(1) if lt["point"] else weight_f32(fn, lt["p_l"], fm, lt["p_b"])
+            t = (lt["prod"].astype(f) * w).astype(f)
+            shadow = bool((t != 0).any())
+            shadows.append(shadow)
+            if shadow and not lt["occluded"]:
+                res = (res + (t / fn).astype(f)).astype(f)
+        for bt in terms["bsdf"]:
+            if bt["reached"]:
+                w = weight_f32(fm, bt["p_b"], fn, bt["p_e"])
+                t = (bt["prod"].astype(f) * w).astype(f)
+                res = (res + (t / fm).astype(f)).astype(f)
+    return res, shadows
+
+
 # ----------------------------------------------------------------------------- geometry, brute force
 class Triangles:
     """the flattened scene's triangles in float64: v0, e1, e2, unit normal (e1 x e2), the mesh of each, and which mesh emits"""

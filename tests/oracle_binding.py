@@ -36,6 +36,12 @@ class Oracle:
         lib.msk_oracle_render.argtypes = [vp, C.POINTER(abi.RenderParams), vp, C.POINTER(abi.Stats), C.c_int]
         lib.msk_oracle_render_aov.argtypes = [vp, C.POINTER(abi.RenderParams), vp, C.c_uint32, vp, C.POINTER(abi.Stats), C.c_int]
         lib.msk_oracle_sample_pixels.argtypes = [vp, C.POINTER(abi.RenderParams), C.c_uint64, vp, vp, vp]
+        lib.msk_oracle_render_direct.argtypes = [vp, C.POINTER(abi.RenderParams), C.POINTER(abi.DirectParams), vp, C.POINTER(abi.Stats), C.c_int]
+        lib.msk_oracle_sample_pixels_direct.argtypes = [vp, C.POINTER(abi.RenderParams), C.POINTER(abi.DirectParams), C.c_uint64, vp, vp, vp]
+        lib.msk_oracle_direct_terms.argtypes = [vp, C.POINTER(abi.RenderParams), C.POINTER(abi.DirectParams), C.c_int32, C.c_int32, C.c_uint32,
+                                                vp, vp, vp, vp, vp, vp, vp]
+        lib.msk_oracle_direct_tally_count.restype = C.c_int
+        lib.msk_oracle_direct_tallies.argtypes = [vp]
         lib.msk_oracle_trace_closest.argtypes = [vp, C.c_uint64, vp, vp]
         lib.msk_oracle_trace_any.argtypes = [vp, C.c_uint64, vp, vp]
         lib.msk_oracle_camera_ray.argtypes = [vp, C.c_float, C.c_float, C.c_float, vp, vp, vp]
@@ -174,6 +180,20 @@ class Oracle:
         a = (C.c_uint64 * n)()
         self.lib.msk_oracle_path_tallies(a)
         return dict(zip(self.PATH_TALLIES, [int(x) for x in a]))
+
+    DIRECT_TALLIES = ("primary_miss_env", "primary_emitter_seen", "primary_emitter_hidden", "twosided_flipped", "light_skipped_delta",
+                      "light_area_visible", "light_area_occluded", "light_area_back", "light_constant_sky", "light_image", "light_point_visible",
+                      "light_point_occluded", "light_last_emitter", "bsdf_not_traced", "bsdf_emitter_front_mis", "bsdf_emitter_back",
+                      "bsdf_non_emitter", "bsdf_miss_image", "bsdf_miss_constant", "bsdf_miss_nothing", "bsdf_emitter_after_delta")
+
+    def direct_tallies(self):
+        """Reads and clears the oracle's tallies of the `direct` integrator (oracle.cpp: DirectTally) -> dict: which branches of
+        direct_sample the renders since the last call reached"""
+        n = self.lib.msk_oracle_direct_tally_count()
+        assert n == len(self.DIRECT_TALLIES)
+        a = (C.c_uint64 * n)()
+        self.lib.msk_oracle_direct_tallies(a)
+        return dict(zip(self.DIRECT_TALLIES, [int(x) for x in a]))
 
     def gaussian_filter(self, stddev):
         r, sf = C.c_float(), C.c_float()
@@ -319,6 +339,52 @@ class OracleScene:
         rc = self.orc.lib.msk_oracle_sample_pixels(self.h, C.byref(params), n, _p(pixels), _p(xyz), _p(pos))
         assert rc == 0
         return xyz, pos
+
+    # ---- the "direct" integrator, shaped like abi.Scene's calls; a call the library refuses raises ValueError
+    def render_direct(self, params, light_samples=1, bsdf_samples=1, threads=8):
+        h, w = self._film_shape()
+        film = np.zeros((h, w, 5), np.float32)
+        st, dp = self.abi.Stats(), self.abi.DirectParams(light_samples, bsdf_samples)
+        rc = self.orc.lib.msk_oracle_render_direct(self.h, C.byref(params), C.byref(dp), _p(film), C.byref(st), threads)
+        if rc != 0:
+            raise ValueError("the oracle refuses this `direct` render (code %d), as the library does" % rc)
+        return film, st
+
+    def sample_pixels_direct(self, params, pixels, light_samples=1, bsdf_samples=1):
+        """per listed pixel the samples the call OWNS (s = sample_first + k sample_stride < spp), in order
+        -> (xyz float32[n, owned, 3], pos float32[n, owned, 2])"""
+        pixels = np.ascontiguousarray(pixels, np.int32).reshape(-1, 2)
+        n = pixels.shape[0]
+        stride = params.sample_stride or 1
+        owned = (params.spp - params.sample_first + stride - 1) // stride if params.sample_first < params.spp else 0
+        xyz, pos = np.zeros((n, owned, 3), np.float32), np.zeros((n, owned, 2), np.float32)
+        dp = self.abi.DirectParams(light_samples, bsdf_samples)
+        rc = self.orc.lib.msk_oracle_sample_pixels_direct(self.h, C.byref(params), C.byref(dp), n, _p(pixels), _p(xyz), _p(pos))
+        if rc != 0:
+            raise ValueError("the oracle refuses this `direct` call (code %d), as the library does" % rc)
+        return xyz, pos
+
+    def direct_terms(self, params, pixel, sample, light_samples=1, bsdf_samples=1):
+        """every factor of one camera sample before the weights and the counts are applied (msk_oracle_direct_terms) -> dict:
+        wl, ray_weight, emission, result (float32[4] each; result is the spectral sum before the ray weight), hit,
+        light = list of {pair, emitter, point, shadow, occluded, p_l, p_b, prod}, bsdf = list of {pair_lobe, pair_dir, traced,
+        reached, escaped (the ray left the scene), p_b, p_e, prod}, draws = every pair index the sample drew from, in order"""
+        n, m = int(light_samples), int(bsdf_samples)
+        head, counts = np.zeros(16, np.float32), np.zeros(4, np.int32)
+        li, lf = np.zeros((max(n, 1), 5), np.int32), np.zeros((max(n, 1), 6), np.float32)
+        bi, bf = np.zeros((max(m, 1), 5), np.int32), np.zeros((max(m, 1), 6), np.float32)
+        draws = np.zeros(3 + n + 2 * m, np.int32)
+        dp = self.abi.DirectParams(n, m)
+        rc = self.orc.lib.msk_oracle_direct_terms(self.h, C.byref(params), C.byref(dp), int(pixel[0]), int(pixel[1]), int(sample),
+                                                  _p(head), _p(counts), _p(li), _p(lf), _p(bi), _p(bf), _p(draws))
+        if rc != 0:
+            raise ValueError("the oracle refuses this `direct` call (code %d), as the library does" % rc)
+        light = [dict(pair=int(li[i, 0]), emitter=int(li[i, 1]), point=bool(li[i, 2]), shadow=bool(li[i, 3]), occluded=bool(li[i, 4]),
+                      p_l=lf[i, 0], p_b=lf[i, 1], prod=lf[i, 2:6].copy()) for i in range(counts[1])]
+        bsdf = [dict(pair_lobe=int(bi[j, 0]), pair_dir=int(bi[j, 1]), traced=bool(bi[j, 2]), reached=bool(bi[j, 3]), escaped=bool(bi[j, 4]),
+                     p_b=bf[j, 0], p_e=bf[j, 1], prod=bf[j, 2:6].copy()) for j in range(counts[2])]
+        return dict(wl=head[0:4].copy(), ray_weight=head[4:8].copy(), emission=head[8:12].copy(), result=head[12:16].copy(),
+                    hit=bool(counts[0]), light=light, bsdf=bsdf, draws=[int(x) for x in draws[:counts[3]]])
 
     def film_pixels(self, params, pixels, threads=16):
         """float32[n, 5]: the film's {X,Y,Z,A,W} at the whole-film pixels `pixels` ((x, y) pairs), bit for bit what render()
