@@ -68,6 +68,10 @@ extern "C" {
                                       emitter per scene, `constant` or `envmap`; msk_envmap_desc + msk_gpu_scene_create_env below) */
 #define MSK_EMITTER_POINT      3   /* "point" emitters/point.cpp: an isotropic delta light (mesh_id = -1; any number; its position comes in an
                                       msk_point_desc through msk_gpu_scene_create_ext; semantics at msk_point_desc below) */
+#define MSK_EMITTER_SPOT       4   /* "spot": a point light times a cone factor (delta light; mesh_id = -1; any number; its geometry comes in an
+                                      msk_light_desc through msk_gpu_scene_create_lights; semantics at msk_light_desc below) */
+#define MSK_EMITTER_DIRECTIONAL 5  /* "directional": a sun, parallel light from one direction (delta light; mesh_id = -1; any number; its
+                                      direction comes in an msk_light_desc, as for MSK_EMITTER_SPOT) */
 
 /* AOV channel groups of the "aov" integrator (integrators/aov.cpp:21-28,87-144); channels per type: 1 3 2 3 3 4 */
 #define MSK_AOV_DEPTH          0   /* si.t, 0 on a miss                                  (aov.cpp:97-99)   */
@@ -353,6 +357,52 @@ typedef struct msk_scene_masks {
     const msk_mask_desc *masks;
 } msk_scene_masks;
 
+/*
+ * The geometry of an MSK_EMITTER_SPOT or MSK_EMITTER_DIRECTIONAL emitter: the two other delta lights.  The reference has neither
+ * plugin; the semantics are this back end's own and are fixed here.  The emitter's msk_emitter_desc has mesh_id = -1 and keeps its
+ * spectrum in radiance / d65_scale / radiance_regular, as MSK_EMITTER_POINT does: for a spot the PEAK INTENSITY I(l) (W / sr per nm),
+ * for a sun the IRRADIANCE E(l) (W / m^2 per nm) on a surface that faces it.  Exactly one msk_light_desc per such emitter, in any
+ * order.  Everything below is fp32, one operation at a time, IEEE sqrt and division, no contraction; dot products associate as
+ * x x + (y y + z z).
+ *
+ * Spot, from a reference point p, with a = direction (the axis):  d, dist, inv exactly as at msk_point_desc (dist == 0 gives
+ * pdf = 0);  c = -(d.x a.x + (d.y a.y + d.z a.z));  the falloff f, tested in this order:  c >= cos_beam gives 1;  c <= cos_cutoff
+ * gives 0;  otherwise t = (c - cos_cutoff) / (cos_beam - cos_cutoff) and f = (t * t) * (3.f - 2.f * t).
+ * value(l) = ((I(l) * inv) * inv) * f, pdf = 1;  f == 0 gives pdf = 0: no contribution and no shadow ray.  (A smoothstep in cosine
+ * space, as in pbrt-v4, not Mitsuba's ramp in angle: no inverse trigonometry on the device, and it can be restated exactly.
+ * cos_cutoff == cos_beam is a hard edge.  With cos_cutoff = cos_beam = -1 the first branch is taken wherever c is a number and
+ * the spot is the point light, to the bit.)
+ *
+ * Directional, with w = direction:  d = (-w.x, -w.y, -w.z);  dist = 2.f * env_radius, the radius of the sphere around the scene that
+ * an environment emitter gets (a scene with a sun computes it whether it holds an environment emitter or not);  pdf = 1;
+ * value(l) = E(l).
+ *
+ * For both, everything msk_point_desc says holds: the bounce's two random numbers are drawn, u.x is rescaled with several
+ * emitters, selection is the existing one; the shadow ray is d with length dist * (1 - MSK_SHADOW_EPS); the next-event term has
+ * weight 1 in "path" and in "direct"; the light is never hit or seen, has no emitter density for a BSDF sample, hide_emitters does
+ * not concern it and it does not switch the camera cull off.  The scene runs the kernels of msk_point_desc, so a `constant` sky
+ * follows the rule stated there.
+ * Refused at scene creation (MSK_ERR_INVALID_ARG, the message names the emitter or the descriptor): a spot or sun without its
+ * descriptor or with two, a descriptor whose emitter is of another type or out of range, n_lights without lights, a position
+ * (spot) or direction that is not finite, | |direction|^2 - 1 | > 1e-5, cos_cutoff outside [-1, 1), cos_beam outside
+ * [cos_cutoff, 1], mesh_id != -1.
+ */
+typedef struct msk_light_desc {
+    uint32_t emitter;        /* index into msk_scene_desc.emitters: an MSK_EMITTER_SPOT or MSK_EMITTER_DIRECTIONAL entry   */
+    float    position[3];    /* spot: world space, finite.  directional: ignored                                          */
+    float    direction[3];   /* the way the light TRAVELS (spot: its axis), unit length, finite                           */
+    float    cos_cutoff;     /* spot: cosine of the half-angle beyond which it is dark, in [-1, 1)                        */
+    float    cos_beam;       /* spot: cosine of the half-angle inside which it is at full intensity,
+                                cos_cutoff <= cos_beam <= 1                                                               */
+} msk_light_desc;
+
+/* msk_scene_masks cannot grow in place either: the spot and directional emitters' geometry wraps it. */
+typedef struct msk_scene_lights {
+    msk_scene_masks masks;   /* everything above                                                       */
+    uint32_t n_lights;       /* may be 0, lights then unused                                           */
+    const msk_light_desc *lights;
+} msk_scene_lights;
+
 /* PerspectiveCamera (sensors/perspective.cpp:8-42); matrices are row-major 4x4. */
 typedef struct msk_camera_desc {
     float sample_to_camera[16];  /* m_sample_to_camera, sample space in PIXELS */
@@ -504,6 +554,10 @@ int  msk_gpu_scene_create_ext(msk_ctx *ctx, const msk_scene_desc *desc, const ms
    zero width or height (or without values).  A scene that holds a mask runs kernels of its own (k_shade_gen_m, ...), whatever else
    it holds.  A group context passes the extension to every member. */
 int  msk_gpu_scene_create_masks(msk_ctx *ctx, const msk_scene_desc *desc, const msk_scene_masks *em, msk_scene **out_scene);
+/* The same with everything msk_scene_lights holds: msk_gpu_scene_create_masks(c, d, m, o) is msk_gpu_scene_create_lights(c, d, &{*m, 0, NULL}, o)
+   and el == NULL is no extension at all.  The refusals are listed at msk_light_desc.  A scene that holds a spot or a directional
+   emitter runs the kernels of a scene with a point emitter.  A group context passes the extension to every member. */
+int  msk_gpu_scene_create_lights(msk_ctx *ctx, const msk_scene_desc *desc, const msk_scene_lights *el, msk_scene **out_scene);
 void msk_gpu_scene_destroy(msk_scene *scene);
 
 /* ---- the hot path --------------------------------------------------------- */
@@ -586,6 +640,13 @@ int  msk_gpu_env_sample(msk_scene *scene, uint64_t n, const float *u, float *out
  */
 int  msk_gpu_point_sample(msk_scene *scene, uint32_t emitter, uint64_t n, const float *ref_points, const float *wavelengths, float *out_d_dist, float *out_value);
 int  msk_gpu_conductor_sample(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *cos_theta_i, const float *wavelengths, float *out_value);
+/*
+ * The next-event sample of the spot or directional emitter `emitter` (msk_light_desc), with the arguments and outputs of
+ * msk_gpu_point_sample, through the device function the shading kernels call.  A spot: {d, dist} and value(l) = ((I inv) inv) f, the
+ * value all zeros where f == 0, everything zeros where dist == 0.  A sun: {-direction, 2 env_radius} and E(l), whatever the
+ * reference point.  MSK_ERR_INVALID_ARG for an emitter that is out of range or neither a spot nor a directional emitter.
+ */
+int  msk_gpu_light_sample(msk_scene *scene, uint32_t emitter, uint64_t n, const float *ref_points, const float *wavelengths, float *out_d_dist, float *out_value);
 
 /*
  * The decorated BSDF entry `bsdf` of a scene that holds a mask (msk_mask_desc; an entry without one has the constant opacity 1), at n

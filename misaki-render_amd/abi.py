@@ -21,6 +21,8 @@ MSK_BSDF_CONDUCTOR = 4        # "conductor": smooth metal, one delta reflection 
 MSK_EMITTER_AREA, MSK_EMITTER_CONSTANT = 0, 1
 MSK_EMITTER_ENVMAP = 2        # "envmap": a lat-long radiance image, importance-sampled (EnvmapDesc, msk_gpu_scene_create_env)
 MSK_EMITTER_POINT = 3         # "point": an isotropic delta light (PointDesc + SceneExt, msk_gpu_scene_create_ext)
+MSK_EMITTER_SPOT = 4          # "spot": a point light times a cone factor (LightDesc + SceneLights, msk_gpu_scene_create_lights)
+MSK_EMITTER_DIRECTIONAL = 5   # "directional": a sun (LightDesc, likewise)
 MSK_TEXTURE_CHECKERBOARD = 1
 MSK_TEXTURE_BITMAP, MSK_TEXTURE_BITMAP_NEAREST = 2, 3       # "bitmap": bilinear / nearest (ABI v8)
 MSK_EMITTER_AREA = 0
@@ -83,6 +85,16 @@ class MaskDesc(C.Structure):
 
 class SceneMasks(C.Structure):
     _fields_ = [("ext", SceneExt), ("n_masks", C.c_uint32), ("masks", C.POINTER(MaskDesc))]
+
+
+class LightDesc(C.Structure):
+    """msk_light_desc: the geometry of a spot or directional emitter.  direction: the way the light travels, unit length"""
+    _fields_ = [("emitter", C.c_uint32), ("position", C.c_float * 3), ("direction", C.c_float * 3),
+                ("cos_cutoff", C.c_float), ("cos_beam", C.c_float)]
+
+
+class SceneLights(C.Structure):
+    _fields_ = [("masks", SceneMasks), ("n_lights", C.c_uint32), ("lights", C.POINTER(LightDesc))]
 
 
 class CameraDesc(C.Structure):
@@ -161,6 +173,7 @@ EXPORTS = ["msk_gpu_init", "msk_gpu_shutdown", "msk_gpu_last_error", "msk_gpu_sc
            "msk_gpu_eval_texture", "msk_gpu_scene_create_env", "msk_gpu_env_eval", "msk_gpu_env_sample",
            "msk_gpu_scene_create_ext", "msk_gpu_point_sample", "msk_gpu_conductor_sample",
            "msk_gpu_scene_create_masks", "msk_gpu_mask_sample", "msk_gpu_mask_eval",
+           "msk_gpu_scene_create_lights", "msk_gpu_light_sample",
            "msk_gpu_render_direct", "msk_gpu_render_direct_device", "msk_gpu_sample_pixels_direct"]
 
 # integrators/aov.cpp:21-28
@@ -222,6 +235,13 @@ def load_library(path=None):
     lib.msk_gpu_conductor_sample.restype = C.c_int
     lib.msk_gpu_scene_create_masks.argtypes = [vp, C.POINTER(SceneDesc), C.POINTER(SceneMasks), C.POINTER(vp)]
     lib.msk_gpu_scene_create_masks.restype = C.c_int
+    # (the parent build's library, loaded through MSK_GPU_LIB for an A/B (tools/delta_bench.py), has neither: a scene with lights then
+    # fails on the missing symbol; build() holds the tree's own library to EXPORTS)
+    if path is None and not os.environ.get("MSK_GPU_LIB") or hasattr(lib, "msk_gpu_scene_create_lights"):
+        lib.msk_gpu_scene_create_lights.argtypes = [vp, C.POINTER(SceneDesc), C.POINTER(SceneLights), C.POINTER(vp)]
+        lib.msk_gpu_scene_create_lights.restype = C.c_int
+        lib.msk_gpu_light_sample.argtypes = [vp, C.c_uint32, u64, vp, vp, vp, vp]
+        lib.msk_gpu_light_sample.restype = C.c_int
     lib.msk_gpu_mask_sample.argtypes = [vp, C.c_uint32, u64, vp, vp, vp, vp, vp, vp, vp]
     lib.msk_gpu_mask_sample.restype = C.c_int
     lib.msk_gpu_mask_eval.argtypes = [vp, C.c_uint32, u64, vp, vp, vp, vp, vp, vp]
@@ -284,13 +304,14 @@ class Context:
 class Scene:
     """msk_scene: geometry + BVH + light tables resident in HBM."""
 
-    def __init__(self, ctx, flat, envmap=None, points=None, masks=None):
+    def __init__(self, ctx, flat, envmap=None, points=None, masks=None, lights=None):
         """flat: hostmirror.FlatScene (keeps the numpy arrays the desc points into alive).  envmap: the EnvmapDesc of the scene's
         MSK_EMITTER_ENVMAP emitter; by default the one the flattener made (flat.envmap), if any.  points: the PointDesc array of
         its MSK_EMITTER_POINT emitters (a ctypes array or a list); by default flat.points.  A scene with points is created
         through msk_gpu_scene_create_ext, one with an image alone through _create_env, any other through msk_gpu_scene_create.
         masks: the MaskDesc array of its `mask` BSDFs (a ctypes array or a list); by default flat.masks.  A scene with masks is
-        created through msk_gpu_scene_create_masks."""
+        created through msk_gpu_scene_create_masks.  lights: the LightDesc array of its spot and directional emitters (a ctypes
+        array or a list); by default flat.lights.  A scene with lights is created through msk_gpu_scene_create_lights."""
         self.ctx, self.flat = ctx, flat
         self.handle = C.c_void_p()
         self.envmap = envmap if envmap is not None else getattr(flat, "envmap", None)
@@ -302,7 +323,16 @@ class Scene:
         if mk is not None and not isinstance(mk, C.Array):
             mk = (MaskDesc * max(1, len(mk)))(*mk) if len(mk) else None
         self.masks = mk if (mk is not None and len(mk)) else None
-        if self.masks is not None:
+        lt = lights if lights is not None else getattr(flat, "lights", None)
+        if lt is not None and not isinstance(lt, C.Array):
+            lt = (LightDesc * max(1, len(lt)))(*lt) if len(lt) else None
+        self.lights = lt if (lt is not None and len(lt)) else None
+        if self.lights is not None:
+            ext = SceneExt(C.pointer(self.envmap) if self.envmap is not None else None, len(self.points) if self.points is not None else 0, self.points)
+            em = SceneMasks(ext, len(self.masks) if self.masks is not None else 0, self.masks)
+            self.el = SceneLights(em, len(self.lights), self.lights)
+            ctx.check(ctx.lib.msk_gpu_scene_create_lights(ctx.handle, C.byref(flat.desc), C.byref(self.el), C.byref(self.handle)))
+        elif self.masks is not None:
             ext = SceneExt(C.pointer(self.envmap) if self.envmap is not None else None, len(self.points) if self.points is not None else 0, self.points)
             self.em = SceneMasks(ext, len(self.masks), self.masks)
             ctx.check(ctx.lib.msk_gpu_scene_create_masks(ctx.handle, C.byref(flat.desc), C.byref(self.em), C.byref(self.handle)))
@@ -429,6 +459,18 @@ class Scene:
         d, uv, pdf = np.empty((len(u), 3), np.float32), np.empty((len(u), 2), np.float32), np.empty(len(u), np.float32)
         self.ctx.check(self.ctx.lib.msk_gpu_env_sample(self.handle, len(u), _ptr(u), _ptr(d), _ptr(uv), _ptr(pdf)))
         return d, uv, pdf
+
+    def light_sample(self, emitter, ref_points, wavelengths):
+        """The next-event sample of the spot or directional emitter `emitter` from the reference points (n, 3) at the wavelengths
+        (n, 4): -> (d_dist float32[n, 4] = {d, dist}, value float32[n, 4]), as point_sample (msk_gpu_light_sample)."""
+        p = np.ascontiguousarray(ref_points, np.float32).reshape(-1, 3)
+        wl = np.ascontiguousarray(wavelengths, np.float32).reshape(-1, 4)
+        if len(p) != len(wl):
+            raise ValueError("ref_points and wavelengths must name the same number of points")
+        dd = np.empty((len(p), 4), np.float32)
+        val = np.empty((len(p), 4), np.float32)
+        self.ctx.check(self.ctx.lib.msk_gpu_light_sample(self.handle, int(emitter), len(p), _ptr(p), _ptr(wl), _ptr(dd), _ptr(val)))
+        return dd, val
 
     def point_sample(self, emitter, ref_points, wavelengths):
         """The next-event sample of point emitter `emitter` (index into the scene's emitters) from the reference points

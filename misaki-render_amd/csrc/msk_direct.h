@@ -193,13 +193,12 @@ k_direct(DeviceScene sc, PathState st_unused, PassParams pp, DirectArgs da) {   
                 const float4 e0 = tb.emitters[2 * e], e1 = tb.emitters[2 * e + 1];
                 f3 d; float dist, pdf; spec emitter_val;
                 bool point = false;
-                if (__float_as_uint(e1.x) == MSK_EMITTER_MARK_POINT) {               // point.cpp (msk_gpu.h, msk_point_desc)
-                    float inv_d;
-                    d = point_sample(mk3(e1.y, e1.z, e1.w), is.p, &dist, &inv_d);
+                if (emitter_is_delta(__float_as_uint(e1.x))) {                        // point.cpp (msk_gpu.h, msk_point_desc); spot, sun (msk_light_desc)
+                    f3 k;
+                    d = delta_light_sample(tb, sc, __float_as_uint(e1.x), e0, e1, is.p, &dist, &k, &pdf);
                     point = true;
-                    pdf = 1.f;
-                    emitter_val = emitter_radiance(tb, (int) e, wl) * inv_d * inv_d;
-                    if (dist == 0.f) { pdf = 0.f; emitter_val = splat(0.f); }
+                    emitter_val = emitter_radiance(tb, (int) e, wl) * k.x * k.y * k.z;
+                    if (pdf == 0.f) emitter_val = splat(0.f);
                 } else
                 if ((int) e == sc.env_emitter && env_image) {                         // the image (msk_gpu.h, msk_envmap_desc)
                     const EnvView ev = env_view(tb, (int) e);

@@ -349,16 +349,23 @@ extern "C" int msk_gpu_scene_create_ext(msk_ctx *ctx, const msk_scene_desc *d, c
     return msk_gpu_scene_create_masks(ctx, d, &em, out);
 }
 extern "C" int msk_gpu_scene_create_masks(msk_ctx *ctx, const msk_scene_desc *d, const msk_scene_masks *em, msk_scene **out) {
+    msk_scene_lights el = {{{nullptr, 0u, nullptr}, 0u, nullptr}, 0u, nullptr};
+    if (em) el.masks = *em;
+    return msk_gpu_scene_create_lights(ctx, d, &el, out);
+}
+extern "C" int msk_gpu_scene_create_lights(msk_ctx *ctx, const msk_scene_desc *d, const msk_scene_lights *el, msk_scene **out) {
+    const msk_scene_masks *em = el ? &el->masks : nullptr;
     const msk_scene_ext *ext = em ? &em->ext : nullptr;
     if (!ctx || !d || !out) return fail(ctx, MSK_ERR_INVALID_ARG, "msk_gpu_scene_create: NULL argument");
     *out = nullptr;
     MSK_REFUSE_LOST(ctx);
-    if (ctx->group) return group_scene_create(ctx, d, em, out);
+    if (ctx->group) return group_scene_create(ctx, d, el, out);
     const mskplan::SceneKnobs knobs = mskplan::read_scene_knobs();
     mskscene::HostTables t;
     {
         std::string msg;
-        if (int rc = mskscene::pack(d, ext, knobs.pad_scale, &t, &msg, em ? em->n_masks : 0u, em ? em->masks : nullptr)) return fail(ctx, rc, "%s", msg.c_str());
+        if (int rc = mskscene::pack(d, ext, knobs.pad_scale, &t, &msg, em ? em->n_masks : 0u, em ? em->masks : nullptr, el ? el->n_lights : 0u,
+                                     el ? el->lights : nullptr)) return fail(ctx, rc, "%s", msg.c_str());
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
@@ -1662,27 +1669,32 @@ extern "C" int msk_gpu_env_sample(msk_scene *scene, uint64_t n, const float *u, 
     return env_probe(scene, "msk_gpu_env_sample", 1, n, u, nullptr, nullptr, out_dir, out_uv, out_pdf);
 }
 
-// msk_gpu_point_sample (conductor == 0: `in` = n * 3 reference points, two outputs) / msk_gpu_conductor_sample (`in` = n cosines)
+// msk_gpu_point_sample (conductor == 0: `in` = n * 3 reference points, two outputs) / msk_gpu_conductor_sample (1: `in` = n cosines) /
+// msk_gpu_light_sample (2: as 0, for a spot or directional emitter)
 static int delta_probe(msk_scene *scene, const char *who, uint32_t conductor, uint32_t index, uint64_t n, const float *in, const float *wavelengths, float *out_a, float *out_b) {
     msk_ctx *ctx = scene->ctx;
     MSK_REFUSE_LOST(ctx);
+    if (conductor == 2u) {
+        if (index >= scene->emitter_types.size() || (scene->emitter_types[index] != MSK_EMITTER_SPOT && scene->emitter_types[index] != MSK_EMITTER_DIRECTIONAL))
+            return fail(ctx, MSK_ERR_INVALID_ARG, "%s: emitter %u is neither a spot nor a directional emitter of this scene", who, index);
+    } else
     if (!scene->facts.has_delta) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: the scene holds neither a point emitter nor a conductor", who);
-    if (conductor) {
+    else if (conductor) {
         if (index >= scene->bsdf_types.size() || scene->bsdf_types[index] != MSK_BSDF_CONDUCTOR) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: bsdf %u is not a conductor of this scene", who, index);
     } else if (index >= scene->emitter_types.size() || scene->emitter_types[index] != MSK_EMITTER_POINT) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: emitter %u is not a point emitter of this scene", who, index);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (n == 0) return MSK_OK;
-    const size_t in_f = conductor ? 1 : 3;
+    const size_t in_f = conductor == 1u ? 1 : 3;
     DevBuf d_in, d_wl, d_a, d_b;
     HIP_TRY(ctx, d_in.alloc(n * in_f * 4)); HIP_TRY(ctx, d_wl.alloc(n * 16)); HIP_TRY(ctx, d_b.alloc(n * 16));
-    if (!conductor) HIP_TRY(ctx, d_a.alloc(n * 16));
+    if (conductor != 1u) HIP_TRY(ctx, d_a.alloc(n * 16));
     HIP_TRY(ctx, hipMemcpy(d_in.p, in, n * in_f * 4, hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(d_wl.p, wavelengths, n * 16, hipMemcpyHostToDevice));
     const uint32_t grid = (uint32_t) std::min<uint64_t>((n + MSK_BLOCK - 1) / MSK_BLOCK, 4096);
     hipLaunchKernelGGL(k_delta_probe, dim3(grid), dim3(MSK_BLOCK), 0, ctx->stream, scene->dev, conductor, index, n, d_in.as<float>(), d_wl.as<float4>(), d_a.as<float4>(), d_b.as<float4>());
     HIP_TRY(ctx, hipGetLastError());
     if (int rcw = ctx_sync(ctx, ctx->stream, "k_delta_probe")) { d_in.leak(); d_wl.leak(); d_a.leak(); d_b.leak(); return rcw; }
-    if (!conductor) HIP_TRY(ctx, hipMemcpy(out_a, d_a.p, n * 16, hipMemcpyDeviceToHost));
+    if (conductor != 1u) HIP_TRY(ctx, hipMemcpy(out_a, d_a.p, n * 16, hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipMemcpy(out_b, d_b.p, n * 16, hipMemcpyDeviceToHost));
     return MSK_OK;
 }
@@ -1690,6 +1702,11 @@ extern "C" int msk_gpu_point_sample(msk_scene *scene, uint32_t emitter, uint64_t
     if (!scene || (n && (!ref_points || !wavelengths || !out_d_dist || !out_value))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_point_sample: NULL argument");
     if (scene->ctx->group) { const int rc = delta_probe(scene->parts[0], "msk_gpu_point_sample", 0, emitter, n, ref_points, wavelengths, out_d_dist, out_value); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
     return delta_probe(scene, "msk_gpu_point_sample", 0, emitter, n, ref_points, wavelengths, out_d_dist, out_value);
+}
+extern "C" int msk_gpu_light_sample(msk_scene *scene, uint32_t emitter, uint64_t n, const float *ref_points, const float *wavelengths, float *out_d_dist, float *out_value) {
+    if (!scene || (n && (!ref_points || !wavelengths || !out_d_dist || !out_value))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_light_sample: NULL argument");
+    if (scene->ctx->group) { const int rc = delta_probe(scene->parts[0], "msk_gpu_light_sample", 2, emitter, n, ref_points, wavelengths, out_d_dist, out_value); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
+    return delta_probe(scene, "msk_gpu_light_sample", 2, emitter, n, ref_points, wavelengths, out_d_dist, out_value);
 }
 extern "C" int msk_gpu_conductor_sample(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *cos_theta_i, const float *wavelengths, float *out_value) {
     if (!scene || (n && (!cos_theta_i || !wavelengths || !out_value))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_conductor_sample: NULL argument");

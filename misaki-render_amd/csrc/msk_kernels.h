@@ -66,7 +66,9 @@ struct DeviceScene {
     uint32_t n_bsdf_f4;         // float4 count of `bsdfs` (records + textures)
     const float4 *emitters;     // 2 x float4 per emitter: {c0,c1,c2,inv_area} {mesh,first_face,face_count,cdf_off (uint bits)}; an environment
                                 // emitter: mesh = ~0 and, for an `envmap`, first_face = the float4 offset of its block in `texels` (EnvView)
-                                // and face_count = 1 (0: the `constant` sky); a `point` emitter: {MSK_EMITTER_MARK_POINT, x, y, z}, its position
+                                // and face_count = 1 (0: the `constant` sky); a `point` emitter: {MSK_EMITTER_MARK_POINT, x, y, z}, its position;
+                                // a `directional` one: {MSK_EMITTER_MARK_DIRECTIONAL, d}, the way to the light; a `spot`: {MSK_EMITTER_MARK_SPOT,
+                                // x, y, z} and, in inv_area's place, the offset in `cdf` (uint bits) of {axis, cos_cutoff, cos_beam}
     const float *emitter_d65;   // 95 floats per emitter: d65 * d65_scale, or the values of a `regular` radiance (ABI v7)
     const float4 *emitter_grid; // per emitter {lambda_min, inv_interval, last segment (uint bits), 1 = the table IS the radiance (no
                                 // sigmoid factor)} of that table: {360, 0.2, 93, 0} for the D65 form.  Read by the general shading
@@ -74,7 +76,7 @@ struct DeviceScene {
     const float *spectra;       // values of the scene's other `regular` spectra (BSDF parameters), n_spectra floats; a spectrum
                                 // record {lambda_min, inv_interval, first | last << 24 (uint bits), -1} names its part
     uint32_t n_spectra;
-    const float *cdf;           // concatenated area CDFs (face_count+1 each)
+    const float *cdf;           // concatenated area CDFs (face_count+1 each); a spot's five floats among them
     const float *cie;           // 285 floats
     uint32_t n_nodes, n_tris, n_emitters, n_meshes, n_bsdfs, cdf_len;
     uint32_t root_ref;          // packed child ref of the root
@@ -1794,6 +1796,35 @@ MSK_DEV f3 point_sample(f3 position, f3 p, float *dist, float *inv) {
     *inv = 1.f / *dist;
     return d * *inv;
 }
+// Is word 0 of an emitter's second float4 the mark of a delta light: point, spot or directional (msk_layout.h: three consecutive values)?
+MSK_DEV bool emitter_is_delta(uint32_t mark) { return mark - MSK_EMITTER_MARK_DELTA_FIRST <= MSK_EMITTER_MARK_POINT - MSK_EMITTER_MARK_DELTA_FIRST; }
+// The `spot` emitter's cone factor (msk_gpu.h: msk_light_desc): a smoothstep in the cosine c of the angle to the axis
+MSK_DEV float spot_falloff(float c, float cos_cutoff, float cos_beam) {
+    if (c >= cos_beam) return 1.f;
+    if (c <= cos_cutoff) return 0.f;
+    const float t = (c - cos_cutoff) / (cos_beam - cos_cutoff);
+    return (t * t) * (3.f - 2.f * t);
+}
+// The next-event sample of a delta light from p (msk_gpu.h: msk_point_desc, msk_light_desc): `mark` says which (emitter_is_delta).
+// Returns the direction to the light; *dist; *scale = what the emitter's spectrum is multiplied by, factor by factor in the
+// header's order ({inv, inv, f}: 1 / dist twice, then the cone factor; {1, 1, 1} for a sun and f = 1 for a point light, all exact);
+// *pdf = 1, or 0 where the light adds nothing (dist == 0, or outside a spot's cone).
+template <class TB>
+MSK_DEV f3 delta_light_sample(const TB &tb, const DeviceScene &sc, uint32_t mark, float4 e0, float4 e1, f3 p, float *dist, f3 *scale, float *pdf) {
+    if (mark == MSK_EMITTER_MARK_DIRECTIONAL) {
+        *dist = 2.f * sc.env_radius; *scale = mk3(1.f, 1.f, 1.f); *pdf = 1.f;
+        return mk3(e1.y, e1.z, e1.w);
+    }
+    float inv, f = 1.f;
+    const f3 d = point_sample(mk3(e1.y, e1.z, e1.w), p, dist, &inv);
+    if (mark == MSK_EMITTER_MARK_SPOT) {
+        const float *s = tb.cdf + __float_as_uint(e0.w);           // {axis, cos_cutoff, cos_beam}
+        f = spot_falloff(-(d.x * s[0] + (d.y * s[1] + d.z * s[2])), s[3], s[4]);
+    }
+    *scale = mk3(inv, inv, f);
+    *pdf = (*dist == 0.f || f == 0.f) ? 0.f : 1.f;
+    return d;
+}
 MSK_DEV float clamp_alpha(float a) { return fmax_std(a, 1e-4f); }
 
 // bsdfs/roughdielectric.cpp:118-190 eval + pdf (both lobes, TransportMode::Radiance)
@@ -2380,14 +2411,15 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
                         if (pdf != 0.f) emitter_val = env_radiance(ev, tb, (int) e, uv, wl) / pdf;
                         nee_pdf = pdf;
                     } else
-                    if (tb_traits<TB>::delta && __float_as_uint(e1.x) == MSK_EMITTER_MARK_POINT) {
-                        // point.cpp (msk_gpu.h, msk_point_desc): pdf 1, value = I / dist^2, weight 1 below
-                        float inv;
-                        d = point_sample(mk3(e1.y, e1.z, e1.w), si.p, &dist, &inv);
+                    if (tb_traits<TB>::delta && emitter_is_delta(__float_as_uint(e1.x))) {
+                        // point.cpp (msk_gpu.h, msk_point_desc): pdf 1, value = I / dist^2, weight 1 below; a spot's cone factor
+                        // and the sun (msk_light_desc) likewise
+                        f3 k;
+                        d = delta_light_sample(tb, sc, __float_as_uint(e1.x), e0, e1, si.p, &dist, &k, &pdf);
                         point = true;
-                        pdf = 1.f; nee_pdf = 0.f;
-                        emitter_val = emitter_radiance(tb, (int) e, wl) * inv * inv;
-                        if (dist == 0.f) { pdf = 0.f; emitter_val = splat(0.f); }
+                        nee_pdf = 0.f;
+                        emitter_val = emitter_radiance(tb, (int) e, wl) * k.x * k.y * k.z;
+                        if (pdf == 0.f) emitter_val = splat(0.f);
                     } else
                     if (!DIFFUSE_ONLY && (int) e == sc.env_emitter) {
                         // constant.cpp:53-72 (radiance at the path's wavelengths, oracle D8)
@@ -2996,7 +3028,8 @@ k_env_probe(DeviceScene sc, uint32_t sample, uint64_t n, const float *in, const 
 }
 
 // msk_gpu_point_sample (conductor == 0: `in` = n * 3 reference points; out_a = {d, dist}, out_b = value) / msk_gpu_conductor_sample
-// (conductor == 1: `in` = n cosines; out_b = the lobe's value, zeros for cos_i <= 0), through the functions the shading kernels call.
+// (conductor == 1: `in` = n cosines; out_b = the lobe's value, zeros for cos_i <= 0) / msk_gpu_light_sample (conductor == 2: as
+// conductor == 0, for a spot or directional emitter), through the functions the shading kernels call.
 // `index` = the emitter / the BSDF, checked by the host.  One point per thread.
 __global__ void __launch_bounds__(MSK_BLOCK)
 k_delta_probe(DeviceScene sc, uint32_t conductor, uint32_t index, uint64_t n, const float *in, const float4 *wl, float4 *out_a, float4 *out_b) {
@@ -3004,13 +3037,22 @@ k_delta_probe(DeviceScene sc, uint32_t conductor, uint32_t index, uint64_t n, co
     static_cast<SceneTables &>(tb) = stage_tables<false>(sc, nullptr);
     for (uint64_t i = (uint64_t) blockIdx.x * MSK_BLOCK + threadIdx.x; i < n; i += (uint64_t) gridDim.x * MSK_BLOCK) {
         const spec w = from4(wl[i]);
-        if (conductor) {
+        if (conductor == 1u) {
             const BsdfRec bs = load_bsdf(tb, (int) index);
             const float c = in[i];
             f3 wo; float pdf = 0.f; bool ok = false;
             // (wi = (0, 0, cos_i): the lobe's value depends on wi.z alone)
             const spec v = conductor_sample(tb, bs, mk3(0.f, 0.f, c), w, &wo, &pdf, &ok);
             out_b[i] = make_float4(v.v[0], v.v[1], v.v[2], v.v[3]);
+        } else if (conductor == 2u) {      // msk_gpu_light_sample: a spot or a sun, through the function the shading kernels call
+            const float4 e0 = tb.emitters[2 * index], e1 = tb.emitters[2 * index + 1];
+            float dist, pdf; f3 k;
+            const f3 d = delta_light_sample(tb, sc, __float_as_uint(e1.x), e0, e1, mk3(in[i * 3], in[i * 3 + 1], in[i * 3 + 2]), &dist, &k, &pdf);
+            spec v = emitter_radiance(tb, (int) index, w) * k.x * k.y * k.z;
+            float4 a = make_float4(d.x, d.y, d.z, dist);
+            if (pdf == 0.f) v = splat(0.f);
+            if (dist == 0.f) a = make_float4(0.f, 0.f, 0.f, 0.f);
+            out_a[i] = a; out_b[i] = make_float4(v.v[0], v.v[1], v.v[2], v.v[3]);
         } else {
             const float4 e1 = tb.emitters[2 * index + 1];
             float dist, inv;

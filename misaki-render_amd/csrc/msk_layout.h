@@ -11,6 +11,12 @@
 #define MSK_CLASS_SHIFT 27
 #define MSK_N_CLASSES 4
 #define MSK_EMITTER_MARK_POINT 0xfffffffeu      /* word 0 of a point emitter's second float4 (an environment emitter's: 0xffffffff) */
+/* the other delta lights (msk_gpu.h, msk_light_desc).  A spot: {MARK_SPOT, position}; word 3 of its FIRST float4 holds, as bits,
+   the offset in the CDF pool of its five floats {axis.x, axis.y, axis.z, cos_cutoff, cos_beam}.  A sun: {MARK_DIRECTIONAL, d} with
+   d = -direction, the way to the light.  The three marks are consecutive: MSK_EMITTER_MARK_DELTA_FIRST <= mark <= MARK_POINT. */
+#define MSK_EMITTER_MARK_SPOT 0xfffffffdu
+#define MSK_EMITTER_MARK_DIRECTIONAL 0xfffffffcu
+#define MSK_EMITTER_MARK_DELTA_FIRST MSK_EMITTER_MARK_DIRECTIONAL
 
 /* core/mathutils.h:10-20 */
 #define MSK_EPSILON_F   5.9604644775390625e-08f

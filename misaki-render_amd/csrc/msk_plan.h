@@ -154,7 +154,8 @@ struct SceneFacts {
     bool lds_scene = false, lds_tables = false, all_diffuse = true, has_regular = false, has_dielectric = false, cull_ok = false;
     bool has_bitmap = false;      // a `bitmap` texture (ABI v8): the instantiations with the texel lookup run, whatever else the scene holds
     bool has_envmap = false;      // an `envmap` emitter (MSK_EMITTER_ENVMAP): the instantiations with the image lookup and its sampling run
-    bool has_delta = false;       // a `point` emitter or a smooth `conductor` (MSK_EMITTER_POINT, MSK_BSDF_CONDUCTOR): the instantiations with the
+    bool has_delta = false;       // a `point`, `spot` or `directional` emitter or a smooth `conductor` (MSK_EMITTER_POINT / _SPOT / _DIRECTIONAL,
+                                  // MSK_BSDF_CONDUCTOR): the instantiations with the
                                   // delta light, the mirror lobe and the `constant` sky's own density run, whatever else the scene holds
     bool has_mask = false;        // a `mask` (msk_mask_desc): the instantiations with the opacity lookup, the null lobe and the `scattered` bit run,
                                   // whatever else the scene holds

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "msk_mask_tables.h"
+#include "msk_light_tables.h"
 
 namespace mskscene {
 
@@ -70,10 +71,14 @@ struct Packer : HostTables {
     uint32_t n_masks;
     const msk_mask_desc *masks;
     std::vector<float> mask_values;         // the mask images' values, in the order of `masks`
+    uint32_t n_lights;
+    const msk_light_desc *lights;           // what msk_scene_lights holds beyond msk_scene_masks
+    bool has_directional = false;           // a sun needs env_radius, with or without an environment emitter
 
     Packer(const msk_scene_desc *d_, const msk_scene_ext *ext_, const char *pad_scale_text_, std::string *msg_, uint32_t n_masks_ = 0,
-           const msk_mask_desc *masks_ = nullptr)
-        : d(d_), ext(ext_), env(ext_ ? ext_->envmap : nullptr), pad_scale_text(pad_scale_text_), msg(msg_), n_masks(n_masks_), masks(masks_) {}
+           const msk_mask_desc *masks_ = nullptr, uint32_t n_lights_ = 0, const msk_light_desc *lights_ = nullptr)
+        : d(d_), ext(ext_), env(ext_ ? ext_->envmap : nullptr), pad_scale_text(pad_scale_text_), msg(msg_), n_masks(n_masks_), masks(masks_),
+          n_lights(n_lights_), lights(lights_) {}
 
     int run() {
         int rc;
@@ -325,8 +330,9 @@ struct Packer : HostTables {
         return MSK_OK;
     }
 
-    // emitter records, their D65 tables and grids, the area emitters' CDFs; then the msk_point_desc list itself
+    // emitter records, their D65 tables and grids, the area emitters' CDFs; then the msk_point_desc and msk_light_desc lists themselves
     int pack_emitters() {
+        if (int rc = check_light_list(n_lights, lights, msg)) return rc;
         emitters.assign((size_t) std::max(1u, d->n_emitters) * 8, 0.f); d65.assign((size_t) std::max(1u, d->n_emitters) * 95, 0.f);
         emitter_grid.assign((size_t) std::max(1u, d->n_emitters) * 4, 0.f);
         for (uint32_t e = 0; e < d->n_emitters; ++e) {
@@ -374,6 +380,8 @@ struct Packer : HostTables {
                 o[3] = 0.f;
                 const uint32_t mark = MSK_EMITTER_MARK_POINT;
                 std::memcpy(&o[4], &mark, 4); std::memcpy(&o[5], pd->position, 12);
+            } else if (ed.type == MSK_EMITTER_SPOT || ed.type == MSK_EMITTER_DIRECTIONAL) {
+                if (int rc = pack_light_record(e, ed, n_lights, lights, o, cdf_all, has_delta, has_directional, msg)) return rc;      // msk_light_tables.h
             } else {
                 return refuse(msg, MSK_ERR_UNSUPPORTED, "emitter %u: type %d is not supported (area, constant, envmap, point)", e, ed.type);
             }
@@ -399,6 +407,7 @@ struct Packer : HostTables {
             if (d->emitters[pe].type != MSK_EMITTER_POINT)
                 return refuse(msg, MSK_ERR_INVALID_ARG, "msk_point_desc %u: emitter %u is of type %d, not a point emitter (type %d)", k, pe, d->emitters[pe].type, MSK_EMITTER_POINT);
         }
+        if (int rc = check_light_emitters(d, n_lights, lights, msg)) return rc;
         return MSK_OK;
     }
 
@@ -473,9 +482,10 @@ struct Packer : HostTables {
         if (has_mask_image) place_mask_values(d->n_bsdfs, mask_base, bsdfs, mask_values, tx4);      // the mask images' values behind them (msk_mask_tables.h)
     }
 
-    // constant.cpp:21-28 set_scene: the sphere around Scene::bbox() (bbox.h:105-112), in fp32 exactly as the oracle does
+    // constant.cpp:21-28 set_scene: the sphere around Scene::bbox() (bbox.h:105-112), in fp32 exactly as the oracle does.
+    // A directional emitter's shadow ray has the same length as an environment emitter's: its scene gets the radius too
     void pack_env_radius() {
-        if (env_emitter < 0) return;
+        if (env_emitter < 0 && !has_directional) return;
         float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
         for (uint32_t v = 0; v < d->n_vertices; ++v)
             for (int k = 0; k < 3; ++k) { const float q = d->vertices[(size_t) v * 8 + k]; lo[k] = std::min(lo[k], q); hi[k] = std::max(hi[k], q); }
@@ -490,9 +500,10 @@ struct Packer : HostTables {
 // Fills *out from the descriptor; pad_scale_text = MSK_PAD_SCALE as the environment holds it (mskplan::SceneKnobs), or nullptr.
 // MSK_OK, or the code of the first refusal with its text in *msg (*out is then untouched).
 // n_masks / masks: what msk_scene_masks holds beyond msk_scene_ext (none: the tables are those of the scene without the argument).
+// n_lights / lights: what msk_scene_lights holds beyond msk_scene_masks, likewise.
 inline int pack(const msk_scene_desc *d, const msk_scene_ext *ext, const char *pad_scale_text, HostTables *out, std::string *msg, uint32_t n_masks = 0,
-                const msk_mask_desc *masks = nullptr) {
-    Packer p(d, ext, pad_scale_text, msg, n_masks, masks);
+                const msk_mask_desc *masks = nullptr, uint32_t n_lights = 0, const msk_light_desc *lights = nullptr) {
+    Packer p(d, ext, pad_scale_text, msg, n_masks, masks, n_lights, lights);
     const int rc = p.run();
     if (rc == MSK_OK) *out = std::move(static_cast<HostTables &>(p));
     return rc;

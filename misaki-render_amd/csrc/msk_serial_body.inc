@@ -107,13 +107,12 @@
                             const float4 e0 = tb.emitters[2 * e], e1 = tb.emitters[2 * e + 1];
                             f3 d; float dist, pdf; spec emitter_val;
                             bool point = false;
-                            if (tb_traits<TB>::delta && __float_as_uint(e1.x) == MSK_EMITTER_MARK_POINT) {   // point.cpp (msk_gpu.h, msk_point_desc)
-                                float inv;
-                                d = point_sample(mk3(e1.y, e1.z, e1.w), si.p, &dist, &inv);
+                            if (tb_traits<TB>::delta && emitter_is_delta(__float_as_uint(e1.x))) {   // point.cpp (msk_gpu.h, msk_point_desc); spot, sun (msk_light_desc)
+                                f3 k;
+                                d = delta_light_sample(tb, sc, __float_as_uint(e1.x), e0, e1, si.p, &dist, &k, &pdf);
                                 point = true;
-                                pdf = 1.f;
-                                emitter_val = emitter_radiance(tb, (int) e, wl) * inv * inv;
-                                if (dist == 0.f) { pdf = 0.f; emitter_val = splat(0.f); }
+                                emitter_val = emitter_radiance(tb, (int) e, wl) * k.x * k.y * k.z;
+                                if (pdf == 0.f) emitter_val = splat(0.f);
                             } else
                             if (tb_traits<TB>::envmap && (int) e == sc.env_emitter && (!tb_traits<TB>::delta || env_is_image(tb, sc))) {  // the image (msk_gpu.h, msk_envmap_desc)
                                 const EnvView ev = env_view(tb, (int) e);

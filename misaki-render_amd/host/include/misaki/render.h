@@ -161,6 +161,8 @@ public:
     virtual bool flatten_envmap(msk_envmap_desc &out, std::vector<float> &texels, std::vector<float> &weights) const { (void) out; (void) texels; (void) weights; return false; }
     // a `point` emitter (MSK_EMITTER_POINT): its world-space position, for the scene's msk_point_desc
     virtual bool flatten_point(float position[3]) const { (void) position; return false; }
+    // a `spot` or `directional` emitter (MSK_EMITTER_SPOT / _DIRECTIONAL): its geometry, for the scene's msk_light_desc (all but `emitter`)
+    virtual bool flatten_light(msk_light_desc &out) const { (void) out; return false; }
     void set_shape(Shape *shape);
     Shape *shape() const { return m_shape; }
     MSK_DECLARE_CLASS()
@@ -303,6 +305,10 @@ struct FlatScene {
     std::vector<std::vector<float>> mask_values;
     msk_scene_masks em = {{nullptr, 0, nullptr}, 0, nullptr};
     const msk_scene_masks *masks_ptr() const { return &em; }
+    // the geometry of the scene's `spot` and `directional` emitters, and the extension that holds it too (msk_gpu_scene_create_lights)
+    std::vector<msk_light_desc> lights;
+    msk_scene_lights el = {{{nullptr, 0, nullptr}, 0, nullptr}, 0, nullptr};
+    const msk_scene_lights *lights_ptr() const { return &el; }
 };
 void flatten_scene(const Scene *scene, const Sensor *sensor, FlatScene &out);
 

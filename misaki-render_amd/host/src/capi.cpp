@@ -81,6 +81,14 @@ int msk_host_masks(msk_host_scene *h, msk_mask_desc *masks, size_t cap) {
     return (int) n;
 }
 
+// the geometry of the flattened scene's `spot` and `directional` emitters (after msk_host_flatten): returns their number and, when
+// `lights` is not NULL, copies up to `cap` of them
+int msk_host_lights(msk_host_scene *h, msk_light_desc *lights, size_t cap) {
+    const size_t n = h->flat.lights.size();
+    if (lights) std::memcpy(lights, h->flat.lights.data(), std::min(n, cap) * sizeof(msk_light_desc));
+    return (int) n;
+}
+
 // scene->integrator()->render(scene, sensor) followed by HDRFilm::image(); optionally develop() to a file
 int msk_host_render(msk_host_scene *h, float *film_xyzaw, float *rgba, const char *develop_to, msk_stats *stats) {
     try {

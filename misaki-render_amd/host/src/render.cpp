@@ -843,6 +843,81 @@ private:
 MSK_IMPLEMENT_CLASS(PointLight, Emitter)
 MSK_REGISTER_INSTANCE(PointLight, "point")
 
+// The other delta lights (include/msk_gpu.h at msk_light_desc; the reference has neither plugin).  Both take a `to_world` (for
+// example a lookat): the light travels along its +z axis, normalised in fp32 as v / sqrt(x x + (y y + z z)).
+static Vector3f light_unit(const Vector3f &v, const char *what) {
+    const float l = std::sqrt(v.x * v.x + (v.y * v.y + v.z * v.z));
+    if (!(l > 0.f)) Throw("{}: the direction must not be the zero vector", what);
+    return Vector3f{v.x / l, v.y / l, v.z / l};
+}
+static bool flatten_light_spectrum(const Texture *t, int type, msk_emitter_desc &out, FlatTables &tables) {
+    Texture::Flat f;
+    if (!t->flatten(f) || !(f.uses_d65 || f.regular)) return false;
+    std::memset(&out, 0, sizeof out);
+    out.type = type;
+    out.mesh_id = -1;
+    if (f.regular) { out.radiance_regular = tables.add_regular(f); return true; }
+    std::memcpy(out.radiance, f.coeff, sizeof f.coeff);
+    out.d65_scale = f.d65_scale;
+    return true;
+}
+
+// `spot`: `intensity` (the peak, W / sr per nm; D65 by default), `cutoff_angle` (degrees, default 20, in (0, 180]), `beam_width`
+// (degrees, default 3/4 of the cutoff, in (0, cutoff_angle]), `to_world`: the lamp sits at its origin.  The cosines are std::cos of
+// the angle in double, rounded to float.
+class SpotLight final : public Emitter {
+public:
+    SpotLight(const Properties &props) : Emitter(props) {
+        m_intensity = props.texture("intensity", Texture::D65(1.f));
+        m_cutoff = props.float_("cutoff_angle", 20.f);
+        if (!(m_cutoff > 0.f && m_cutoff <= 180.f)) Throw("spot: cutoff_angle must be in (0, 180] degrees");
+        m_beam = props.has_property("beam_width") ? props.float_("beam_width") : m_cutoff * 0.75f;
+        if (!(m_beam > 0.f && m_beam <= m_cutoff)) Throw("spot: beam_width must be in (0, cutoff_angle] degrees");
+        const Transform4f to_world = props.transform("to_world", Transform4f());
+        m_position = to_world.apply_point(Vector3f{0.f, 0.f, 0.f});
+        m_axis = light_unit(to_world.apply_vector(Vector3f{0.f, 0.f, 1.f}), "spot");
+    }
+    bool flatten(msk_emitter_desc &out, FlatTables &tables) const override { return flatten_light_spectrum(m_intensity.get(), MSK_EMITTER_SPOT, out, tables); }
+    bool flatten_light(msk_light_desc &out) const override {
+        out.position[0] = m_position.x; out.position[1] = m_position.y; out.position[2] = m_position.z;
+        out.direction[0] = m_axis.x; out.direction[1] = m_axis.y; out.direction[2] = m_axis.z;
+        out.cos_cutoff = (float) std::cos((double) m_cutoff * (M_PI / 180.0));
+        out.cos_beam = (float) std::cos((double) m_beam * (M_PI / 180.0));
+        return true;
+    }
+    MSK_DECLARE_CLASS()
+private:
+    ref<Texture> m_intensity;
+    float m_cutoff, m_beam;
+    Vector3f m_position, m_axis;
+};
+MSK_IMPLEMENT_CLASS(SpotLight, Emitter)
+MSK_REGISTER_INSTANCE(SpotLight, "spot")
+
+// `directional`: `irradiance` (W / m^2 per nm on a surface that faces the light; D65 by default) and exactly one of `direction` (the
+// way the light travels) and `to_world`.
+class DirectionalLight final : public Emitter {
+public:
+    DirectionalLight(const Properties &props) : Emitter(props) {
+        m_irradiance = props.texture("irradiance", Texture::D65(1.f));
+        if (props.has_property("direction") == props.has_property("to_world"))
+            Throw("directional: exactly one of the parameters \"direction\" and \"to_world\" must be specified!");
+        if (props.has_property("direction")) m_direction = light_unit(props.vector3("direction"), "directional");
+        else m_direction = light_unit(props.transform("to_world").apply_vector(Vector3f{0.f, 0.f, 1.f}), "directional");
+    }
+    bool flatten(msk_emitter_desc &out, FlatTables &tables) const override { return flatten_light_spectrum(m_irradiance.get(), MSK_EMITTER_DIRECTIONAL, out, tables); }
+    bool flatten_light(msk_light_desc &out) const override {
+        out.direction[0] = m_direction.x; out.direction[1] = m_direction.y; out.direction[2] = m_direction.z;
+        return true;
+    }
+    MSK_DECLARE_CLASS()
+private:
+    ref<Texture> m_irradiance;
+    Vector3f m_direction;
+};
+MSK_IMPLEMENT_CLASS(DirectionalLight, Emitter)
+MSK_REGISTER_INSTANCE(DirectionalLight, "directional")
+
 // The `envmap` emitter: a lat-long radiance image around the scene, importance-sampled on the device (include/msk_gpu.h at
 // msk_envmap_desc; the reference's emitters/envmap.cpp is RGB-typed and not built).  Properties: filename (through the file
 // resolver: PFM, Radiance .hdr, PGM / PPM), scale (default 1), to_world (a rotation; anything else is refused here, by the back end's own
@@ -1090,7 +1165,7 @@ MSK_REGISTER_INSTANCE(OBJMesh, "obj")
 void flatten_scene(const Scene *scene, const Sensor *sensor, FlatScene &out) {
     out.meshes.clear(); out.bsdfs.clear(); out.emitters.clear(); out.textures.clear(); out.vertices.clear(); out.faces.clear();
     out.regular.clear(); out.regular_values.clear(); out.texels.clear();
-    out.has_envmap = false; out.env_texels.clear(); out.env_weights.clear(); out.points.clear(); out.masks.clear(); out.mask_values.clear();
+    out.has_envmap = false; out.env_texels.clear(); out.env_weights.clear(); out.points.clear(); out.masks.clear(); out.mask_values.clear(); out.lights.clear();
     FlatTables tables{out.textures, out.regular, out.regular_values, out.texels};
     // Scene::m_emitters order (scene.cpp:27-41) decides which emitter sample_emitter_direct picks (scene.cpp:80-84)
     std::map<const Emitter *, int> emitter_index;
@@ -1103,6 +1178,13 @@ void flatten_scene(const Scene *scene, const Sensor *sensor, FlatScene &out) {
             pd.emitter = (uint32_t) out.emitters.size();
             if (!e->flatten_point(pd.position)) Throw("Emitter \"{}\" has no position to flatten", e->clazz()->name());
             out.points.push_back(pd);
+        } else
+        if (ed.type == MSK_EMITTER_SPOT || ed.type == MSK_EMITTER_DIRECTIONAL) {
+            msk_light_desc ld;
+            std::memset(&ld, 0, sizeof ld);
+            if (!e->flatten_light(ld)) Throw("Emitter \"{}\" has no geometry to flatten", e->clazz()->name());
+            ld.emitter = (uint32_t) out.emitters.size();
+            out.lights.push_back(ld);
         } else
         if (!e->is_surface() && !e->is_environment())
             Throw("Emitter \"{}\" is not attached to a shape: not supported by the GPU path integrator", e->clazz()->name());
@@ -1175,6 +1257,7 @@ void flatten_scene(const Scene *scene, const Sensor *sensor, FlatScene &out) {
     out.ext.envmap = out.envmap_ptr(); out.ext.n_points = (uint32_t) out.points.size(); out.ext.points = out.points.empty() ? nullptr : out.points.data();
     for (size_t k = 0; k < out.masks.size(); ++k) out.masks[k].values = out.masks[k].filter ? out.mask_values[k].data() : nullptr;
     out.em.ext = out.ext; out.em.n_masks = (uint32_t) out.masks.size(); out.em.masks = out.masks.empty() ? nullptr : out.masks.data();
+    out.el.masks = out.em; out.el.n_lights = (uint32_t) out.lights.size(); out.el.lights = out.lights.empty() ? nullptr : out.lights.data();
 }
 
 // "0,1,2" -> {0,1,2}; empty -> {single}
@@ -1205,7 +1288,7 @@ static msk_stats render_on_gpu(Scene *scene, Sensor *sensor, std::vector<int> &d
     fill(flat.params);
     if (!ctx && msk_gpu_init(devices.data(), (int) devices.size(), &ctx) != MSK_OK) Throw("{}", msk_gpu_last_error(nullptr));
     msk_scene *gs = nullptr;
-    if (msk_gpu_scene_create_masks(ctx, &flat.desc, flat.masks_ptr(), &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(ctx));
+    if (msk_gpu_scene_create_lights(ctx, &flat.desc, flat.lights_ptr(), &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(ctx));
     ref<ImageBlock> whole = new ImageBlock(film->crop_size(), 5);        // the crop window (the whole film by default), as the storage holds it
     whole->set_offset(film->crop_offset());
     msk_stats st;
@@ -1387,7 +1470,7 @@ public:
         fill_params(sensor, flat.params);
         if (!m_ctx && msk_gpu_init(m_devices.data(), (int) m_devices.size(), &m_ctx) != MSK_OK) Throw("{}", msk_gpu_last_error(nullptr));
         msk_scene *gs = nullptr;
-        if (msk_gpu_scene_create_masks(m_ctx, &flat.desc, flat.masks_ptr(), &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(m_ctx));
+        if (msk_gpu_scene_create_lights(m_ctx, &flat.desc, flat.lights_ptr(), &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(m_ctx));
         ref<ImageBlock> whole = new ImageBlock(film->crop_size(), channels.size());   // the crop window, as the storage holds it (as in "path")
         whole->set_offset(film->crop_offset());
         msk_stats st;

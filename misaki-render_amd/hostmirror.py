@@ -430,7 +430,7 @@ def read_integrator(xml_path):
 
 
 def write_scene_xml(meshes, directory, width, height, spp, camera=None, integrator_props=None, film_type="hdrfilm",
-                    filename="scene.xml", env=None, film_props=None, points=(), integrator_type="path"):
+                    filename="scene.xml", env=None, film_props=None, points=(), integrator_type="path", lights=()):
     """Writes <directory>/meshes/*.obj and a Mitsuba-style scene XML the C++ host (and the reference's
     loader) understands; same structure as results/Figure_1_Pathtrace/scene.xml, $-parameters for spp/size."""
     camera = camera or CBOX_CAMERA
@@ -476,11 +476,35 @@ def write_scene_xml(meshes, directory, width, height, spp, camera=None, integrat
                 ['        <spectrum name="intensity" value="%.9g"/>' % float(inten)] if np.isscalar(inten) else \
                 ['        <rgb name="intensity" value="%s"/>' % v3(inten)]
         return ['    <emitter type="point">'] + body + ['    </emitter>']
+    def light_xml(lt):
+        spec = _light_spectrum(lt)
+        name = "intensity" if lt["type"] == "spot" else "irradiance"
+        body = []
+        for key in ("cutoff_angle", "beam_width"):
+            if key in lt:
+                body.append('        <float name="%s" value="%.9g"/>' % (key, float(np.float32(lt[key]))))
+        if "direction" in lt:
+            body.append('        <vector name="direction" x="%.9g" y="%.9g" z="%.9g"/>' % tuple(float(np.float32(x)) for x in lt["direction"]))
+        if "lookat" in lt:
+            la = lt["lookat"]
+            body += ['        <transform name="to_world">',
+                     '            <lookat origin="%s" target="%s" up="%s"/>' % tuple(v3([np.float32(x) for x in la[k]]) for k in ("origin", "target", "up")),
+                     '        </transform>']
+        elif "to_world" in lt:
+            body += ['        <transform name="to_world">', '            <matrix value="%s"/>' % " ".join("%.9g" % float(np.float32(x)) for x in np.asarray(lt["to_world"]).reshape(-1)),
+                     '        </transform>']
+        body += ['        <spectrum name="%s" value="%s"/>' % (name, spec.text)] if isinstance(spec, Regular) else \
+                ['        <spectrum name="%s" value="%.9g"/>' % (name, float(spec))] if np.isscalar(spec) else \
+                ['        <rgb name="%s" value="%s"/>' % (name, v3(spec))]
+        return ['    <emitter type="%s">' % lt["type"]] + body + ['    </emitter>']
     if env is not None and env.get("first"):
         out += env_xml()
     for pt in points:
         if pt.get("first"):
             out += point_xml(pt)
+    for lt in lights:
+        if lt.get("first"):
+            out += light_xml(lt)
     for m in meshes:
         write_obj(m, os.path.join(directory, "meshes", m.name + ".obj"))
         out += ['    <shape type="obj">', '        <string name="filename" value="meshes/%s.obj"/>' % m.name]
@@ -497,6 +521,9 @@ def write_scene_xml(meshes, directory, width, height, spp, camera=None, integrat
     for pt in points:
         if not pt.get("first"):
             out += point_xml(pt)
+    for lt in lights:
+        if not lt.get("first"):
+            out += light_xml(lt)
     out.append('</scene>')
     path = os.path.join(directory, filename)
     open(path, "w").write("\n".join(out) + "\n")
@@ -739,6 +766,7 @@ class FlatScene:
         self.envmap = None            # abi.EnvmapDesc of the scene's `envmap` emitter, if it has one
         self.points = None            # (abi.PointDesc * n) of the scene's `point` emitters, if it has any (abi.Scene: msk_scene_ext)
         self.masks = None             # (abi.MaskDesc * n) of the scene's `mask` BSDFs, if it has any (abi.Scene: msk_scene_masks)
+        self.lights = None            # (abi.LightDesc * n) of the scene's `spot` / `directional` emitters, if it has any (msk_scene_lights)
 
 
 def _radiance_desc(radiance, fetch, scale_in=1.0):
@@ -777,6 +805,62 @@ def _point_position(pt):
     w = m[3, 3]
     col = m[:3, 3]
     return tuple(float(x) for x in (col if w == 1 else (col / w).astype(np.float32)))
+
+
+def _light_spectrum(lt):
+    """A light spec's spectrum with its "scale" folded in, as _point_intensity: a spot's "intensity", a sun's "irradiance"."""
+    key = "intensity" if lt["type"] == "spot" else "irradiance"
+    return _point_intensity({"intensity": lt.get(key, 1.0), "scale": lt.get("scale", 1.0)})
+
+
+def _light_to_world(lt):
+    """A light spec's to_world as float32 [4, 4]: "to_world" (4x4) or "lookat" ({"origin", "target", "up"}); neither = identity"""
+    if "lookat" in lt:
+        la = lt["lookat"]
+        return _T4.lookat(la["origin"], la["target"], la.get("up", (0, 1, 0))).to_float16().reshape(4, 4)
+    return np.asarray(lt.get("to_world", np.eye(4)), np.float32).reshape(4, 4)
+
+
+def _unit3(v, what):
+    """v / sqrt(x x + (y y + z z)) in fp32, as the C++ host does; a zero vector is refused"""
+    f = np.float32
+    x, y, z = (f(c) for c in v)
+    l = f(np.sqrt(f(f(x * x) + f(f(y * y) + f(z * z)))))
+    if not l > 0:
+        raise ValueError("%s: the direction must not be the zero vector" % what)
+    return tuple(float(f(c / l)) for c in (x, y, z))
+
+
+def _light_axis(m, what):
+    """to_world applied to the vector (0, 0, 1) in fp32 (Transform4f::apply_vector), then normalised"""
+    f = np.float32
+    return _unit3([f(m[r, 0] * f(0)) + f(f(m[r, 1] * f(0)) + f(m[r, 2] * f(1))) for r in range(3)], what)
+
+
+def _light_geometry(lt):
+    """A {"type": "spot" | "directional", ...} spec -> (position, direction, cos_cutoff, cos_beam), what abi.LightDesc holds (the C++
+    plugins' arithmetic, host/src/render.cpp: SpotLight, DirectionalLight).  The cosines: math.cos of the angle in double (libm, as
+    the C++ side), rounded to float."""
+    f = np.float32
+    kind = lt.get("type")
+    if kind == "spot":
+        cutoff = float(f(lt.get("cutoff_angle", 20.0)))
+        if not (cutoff > 0 and cutoff <= 180):
+            raise ValueError("spot: cutoff_angle must be in (0, 180] degrees")
+        beam = float(f(lt["beam_width"])) if "beam_width" in lt else float(f(f(cutoff) * f(0.75)))
+        if not (beam > 0 and beam <= cutoff):
+            raise ValueError("spot: beam_width must be in (0, cutoff_angle] degrees")
+        m = _light_to_world(lt)
+        r = [f(f(f(m[i, 0] * f(0)) + f(m[i, 1] * f(0))) + f(m[i, 2] * f(0))) + f(m[i, 3] * f(1)) for i in range(4)]   # Transform4f::apply_point on the origin
+        pos = tuple(float(f(r[i] / r[3])) for i in range(3))
+        cc, cb = float(f(math.cos(cutoff * (math.pi / 180.0)))), float(f(math.cos(beam * (math.pi / 180.0))))
+        return pos, _light_axis(m, "spot"), cc, cb
+    if kind == "directional":
+        if ("direction" in lt) == ("to_world" in lt or "lookat" in lt):
+            raise ValueError('directional: exactly one of the parameters "direction" and "to_world" must be specified!')
+        d = _unit3(lt["direction"], "directional") if "direction" in lt else _light_axis(_light_to_world(lt), "directional")
+        return (0.0, 0.0, 0.0), d, 0.0, 0.0
+    raise ValueError("lights: type %r is neither \"spot\" nor \"directional\"" % (kind,))
 
 
 def _env_to_world4(env):
@@ -835,7 +919,7 @@ def envmap_desc(env, fetch):
     return e, [texels, weights]
 
 
-def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=None, env=None, crop=None, extra_textures=(), points=()):
+def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=None, env=None, crop=None, extra_textures=(), points=(), lights=()):
     """Scene -> msk_scene_desc, the step the `"path"` plugin's render() performs before calling
     the C ABI.  coeff_lookup(rgb)->(c0,c1,c2) overrides the spectral upsampling
     (tests pass the reference's own rgb2spec_fetch results); default = this package's rgb2spec.
@@ -847,6 +931,10 @@ def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=
     points: [{"position": (x, y, z) | "to_world": 4x4, "intensity": rgb | c | Regular, "scale": 1.0, "first": False}] = top-level
     <emitter type="point"> elements, placed like env: those with first=True before the shapes (behind a first env), the others after
     them (behind env), each group in list order; the result's .points is their abi.PointDesc array.
+    lights: [{"type": "spot", "intensity": rgb | c | Regular, "scale": 1.0, "cutoff_angle": 20, "beam_width": 3/4 of the cutoff (degrees),
+    "to_world": 4x4 | "lookat": {"origin", "target", "up"}, "first": False} | {"type": "directional", "irradiance": ..., "scale": 1.0,
+    "direction": (x, y, z) | "to_world" | "lookat", "first": False}] = top-level <emitter type="spot" / "directional"> elements, placed
+    like points and behind them in either group; the result's .lights is their abi.LightDesc array.
     extra_textures: texture specs (as MeshSpec.bsdf["texture"]) appended to the scene's textures after those the BSDFs name:
     no surface shows them, Scene.eval_texture evaluates them."""
     from . import rgb2spec
@@ -880,11 +968,24 @@ def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=
         if np.isscalar(inten):
             return emitter_desc(abi.MSK_EMITTER_POINT, -1, None, inten)
         return emitter_desc(abi.MSK_EMITTER_POINT, -1, inten)
+    ld = []
+
+    def light_desc(lt):
+        pos, direction, cc, cb = _light_geometry(lt)
+        spec = _light_spectrum(lt)
+        ld.append(abi.LightDesc(len(ed), (C.c_float * 3)(*pos), (C.c_float * 3)(*direction), cc, cb))
+        kind = abi.MSK_EMITTER_SPOT if lt["type"] == "spot" else abi.MSK_EMITTER_DIRECTIONAL
+        if np.isscalar(spec):
+            return emitter_desc(kind, -1, None, spec)
+        return emitter_desc(kind, -1, spec)
     if env is not None and env.get("first"):
         ed.append(env_desc())
     for pt in points:
         if pt.get("first"):
             ed.append(point_desc(pt))
+    for lt in lights:
+        if lt.get("first"):
+            ed.append(light_desc(lt))
     for i, m in enumerate(meshes):
         v, f = triangulate(m)
         if m.bsdf is not None and m.bsdf.get("type") == "mask":      # a mask decorates the entry of its nested BSDF
@@ -907,6 +1008,11 @@ def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=
     for pt in points:
         if not pt.get("first"):
             ed.append(point_desc(pt))
+    for lt in lights:
+        if not lt.get("first"):
+            ed.append(light_desc(lt))
+    if ld:
+        fs.lights = (abi.LightDesc * len(ld))(*ld)
     if pd:
         fs.points = (abi.PointDesc * len(pd))(*pd)
     if kd:
