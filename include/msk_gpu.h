@@ -410,6 +410,44 @@ typedef struct msk_camera_desc {
     float near_clip, far_clip;
 } msk_camera_desc;
 
+/*
+ * The `thinlens` sensor: the perspective camera with a lens of radius aperture_radius focused at the distance focus_distance along
+ * the optical axis (sensors/thinlens.cpp of the Mitsuba family; the reference has no such plugin, the semantics are fixed here).
+ * A scene created with an msk_lens_desc generates every camera ray as follows; a scene without one is the pinhole camera it always
+ * was.  Everything is fp32, one operation at a time, IEEE division and square root, no contraction.  Inputs: the film position
+ * (px, py) in pixels, the aperture sample u = counter_pair(key, 2) of the sample's key (pair 2 was reserved for it: no other random
+ * number of a sample moves), R = aperture_radius, f = focus_distance, and msk_camera_desc.
+ *   1. near_p: as the pinhole computes it.  r[q] = ((s2c[q][0] px + s2c[q][1] py) + s2c[q][2] 0) + s2c[q][3] 1 for the four rows q
+ *      of sample_to_camera; near_p = (r[0] / r[3], r[1] / r[3], r[2] / r[3]).
+ *   2. the lens point: (lx, ly) = square_to_uniform_disk_concentric(u) * R, one multiplication per component.  The map (core/warp.h):
+ *      x = 2 u.x - 1, y = 2 u.y - 1;  x == 0 and y == 0: r = phi = 0;  x x > y y: r = x, phi = (pi / 4) (y / x);  otherwise r = y,
+ *      phi = pi / 2 - (x / y) (pi / 4);  the point is (r cos phi, r sin phi) with the library's deterministic sine and cosine.
+ *   3. the focus point: ft = f / near_p.z;  fp = (near_p.x ft, near_p.y ft, near_p.z ft).
+ *   4. dl = normalized((fp.x - lx, fp.y - ly, fp.z)): v / sqrt(x x + (y y + z z));  inv_z = 1 / dl.z;  tnear = near_clip inv_z;
+ *      tfar = far_clip inv_z.
+ *   5. the origin: to_world applied to the point (lx, ly, 0), each row ((m[q][0] lx + m[q][1] ly) + m[q][2] 0) + m[q][3] 1, the
+ *      first three divided by the fourth.
+ *   6. the direction: to_world applied to dl as a vector, m[q][0] dl.x + (m[q][1] dl.y + m[q][2] dl.z), as the pinhole does.
+ * The ray's weight stays 1 (an ideal thin lens, no vignetting).  aperture_radius = 0 is valid and goes through this code: the origin
+ * is then the pinhole's (bit for bit wherever a coordinate of it is not zero; a zero may differ in its sign); the direction goes
+ * through f / near_p.z and back and may differ from the pinhole's in its last bits.
+ * Refused at scene creation (MSK_ERR_INVALID_ARG, the message names the field): aperture_radius negative, NaN or infinite;
+ * focus_distance not finite or not greater than 0.
+ * A scene with a lens runs kernels of its own (k_shade_gen_l, k_wavefront_l, k_wavefront_h_l; "direct": k_direct<*, true>), whatever
+ * else it holds; every other scene runs the kernels it ran before.  MSK_RNG_PCG_BLOCK renders of a scene with a lens are refused
+ * (MSK_ERR_UNSUPPORTED, the message names the sensor): the reference's sampler draws no aperture sample that could pin that mode.
+ */
+typedef struct msk_lens_desc {
+    float aperture_radius;   /* R >= 0, finite, in camera-space units      */
+    float focus_distance;    /* f > 0, finite: the plane z = f is in focus */
+} msk_lens_desc;
+
+/* msk_scene_lights cannot grow in place either: the lens wraps it. */
+typedef struct msk_scene_lens {
+    msk_scene_lights lights;     /* everything above                                   */
+    const msk_lens_desc *lens;   /* NULL: the pinhole camera of msk_camera_desc alone  */
+} msk_scene_lens;
+
 /* Film::size() (film.cpp:10) + ReconstructionFilter discretisation (rfilter.cpp:12-27) + the crop window
  * (film.cpp:12-21,51-63: crop_offset_x / _y, crop_width / _height; HDRFilm's storage is an ImageBlock of the
  * crop size placed at the crop offset, films/hdrfilm.cpp:37-38).  The sensor — sample_to_camera, the pixel
@@ -558,6 +596,10 @@ int  msk_gpu_scene_create_masks(msk_ctx *ctx, const msk_scene_desc *desc, const 
    and el == NULL is no extension at all.  The refusals are listed at msk_light_desc.  A scene that holds a spot or a directional
    emitter runs the kernels of a scene with a point emitter.  A group context passes the extension to every member. */
 int  msk_gpu_scene_create_lights(msk_ctx *ctx, const msk_scene_desc *desc, const msk_scene_lights *el, msk_scene **out_scene);
+/* The same with everything msk_scene_lens holds: msk_gpu_scene_create_lights(c, d, l, o) is msk_gpu_scene_create_lens(c, d, &{*l, NULL}, o);
+   with lens == NULL the call IS msk_gpu_scene_create_lights(c, d, &el->lights, o), and el == NULL is no extension at all.  The
+   refusals are listed at msk_lens_desc.  A group context passes the extension to every member. */
+int  msk_gpu_scene_create_lens(msk_ctx *ctx, const msk_scene_desc *desc, const msk_scene_lens *el, msk_scene **out_scene);
 void msk_gpu_scene_destroy(msk_scene *scene);
 
 /* ---- the hot path --------------------------------------------------------- */
@@ -614,6 +656,14 @@ int  msk_gpu_trace_any(msk_scene *scene, uint64_t n, const float *rays, uint8_t 
 int  msk_gpu_sample_pixels(msk_scene *scene, const msk_render_params *params,
                            uint64_t n_pixels, const int32_t *pixels,
                            float *out_xyz, float *out_pos);
+
+/*
+ * The camera ray of n film positions: film_pos n * 2 floats (px, py) in pixels, aperture_u n * 2 floats in [0, 1) (the aperture
+ * sample; read only by a scene with a lens, may be NULL otherwise); out_rays n * 8 floats {o.x, o.y, o.z, tnear, d.x, d.y, d.z, tfar},
+ * the layout msk_gpu_trace_closest reads.  The kernel calls the one device function the render kernels call, for the pinhole as for
+ * the lens (msk_lens_desc).  Host pointers.  A group context runs it on its first member.
+ */
+int  msk_gpu_camera_sample(msk_scene *scene, uint64_t n, const float *film_pos, const float *aperture_u, float *out_rays);
 
 /*
  * A texture's value at n surface points (SmoothDiffuse::m_reflectance->eval(si) for given si.uv): uv n * 2 floats,

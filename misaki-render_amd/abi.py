@@ -97,6 +97,15 @@ class SceneLights(C.Structure):
     _fields_ = [("masks", SceneMasks), ("n_lights", C.c_uint32), ("lights", C.POINTER(LightDesc))]
 
 
+class LensDesc(C.Structure):
+    """msk_lens_desc: the `thinlens` sensor's aperture radius (>= 0) and focus distance (> 0), in camera-space units"""
+    _fields_ = [("aperture_radius", C.c_float), ("focus_distance", C.c_float)]
+
+
+class SceneLens(C.Structure):
+    _fields_ = [("lights", SceneLights), ("lens", C.POINTER(LensDesc))]
+
+
 class CameraDesc(C.Structure):
     _fields_ = [("sample_to_camera", C.c_float * 16), ("to_world", C.c_float * 16),
                 ("near_clip", C.c_float), ("far_clip", C.c_float)]
@@ -174,6 +183,7 @@ EXPORTS = ["msk_gpu_init", "msk_gpu_shutdown", "msk_gpu_last_error", "msk_gpu_sc
            "msk_gpu_scene_create_ext", "msk_gpu_point_sample", "msk_gpu_conductor_sample",
            "msk_gpu_scene_create_masks", "msk_gpu_mask_sample", "msk_gpu_mask_eval",
            "msk_gpu_scene_create_lights", "msk_gpu_light_sample",
+           "msk_gpu_scene_create_lens", "msk_gpu_camera_sample",
            "msk_gpu_render_direct", "msk_gpu_render_direct_device", "msk_gpu_sample_pixels_direct"]
 
 # integrators/aov.cpp:21-28
@@ -242,6 +252,11 @@ def load_library(path=None):
         lib.msk_gpu_scene_create_lights.restype = C.c_int
         lib.msk_gpu_light_sample.argtypes = [vp, C.c_uint32, u64, vp, vp, vp, vp]
         lib.msk_gpu_light_sample.restype = C.c_int
+    if path is None and not os.environ.get("MSK_GPU_LIB") or hasattr(lib, "msk_gpu_scene_create_lens"):       # (likewise: tools/lens_bench.py)
+        lib.msk_gpu_scene_create_lens.argtypes = [vp, C.POINTER(SceneDesc), C.POINTER(SceneLens), C.POINTER(vp)]
+        lib.msk_gpu_scene_create_lens.restype = C.c_int
+        lib.msk_gpu_camera_sample.argtypes = [vp, u64, vp, vp, vp]
+        lib.msk_gpu_camera_sample.restype = C.c_int
     lib.msk_gpu_mask_sample.argtypes = [vp, C.c_uint32, u64, vp, vp, vp, vp, vp, vp, vp]
     lib.msk_gpu_mask_sample.restype = C.c_int
     lib.msk_gpu_mask_eval.argtypes = [vp, C.c_uint32, u64, vp, vp, vp, vp, vp, vp]
@@ -304,14 +319,15 @@ class Context:
 class Scene:
     """msk_scene: geometry + BVH + light tables resident in HBM."""
 
-    def __init__(self, ctx, flat, envmap=None, points=None, masks=None, lights=None):
+    def __init__(self, ctx, flat, envmap=None, points=None, masks=None, lights=None, lens=None):
         """flat: hostmirror.FlatScene (keeps the numpy arrays the desc points into alive).  envmap: the EnvmapDesc of the scene's
         MSK_EMITTER_ENVMAP emitter; by default the one the flattener made (flat.envmap), if any.  points: the PointDesc array of
         its MSK_EMITTER_POINT emitters (a ctypes array or a list); by default flat.points.  A scene with points is created
         through msk_gpu_scene_create_ext, one with an image alone through _create_env, any other through msk_gpu_scene_create.
         masks: the MaskDesc array of its `mask` BSDFs (a ctypes array or a list); by default flat.masks.  A scene with masks is
         created through msk_gpu_scene_create_masks.  lights: the LightDesc array of its spot and directional emitters (a ctypes
-        array or a list); by default flat.lights.  A scene with lights is created through msk_gpu_scene_create_lights."""
+        array or a list); by default flat.lights.  A scene with lights is created through msk_gpu_scene_create_lights.  lens: the LensDesc of
+        its `thinlens` sensor; by default flat.lens.  A scene with a lens is created through msk_gpu_scene_create_lens."""
         self.ctx, self.flat = ctx, flat
         self.handle = C.c_void_p()
         self.envmap = envmap if envmap is not None else getattr(flat, "envmap", None)
@@ -327,7 +343,14 @@ class Scene:
         if lt is not None and not isinstance(lt, C.Array):
             lt = (LightDesc * max(1, len(lt)))(*lt) if len(lt) else None
         self.lights = lt if (lt is not None and len(lt)) else None
-        if self.lights is not None:
+        self.lens = lens if lens is not None else getattr(flat, "lens", None)
+        if self.lens is not None:
+            ext = SceneExt(C.pointer(self.envmap) if self.envmap is not None else None, len(self.points) if self.points is not None else 0, self.points)
+            em = SceneMasks(ext, len(self.masks) if self.masks is not None else 0, self.masks)
+            el = SceneLights(em, len(self.lights) if self.lights is not None else 0, self.lights)
+            self.eln = SceneLens(el, C.pointer(self.lens))
+            ctx.check(ctx.lib.msk_gpu_scene_create_lens(ctx.handle, C.byref(flat.desc), C.byref(self.eln), C.byref(self.handle)))
+        elif self.lights is not None:
             ext = SceneExt(C.pointer(self.envmap) if self.envmap is not None else None, len(self.points) if self.points is not None else 0, self.points)
             em = SceneMasks(ext, len(self.masks) if self.masks is not None else 0, self.masks)
             self.el = SceneLights(em, len(self.lights), self.lights)
@@ -459,6 +482,19 @@ class Scene:
         d, uv, pdf = np.empty((len(u), 3), np.float32), np.empty((len(u), 2), np.float32), np.empty(len(u), np.float32)
         self.ctx.check(self.ctx.lib.msk_gpu_env_sample(self.handle, len(u), _ptr(u), _ptr(d), _ptr(uv), _ptr(pdf)))
         return d, uv, pdf
+
+    def camera_sample(self, film_pos, aperture_u=None):
+        """The camera ray of the film positions (n, 2), in pixels, and — for a scene with a lens — the aperture samples (n, 2):
+        -> rays float32[n, 8] = {o, tnear, d, tfar}, what trace_closest reads (msk_gpu_camera_sample)."""
+        p = np.ascontiguousarray(film_pos, np.float32).reshape(-1, 2)
+        u = None
+        if aperture_u is not None:
+            u = np.ascontiguousarray(aperture_u, np.float32).reshape(-1, 2)
+            if len(u) != len(p):
+                raise ValueError("film_pos and aperture_u must name the same number of rays")
+        rays = np.empty((len(p), 8), np.float32)
+        self.ctx.check(self.ctx.lib.msk_gpu_camera_sample(self.handle, len(p), _ptr(p), _ptr(u) if u is not None else None, _ptr(rays)))
+        return rays
 
     def light_sample(self, emitter, ref_points, wavelengths):
         """The next-event sample of the spot or directional emitter `emitter` from the reference points (n, 3) at the wavelengths

@@ -49,7 +49,8 @@ MSK_DEV float direct_weight(float na, float pa, float nb, float pb) {
 #ifndef MSK_DIRECT_WAVES
 #define MSK_DIRECT_WAVES 3, 3
 #endif
-template <int MODE>
+// LENS: the scene's sensor is a `thinlens` (msk_gpu.h: msk_lens_desc): the camera ray starts on the lens, from pair 2 of the key
+template <int MODE, bool LENS = false>
 __global__ void __launch_bounds__(MSK_BLOCK) __attribute__((amdgpu_waves_per_eu(MSK_DIRECT_WAVES)))
 k_direct(DeviceScene sc, PathState st_unused, PassParams pp, DirectArgs da) {       // (the argument layout emit_record reads: MSK_COLD_KARGS)
     typedef SceneTablesP TB;
@@ -113,23 +114,14 @@ k_direct(DeviceScene sc, PathState st_unused, PassParams pp, DirectArgs da) {   
                 const f2 jit = counter_pair(key, 0);
                 const float wsample = counter_pair(key, 1).x;
                 const float px = (float) pixel_x(sc.filter_border, pt) + jit.x, py = (float) pixel_y(sc.filter_border, pt) + jit.y;
-                float r4[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    r4[q] = ((sc.s2c[q * 4 + 0] * px + sc.s2c[q * 4 + 1] * py) + sc.s2c[q * 4 + 2] * 0.f) + sc.s2c[q * 4 + 3] * 1.f;
-                const f3 near_p = mk3(r4[0] / r4[3], r4[1] / r4[3], r4[2] / r4[3]);
-                const f3 dl = normalized(near_p);
-                const float inv_z = 1.f / dl.z;
-                float o4[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    o4[q] = ((sc.to_world[q * 4 + 0] * 0.f + sc.to_world[q * 4 + 1] * 0.f) + sc.to_world[q * 4 + 2] * 0.f) + sc.to_world[q * 4 + 3] * 1.f;
-                const f3 ro = mk3(o4[0] / o4[3], o4[1] / o4[3], o4[2] / o4[3]);
-                const float *m = sc.to_world;
-                rd = mk3(m[0] * dl.x + (m[1] * dl.y + m[2] * dl.z), m[4] * dl.x + (m[5] * dl.y + m[6] * dl.z), m[8] * dl.x + (m[9] * dl.y + m[10] * dl.z));
+                f2 ap; ap.x = 0.f; ap.y = 0.f;
+                if (LENS) ap = counter_pair(key, 2);
+                const CameraRay cr = camera_ray<LENS>(sc.s2c, sc.to_world, sc.near_clip, sc.far_clip, sc.lens_radius, sc.focus_distance, px, py, ap);   // msk_lens.h
+                const f3 ro = cr.o;
+                rd = cr.d;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) { wl.v[q] = wavelength_of(wsample, q); __builtin_amdgcn_sched_barrier(0); }
-                hit = closest(ro, rd, sc.near_clip * inv_z, sc.far_clip * inv_z);
+                hit = closest(ro, rd, cr.tnear, cr.tfar);
                 have = hit.x != MSK_INF_F;
                 miss = !have;
                 if (miss && !pp.hide_emitters && sc.env_emitter >= 0) {               // path.cpp:34-41

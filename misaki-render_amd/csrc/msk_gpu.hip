@@ -10,6 +10,7 @@
 #include "msk_bvh.h"
 #include "msk_plan.h"
 #include "msk_scene_tables.h"
+#include "msk_lens_tables.h"
 #include "msk_envmap.h"
 #include "msk_lbvh.h"
 #define MSK_WATCHDOG_SYNC
@@ -354,18 +355,27 @@ extern "C" int msk_gpu_scene_create_masks(msk_ctx *ctx, const msk_scene_desc *d,
     return msk_gpu_scene_create_lights(ctx, d, &el, out);
 }
 extern "C" int msk_gpu_scene_create_lights(msk_ctx *ctx, const msk_scene_desc *d, const msk_scene_lights *el, msk_scene **out) {
+    msk_scene_lens ln = {{{{nullptr, 0u, nullptr}, 0u, nullptr}, 0u, nullptr}, nullptr};
+    if (el) ln.lights = *el;
+    return msk_gpu_scene_create_lens(ctx, d, &ln, out);
+}
+extern "C" int msk_gpu_scene_create_lens(msk_ctx *ctx, const msk_scene_desc *d, const msk_scene_lens *eln, msk_scene **out) {
+    const msk_scene_lights *el = eln ? &eln->lights : nullptr;
+    const msk_lens_desc *lens = eln ? eln->lens : nullptr;
     const msk_scene_masks *em = el ? &el->masks : nullptr;
     const msk_scene_ext *ext = em ? &em->ext : nullptr;
     if (!ctx || !d || !out) return fail(ctx, MSK_ERR_INVALID_ARG, "msk_gpu_scene_create: NULL argument");
     *out = nullptr;
     MSK_REFUSE_LOST(ctx);
-    if (ctx->group) return group_scene_create(ctx, d, el, out);
+    if (ctx->group) return group_scene_create(ctx, d, eln, out);
     const mskplan::SceneKnobs knobs = mskplan::read_scene_knobs();
     mskscene::HostTables t;
     {
         std::string msg;
         if (int rc = mskscene::pack(d, ext, knobs.pad_scale, &t, &msg, em ? em->n_masks : 0u, em ? em->masks : nullptr, el ? el->n_lights : 0u,
                                      el ? el->lights : nullptr)) return fail(ctx, rc, "%s", msg.c_str());
+        if (int rc = mskscene::check_lens(lens, &msg)) return fail(ctx, rc, "%s", msg.c_str());
+        if (lens) mskscene::add_lens_tables(d, &t);      // (msk_lens_tables.h: the lens kernels carry the mask code)
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
@@ -408,7 +418,7 @@ extern "C" int msk_gpu_scene_create_lights(msk_ctx *ctx, const msk_scene_desc *d
     f.trace_mode = tree.trace_mode; f.lds_scene = tree.lds_scene; f.trace_lds_bytes = tree.trace_lds_bytes;
     f.lds_tables = tables.lds_tables; f.shade_lds_bytes = tables.shade_lds_bytes;
     f.all_diffuse = t.all_diffuse; f.has_regular = t.has_regular; f.has_dielectric = t.has_dielectric; f.has_bitmap = t.has_bitmap;
-    f.has_envmap = t.has_envmap; f.has_delta = t.has_delta; f.has_mask = t.has_mask;
+    f.has_envmap = t.has_envmap; f.has_delta = t.has_delta; f.has_mask = t.has_mask; f.has_lens = lens != nullptr;
     f.cull_ok = cb.on && t.env_emitter < 0;
     if (f.trace_lds_bytes > ctx->prop.sharedMemPerBlock)
         return fail(ctx, MSK_ERR_UNSUPPORTED, "BVH depth %d needs %zu B of traversal stack per block", bvh.max_depth, tree.binary_stack_bytes);
@@ -417,6 +427,7 @@ extern "C" int msk_gpu_scene_create_lights(msk_ctx *ctx, const msk_scene_desc *d
     hipError_t ef = s->tri_frames.alloc(std::max<size_t>((size_t) d->n_faces * 48, 16));
     if (ef != hipSuccess) return fail(ctx, MSK_ERR_OOM, "scene upload: %s", hipGetErrorString(ef));
     fill_device_scene(s.get(), t, d, bvh, binary.n_nodes, cb, tree);
+    if (lens) { s->dev.lens_radius = lens->aperture_radius; s->dev.focus_distance = lens->focus_distance; }
     if (d->n_faces) {
         hipLaunchKernelGGL(k_tri_frames, dim3((d->n_faces + MSK_BLOCK - 1) / MSK_BLOCK), dim3(MSK_BLOCK), 0, ctx->stream, s->dev, s->tri_frames.as<float4>());
         ef = hipStreamSynchronize(ctx->stream);
@@ -601,6 +612,7 @@ static void launch_shade_t(const msk_scene *sc, const mskplan::LaunchPlan &plan,
     case mskplan::SHADE_ENVMAP: MSK_SHADE(k_shade_gen_e<LDS_TABLES>); break;
     case mskplan::SHADE_DELTA: MSK_SHADE(k_shade_gen_p<LDS_TABLES>); break;
     case mskplan::SHADE_MASK: MSK_SHADE(k_shade_gen_m<LDS_TABLES>); break;
+    case mskplan::SHADE_LENS: MSK_SHADE(k_shade_gen_l<LDS_TABLES>); break;
     }
 #undef MSK_SHADE
 }
@@ -623,6 +635,7 @@ static void launch_fused(const msk_scene *sc, const mskplan::LaunchPlan &plan, d
     case mskplan::SHADE_ENVMAP: MSK_FUSED(k_wavefront_h_e); break;
     case mskplan::SHADE_DELTA: MSK_FUSED(k_wavefront_h_p); break;
     case mskplan::SHADE_MASK: MSK_FUSED(k_wavefront_h_m); break;
+    case mskplan::SHADE_LENS: MSK_FUSED(k_wavefront_h_l); break;
     }
     else switch (plan.shade_kind) {                   // everything in LDS (trace mode 0)
     case mskplan::SHADE_DIELECTRIC: MSK_FUSED(k_wavefront_d); break;
@@ -633,6 +646,7 @@ static void launch_fused(const msk_scene *sc, const mskplan::LaunchPlan &plan, d
     case mskplan::SHADE_ENVMAP: MSK_FUSED(k_wavefront_e); break;
     case mskplan::SHADE_DELTA: MSK_FUSED(k_wavefront_p); break;
     case mskplan::SHADE_MASK: MSK_FUSED(k_wavefront_m); break;
+    case mskplan::SHADE_LENS: MSK_FUSED(k_wavefront_l); break;
     }
 #undef MSK_FUSED
 }
@@ -981,6 +995,11 @@ static int run_direct(msk_scene *sc, hipStream_t stream, const msk_render_params
     for (uint64_t first = 0; first < total; first += plan.records_per_launch) {
         da.rec_first = first; da.rec_count = std::min<uint64_t>(plan.records_per_launch, total - first);
         const dim3 grid(plan.grid_blocks(da.rec_count)), block(MSK_BLOCK);
+        if (sc->facts.has_lens) {              // the `thinlens` sensor: the instantiations whose camera ray starts on the lens
+            if (plan.form == mskplan::TRACE_BIN_LDS) hipLaunchKernelGGL((k_direct<0, true>), grid, block, plan.lds_bytes, stream, ds, st, pp, da);
+            else if (plan.form == mskplan::TRACE_WIDE4_HALF) hipLaunchKernelGGL((k_direct<6, true>), grid, block, plan.lds_bytes, stream, ds, st, pp, da);
+            else hipLaunchKernelGGL((k_direct<1, true>), grid, block, plan.lds_bytes, stream, ds, st, pp, da);
+        } else
         if (plan.form == mskplan::TRACE_BIN_LDS) hipLaunchKernelGGL(k_direct<0>, grid, block, plan.lds_bytes, stream, ds, st, pp, da);
         else if (plan.form == mskplan::TRACE_WIDE4_HALF) hipLaunchKernelGGL(k_direct<6>, grid, block, plan.lds_bytes, stream, ds, st, pp, da);
         else hipLaunchKernelGGL(k_direct<1>, grid, block, plan.lds_bytes, stream, ds, st, pp, da);
@@ -1149,6 +1168,9 @@ static int render_impl(msk_scene *sc, const msk_render_params *prm, float *d_fil
     if (prm->rng_mode == MSK_RNG_PCG_BLOCK) {
         if (direct) return fail(ctx, MSK_ERR_UNSUPPORTED, "MSK_RNG_PCG_BLOCK is not supported by the \"direct\" integrator (it uses MSK_RNG_COUNTER)");
         if (aov) return fail(ctx, MSK_ERR_UNSUPPORTED, "MSK_RNG_PCG_BLOCK renders the \"path\" integrator only (the \"aov\" integrator uses MSK_RNG_COUNTER)");
+        if (sc->facts.has_lens)
+            return fail(ctx, MSK_ERR_UNSUPPORTED, "MSK_RNG_PCG_BLOCK does not render a scene with a `thinlens` sensor (the reference's sampler draws no aperture "
+                        "sample; use MSK_RNG_COUNTER)");
         if (stats) std::memset(stats, 0, sizeof *stats);
         return render_serial(sc, prm, d_film, user_stream ? user_stream : ctx->stream, stats);
     }
@@ -1707,6 +1729,31 @@ extern "C" int msk_gpu_light_sample(msk_scene *scene, uint32_t emitter, uint64_t
     if (!scene || (n && (!ref_points || !wavelengths || !out_d_dist || !out_value))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_light_sample: NULL argument");
     if (scene->ctx->group) { const int rc = delta_probe(scene->parts[0], "msk_gpu_light_sample", 2, emitter, n, ref_points, wavelengths, out_d_dist, out_value); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
     return delta_probe(scene, "msk_gpu_light_sample", 2, emitter, n, ref_points, wavelengths, out_d_dist, out_value);
+}
+// msk_gpu_camera_sample: k_camera_probe, with or without the lens
+static int camera_probe(msk_scene *scene, uint64_t n, const float *film_pos, const float *aperture_u, float *out_rays) {
+    msk_ctx *ctx = scene->ctx;
+    MSK_REFUSE_LOST(ctx);
+    const bool lens = scene->facts.has_lens;
+    if (n && lens && !aperture_u) return fail(ctx, MSK_ERR_INVALID_ARG, "msk_gpu_camera_sample: a scene with a `thinlens` sensor needs aperture_u");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n == 0) return MSK_OK;
+    DevBuf d_pos, d_u, d_out;
+    HIP_TRY(ctx, d_pos.alloc(n * 8)); HIP_TRY(ctx, d_out.alloc(n * 32));
+    HIP_TRY(ctx, hipMemcpy(d_pos.p, film_pos, n * 8, hipMemcpyHostToDevice));
+    if (lens) { HIP_TRY(ctx, d_u.alloc(n * 8)); HIP_TRY(ctx, hipMemcpy(d_u.p, aperture_u, n * 8, hipMemcpyHostToDevice)); }
+    const uint32_t grid = (uint32_t) std::min<uint64_t>((n + MSK_BLOCK - 1) / MSK_BLOCK, 4096);
+    if (lens) hipLaunchKernelGGL(k_camera_probe<true>, dim3(grid), dim3(MSK_BLOCK), 0, ctx->stream, scene->dev, n, d_pos.as<float2>(), d_u.as<float2>(), d_out.as<float4>());
+    else hipLaunchKernelGGL(k_camera_probe<false>, dim3(grid), dim3(MSK_BLOCK), 0, ctx->stream, scene->dev, n, d_pos.as<float2>(), (const float2 *) nullptr, d_out.as<float4>());
+    HIP_TRY(ctx, hipGetLastError());
+    if (int rcw = ctx_sync(ctx, ctx->stream, "k_camera_probe")) { d_pos.leak(); d_u.leak(); d_out.leak(); return rcw; }
+    HIP_TRY(ctx, hipMemcpy(out_rays, d_out.p, n * 32, hipMemcpyDeviceToHost));
+    return MSK_OK;
+}
+extern "C" int msk_gpu_camera_sample(msk_scene *scene, uint64_t n, const float *film_pos, const float *aperture_u, float *out_rays) {
+    if (!scene || (n && (!film_pos || !out_rays))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_camera_sample: NULL argument");
+    if (scene->ctx->group) { const int rc = camera_probe(scene->parts[0], n, film_pos, aperture_u, out_rays); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
+    return camera_probe(scene, n, film_pos, aperture_u, out_rays);
 }
 extern "C" int msk_gpu_conductor_sample(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *cos_theta_i, const float *wavelengths, float *out_value) {
     if (!scene || (n && (!cos_theta_i || !wavelengths || !out_value))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_conductor_sample: NULL argument");

@@ -23,6 +23,7 @@
 #pragma once
 #include "msk_layout.h"
 #include "msk_device.h"
+#include "msk_lens.h"
 #include <type_traits>
 #include "../../include/msk_gpu.h"
 
@@ -99,6 +100,8 @@ struct DeviceScene {
                                 // texel, or nullptr; always read from HBM / L2, never staged.  (Last: the older fields keep their offsets.)
                                 // Behind the bitmaps' texels: the block of the `envmap` emitter (EnvView below), whose float4 offset
                                 // the emitter's record carries — this struct, a kernel argument of every kernel, does not change for it
+    float lens_radius, focus_distance;   // the `thinlens` sensor (msk_gpu.h: msk_lens_desc), read by the instantiations a scene with a lens runs
+                                // (SceneTablesL, k_direct<*, true>, k_camera_probe) and by no other.  Appended: no older field moves
 };
 
 struct PathState {
@@ -1426,14 +1429,20 @@ struct SceneTablesP : SceneTablesE {};
 // (k_shade_gen_m, k_wavefront_m, k_wavefront_h_m, k_path_serial_m, k_mask_probe).  They carry everything SceneTablesP does, the
 // `constant` sky's own density included.
 struct SceneTablesM : SceneTablesP {};
+// ... and of a scene whose sensor is a `thinlens` (msk_gpu.h: msk_lens_desc), whatever else it holds: the aperture sample and the lens
+// point of a new camera sample are compiled only into the instantiations that carry this type (k_shade_gen_l, k_wavefront_l,
+// k_wavefront_h_l).  They carry everything SceneTablesM does; a scene with a lens and no mask gets mask records of the constant
+// opacity 1 (msk_lens_tables.h), under which the mask code computes the nested BSDF to the bit.
+struct SceneTablesL : SceneTablesM {};
 // (MSK_EMITTER_MARK_POINT, word 0 of a point emitter's second float4: msk_layout.h)
-template <class TB> struct tb_traits { static constexpr bool regular = false, dielectric = false, bitmap = false, envmap = false, delta = false, mask = false; };
-template <> struct tb_traits<SceneTablesR> { static constexpr bool regular = true, dielectric = false, bitmap = false, envmap = false, delta = false, mask = false; };
-template <> struct tb_traits<SceneTablesD> { static constexpr bool regular = true, dielectric = true, bitmap = false, envmap = false, delta = false, mask = false; };
-template <> struct tb_traits<SceneTablesB> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = false, delta = false, mask = false; };
-template <> struct tb_traits<SceneTablesE> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = true, delta = false, mask = false; };
-template <> struct tb_traits<SceneTablesP> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = true, delta = true, mask = false; };
-template <> struct tb_traits<SceneTablesM> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = true, delta = true, mask = true; };
+template <class TB> struct tb_traits { static constexpr bool regular = false, dielectric = false, bitmap = false, envmap = false, delta = false, mask = false, lens = false; };
+template <> struct tb_traits<SceneTablesR> { static constexpr bool regular = true, dielectric = false, bitmap = false, envmap = false, delta = false, mask = false, lens = false; };
+template <> struct tb_traits<SceneTablesD> { static constexpr bool regular = true, dielectric = true, bitmap = false, envmap = false, delta = false, mask = false, lens = false; };
+template <> struct tb_traits<SceneTablesB> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = false, delta = false, mask = false, lens = false; };
+template <> struct tb_traits<SceneTablesE> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = true, delta = false, mask = false, lens = false; };
+template <> struct tb_traits<SceneTablesP> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = true, delta = true, mask = false, lens = false; };
+template <> struct tb_traits<SceneTablesM> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = true, delta = true, mask = true, lens = false; };
+template <> struct tb_traits<SceneTablesL> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = true, delta = true, mask = true, lens = true; };
 MSK_DEV uint32_t tables_lds_float4s(const DeviceScene &sc) {
     return sc.n_tris * 6 + sc.n_meshes + sc.n_bsdf_f4 + sc.n_emitters * 3 + (sc.n_emitters * 95 + 3) / 4 + (sc.cdf_len + 3) / 4 + 72 + (sc.n_spectra + 3) / 4;
 }
@@ -2614,6 +2623,12 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
         for (int q = 0; q < 3; ++q) { k.cull_lo[q] = sc.cull_lo[q]; k.cull_hi[q] = sc.cull_hi[q]; }
         k.filter_radius = sc.filter_radius; k.filter_scale = sc.filter_scale; k.rec_a = pp.rec_a; k.rec_b = pp.rec_b;
     }
+    // the lens (msk_lens_desc): read by the instantiations a scene with a lens runs, and only by them
+    float lens_radius = 0.f, focus_distance = 0.f;
+    if (tb_traits<TB>::lens) {
+        if (MSK_COLD_KARGS) { const karg_ptr ka = karg_base(); lens_radius = MSK_KARG_SC(ka, float, lens_radius); focus_distance = MSK_KARG_SC(ka, float, focus_distance); }
+        else { lens_radius = sc.lens_radius; focus_distance = sc.focus_distance; }
+    }
     // how many samples this sweep may examine: without the cull every one takes a slot
     const unsigned long long scan = k.cull ? (unsigned long long) MSK_CULL_SCAN * pp.region_size : (unsigned long long) n_free;
     const uint32_t limit = (uint32_t) (left < scan ? left : scan);
@@ -2640,24 +2655,13 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
             const f2 jit = counter_pair(key, 0);
             wsample = counter_pair(key, 1).x;
             px = (float) pixel_x(k.filter_border, pt) + jit.x; py = (float) pixel_y(k.filter_border, pt) + jit.y;
-            // PerspectiveCamera::sample_ray (perspective.cpp:22-42), Transform4f::apply_point/apply_vector
-            float r4[4];
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4)
-                r4[q4] = ((k.s2c[q4 * 4 + 0] * px + k.s2c[q4 * 4 + 1] * py) + k.s2c[q4 * 4 + 2] * 0.f) + k.s2c[q4 * 4 + 3] * 1.f;
-            const f3 near_p = mk3(r4[0] / r4[3], r4[1] / r4[3], r4[2] / r4[3]);
-            const f3 dl = normalized(near_p);
-            const float inv_z = 1.f / dl.z;
-            float o4[4];
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4)
-                o4[q4] = ((k.to_world[q4 * 4 + 0] * 0.f + k.to_world[q4 * 4 + 1] * 0.f) + k.to_world[q4 * 4 + 2] * 0.f) +
-                         k.to_world[q4 * 4 + 3] * 1.f;
-            ow = mk3(o4[0] / o4[3], o4[1] / o4[3], o4[2] / o4[3]);
-            const float *m = k.to_world;
-            dw = mk3(m[0] * dl.x + (m[1] * dl.y + m[2] * dl.z), m[4] * dl.x + (m[5] * dl.y + m[6] * dl.z),
-                     m[8] * dl.x + (m[9] * dl.y + m[10] * dl.z));
-            tnear = k.near_clip * inv_z; tfar = k.far_clip * inv_z;
+            // PerspectiveCamera::sample_ray (perspective.cpp:22-42), Transform4f::apply_point/apply_vector; with a lens the aperture
+            // sample, pair 2 of the key (msk_lens.h: the one function every camera ray comes from)
+            f2 ap; ap.x = 0.f; ap.y = 0.f;
+            if (tb_traits<TB>::lens) ap = counter_pair(key, 2);
+            const CameraRay cr = camera_ray<tb_traits<TB>::lens>(k.s2c, k.to_world, k.near_clip, k.far_clip, lens_radius, focus_distance, px, py, ap);
+            ow = cr.o; dw = cr.d;
+            tnear = cr.tnear; tfar = cr.tfar;
             keep = true;
             if (k.cull) {        // the root's test of every traversal kernel, on the box that encloses the root's children in every tree form
                 const f3 idir = slab_idir(dw);
@@ -2788,6 +2792,25 @@ k_shade_gen_p(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_
 template <bool LDS_TABLES>
 __global__ void __launch_bounds__(MSK_BLOCK)
 k_shade_gen_m(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_TABLES, false, true, true, true, true, true, true>(sc, st, pp); }
+// ... and the two that scenes with a `thinlens` sensor run, and only they (SceneTablesL), whatever else they hold.  Not held at a
+// wave count by attribute either: they carry everything k_shade_gen_m does, and the lens point of a new camera sample
+template <bool LDS_TABLES>
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_shade_gen_l(DeviceScene sc, PathState st, PassParams pp) {
+    extern __shared__ float4 lds_dyn[];
+    SceneTablesL tb;
+    static_cast<SceneTables &>(tb) = stage_tables<LDS_TABLES>(sc, lds_dyn);
+    const uint32_t lwave = (blockIdx.x * MSK_BLOCK + threadIdx.x) / MSK_WAVE;
+    const uint32_t queue_f4 = LDS_TABLES ? tables_lds_float4s(sc) : small_tables_float4s(sc);   // after the staged tables
+    const DoneQueue dq = done_queue(lds_dyn + queue_f4);
+    SortScratch ss{nullptr, nullptr};
+    if (pp.sort_scratch) {                          // as shade_gen_body
+        uint8_t *p = (uint8_t *) (lds_dyn + queue_f4 + (MSK_BLOCK / MSK_WAVE) * MSK_DONE_Q_F4) + (size_t) (threadIdx.x / MSK_WAVE) * 3u * pp.region_size;
+        ss.perm = (uint16_t *) p; ss.cls = p + 2u * pp.region_size;
+    }
+    if (lwave >= pp.region_count) return;
+    shade_region<false>(sc, tb, dq, ss, st, pp, pp.region_first + lwave, threadIdx.x & (MSK_WAVE - 1));
+}
 // The diffuse-only variants fit four waves per SIMD (128 VGPRs, no scratch); left alone, the allocator spends 24 more registers
 // on the explicit fp64 fma chains of det_sincos and lands at three.
 #ifndef MSK_NO_SHADE4
@@ -2897,6 +2920,14 @@ k_wavefront_m(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, u
     constexpr bool CULL = false;      // (as k_wavefront_d)
     MSK_WAVEFRONT_BODY
 }
+// the one scenes with a `thinlens` sensor run (see k_shade_gen_l)
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_wavefront_l(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
+    typedef SceneTablesL TB;
+    constexpr bool DIFFUSE_ONLY = false;
+    constexpr bool CULL = false;      // (as k_wavefront_d)
+    MSK_WAVEFRONT_BODY
+}
 #undef MSK_WAVEFRONT_BODY
 
 // k_wavefront_h (round 6): the same device-side loop for scenes whose TREE STAYS IN HBM / L2 (trace mode 6: the 4-wide tree with
@@ -2988,6 +3019,13 @@ k_wavefront_h_m(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters,
     constexpr bool DIFFUSE_ONLY = false;
     MSK_WAVEFRONT_H_BODY
 }
+// the one scenes with a `thinlens` sensor run (see k_shade_gen_l)
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_wavefront_h_l(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
+    typedef SceneTablesL TB;
+    constexpr bool DIFFUSE_ONLY = false;
+    MSK_WAVEFRONT_H_BODY
+}
 #undef MSK_WAVEFRONT_H_BODY
 
 // msk_gpu_eval_texture: the value of the texture whose record sits at float4 offset `rec` of the BSDF table, at n given uv and
@@ -3062,6 +3100,21 @@ k_delta_probe(DeviceScene sc, uint32_t conductor, uint32_t index, uint64_t n, co
             if (dist == 0.f) { v = splat(0.f); a = make_float4(0.f, 0.f, 0.f, 0.f); }
             out_a[i] = a; out_b[i] = make_float4(v.v[0], v.v[1], v.v[2], v.v[3]);
         }
+    }
+}
+
+// msk_gpu_camera_sample: the camera ray of n film positions (and, for a scene with a lens, aperture samples) through the function the
+// render kernels call (msk_lens.h).  out: {o, tnear} {d, tfar} per ray.  One ray per thread.
+template <bool LENS>
+__global__ void __launch_bounds__(MSK_BLOCK)
+k_camera_probe(DeviceScene sc, uint64_t n, const float2 *film_pos, const float2 *aperture_u, float4 *out) {
+    for (uint64_t i = (uint64_t) blockIdx.x * MSK_BLOCK + threadIdx.x; i < n; i += (uint64_t) gridDim.x * MSK_BLOCK) {
+        const float2 p = film_pos[i];
+        f2 u; u.x = 0.f; u.y = 0.f;
+        if (LENS) { const float2 a = aperture_u[i]; u.x = a.x; u.y = a.y; }
+        const CameraRay cr = camera_ray<LENS>(sc.s2c, sc.to_world, sc.near_clip, sc.far_clip, sc.lens_radius, sc.focus_distance, p.x, p.y, u);
+        out[2 * i] = make_float4(cr.o.x, cr.o.y, cr.o.z, cr.tnear);
+        out[2 * i + 1] = make_float4(cr.d.x, cr.d.y, cr.d.z, cr.tfar);
     }
 }
 

@@ -96,13 +96,13 @@ static int group_fail(msk_ctx *g, size_t k, int rc) {
                 g->group->ctxs[k]->last_error.c_str());
 }
 
-static int group_scene_create(msk_ctx *g, const msk_scene_desc *d, const msk_scene_lights *ext, msk_scene **out) {
+static int group_scene_create(msk_ctx *g, const msk_scene_desc *d, const msk_scene_lens *ext, msk_scene **out) {
     const size_t n = g->group->ctxs.size();
     msk_scene *s = new msk_scene();
     s->ctx = g;
     s->parts.assign(n, nullptr);
     std::vector<int> rcs(n, MSK_OK);
-    auto make = [&](size_t k) { rcs[k] = msk_gpu_scene_create_lights(g->group->ctxs[k], d, ext, &s->parts[k]); };
+    auto make = [&](size_t k) { rcs[k] = msk_gpu_scene_create_lens(g->group->ctxs[k], d, ext, &s->parts[k]); };
     std::vector<std::thread> th;
     for (size_t k = 1; k < n; ++k) th.emplace_back(make, k);          // the BVH build is host work: one thread per member
     make(0);

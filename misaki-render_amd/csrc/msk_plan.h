@@ -159,6 +159,8 @@ struct SceneFacts {
                                   // delta light, the mirror lobe and the `constant` sky's own density run, whatever else the scene holds
     bool has_mask = false;        // a `mask` (msk_mask_desc): the instantiations with the opacity lookup, the null lobe and the `scattered` bit run,
                                   // whatever else the scene holds
+    bool has_lens = false;        // a `thinlens` sensor (msk_lens_desc): the instantiations whose new camera samples start on the lens run, whatever
+                                  // else the scene holds
     size_t trace_lds_bytes = 0, shade_lds_bytes = 0;
 };
 // LDS plan of k_shade_gen: the small lookup tables (mesh / BSDF / emitter records, cdf, d65, cie, tabulated spectra), and with
@@ -265,8 +267,10 @@ enum ShadeKind : int {     // in the order they are tried: a dielectric scene is
                            // an `envmap` emitter runs these whatever else it holds (they carry the bitmap lookup and the delta lobes)
     SHADE_DELTA,           // k_shade_gen_p<lds_tables>;                k_wavefront_p / k_wavefront_h_p.  Tried before those above: a scene with a
                            // `point` emitter or a smooth `conductor` runs these whatever else it holds (they carry the envmap lookup as well)
-    SHADE_MASK             // k_shade_gen_m<lds_tables>;                k_wavefront_m / k_wavefront_h_m.  Tried FIRST: a scene with a `mask` runs
-                           // these whatever else it holds (they carry everything the delta ones do)
+    SHADE_MASK,            // k_shade_gen_m<lds_tables>;                k_wavefront_m / k_wavefront_h_m.  Tried before those above: a scene with a
+                           // `mask` runs these whatever else it holds (they carry everything the delta ones do)
+    SHADE_LENS             // k_shade_gen_l<lds_tables>;                k_wavefront_l / k_wavefront_h_l.  Tried FIRST: a scene with a `thinlens`
+                           // sensor runs these whatever else it holds (they carry everything the mask ones do)
 };
 
 struct LaunchPlan {
@@ -304,9 +308,9 @@ inline LaunchPlan make_launch_plan(const SceneFacts &sc, const CallFacts &call, 
     // (MSK_FORCE_GENERAL_SHADE=1, measurements only: an all-diffuse scene through the general variant — what a per-class diffuse
     // instantiation could save a mixed scene's diffuse chunks)
     // (the AOV RGB record and the validity test over an "aov" render's record groups live in the general shading variant)
-    p.lds_tables = sc.lds_tables; p.regular = sc.has_regular; p.dielectric = sc.has_dielectric || sc.has_bitmap || sc.has_envmap || sc.has_delta || sc.has_mask;      // (the bitmap / envmap / delta / mask instantiations carry the delta lobes)
+    p.lds_tables = sc.lds_tables; p.regular = sc.has_regular; p.dielectric = sc.has_dielectric || sc.has_bitmap || sc.has_envmap || sc.has_delta || sc.has_mask || sc.has_lens;      // (the bitmap / envmap / delta / mask / lens instantiations carry the delta lobes)
     p.diffuse_only = sc.all_diffuse && !aov_any && !knobs.force_general_shade;
-    p.shade_kind = sc.has_mask ? SHADE_MASK : sc.has_delta ? SHADE_DELTA : sc.has_envmap ? SHADE_ENVMAP : sc.has_bitmap ? SHADE_BITMAP : p.dielectric ? SHADE_DIELECTRIC : p.diffuse_only ? SHADE_DIFFUSE : p.regular ? SHADE_REGULAR : SHADE_GENERAL;
+    p.shade_kind = sc.has_lens ? SHADE_LENS : sc.has_mask ? SHADE_MASK : sc.has_delta ? SHADE_DELTA : sc.has_envmap ? SHADE_ENVMAP : sc.has_bitmap ? SHADE_BITMAP : p.dielectric ? SHADE_DIELECTRIC : p.diffuse_only ? SHADE_DIFFUSE : p.regular ? SHADE_REGULAR : SHADE_GENERAL;
     // material-sorted shading (general variant): LDS for the permutation, 3 bytes per slot of a region and wave (MSK_SORT=0: off)
     const size_t sort_lds = kWavesPerBlock * 3 * call.region_size;
     p.sort_on = !p.diffuse_only && (!sc.all_diffuse || knobs.force_general_shade) && call.region_size <= 4096 && knobs.sort &&

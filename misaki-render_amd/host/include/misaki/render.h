@@ -214,6 +214,8 @@ public:
     Sampler *sampler() const { return m_sampler.get(); }
     const Transform4f &world_transform() const { return m_world_transform; }
     virtual bool flatten(msk_camera_desc &out) const { (void) out; return false; }
+    // a `thinlens` sensor: its aperture radius and focus distance, for the scene's msk_lens_desc; false for a pinhole
+    virtual bool flatten_lens(msk_lens_desc &out) const { (void) out; return false; }
     MSK_DECLARE_CLASS()
 protected:
     Sensor(const Properties &props);        // sensor.cpp:9-45
@@ -309,6 +311,11 @@ struct FlatScene {
     std::vector<msk_light_desc> lights;
     msk_scene_lights el = {{{nullptr, 0, nullptr}, 0, nullptr}, 0, nullptr};
     const msk_scene_lights *lights_ptr() const { return &el; }
+    // the `thinlens` sensor's descriptor, and the extension that holds it too (msk_gpu_scene_create_lens); eln.lens is NULL for a pinhole
+    bool has_lens = false;
+    msk_lens_desc lens = {0.f, 0.f};
+    msk_scene_lens eln = {{{{nullptr, 0, nullptr}, 0, nullptr}, 0, nullptr}, nullptr};
+    const msk_scene_lens *lens_ptr() const { return &eln; }
 };
 void flatten_scene(const Scene *scene, const Sensor *sensor, FlatScene &out);
 

@@ -89,6 +89,13 @@ int msk_host_lights(msk_host_scene *h, msk_light_desc *lights, size_t cap) {
     return (int) n;
 }
 
+// the flattened scene's `thinlens` descriptor (after msk_host_flatten): 1 and *lens filled, or 0 for a pinhole
+int msk_host_lens(msk_host_scene *h, msk_lens_desc *lens) {
+    if (!h->flat.has_lens) return 0;
+    if (lens) *lens = h->flat.lens;
+    return 1;
+}
+
 // scene->integrator()->render(scene, sensor) followed by HDRFilm::image(); optionally develop() to a file
 int msk_host_render(msk_host_scene *h, float *film_xyzaw, float *rgba, const char *develop_to, msk_stats *stats) {
     try {

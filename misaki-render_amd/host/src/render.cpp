@@ -1000,7 +1000,7 @@ MSK_IMPLEMENT_CLASS(EnvironmentMapEmitter, Emitter)
 MSK_REGISTER_INSTANCE(EnvironmentMapEmitter, "envmap")
 
 // sensors/perspective.cpp:8-42
-class PerspectiveCamera final : public ProjectiveCamera {
+class PerspectiveCamera : public ProjectiveCamera {
 public:
     PerspectiveCamera(const Properties &props) : ProjectiveCamera(props) {
         m_fov = props.float_("fov", 30);
@@ -1023,6 +1023,25 @@ private:
 };
 MSK_IMPLEMENT_CLASS(PerspectiveCamera, ProjectiveCamera)
 MSK_REGISTER_INSTANCE(PerspectiveCamera, "perspective")
+
+// `thinlens`: the perspective camera with a lens (include/msk_gpu.h at msk_lens_desc; the reference has no such plugin).  Properties:
+// everything `perspective` takes, `aperture_radius` (required) and `focus_distance` (ProjectiveCamera's: the far clip distance by default).
+class ThinLensCamera final : public PerspectiveCamera {
+public:
+    ThinLensCamera(const Properties &props) : PerspectiveCamera(props) {
+        if (!props.has_property("aperture_radius")) Throw("thinlens: the parameter \"aperture_radius\" must be specified!");
+        m_aperture_radius = props.float_("aperture_radius");
+    }
+    bool flatten_lens(msk_lens_desc &out) const override {
+        out.aperture_radius = m_aperture_radius; out.focus_distance = m_focus_distance;
+        return true;
+    }
+    MSK_DECLARE_CLASS()
+private:
+    float m_aperture_radius;
+};
+MSK_IMPLEMENT_CLASS(ThinLensCamera, PerspectiveCamera)
+MSK_REGISTER_INSTANCE(ThinLensCamera, "thinlens")
 
 // shapes/obj.cpp:58-181
 class OBJMesh final : public Mesh {
@@ -1258,6 +1277,8 @@ void flatten_scene(const Scene *scene, const Sensor *sensor, FlatScene &out) {
     for (size_t k = 0; k < out.masks.size(); ++k) out.masks[k].values = out.masks[k].filter ? out.mask_values[k].data() : nullptr;
     out.em.ext = out.ext; out.em.n_masks = (uint32_t) out.masks.size(); out.em.masks = out.masks.empty() ? nullptr : out.masks.data();
     out.el.masks = out.em; out.el.n_lights = (uint32_t) out.lights.size(); out.el.lights = out.lights.empty() ? nullptr : out.lights.data();
+    out.has_lens = sensor->flatten_lens(out.lens);
+    out.eln.lights = out.el; out.eln.lens = out.has_lens ? &out.lens : nullptr;
 }
 
 // "0,1,2" -> {0,1,2}; empty -> {single}
@@ -1288,7 +1309,7 @@ static msk_stats render_on_gpu(Scene *scene, Sensor *sensor, std::vector<int> &d
     fill(flat.params);
     if (!ctx && msk_gpu_init(devices.data(), (int) devices.size(), &ctx) != MSK_OK) Throw("{}", msk_gpu_last_error(nullptr));
     msk_scene *gs = nullptr;
-    if (msk_gpu_scene_create_lights(ctx, &flat.desc, flat.lights_ptr(), &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(ctx));
+    if (msk_gpu_scene_create_lens(ctx, &flat.desc, flat.lens_ptr(), &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(ctx));
     ref<ImageBlock> whole = new ImageBlock(film->crop_size(), 5);        // the crop window (the whole film by default), as the storage holds it
     whole->set_offset(film->crop_offset());
     msk_stats st;
@@ -1470,7 +1491,7 @@ public:
         fill_params(sensor, flat.params);
         if (!m_ctx && msk_gpu_init(m_devices.data(), (int) m_devices.size(), &m_ctx) != MSK_OK) Throw("{}", msk_gpu_last_error(nullptr));
         msk_scene *gs = nullptr;
-        if (msk_gpu_scene_create_lights(m_ctx, &flat.desc, flat.lights_ptr(), &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(m_ctx));
+        if (msk_gpu_scene_create_lens(m_ctx, &flat.desc, flat.lens_ptr(), &gs) != MSK_OK) Throw("{}", msk_gpu_last_error(m_ctx));
         ref<ImageBlock> whole = new ImageBlock(film->crop_size(), channels.size());   // the crop window, as the storage holds it (as in "path")
         whole->set_offset(film->crop_offset());
         msk_stats st;

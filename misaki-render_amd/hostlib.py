@@ -32,6 +32,7 @@ def load():
         lib.msk_host_points.argtypes = [vp, C.POINTER(abi.PointDesc), C.c_size_t]
         lib.msk_host_masks.argtypes = [vp, C.POINTER(abi.MaskDesc), C.c_size_t]
         lib.msk_host_lights.argtypes = [vp, C.POINTER(abi.LightDesc), C.c_size_t]
+        lib.msk_host_lens.argtypes = [vp, C.POINTER(abi.LensDesc)]
         lib.msk_host_render.argtypes = [vp, vp, vp, C.c_char_p, C.POINTER(abi.Stats)]
         lib.msk_host_film_size.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         lib.msk_host_film_crop.argtypes = [vp, C.POINTER(C.c_int * 4)]
@@ -57,11 +58,12 @@ def _check(rc):
 class HostFlat:
     """Same shape as hostmirror.FlatScene: .desc plus the numpy views tests use."""
 
-    def __init__(self, desc, params, owner, envmap=None, points=None, masks=None, lights=None):
+    def __init__(self, desc, params, owner, envmap=None, points=None, masks=None, lights=None, lens=None):
         self.desc, self.params, self.owner = desc, params, owner
         self.envmap = envmap              # abi.EnvmapDesc of the scene's `envmap` emitter, or None (abi.Scene picks it up)
         self.points = points              # (abi.PointDesc * n) of the scene's `point` emitters, or None (likewise: msk_scene_ext)
         self.masks = masks                # (abi.MaskDesc * n) of the scene's `mask` BSDFs, or None (likewise: msk_scene_masks)
+        self.lens = lens                  # abi.LensDesc of the scene's `thinlens` sensor, or None (msk_scene_lens)
         self.lights = lights              # (abi.LightDesc * n) of the scene's `spot` / `directional` emitters, or None (msk_scene_lights)
         self.vertices = np.ctypeslib.as_array(desc.vertices, (desc.n_vertices, 8)) if desc.n_vertices else np.zeros((0, 8), np.float32)
         self.faces = np.ctypeslib.as_array(desc.faces, (desc.n_faces, 3)) if desc.n_faces else np.zeros((0, 3), np.uint32)
@@ -105,7 +107,9 @@ class HostScene:
         if nl > 0:
             lights = (abi.LightDesc * nl)()
             self.lib.msk_host_lights(self.h, lights, nl)
-        return HostFlat(d, p, self, env if self.lib.msk_host_envmap(self.h, C.byref(env)) == 1 else None, pts, masks, lights)
+        lens = abi.LensDesc()
+        return HostFlat(d, p, self, env if self.lib.msk_host_envmap(self.h, C.byref(env)) == 1 else None, pts, masks, lights,
+                        lens if self.lib.msk_host_lens(self.h, C.byref(lens)) == 1 else None)
 
     def aov_names(self):
         buf = C.create_string_buffer(1 << 16)

@@ -441,7 +441,9 @@ def write_scene_xml(meshes, directory, width, height, spp, camera=None, integrat
     for k, val in (integrator_props or {}).items():
         tag = "boolean" if isinstance(val, bool) else "string" if isinstance(val, str) else "integer"
         out.append('        <%s name="%s" value="%s"/>' % (tag, k, str(val).lower()))
-    out += ['    </integrator>', '    <sensor type="perspective">',
+    # a camera with "aperture_radius" is a `thinlens` sensor ("focus_distance" is written when given: the plugin's default is far_clip)
+    lens = ['        <float name="%s" value="%.9g"/>' % (k, float(np.float32(camera[k]))) for k in ("aperture_radius", "focus_distance") if k in camera]
+    out += ['    </integrator>', '    <sensor type="%s">' % ("thinlens" if "aperture_radius" in camera else "perspective")] + lens + [
             '        <float name="near_clip" value="%.9g"/>' % camera["near"], '        <float name="far_clip" value="%.9g"/>' % camera["far"],
             '        <float name="fov" value="%.9g"/>' % camera["fov"], '        <transform name="to_world">',
             '            <lookat origin="%s" target="%s" up="%s"/>' % (v3(camera["origin"]), v3(camera["target"]), v3(camera["up"])),
@@ -766,6 +768,7 @@ class FlatScene:
         self.envmap = None            # abi.EnvmapDesc of the scene's `envmap` emitter, if it has one
         self.points = None            # (abi.PointDesc * n) of the scene's `point` emitters, if it has any (abi.Scene: msk_scene_ext)
         self.masks = None             # (abi.MaskDesc * n) of the scene's `mask` BSDFs, if it has any (abi.Scene: msk_scene_masks)
+        self.lens = None              # abi.LensDesc of the scene's `thinlens` sensor, if that is its sensor (abi.Scene: msk_scene_lens)
         self.lights = None            # (abi.LightDesc * n) of the scene's `spot` / `directional` emitters, if it has any (msk_scene_lights)
 
 
@@ -863,6 +866,17 @@ def _light_geometry(lt):
     raise ValueError("lights: type %r is neither \"spot\" nor \"directional\"" % (kind,))
 
 
+def lens_desc(camera):
+    """The abi.LensDesc of a camera spec, or None for a pinhole: a camera with "aperture_radius" is the `thinlens` sensor
+    (host/src/render.cpp: ThinLensCamera), whose "focus_distance" defaults to the far clip distance, as ProjectiveCamera's does.  A
+    "focus_distance" without an "aperture_radius" is refused: the plugin needs the radius."""
+    if "aperture_radius" not in camera:
+        if "focus_distance" in camera:
+            raise ValueError('thinlens: the parameter "aperture_radius" must be specified!')
+        return None
+    return abi.LensDesc(float(np.float32(camera["aperture_radius"])), float(np.float32(camera.get("focus_distance", camera["far"]))))
+
+
 def _env_to_world4(env):
     """env["to_world"] (3x3 or 4x4, a rotation) -> float32 [4, 4]"""
     m = np.asarray(env.get("to_world", np.eye(3)), np.float32)
@@ -935,6 +949,8 @@ def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=
     "to_world": 4x4 | "lookat": {"origin", "target", "up"}, "first": False} | {"type": "directional", "irradiance": ..., "scale": 1.0,
     "direction": (x, y, z) | "to_world" | "lookat", "first": False}] = top-level <emitter type="spot" / "directional"> elements, placed
     like points and behind them in either group; the result's .lights is their abi.LightDesc array.
+    camera: {"fov", "near", "far", "origin", "target", "up"} and, for a `thinlens` sensor, "aperture_radius" (then required) and
+    "focus_distance" (default: "far"); the result's .lens is then its abi.LensDesc.
     extra_textures: texture specs (as MeshSpec.bsdf["texture"]) appended to the scene's textures after those the BSDFs name:
     no surface shows them, Scene.eval_texture evaluates them."""
     from . import rgb2spec
@@ -1049,6 +1065,7 @@ def flatten(meshes, width, height, camera=None, filter_stddev=0.5, coeff_lookup=
     d.camera.sample_to_camera[:] = s2c.tolist()
     d.camera.to_world[:] = tw.tolist()
     d.camera.near_clip, d.camera.far_clip = camera["near"], camera["far"]
+    fs.lens = lens_desc(camera)
     radius, lut = gaussian_filter(filter_stddev)
     d.film.width, d.film.height, d.film.filter_radius = width, height, radius
     d.film.filter_lut[:] = lut.tolist()
