@@ -25,6 +25,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <string>
 #include <thread>
@@ -603,17 +604,15 @@ template <bool LDS_TABLES>
 static void launch_shade_t(const msk_scene *sc, const mskplan::LaunchPlan &plan, dim3 grid, hipStream_t stream, const PathState &st, const PassParams &pp,
                            hipEvent_t t0, hipEvent_t t1) {
 #define MSK_SHADE(...) hipExtLaunchKernelGGL((__VA_ARGS__), grid, dim3(MSK_BLOCK), plan.shade_lds_bytes, stream, t0, t1, 0, sc->dev, st, pp)
+    // (the families' cases come from the list, msk_kernels.h; no default: -Wswitch names a kind that has no case)
+#define MSK_CASE(S, TABLES, KIND, SHADE, SERIAL) case mskplan::KIND: MSK_SHADE(k_shade_gen_##S<LDS_TABLES>); break;
     switch (plan.shade_kind) {
-    case mskplan::SHADE_DIELECTRIC: MSK_SHADE(k_shade_gen_d<LDS_TABLES>); break;
     case mskplan::SHADE_DIFFUSE: MSK_SHADE(k_shade_gen<LDS_TABLES, true>); break;
     case mskplan::SHADE_REGULAR: MSK_SHADE(k_shade_gen<LDS_TABLES, false, true>); break;
     case mskplan::SHADE_GENERAL: MSK_SHADE(k_shade_gen<LDS_TABLES, false>); break;
-    case mskplan::SHADE_BITMAP: MSK_SHADE(k_shade_gen_b<LDS_TABLES>); break;
-    case mskplan::SHADE_ENVMAP: MSK_SHADE(k_shade_gen_e<LDS_TABLES>); break;
-    case mskplan::SHADE_DELTA: MSK_SHADE(k_shade_gen_p<LDS_TABLES>); break;
-    case mskplan::SHADE_MASK: MSK_SHADE(k_shade_gen_m<LDS_TABLES>); break;
-    case mskplan::SHADE_LENS: MSK_SHADE(k_shade_gen_l<LDS_TABLES>); break;
+    MSK_FAMILIES(MSK_CASE)
     }
+#undef MSK_CASE
 #undef MSK_SHADE
 }
 static void launch_shade(const msk_scene *sc, const mskplan::LaunchPlan &plan, dim3 grid, hipStream_t stream, const PathState &st, const PassParams &pp,
@@ -626,28 +625,22 @@ static void launch_shade(const msk_scene *sc, const mskplan::LaunchPlan &plan, d
 static void launch_fused(const msk_scene *sc, const mskplan::LaunchPlan &plan, dim3 grid, hipStream_t stream, const PathState &st, const PassParams &pp) {
 #define MSK_FUSED(...) hipExtLaunchKernelGGL((__VA_ARGS__), grid, dim3(MSK_BLOCK), plan.fused_lds_bytes, stream, nullptr, nullptr, 0, sc->dev, st, pp, \
                                              plan.fused_iters, plan.fused_queue_f4, plan.fused_trace_f4)
+#define MSK_CASE_H(S, TABLES, KIND, SHADE, SERIAL) case mskplan::KIND: MSK_FUSED(k_wavefront_h_##S); break;
+#define MSK_CASE(S, TABLES, KIND, SHADE, SERIAL) case mskplan::KIND: MSK_FUSED(k_wavefront_##S); break;
     if (plan.fused_h) switch (plan.shade_kind) {      // the tree in HBM (trace mode 6)
-    case mskplan::SHADE_DIELECTRIC: MSK_FUSED(k_wavefront_h_d); break;
     case mskplan::SHADE_DIFFUSE: MSK_FUSED(k_wavefront_h<true>); break;
     case mskplan::SHADE_REGULAR: MSK_FUSED(k_wavefront_h<false, true>); break;
     case mskplan::SHADE_GENERAL: MSK_FUSED(k_wavefront_h<false>); break;
-    case mskplan::SHADE_BITMAP: MSK_FUSED(k_wavefront_h_b); break;
-    case mskplan::SHADE_ENVMAP: MSK_FUSED(k_wavefront_h_e); break;
-    case mskplan::SHADE_DELTA: MSK_FUSED(k_wavefront_h_p); break;
-    case mskplan::SHADE_MASK: MSK_FUSED(k_wavefront_h_m); break;
-    case mskplan::SHADE_LENS: MSK_FUSED(k_wavefront_h_l); break;
+    MSK_FAMILIES(MSK_CASE_H)
     }
     else switch (plan.shade_kind) {                   // everything in LDS (trace mode 0)
-    case mskplan::SHADE_DIELECTRIC: MSK_FUSED(k_wavefront_d); break;
     case mskplan::SHADE_DIFFUSE: MSK_FUSED(k_wavefront<true>); break;
     case mskplan::SHADE_REGULAR: MSK_FUSED(k_wavefront<false, true>); break;
     case mskplan::SHADE_GENERAL: MSK_FUSED(k_wavefront<false>); break;
-    case mskplan::SHADE_BITMAP: MSK_FUSED(k_wavefront_b); break;
-    case mskplan::SHADE_ENVMAP: MSK_FUSED(k_wavefront_e); break;
-    case mskplan::SHADE_DELTA: MSK_FUSED(k_wavefront_p); break;
-    case mskplan::SHADE_MASK: MSK_FUSED(k_wavefront_m); break;
-    case mskplan::SHADE_LENS: MSK_FUSED(k_wavefront_l); break;
+    MSK_FAMILIES(MSK_CASE)
     }
+#undef MSK_CASE
+#undef MSK_CASE_H
 #undef MSK_FUSED
 }
 
@@ -1132,12 +1125,18 @@ static int render_serial(msk_scene *sc, const msk_render_params *prm, float *d_f
         sp.blocks = ws.blocks.as<BlockInfo>(); sp.n_blocks = (uint32_t) owned.size();
         sp.block_buf = ws.block_buf.as<float>(); sp.buf_stride = buf_stride;
         sp.stack_ovf = ovf.as<uint32_t>(); sp.counters = counters.as<unsigned long long>(); sp.per_wave = per_wave ? 1u : 0u;
-        if (sc->facts.has_mask) hipLaunchKernelGGL(k_path_serial_m, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
-        else if (sc->facts.has_delta) hipLaunchKernelGGL(k_path_serial_p, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
-        else if (sc->facts.has_envmap) hipLaunchKernelGGL(k_path_serial_e, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
-        else if (sc->facts.has_bitmap) hipLaunchKernelGGL(k_path_serial_b, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
-        else if (sc->facts.has_dielectric) hipLaunchKernelGGL(k_path_serial_d, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
-        else hipLaunchKernelGGL(k_path_serial, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp);
+#define MSK_SERIAL(K) hipLaunchKernelGGL(K, dim3(grid), dim3(MSK_BLOCK), (size_t) ds.stack_entries * MSK_BLOCK * 4, stream, ds, sp)
+#define MSK_LAUNCH_YES(S) MSK_SERIAL(k_path_serial_##S); break;
+#define MSK_LAUNCH_NO(S) break;      /* (no such kernel, and not reached: render_impl refuses the call) */
+#define MSK_CASE(S, TABLES, KIND, SHADE, SERIAL) case mskplan::KIND: MSK_LAUNCH_##SERIAL(S)
+        switch (mskplan::shade_family(sc->facts)) {       // the scene's family (msk_plan.h), as the wavefront path's plan
+        case mskplan::SHADE_DIFFUSE: case mskplan::SHADE_REGULAR: case mskplan::SHADE_GENERAL: MSK_SERIAL(k_path_serial); break;
+        MSK_FAMILIES(MSK_CASE)
+        }
+#undef MSK_CASE
+#undef MSK_LAUNCH_NO
+#undef MSK_LAUNCH_YES
+#undef MSK_SERIAL
     }
     FilmOut fo;
     fo.film = d_film; fo.stride = 5;
@@ -1604,28 +1603,77 @@ extern "C" int msk_gpu_sample_pixels_direct(msk_scene *scene, const msk_render_p
     return sample_pixels_impl(scene, &p, n_pixels, pixels, out_xyz, out_pos, direct);
 }
 
+// ------------------------------------------------------------------------------------------
+// the probe calls: n points through one small kernel that calls what the render kernels call (msk_gpu.h).  Each entry point keeps its
+// own argument checks and refusals; the two helpers are what they all do besides.
+// ------------------------------------------------------------------------------------------
+struct ProbeIn { const void *host; size_t bytes; };      // host == nullptr: the call does not use this one; the kernel gets a null pointer
+struct ProbeOut { void *host; size_t bytes; };
+
+// One probe kernel over n points on the scene's device: the inputs go up, `launch(in, out, grid)` starts the kernel on ctx->stream with
+// the device pointers (in the order of the two lists) and returns what allocations of its own returned, the wait is timed under the
+// kernel's name, the outputs come down.  n == 0 succeeds with nothing done.  After a wait that fails nothing is freed (DevBuf::leak).
+template <class Launch>
+static int run_probe(msk_scene *scene, const char *kernel, uint64_t n, std::initializer_list<ProbeIn> ins, std::initializer_list<ProbeOut> outs, Launch &&launch) {
+    msk_ctx *ctx = scene->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n == 0) return MSK_OK;
+    std::vector<DevBuf> bufs(ins.size() + outs.size());
+    std::vector<void *> d;
+    for (const ProbeIn &b : ins) {
+        DevBuf &buf = bufs[d.size()];
+        if (b.host) { HIP_TRY(ctx, buf.alloc(b.bytes)); HIP_TRY(ctx, hipMemcpy(buf.p, b.host, b.bytes, hipMemcpyHostToDevice)); }
+        d.push_back(buf.p);
+    }
+    for (const ProbeOut &b : outs) {
+        DevBuf &buf = bufs[d.size()];
+        if (b.host) HIP_TRY(ctx, buf.alloc(b.bytes));
+        d.push_back(buf.p);
+    }
+    void *const *d_out = d.data() + ins.size();
+    const uint32_t grid = (uint32_t) std::min<uint64_t>((n + MSK_BLOCK - 1) / MSK_BLOCK, 4096);
+    HIP_TRY(ctx, launch(d.data(), d_out, grid));
+    HIP_TRY(ctx, hipGetLastError());
+    if (int rcw = ctx_sync(ctx, ctx->stream, kernel)) { for (DevBuf &b : bufs) b.leak(); return rcw; }
+    size_t k = 0;
+    for (const ProbeOut &b : outs) {
+        if (b.host) HIP_TRY(ctx, hipMemcpy(b.host, d_out[k], b.bytes, hipMemcpyDeviceToHost));
+        ++k;
+    }
+    return MSK_OK;
+}
+// a probe of a group's scene runs on its first member's; a failure there is reported as the group's
+template <class F>
+static int on_first_part(msk_scene *scene, F &&f) {
+    if (!scene->ctx->group) return f(scene);
+    const int rc = f(scene->parts[0]);
+    return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK;
+}
+
 static int trace_batch(msk_scene *scene, uint64_t n, const float *rays, float *out_hit, uint8_t *out_any) {
     msk_ctx *ctx = scene->ctx;
     MSK_REFUSE_LOST(ctx);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n == 0) return MSK_OK;
-    DevBuf d_rays, d_out;
-    HIP_TRY(ctx, d_rays.alloc(n * 32)); HIP_TRY(ctx, d_out.alloc(out_any ? n : n * 16));
-    HIP_TRY(ctx, hipMemcpy(d_rays.p, rays, n * 32, hipMemcpyHostToDevice));
-    const uint32_t grid = (uint32_t) std::min<uint64_t>((n + MSK_BLOCK - 1) / MSK_BLOCK, 4096);
-    float4 *oh = out_any ? nullptr : d_out.as<float4>();
-    uint8_t *oa = out_any ? d_out.as<uint8_t>() : nullptr;
-    DevBuf d_ovf;
-    if (scene->dev.stack_total > scene->dev.stack_entries)
-        HIP_TRY(ctx, d_ovf.alloc((size_t) (scene->dev.stack_total - scene->dev.stack_entries) * grid * MSK_BLOCK * 4));
-    with_trace_mode(scene->facts.trace_mode, [&](auto m) {
-        hipLaunchKernelGGL(k_trace_batch<decltype(m)::value>, dim3(grid), dim3(MSK_BLOCK), scene->facts.trace_lds_bytes, ctx->stream, scene->dev,
-                           d_rays.as<float4>(), n, oh, oa, d_ovf.as<uint32_t>());
+    DevBuf d_ovf;                 // the lanes' overflow stacks: sized by the grid
+    const int rc = run_probe(scene, "k_trace_batch", n, {{rays, n * 32}}, {{out_any ? (void *) out_any : (void *) out_hit, out_any ? n : n * 16}},
+                             [&](void *const *in, void *const *out, uint32_t grid) {
+        if (scene->dev.stack_total > scene->dev.stack_entries)
+            if (hipError_t e = d_ovf.alloc((size_t) (scene->dev.stack_total - scene->dev.stack_entries) * grid * MSK_BLOCK * 4)) return e;
+        with_trace_mode(scene->facts.trace_mode, [&](auto m) {
+            hipLaunchKernelGGL(k_trace_batch<decltype(m)::value>, dim3(grid), dim3(MSK_BLOCK), scene->facts.trace_lds_bytes, ctx->stream, scene->dev,
+                               (const float4 *) in[0], n, out_any ? nullptr : (float4 *) out[0], out_any ? (uint8_t *) out[0] : nullptr, d_ovf.as<uint32_t>());
+        });
+        return hipSuccess;
     });
-    HIP_TRY(ctx, hipGetLastError());
-    if (int rcw = ctx_sync(ctx, ctx->stream, "k_trace_batch")) { d_rays.leak(); d_out.leak(); d_ovf.leak(); return rcw; }
-    HIP_TRY(ctx, hipMemcpy(out_any ? (void *) out_any : (void *) out_hit, d_out.p, out_any ? n : n * 16, hipMemcpyDeviceToHost));
-    return MSK_OK;
+    if (ctx->lost) d_ovf.leak();
+    return rc;
+}
+extern "C" int msk_gpu_trace_closest(msk_scene *scene, uint64_t n, const float *rays, float *out_hit) {
+    if (!scene || (n && (!rays || !out_hit))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_trace_closest: NULL argument");
+    return on_first_part(scene, [&](msk_scene *s) { return trace_batch(s, n, rays, out_hit, nullptr); });
+}
+extern "C" int msk_gpu_trace_any(msk_scene *scene, uint64_t n, const float *rays, uint8_t *out_occluded) {
+    if (!scene || (n && (!rays || !out_occluded))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_trace_any: NULL argument");
+    return on_first_part(scene, [&](msk_scene *s) { return trace_batch(s, n, rays, nullptr, out_occluded); });
 }
 
 static int eval_texture(msk_scene *scene, uint32_t texture, uint64_t n, const float *uv, const float *wavelengths, float *out) {
@@ -1633,24 +1681,15 @@ static int eval_texture(msk_scene *scene, uint32_t texture, uint64_t n, const fl
     MSK_REFUSE_LOST(ctx);
     if (texture < 1 || texture > scene->n_textures)
         return fail(ctx, MSK_ERR_INVALID_ARG, "msk_gpu_eval_texture: texture %u out of range (1 .. %u)", texture, scene->n_textures);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n == 0) return MSK_OK;
-    DevBuf d_uv, d_wl, d_out;
-    HIP_TRY(ctx, d_uv.alloc(n * 8)); HIP_TRY(ctx, d_wl.alloc(n * 16)); HIP_TRY(ctx, d_out.alloc(n * 16));
-    HIP_TRY(ctx, hipMemcpy(d_uv.p, uv, n * 8, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(d_wl.p, wavelengths, n * 16, hipMemcpyHostToDevice));
-    const uint32_t grid = (uint32_t) std::min<uint64_t>((n + MSK_BLOCK - 1) / MSK_BLOCK, 4096);
-    hipLaunchKernelGGL(k_eval_texture, dim3(grid), dim3(MSK_BLOCK), 0, ctx->stream, scene->dev, scene->tex_base + (texture - 1) * 3, n,
-                       d_uv.as<float2>(), d_wl.as<float4>(), d_out.as<float4>());
-    HIP_TRY(ctx, hipGetLastError());
-    if (int rcw = ctx_sync(ctx, ctx->stream, "k_eval_texture")) { d_uv.leak(); d_wl.leak(); d_out.leak(); return rcw; }
-    HIP_TRY(ctx, hipMemcpy(out, d_out.p, n * 16, hipMemcpyDeviceToHost));
-    return MSK_OK;
+    return run_probe(scene, "k_eval_texture", n, {{uv, n * 8}, {wavelengths, n * 16}}, {{out, n * 16}}, [&](void *const *in, void *const *o, uint32_t grid) {
+        hipLaunchKernelGGL(k_eval_texture, dim3(grid), dim3(MSK_BLOCK), 0, ctx->stream, scene->dev, scene->tex_base + (texture - 1) * 3, n,
+                           (const float2 *) in[0], (const float4 *) in[1], (float4 *) o[0]);
+        return hipSuccess;
+    });
 }
 extern "C" int msk_gpu_eval_texture(msk_scene *scene, uint32_t texture, uint64_t n, const float *uv, const float *wavelengths, float *out) {
     if (!scene || (n && (!uv || !wavelengths || !out))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_eval_texture: NULL argument");
-    if (scene->ctx->group) { const int rc = eval_texture(scene->parts[0], texture, n, uv, wavelengths, out); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
-    return eval_texture(scene, texture, n, uv, wavelengths, out);
+    return on_first_part(scene, [&](msk_scene *s) { return eval_texture(s, texture, n, uv, wavelengths, out); });
 }
 
 // msk_gpu_env_eval (sample == 0: `in` = n * 3 directions) / msk_gpu_env_sample (sample == 1: `in` = n * 2 random numbers)
@@ -1659,40 +1698,24 @@ static int env_probe(msk_scene *scene, const char *who, uint32_t sample, uint64_
     msk_ctx *ctx = scene->ctx;
     MSK_REFUSE_LOST(ctx);
     if (!scene->facts.has_envmap) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: the scene has no envmap emitter", who);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n == 0) return MSK_OK;
-    const size_t in_f = sample ? 2 : 3;
-    DevBuf d_in, d_wl, d_rad, d_dir, d_uv, d_pdf;
-    HIP_TRY(ctx, d_in.alloc(n * in_f * 4)); HIP_TRY(ctx, d_pdf.alloc(n * 4));
-    HIP_TRY(ctx, hipMemcpy(d_in.p, in, n * in_f * 4, hipMemcpyHostToDevice));
-    if (sample) { HIP_TRY(ctx, d_dir.alloc(n * 12)); HIP_TRY(ctx, d_uv.alloc(n * 8)); }
-    else {
-        HIP_TRY(ctx, d_wl.alloc(n * 16)); HIP_TRY(ctx, d_rad.alloc(n * 16));
-        HIP_TRY(ctx, hipMemcpy(d_wl.p, wavelengths, n * 16, hipMemcpyHostToDevice));
-    }
-    const uint32_t grid = (uint32_t) std::min<uint64_t>((n + MSK_BLOCK - 1) / MSK_BLOCK, 4096);
-    hipLaunchKernelGGL(k_env_probe, dim3(grid), dim3(MSK_BLOCK), 0, ctx->stream, scene->dev, sample, n, d_in.as<float>(), d_wl.as<float4>(), d_rad.as<float4>(),
-                       d_dir.as<float>(), d_uv.as<float2>(), d_pdf.as<float>());
-    HIP_TRY(ctx, hipGetLastError());
-    if (int rcw = ctx_sync(ctx, ctx->stream, "k_env_probe")) { d_in.leak(); d_wl.leak(); d_rad.leak(); d_dir.leak(); d_uv.leak(); d_pdf.leak(); return rcw; }
-    if (sample) { HIP_TRY(ctx, hipMemcpy(out_dir, d_dir.p, n * 12, hipMemcpyDeviceToHost)); HIP_TRY(ctx, hipMemcpy(out_uv, d_uv.p, n * 8, hipMemcpyDeviceToHost)); }
-    else HIP_TRY(ctx, hipMemcpy(out_rad, d_rad.p, n * 16, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out_pdf, d_pdf.p, n * 4, hipMemcpyDeviceToHost));
-    return MSK_OK;
+    return run_probe(scene, "k_env_probe", n, {{in, n * (sample ? 2 : 3) * 4}, {wavelengths, n * 16}},
+                     {{out_rad, n * 16}, {out_dir, n * 12}, {out_uv, n * 8}, {out_pdf, n * 4}}, [&](void *const *i, void *const *o, uint32_t grid) {
+        hipLaunchKernelGGL(k_env_probe, dim3(grid), dim3(MSK_BLOCK), 0, ctx->stream, scene->dev, sample, n, (const float *) i[0], (const float4 *) i[1],
+                           (float4 *) o[0], (float *) o[1], (float2 *) o[2], (float *) o[3]);
+        return hipSuccess;
+    });
 }
 extern "C" int msk_gpu_env_eval(msk_scene *scene, uint64_t n, const float *dirs, const float *wavelengths, float *out_radiance, float *out_pdf) {
     if (!scene || (n && (!dirs || !wavelengths || !out_radiance || !out_pdf))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_env_eval: NULL argument");
-    if (scene->ctx->group) { const int rc = env_probe(scene->parts[0], "msk_gpu_env_eval", 0, n, dirs, wavelengths, out_radiance, nullptr, nullptr, out_pdf); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
-    return env_probe(scene, "msk_gpu_env_eval", 0, n, dirs, wavelengths, out_radiance, nullptr, nullptr, out_pdf);
+    return on_first_part(scene, [&](msk_scene *s) { return env_probe(s, "msk_gpu_env_eval", 0, n, dirs, wavelengths, out_radiance, nullptr, nullptr, out_pdf); });
 }
 extern "C" int msk_gpu_env_sample(msk_scene *scene, uint64_t n, const float *u, float *out_dir, float *out_uv, float *out_pdf) {
     if (!scene || (n && (!u || !out_dir || !out_uv || !out_pdf))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_env_sample: NULL argument");
-    if (scene->ctx->group) { const int rc = env_probe(scene->parts[0], "msk_gpu_env_sample", 1, n, u, nullptr, nullptr, out_dir, out_uv, out_pdf); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
-    return env_probe(scene, "msk_gpu_env_sample", 1, n, u, nullptr, nullptr, out_dir, out_uv, out_pdf);
+    return on_first_part(scene, [&](msk_scene *s) { return env_probe(s, "msk_gpu_env_sample", 1, n, u, nullptr, nullptr, out_dir, out_uv, out_pdf); });
 }
 
-// msk_gpu_point_sample (conductor == 0: `in` = n * 3 reference points, two outputs) / msk_gpu_conductor_sample (1: `in` = n cosines) /
-// msk_gpu_light_sample (2: as 0, for a spot or directional emitter)
+// msk_gpu_point_sample (conductor == 0: `in` = n * 3 reference points, two outputs) / msk_gpu_conductor_sample (1: `in` = n cosines,
+// out_a unused) / msk_gpu_light_sample (2: as 0, for a spot or directional emitter)
 static int delta_probe(msk_scene *scene, const char *who, uint32_t conductor, uint32_t index, uint64_t n, const float *in, const float *wavelengths, float *out_a, float *out_b) {
     msk_ctx *ctx = scene->ctx;
     MSK_REFUSE_LOST(ctx);
@@ -1704,115 +1727,70 @@ static int delta_probe(msk_scene *scene, const char *who, uint32_t conductor, ui
     else if (conductor) {
         if (index >= scene->bsdf_types.size() || scene->bsdf_types[index] != MSK_BSDF_CONDUCTOR) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: bsdf %u is not a conductor of this scene", who, index);
     } else if (index >= scene->emitter_types.size() || scene->emitter_types[index] != MSK_EMITTER_POINT) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: emitter %u is not a point emitter of this scene", who, index);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n == 0) return MSK_OK;
-    const size_t in_f = conductor == 1u ? 1 : 3;
-    DevBuf d_in, d_wl, d_a, d_b;
-    HIP_TRY(ctx, d_in.alloc(n * in_f * 4)); HIP_TRY(ctx, d_wl.alloc(n * 16)); HIP_TRY(ctx, d_b.alloc(n * 16));
-    if (conductor != 1u) HIP_TRY(ctx, d_a.alloc(n * 16));
-    HIP_TRY(ctx, hipMemcpy(d_in.p, in, n * in_f * 4, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(d_wl.p, wavelengths, n * 16, hipMemcpyHostToDevice));
-    const uint32_t grid = (uint32_t) std::min<uint64_t>((n + MSK_BLOCK - 1) / MSK_BLOCK, 4096);
-    hipLaunchKernelGGL(k_delta_probe, dim3(grid), dim3(MSK_BLOCK), 0, ctx->stream, scene->dev, conductor, index, n, d_in.as<float>(), d_wl.as<float4>(), d_a.as<float4>(), d_b.as<float4>());
-    HIP_TRY(ctx, hipGetLastError());
-    if (int rcw = ctx_sync(ctx, ctx->stream, "k_delta_probe")) { d_in.leak(); d_wl.leak(); d_a.leak(); d_b.leak(); return rcw; }
-    if (conductor != 1u) HIP_TRY(ctx, hipMemcpy(out_a, d_a.p, n * 16, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out_b, d_b.p, n * 16, hipMemcpyDeviceToHost));
-    return MSK_OK;
+    return run_probe(scene, "k_delta_probe", n, {{in, n * (conductor == 1u ? 1 : 3) * 4}, {wavelengths, n * 16}}, {{out_a, n * 16}, {out_b, n * 16}},
+                     [&](void *const *i, void *const *o, uint32_t grid) {
+        hipLaunchKernelGGL(k_delta_probe, dim3(grid), dim3(MSK_BLOCK), 0, ctx->stream, scene->dev, conductor, index, n, (const float *) i[0], (const float4 *) i[1],
+                           (float4 *) o[0], (float4 *) o[1]);
+        return hipSuccess;
+    });
 }
 extern "C" int msk_gpu_point_sample(msk_scene *scene, uint32_t emitter, uint64_t n, const float *ref_points, const float *wavelengths, float *out_d_dist, float *out_value) {
     if (!scene || (n && (!ref_points || !wavelengths || !out_d_dist || !out_value))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_point_sample: NULL argument");
-    if (scene->ctx->group) { const int rc = delta_probe(scene->parts[0], "msk_gpu_point_sample", 0, emitter, n, ref_points, wavelengths, out_d_dist, out_value); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
-    return delta_probe(scene, "msk_gpu_point_sample", 0, emitter, n, ref_points, wavelengths, out_d_dist, out_value);
+    return on_first_part(scene, [&](msk_scene *s) { return delta_probe(s, "msk_gpu_point_sample", 0, emitter, n, ref_points, wavelengths, out_d_dist, out_value); });
 }
 extern "C" int msk_gpu_light_sample(msk_scene *scene, uint32_t emitter, uint64_t n, const float *ref_points, const float *wavelengths, float *out_d_dist, float *out_value) {
     if (!scene || (n && (!ref_points || !wavelengths || !out_d_dist || !out_value))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_light_sample: NULL argument");
-    if (scene->ctx->group) { const int rc = delta_probe(scene->parts[0], "msk_gpu_light_sample", 2, emitter, n, ref_points, wavelengths, out_d_dist, out_value); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
-    return delta_probe(scene, "msk_gpu_light_sample", 2, emitter, n, ref_points, wavelengths, out_d_dist, out_value);
+    return on_first_part(scene, [&](msk_scene *s) { return delta_probe(s, "msk_gpu_light_sample", 2, emitter, n, ref_points, wavelengths, out_d_dist, out_value); });
 }
+extern "C" int msk_gpu_conductor_sample(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *cos_theta_i, const float *wavelengths, float *out_value) {
+    if (!scene || (n && (!cos_theta_i || !wavelengths || !out_value))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_conductor_sample: NULL argument");
+    return on_first_part(scene, [&](msk_scene *s) { return delta_probe(s, "msk_gpu_conductor_sample", 1, bsdf, n, cos_theta_i, wavelengths, nullptr, out_value); });
+}
+
 // msk_gpu_camera_sample: k_camera_probe, with or without the lens
 static int camera_probe(msk_scene *scene, uint64_t n, const float *film_pos, const float *aperture_u, float *out_rays) {
     msk_ctx *ctx = scene->ctx;
     MSK_REFUSE_LOST(ctx);
     const bool lens = scene->facts.has_lens;
     if (n && lens && !aperture_u) return fail(ctx, MSK_ERR_INVALID_ARG, "msk_gpu_camera_sample: a scene with a `thinlens` sensor needs aperture_u");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n == 0) return MSK_OK;
-    DevBuf d_pos, d_u, d_out;
-    HIP_TRY(ctx, d_pos.alloc(n * 8)); HIP_TRY(ctx, d_out.alloc(n * 32));
-    HIP_TRY(ctx, hipMemcpy(d_pos.p, film_pos, n * 8, hipMemcpyHostToDevice));
-    if (lens) { HIP_TRY(ctx, d_u.alloc(n * 8)); HIP_TRY(ctx, hipMemcpy(d_u.p, aperture_u, n * 8, hipMemcpyHostToDevice)); }
-    const uint32_t grid = (uint32_t) std::min<uint64_t>((n + MSK_BLOCK - 1) / MSK_BLOCK, 4096);
-    if (lens) hipLaunchKernelGGL(k_camera_probe<true>, dim3(grid), dim3(MSK_BLOCK), 0, ctx->stream, scene->dev, n, d_pos.as<float2>(), d_u.as<float2>(), d_out.as<float4>());
-    else hipLaunchKernelGGL(k_camera_probe<false>, dim3(grid), dim3(MSK_BLOCK), 0, ctx->stream, scene->dev, n, d_pos.as<float2>(), (const float2 *) nullptr, d_out.as<float4>());
-    HIP_TRY(ctx, hipGetLastError());
-    if (int rcw = ctx_sync(ctx, ctx->stream, "k_camera_probe")) { d_pos.leak(); d_u.leak(); d_out.leak(); return rcw; }
-    HIP_TRY(ctx, hipMemcpy(out_rays, d_out.p, n * 32, hipMemcpyDeviceToHost));
-    return MSK_OK;
+    return run_probe(scene, "k_camera_probe", n, {{film_pos, n * 8}, {lens ? aperture_u : nullptr, n * 8}}, {{out_rays, n * 32}},
+                     [&](void *const *in, void *const *o, uint32_t grid) {
+        if (lens) hipLaunchKernelGGL(k_camera_probe<true>, dim3(grid), dim3(MSK_BLOCK), 0, ctx->stream, scene->dev, n, (const float2 *) in[0], (const float2 *) in[1], (float4 *) o[0]);
+        else hipLaunchKernelGGL(k_camera_probe<false>, dim3(grid), dim3(MSK_BLOCK), 0, ctx->stream, scene->dev, n, (const float2 *) in[0], (const float2 *) nullptr, (float4 *) o[0]);
+        return hipSuccess;
+    });
 }
 extern "C" int msk_gpu_camera_sample(msk_scene *scene, uint64_t n, const float *film_pos, const float *aperture_u, float *out_rays) {
     if (!scene || (n && (!film_pos || !out_rays))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_camera_sample: NULL argument");
-    if (scene->ctx->group) { const int rc = camera_probe(scene->parts[0], n, film_pos, aperture_u, out_rays); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
-    return camera_probe(scene, n, film_pos, aperture_u, out_rays);
-}
-extern "C" int msk_gpu_conductor_sample(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *cos_theta_i, const float *wavelengths, float *out_value) {
-    if (!scene || (n && (!cos_theta_i || !wavelengths || !out_value))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_conductor_sample: NULL argument");
-    if (scene->ctx->group) { const int rc = delta_probe(scene->parts[0], "msk_gpu_conductor_sample", 1, bsdf, n, cos_theta_i, wavelengths, nullptr, out_value); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
-    return delta_probe(scene, "msk_gpu_conductor_sample", 1, bsdf, n, cos_theta_i, wavelengths, nullptr, out_value);
+    return on_first_part(scene, [&](msk_scene *s) { return camera_probe(s, n, film_pos, aperture_u, out_rays); });
 }
 
-// msk_gpu_mask_sample (eval == 0: in_b = {sample1, u.x, u.y}, three outputs) / msk_gpu_mask_eval (in_b = wo; out_a = n * 2 {a, pdf})
+// msk_gpu_mask_sample (eval == 0: in_b = {sample1, u.x, u.y}, three outputs) / msk_gpu_mask_eval (in_b = wo; out_a = n * 2 {a, pdf}, no out_c)
 static int mask_probe(msk_scene *scene, const char *who, uint32_t eval, uint32_t bsdf, uint64_t n, const float *uv, const float *in_a, const float *in_b,
                       const float *wavelengths, float *out_a, float *out_b, float *out_c) {
     msk_ctx *ctx = scene->ctx;
     MSK_REFUSE_LOST(ctx);
     if (!scene->facts.has_mask) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: the scene holds no mask", who);
     if (bsdf >= scene->bsdf_types.size()) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: bsdf %u out of range (the scene has %zu)", who, bsdf, scene->bsdf_types.size());
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n == 0) return MSK_OK;
-    DevBuf d_uv, d_a, d_b, d_wl, o_a, o_b, o_c;
-    HIP_TRY(ctx, d_uv.alloc(n * 8)); HIP_TRY(ctx, d_a.alloc(n * 12)); HIP_TRY(ctx, d_b.alloc(n * 12)); HIP_TRY(ctx, d_wl.alloc(n * 16));
-    HIP_TRY(ctx, o_a.alloc(n * 16)); HIP_TRY(ctx, o_b.alloc(n * 16)); HIP_TRY(ctx, o_c.alloc(n * 16));
-    HIP_TRY(ctx, hipMemcpy(d_uv.p, uv, n * 8, hipMemcpyHostToDevice)); HIP_TRY(ctx, hipMemcpy(d_a.p, in_a, n * 12, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(d_b.p, in_b, n * 12, hipMemcpyHostToDevice)); HIP_TRY(ctx, hipMemcpy(d_wl.p, wavelengths, n * 16, hipMemcpyHostToDevice));
-    const uint32_t grid = (uint32_t) std::min<uint64_t>((n + MSK_BLOCK - 1) / MSK_BLOCK, 4096);
-    hipLaunchKernelGGL(k_mask_probe, dim3(grid), dim3(MSK_BLOCK), 0, ctx->stream, scene->dev, eval, bsdf, n, d_uv.as<float>(), d_a.as<float>(), d_b.as<float>(),
-                       d_wl.as<float4>(), o_a.as<float4>(), o_b.as<float4>(), o_c.as<float4>());
-    HIP_TRY(ctx, hipGetLastError());
-    if (int rcw = ctx_sync(ctx, ctx->stream, "k_mask_probe")) { for (DevBuf *b : {&d_uv, &d_a, &d_b, &d_wl, &o_a, &o_b, &o_c}) b->leak(); return rcw; }
-    if (eval) {
-        std::vector<float> tmp(n * 4);
-        HIP_TRY(ctx, hipMemcpy(tmp.data(), o_a.p, n * 16, hipMemcpyDeviceToHost));
-        for (uint64_t i = 0; i < n; ++i) { out_a[i * 2] = tmp[i * 4]; out_a[i * 2 + 1] = tmp[i * 4 + 1]; }
-    } else {
-        HIP_TRY(ctx, hipMemcpy(out_a, o_a.p, n * 16, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(out_c, o_c.p, n * 16, hipMemcpyDeviceToHost));
-    }
-    HIP_TRY(ctx, hipMemcpy(out_b, o_b.p, n * 16, hipMemcpyDeviceToHost));
-    return MSK_OK;
+    std::vector<float> tmp(eval ? n * 4 : 0);           // eval: the kernel's float4 {a, pdf, 0, 0}, of which the caller gets two floats
+    const int rc = run_probe(scene, "k_mask_probe", n, {{uv, n * 8}, {in_a, n * 12}, {in_b, n * 12}, {wavelengths, n * 16}},
+                             {{eval ? tmp.data() : out_a, n * 16}, {out_b, n * 16}, {out_c, n * 16}}, [&](void *const *in, void *const *o, uint32_t grid) {
+        hipLaunchKernelGGL(k_mask_probe, dim3(grid), dim3(MSK_BLOCK), 0, ctx->stream, scene->dev, eval, bsdf, n, (const float *) in[0], (const float *) in[1],
+                           (const float *) in[2], (const float4 *) in[3], (float4 *) o[0], (float4 *) o[1], (float4 *) o[2]);
+        return hipSuccess;
+    });
+    if (rc == MSK_OK && eval) for (uint64_t i = 0; i < n; ++i) { out_a[i * 2] = tmp[i * 4]; out_a[i * 2 + 1] = tmp[i * 4 + 1]; }
+    return rc;
 }
 extern "C" int msk_gpu_mask_sample(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *sample1_u, const float *wavelengths,
                                    float *out_wo_pdf, float *out_value, float *out_flags) {
     if (!scene || (n && (!uv || !wi || !sample1_u || !wavelengths || !out_wo_pdf || !out_value || !out_flags)))
         return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_mask_sample: NULL argument");
-    if (scene->ctx->group) { const int rc = mask_probe(scene->parts[0], "msk_gpu_mask_sample", 0, bsdf, n, uv, wi, sample1_u, wavelengths, out_wo_pdf, out_value, out_flags); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
-    return mask_probe(scene, "msk_gpu_mask_sample", 0, bsdf, n, uv, wi, sample1_u, wavelengths, out_wo_pdf, out_value, out_flags);
+    return on_first_part(scene, [&](msk_scene *s) { return mask_probe(s, "msk_gpu_mask_sample", 0, bsdf, n, uv, wi, sample1_u, wavelengths, out_wo_pdf, out_value, out_flags); });
 }
 extern "C" int msk_gpu_mask_eval(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *wo, const float *wavelengths,
                                  float *out_a_pdf, float *out_value) {
     if (!scene || (n && (!uv || !wi || !wo || !wavelengths || !out_a_pdf || !out_value)))
         return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_mask_eval: NULL argument");
-    if (scene->ctx->group) { const int rc = mask_probe(scene->parts[0], "msk_gpu_mask_eval", 1, bsdf, n, uv, wi, wo, wavelengths, out_a_pdf, out_value, nullptr); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
-    return mask_probe(scene, "msk_gpu_mask_eval", 1, bsdf, n, uv, wi, wo, wavelengths, out_a_pdf, out_value, nullptr);
-}
-
-extern "C" int msk_gpu_trace_closest(msk_scene *scene, uint64_t n, const float *rays, float *out_hit) {
-    if (!scene || (n && (!rays || !out_hit))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_trace_closest: NULL argument");
-    if (scene->ctx->group) { const int rc = trace_batch(scene->parts[0], n, rays, out_hit, nullptr); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
-    return trace_batch(scene, n, rays, out_hit, nullptr);
-}
-extern "C" int msk_gpu_trace_any(msk_scene *scene, uint64_t n, const float *rays, uint8_t *out_occluded) {
-    if (!scene || (n && (!rays || !out_occluded))) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_trace_any: NULL argument");
-    if (scene->ctx->group) { const int rc = trace_batch(scene->parts[0], n, rays, nullptr, out_occluded); return rc ? group_fail(scene->ctx, 0, rc) : MSK_OK; }
-    return trace_batch(scene, n, rays, nullptr, out_occluded);
+    return on_first_part(scene, [&](msk_scene *s) { return mask_probe(s, "msk_gpu_mask_eval", 1, bsdf, n, uv, wi, wo, wavelengths, out_a_pdf, out_value, nullptr); });
 }

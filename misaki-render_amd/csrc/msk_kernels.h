@@ -1396,6 +1396,7 @@ struct Interaction {
 // Small read-only scene tables of the shading kernel; staged in LDS when they fit (every hit
 // looks them up through a chain of dependent indices, which from HBM/L2 costs a round trip each).
 struct SceneTables {
+    static constexpr int level = 0;             // how many of the features below the type carries: tb_traits
     const float4 *tri_verts, *tri_frames, *tri_normals, *tri_uvs;
     const int4 *mesh_info;
     const float4 *bsdfs, *emitters;
@@ -1407,42 +1408,59 @@ struct SceneTables {
 // The same tables for a scene that holds tabulated (`regular`) spectra: the TYPE selects the code that can evaluate them (spectrum
 // records of the table form, emitters' tables on their own grids).  Scenes without any — every BASELINE config — run the
 // instantiations that do not carry those branches (measured: 3.2 % of the config-3-class render, 1.4 % of the config-5-class one).
-struct SceneTablesR : SceneTables {};
+struct SceneTablesR : SceneTables { static constexpr int level = 1; };
 // ... and the tables of a scene that holds a smooth `dielectric` (MSK_BSDF_DIELECTRIC): the delta lobes, the guard around next-event
 // estimation and the delta mark of the path state are compiled only into the instantiations that carry this type, which such
 // scenes alone run.  It carries the table forms of tabulated spectra always (as k_path_serial does): one set of instantiations.
-struct SceneTablesD : SceneTablesR {};
+struct SceneTablesD : SceneTablesR { static constexpr int level = 2; };
 // ... and of a scene that holds a `bitmap` texture (MSK_TEXTURE_BITMAP*), with or without glass: the texel lookup of reflectance_eval
 // is compiled only into the instantiations that carry this type (k_shade_gen_b, k_wavefront_b, k_wavefront_h_b, k_path_serial_b).
-struct SceneTablesB : SceneTablesD {};
+struct SceneTablesB : SceneTablesD { static constexpr int level = 3; };
 // ... and of a scene whose environment emitter is an image (MSK_EMITTER_ENVMAP), whatever else it holds: the image lookup, its
 // density and the sampling of light directions from it are compiled only into the instantiations that carry this type
 // (k_shade_gen_e, k_wavefront_e, k_wavefront_h_e, k_path_serial_e).  In them the scene's environment emitter IS the image.
-struct SceneTablesE : SceneTablesB {};
+struct SceneTablesE : SceneTablesB { static constexpr int level = 4; };
 // ... and of a scene that holds a `point` emitter (MSK_EMITTER_POINT) or a smooth `conductor` (MSK_BSDF_CONDUCTOR), whatever else
 // it holds: the delta light's next-event branch, the mirror lobe and the `constant` sky's own density on the miss branch are compiled
 // only into the instantiations that carry this type (k_shade_gen_p, k_wavefront_p, k_wavefront_h_p, k_path_serial_p).  In them the
 // environment emitter, if any, is the image OR the `constant` sky: the emitter's record says which (env_is_image).
-struct SceneTablesP : SceneTablesE {};
+struct SceneTablesP : SceneTablesE { static constexpr int level = 5; };
 // ... and of a scene that holds a `mask` (msk_gpu.h: msk_mask_desc), whatever else it holds: the opacity lookup, the null lobe, the
 // per-sample delta mark and the `scattered` bit of the path state are compiled only into the instantiations that carry this type
 // (k_shade_gen_m, k_wavefront_m, k_wavefront_h_m, k_path_serial_m, k_mask_probe).  They carry everything SceneTablesP does, the
 // `constant` sky's own density included.
-struct SceneTablesM : SceneTablesP {};
+struct SceneTablesM : SceneTablesP { static constexpr int level = 6; };
 // ... and of a scene whose sensor is a `thinlens` (msk_gpu.h: msk_lens_desc), whatever else it holds: the aperture sample and the lens
 // point of a new camera sample are compiled only into the instantiations that carry this type (k_shade_gen_l, k_wavefront_l,
 // k_wavefront_h_l).  They carry everything SceneTablesM does; a scene with a lens and no mask gets mask records of the constant
 // opacity 1 (msk_lens_tables.h), under which the mask code computes the nested BSDF to the bit.
-struct SceneTablesL : SceneTablesM {};
+struct SceneTablesL : SceneTablesM { static constexpr int level = 7; };
 // (MSK_EMITTER_MARK_POINT, word 0 of a point emitter's second float4: msk_layout.h)
-template <class TB> struct tb_traits { static constexpr bool regular = false, dielectric = false, bitmap = false, envmap = false, delta = false, mask = false, lens = false; };
-template <> struct tb_traits<SceneTablesR> { static constexpr bool regular = true, dielectric = false, bitmap = false, envmap = false, delta = false, mask = false, lens = false; };
-template <> struct tb_traits<SceneTablesD> { static constexpr bool regular = true, dielectric = true, bitmap = false, envmap = false, delta = false, mask = false, lens = false; };
-template <> struct tb_traits<SceneTablesB> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = false, delta = false, mask = false, lens = false; };
-template <> struct tb_traits<SceneTablesE> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = true, delta = false, mask = false, lens = false; };
-template <> struct tb_traits<SceneTablesP> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = true, delta = true, mask = false, lens = false; };
-template <> struct tb_traits<SceneTablesM> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = true, delta = true, mask = true, lens = false; };
-template <> struct tb_traits<SceneTablesL> { static constexpr bool regular = true, dielectric = true, bitmap = true, envmap = true, delta = true, mask = true, lens = true; };
+// What a table type compiles in.  The types form a chain, each carrying everything its base does and one feature more, so a
+// feature is on from its own level up.
+template <class TB> struct tb_traits {
+    static constexpr bool regular = TB::level >= 1, dielectric = TB::level >= 2, bitmap = TB::level >= 3, envmap = TB::level >= 4,
+                          delta = TB::level >= 5, mask = TB::level >= 6, lens = TB::level >= 7;
+};
+// The shading families: one line per table type above that has kernels of its own, X(suffix, table type, mskplan::ShadeKind, SHADE,
+// SERIAL) — the one place where a family's suffix and its table type are paired.  Stamped from it: k_shade_gen_<suffix>,
+// k_wavefront_<suffix> and k_wavefront_h_<suffix> (below) and the cases of the dispatch, render_serial's included (msk_gpu.hip);
+// k_path_serial_<suffix> is written by hand (msk_serial.h says why).  Which family a scene runs: mskplan::shade_family (msk_plan.h).
+// SHADE, how k_shade_gen_<suffix> is made:
+//   HELD         held at MSK_SHADE_GEN_WAVES, as the general variants of k_shade_gen are (see there).
+//   FREE         not held at a wave count by attribute.  `e`: at 168 VGPRs the image's sampling (two table searches, two det_sincos,
+//                four gathers) spills 8 bytes; `p` carries everything `e` does, `m` everything `p` does.
+//   WRITTEN_OUT  not held either (`l` carries everything `m` does, and the lens point of a new camera sample), and written by hand
+//                below: through shade_gen_body the compiler lays this one's code out differently (EXPERIMENTS.md, "Name each
+//                shading family once"), and this list is not allowed to move a kernel.
+// SERIAL: whether k_path_serial_<suffix> exists.  `l` has none: MSK_RNG_PCG_BLOCK refuses a lens.
+#define MSK_FAMILIES(X)                                    \
+    X(d, SceneTablesD, SHADE_DIELECTRIC, HELD,        YES) \
+    X(b, SceneTablesB, SHADE_BITMAP,     HELD,        YES) \
+    X(e, SceneTablesE, SHADE_ENVMAP,     FREE,        YES) \
+    X(p, SceneTablesP, SHADE_DELTA,      FREE,        YES) \
+    X(m, SceneTablesM, SHADE_MASK,       FREE,        YES) \
+    X(l, SceneTablesL, SHADE_LENS,       WRITTEN_OUT, NO)
 MSK_DEV uint32_t tables_lds_float4s(const DeviceScene &sc) {
     return sc.n_tris * 6 + sc.n_meshes + sc.n_bsdf_f4 + sc.n_emitters * 3 + (sc.n_emitters * 95 + 3) / 4 + (sc.cdf_len + 3) / 4 + 72 + (sc.n_spectra + 3) / 4;
 }
@@ -2725,16 +2743,13 @@ MSK_DEV DoneQueue done_queue(float4 *base) {
     return dq;
 }
 
-// the table type of an instantiation: plain, with tabulated spectra, with the smooth dielectric (which includes them), with bitmap
-// textures (which includes both)
-template <bool REGULAR, bool DIELECTRIC, bool BITMAP = false, bool ENVMAP = false, bool DELTA = false, bool MASK = false>
-using tables_of = typename std::conditional<MASK, SceneTablesM, typename std::conditional<DELTA, SceneTablesP, typename std::conditional<ENVMAP, SceneTablesE, typename std::conditional<BITMAP, SceneTablesB, typename std::conditional<DIELECTRIC, SceneTablesD,
-                                            typename std::conditional<REGULAR, SceneTablesR, SceneTables>::type>::type>::type>::type>::type>::type;
+// the table type of a k_shade_gen / k_wavefront / k_wavefront_h instantiation: plain, or with tabulated spectra
+template <bool REGULAR> using tables_of = typename std::conditional<REGULAR, SceneTablesR, SceneTables>::type;
 
-template <bool LDS_TABLES, bool DIFFUSE_ONLY, bool REGULAR = false, bool DIELECTRIC = false, bool BITMAP = false, bool ENVMAP = false, bool DELTA = false, bool MASK = false>
+template <bool LDS_TABLES, bool DIFFUSE_ONLY, class TB>
 MSK_DEV void shade_gen_body(const DeviceScene &sc, const PathState &st, const PassParams &pp) {
     extern __shared__ float4 lds_dyn[];
-    tables_of<REGULAR, DIELECTRIC, BITMAP, ENVMAP, DELTA, MASK> tb;
+    TB tb;
     static_cast<SceneTables &>(tb) = stage_tables<LDS_TABLES>(sc, lds_dyn);
     const uint32_t lwave = (blockIdx.x * MSK_BLOCK + threadIdx.x) / MSK_WAVE;
     const uint32_t queue_f4 = LDS_TABLES ? tables_lds_float4s(sc) : small_tables_float4s(sc);   // after the staged tables
@@ -2749,7 +2764,7 @@ MSK_DEV void shade_gen_body(const DeviceScene &sc, const PathState &st, const Pa
 }
 template <bool LDS_TABLES, bool DIFFUSE_ONLY, bool REGULAR = false>
 __global__ void __launch_bounds__(MSK_BLOCK)
-k_shade_gen(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_TABLES, DIFFUSE_ONLY, REGULAR>(sc, st, pp); }
+k_shade_gen(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_TABLES, DIFFUSE_ONLY, tables_of<REGULAR>>(sc, st, pp); }
 // The general variants sit a few registers above the 168 that three waves per SIMD allow (two cost 20 % of the shading time
 // on the mesh scenes): the allocator is told to stay at three.
 #ifndef MSK_SHADE_GEN_WAVES
@@ -2757,46 +2772,36 @@ k_shade_gen(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_TA
 #endif
 template <>
 __global__ void __launch_bounds__(MSK_BLOCK) __attribute__((amdgpu_waves_per_eu(MSK_SHADE_GEN_WAVES)))
-k_shade_gen<false, false>(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<false, false>(sc, st, pp); }
+k_shade_gen<false, false>(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<false, false, SceneTables>(sc, st, pp); }
 template <>
 __global__ void __launch_bounds__(MSK_BLOCK) __attribute__((amdgpu_waves_per_eu(MSK_SHADE_GEN_WAVES)))
-k_shade_gen<true, false>(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<true, false>(sc, st, pp); }
+k_shade_gen<true, false>(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<true, false, SceneTables>(sc, st, pp); }
 // ... and the same two for scenes with tabulated spectra
 template <>
 __global__ void __launch_bounds__(MSK_BLOCK) __attribute__((amdgpu_waves_per_eu(MSK_SHADE_GEN_WAVES)))
-k_shade_gen<false, false, true>(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<false, false, true>(sc, st, pp); }
+k_shade_gen<false, false, true>(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<false, false, SceneTablesR>(sc, st, pp); }
 template <>
 __global__ void __launch_bounds__(MSK_BLOCK) __attribute__((amdgpu_waves_per_eu(MSK_SHADE_GEN_WAVES)))
-k_shade_gen<true, false, true>(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<true, false, true>(sc, st, pp); }
-// ... and the two that scenes with a smooth `dielectric` run, and only they (SceneTablesD): kernels of their own, so that every
-// other scene launches the kernels above, unchanged
-template <bool LDS_TABLES>
-__global__ void __launch_bounds__(MSK_BLOCK) __attribute__((amdgpu_waves_per_eu(MSK_SHADE_GEN_WAVES)))
-k_shade_gen_d(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_TABLES, false, true, true>(sc, st, pp); }
-// ... and the two that scenes with a `bitmap` texture run, and only they (SceneTablesB), with or without glass
-template <bool LDS_TABLES>
-__global__ void __launch_bounds__(MSK_BLOCK) __attribute__((amdgpu_waves_per_eu(MSK_SHADE_GEN_WAVES)))
-k_shade_gen_b(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_TABLES, false, true, true, true>(sc, st, pp); }
-// ... and the two that scenes with an `envmap` emitter run, and only they (SceneTablesE), whatever else they hold.  Not held at
-// three waves per SIMD: at 168 VGPRs the image's sampling (two table searches, two det_sincos, four gathers) spills 8 bytes
-template <bool LDS_TABLES>
-__global__ void __launch_bounds__(MSK_BLOCK)
-k_shade_gen_e(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_TABLES, false, true, true, true, true>(sc, st, pp); }
-// ... and the two that scenes with a `point` emitter or a smooth `conductor` run, and only they (SceneTablesP), whatever else they
-// hold.  Not held at three waves per SIMD either: they carry everything k_shade_gen_e does
-template <bool LDS_TABLES>
-__global__ void __launch_bounds__(MSK_BLOCK)
-k_shade_gen_p(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_TABLES, false, true, true, true, true, true>(sc, st, pp); }
-// ... and the two that scenes with a `mask` run, and only they (SceneTablesM), whatever else they hold.  Not held at a wave count by
-// attribute either: they carry everything k_shade_gen_p does
+k_shade_gen<true, false, true>(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<true, false, SceneTablesR>(sc, st, pp); }
+// ... and k_shade_gen_<suffix><LDS_TABLES>, the two that the scenes of a family run, and only they: kernels of their own, so that
+// every other scene launches the kernels above, unchanged (MSK_FAMILIES: which are held at the wave count, and why)
+#define MSK_SHADE_GEN_KERNEL(S, TABLES, ATTR)                                                                                                  \
+    template <bool LDS_TABLES>                                                                                                                 \
+    __global__ void __launch_bounds__(MSK_BLOCK) ATTR                                                                                          \
+    k_shade_gen_##S(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_TABLES, false, TABLES>(sc, st, pp); }
+#define MSK_SHADE_GEN_HELD(S, TABLES) MSK_SHADE_GEN_KERNEL(S, TABLES, __attribute__((amdgpu_waves_per_eu(MSK_SHADE_GEN_WAVES))))
+#define MSK_SHADE_GEN_FREE(S, TABLES) MSK_SHADE_GEN_KERNEL(S, TABLES, )
+#define MSK_SHADE_GEN_WRITTEN_OUT(S, TABLES)
+#define MSK_STAMP(S, TABLES, KIND, SHADE, SERIAL) MSK_SHADE_GEN_##SHADE(S, TABLES)
+MSK_FAMILIES(MSK_STAMP)
+#undef MSK_STAMP
+#undef MSK_SHADE_GEN_WRITTEN_OUT
+#undef MSK_SHADE_GEN_FREE
+#undef MSK_SHADE_GEN_HELD
+#undef MSK_SHADE_GEN_KERNEL
 template <bool LDS_TABLES>
 __global__ void __launch_bounds__(MSK_BLOCK)
-k_shade_gen_m(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<LDS_TABLES, false, true, true, true, true, true, true>(sc, st, pp); }
-// ... and the two that scenes with a `thinlens` sensor run, and only they (SceneTablesL), whatever else they hold.  Not held at a
-// wave count by attribute either: they carry everything k_shade_gen_m does, and the lens point of a new camera sample
-template <bool LDS_TABLES>
-__global__ void __launch_bounds__(MSK_BLOCK)
-k_shade_gen_l(DeviceScene sc, PathState st, PassParams pp) {
+k_shade_gen_l(DeviceScene sc, PathState st, PassParams pp) {       // shade_gen_body<LDS_TABLES, false, SceneTablesL>, WRITTEN_OUT
     extern __shared__ float4 lds_dyn[];
     SceneTablesL tb;
     static_cast<SceneTables &>(tb) = stage_tables<LDS_TABLES>(sc, lds_dyn);
@@ -2816,10 +2821,10 @@ k_shade_gen_l(DeviceScene sc, PathState st, PassParams pp) {
 #ifndef MSK_NO_SHADE4
 template <>
 __global__ void __launch_bounds__(MSK_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4)))
-k_shade_gen<false, true>(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<false, true>(sc, st, pp); }
+k_shade_gen<false, true>(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<false, true, SceneTables>(sc, st, pp); }
 template <>
 __global__ void __launch_bounds__(MSK_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4)))
-k_shade_gen<true, true>(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<true, true>(sc, st, pp); }
+k_shade_gen<true, true>(DeviceScene sc, PathState st, PassParams pp) { shade_gen_body<true, true, SceneTables>(sc, st, pp); }
 #endif
 
 // ------------------------------------------------------------------------------------------
@@ -2876,58 +2881,22 @@ k_shade_gen<true, true>(DeviceScene sc, PathState st, PassParams pp) { shade_gen
 template <bool DIFFUSE_ONLY, bool REGULAR = false>
 __global__ void __launch_bounds__(MSK_BLOCK)
 k_wavefront(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
-    typedef typename std::conditional<REGULAR, SceneTablesR, SceneTables>::type TB;
+    typedef tables_of<REGULAR> TB;
     constexpr bool CULL = true;
     MSK_WAVEFRONT_BODY
 }
-// the one scenes with a smooth `dielectric` run (see k_shade_gen_d)
-__global__ void __launch_bounds__(MSK_BLOCK)
-k_wavefront_d(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
-    typedef SceneTablesD TB;
-    constexpr bool DIFFUSE_ONLY = false;
-    constexpr bool CULL = false;      // (see shade_region: the register budget of this instantiation)
-    MSK_WAVEFRONT_BODY
-}
-// the one scenes with a `bitmap` texture run (see k_shade_gen_b)
-__global__ void __launch_bounds__(MSK_BLOCK)
-k_wavefront_b(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
-    typedef SceneTablesB TB;
-    constexpr bool DIFFUSE_ONLY = false;
-    constexpr bool CULL = false;      // (as k_wavefront_d)
-    MSK_WAVEFRONT_BODY
-}
-// the one scenes with an `envmap` emitter run (see k_shade_gen_e)
-__global__ void __launch_bounds__(MSK_BLOCK)
-k_wavefront_e(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
-    typedef SceneTablesE TB;
-    constexpr bool DIFFUSE_ONLY = false;
-    constexpr bool CULL = false;      // (no camera cull with an environment emitter)
-    MSK_WAVEFRONT_BODY
-}
-// the one scenes with a `point` emitter or a smooth `conductor` run (see k_shade_gen_p)
-__global__ void __launch_bounds__(MSK_BLOCK)
-k_wavefront_p(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
-    typedef SceneTablesP TB;
-    constexpr bool DIFFUSE_ONLY = false;
-    constexpr bool CULL = false;      // (as k_wavefront_d)
-    MSK_WAVEFRONT_BODY
-}
-// the one scenes with a `mask` run (see k_shade_gen_m)
-__global__ void __launch_bounds__(MSK_BLOCK)
-k_wavefront_m(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
-    typedef SceneTablesM TB;
-    constexpr bool DIFFUSE_ONLY = false;
-    constexpr bool CULL = false;      // (as k_wavefront_d)
-    MSK_WAVEFRONT_BODY
-}
-// the one scenes with a `thinlens` sensor run (see k_shade_gen_l)
-__global__ void __launch_bounds__(MSK_BLOCK)
-k_wavefront_l(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
-    typedef SceneTablesL TB;
-    constexpr bool DIFFUSE_ONLY = false;
-    constexpr bool CULL = false;      // (as k_wavefront_d)
-    MSK_WAVEFRONT_BODY
-}
+// k_wavefront_<suffix>: the one that the scenes of a family run (see k_shade_gen_<suffix>).  No camera cull in them — shade_region:
+// the register budget of these instantiations; and a scene with an environment emitter (`e` and up) has none to begin with.
+#define MSK_STAMP(S, TABLES, KIND, SHADE, SERIAL)                                                                             \
+    __global__ void __launch_bounds__(MSK_BLOCK)                                                                              \
+    k_wavefront_##S(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {  \
+        typedef TABLES TB;                                                                                                    \
+        constexpr bool DIFFUSE_ONLY = false;                                                                                  \
+        constexpr bool CULL = false;                                                                                          \
+        MSK_WAVEFRONT_BODY                                                                                                    \
+    }
+MSK_FAMILIES(MSK_STAMP)
+#undef MSK_STAMP
 #undef MSK_WAVEFRONT_BODY
 
 // k_wavefront_h (round 6): the same device-side loop for scenes whose TREE STAYS IN HBM / L2 (trace mode 6: the 4-wide tree with
@@ -2981,51 +2950,19 @@ k_wavefront_l(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, u
 template <bool DIFFUSE_ONLY, bool REGULAR = false>
 __global__ void __launch_bounds__(MSK_BLOCK)
 k_wavefront_h(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
-    typedef typename std::conditional<REGULAR, SceneTablesR, SceneTables>::type TB;
+    typedef tables_of<REGULAR> TB;
     MSK_WAVEFRONT_H_BODY
 }
-// the one scenes with a smooth `dielectric` run (see k_shade_gen_d)
-__global__ void __launch_bounds__(MSK_BLOCK)
-k_wavefront_h_d(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
-    typedef SceneTablesD TB;
-    constexpr bool DIFFUSE_ONLY = false;
-    MSK_WAVEFRONT_H_BODY
-}
-// the one scenes with a `bitmap` texture run (see k_shade_gen_b)
-__global__ void __launch_bounds__(MSK_BLOCK)
-k_wavefront_h_b(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
-    typedef SceneTablesB TB;
-    constexpr bool DIFFUSE_ONLY = false;
-    MSK_WAVEFRONT_H_BODY
-}
-// the one scenes with an `envmap` emitter run (see k_shade_gen_e)
-__global__ void __launch_bounds__(MSK_BLOCK)
-k_wavefront_h_e(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
-    typedef SceneTablesE TB;
-    constexpr bool DIFFUSE_ONLY = false;
-    MSK_WAVEFRONT_H_BODY
-}
-// the one scenes with a `point` emitter or a smooth `conductor` run (see k_shade_gen_p)
-__global__ void __launch_bounds__(MSK_BLOCK)
-k_wavefront_h_p(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
-    typedef SceneTablesP TB;
-    constexpr bool DIFFUSE_ONLY = false;
-    MSK_WAVEFRONT_H_BODY
-}
-// the one scenes with a `mask` run (see k_shade_gen_m)
-__global__ void __launch_bounds__(MSK_BLOCK)
-k_wavefront_h_m(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
-    typedef SceneTablesM TB;
-    constexpr bool DIFFUSE_ONLY = false;
-    MSK_WAVEFRONT_H_BODY
-}
-// the one scenes with a `thinlens` sensor run (see k_shade_gen_l)
-__global__ void __launch_bounds__(MSK_BLOCK)
-k_wavefront_h_l(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) {
-    typedef SceneTablesL TB;
-    constexpr bool DIFFUSE_ONLY = false;
-    MSK_WAVEFRONT_H_BODY
-}
+// k_wavefront_h_<suffix>: the one that the scenes of a family run (see k_shade_gen_<suffix>)
+#define MSK_STAMP(S, TABLES, KIND, SHADE, SERIAL)                                                                              \
+    __global__ void __launch_bounds__(MSK_BLOCK)                                                                               \
+    k_wavefront_h_##S(DeviceScene sc, PathState st, PassParams pp, uint32_t max_iters, uint32_t queue_f4, uint32_t trace_f4) { \
+        typedef TABLES TB;                                                                                                     \
+        constexpr bool DIFFUSE_ONLY = false;                                                                                   \
+        MSK_WAVEFRONT_H_BODY                                                                                                   \
+    }
+MSK_FAMILIES(MSK_STAMP)
+#undef MSK_STAMP
 #undef MSK_WAVEFRONT_H_BODY
 
 // msk_gpu_eval_texture: the value of the texture whose record sits at float4 offset `rec` of the BSDF table, at n given uv and

@@ -299,8 +299,17 @@ struct LaunchPlan {
     uint32_t sync_group = 8, timing_every = 1;
 };
 
+// The shading family a scene runs, whatever the call: the first feature it holds in the order lens, mask, delta, envmap, bitmap,
+// dielectric — each family's kernels carry everything the later ones' do.  SHADE_GENERAL: none of them; the wavefront path then
+// picks among the three base kinds per call (make_launch_plan), MSK_RNG_PCG_BLOCK runs k_path_serial.
+inline ShadeKind shade_family(const SceneFacts &sc) {
+    return sc.has_lens ? SHADE_LENS : sc.has_mask ? SHADE_MASK : sc.has_delta ? SHADE_DELTA : sc.has_envmap ? SHADE_ENVMAP : sc.has_bitmap ? SHADE_BITMAP :
+           sc.has_dielectric ? SHADE_DIELECTRIC : SHADE_GENERAL;
+}
+
 inline LaunchPlan make_launch_plan(const SceneFacts &sc, const CallFacts &call, const RenderKnobs &knobs) {
     LaunchPlan p;
+    const ShadeKind family = shade_family(sc);
     const bool aov_any = call.aov_rgb || call.aov_groups;
     // camera samples that miss the scene's bounds are finished where they are made (shade_region's regeneration) — unless a miss
     // is more than a record of zeros: an "aov" render's record groups and nested RGB record are written per sample by other code
@@ -308,9 +317,9 @@ inline LaunchPlan make_launch_plan(const SceneFacts &sc, const CallFacts &call, 
     // (MSK_FORCE_GENERAL_SHADE=1, measurements only: an all-diffuse scene through the general variant — what a per-class diffuse
     // instantiation could save a mixed scene's diffuse chunks)
     // (the AOV RGB record and the validity test over an "aov" render's record groups live in the general shading variant)
-    p.lds_tables = sc.lds_tables; p.regular = sc.has_regular; p.dielectric = sc.has_dielectric || sc.has_bitmap || sc.has_envmap || sc.has_delta || sc.has_mask || sc.has_lens;      // (the bitmap / envmap / delta / mask / lens instantiations carry the delta lobes)
+    p.lds_tables = sc.lds_tables; p.regular = sc.has_regular; p.dielectric = family != SHADE_GENERAL;      // (the bitmap / envmap / delta / mask / lens instantiations carry the delta lobes)
     p.diffuse_only = sc.all_diffuse && !aov_any && !knobs.force_general_shade;
-    p.shade_kind = sc.has_lens ? SHADE_LENS : sc.has_mask ? SHADE_MASK : sc.has_delta ? SHADE_DELTA : sc.has_envmap ? SHADE_ENVMAP : sc.has_bitmap ? SHADE_BITMAP : p.dielectric ? SHADE_DIELECTRIC : p.diffuse_only ? SHADE_DIFFUSE : p.regular ? SHADE_REGULAR : SHADE_GENERAL;
+    p.shade_kind = family != SHADE_GENERAL ? family : p.diffuse_only ? SHADE_DIFFUSE : p.regular ? SHADE_REGULAR : SHADE_GENERAL;
     // material-sorted shading (general variant): LDS for the permutation, 3 bytes per slot of a region and wave (MSK_SORT=0: off)
     const size_t sort_lds = kWavesPerBlock * 3 * call.region_size;
     p.sort_on = !p.diffuse_only && (!sc.all_diffuse || knobs.force_general_shade) && call.region_size <= 4096 && knobs.sort &&

@@ -64,6 +64,8 @@ MSK_DEV void serial_put(const DeviceScene &sc, float *data, int sx, int sy, int 
 
 // The kernel's body lives in msk_serial_body.inc and is included into each kernel: TB = SceneTablesR, or SceneTablesD for a scene
 // that holds a smooth `dielectric` (k_path_serial_d), which alone compiles the guard around next-event estimation.
+// One kernel per family of MSK_FAMILIES (msk_kernels.h) whose SERIAL field says YES, written by hand: an #include cannot be stamped from
+// a list, and through a function over TB the compiler lays all six out differently (EXPERIMENTS.md, "Name each shading family once").
 __global__ void __launch_bounds__(MSK_BLOCK)
 k_path_serial(DeviceScene sc, SerialParams prm) {
     typedef SceneTablesR TB;
