@@ -58,6 +58,8 @@ extern "C" {
 #define MSK_BSDF_ROUGHDIELECTRIC 2 /* "roughdielectric" bsdfs/roughdielectric.cpp:209 (GGX only) */
 #define MSK_BSDF_DIELECTRIC     3  /* "dielectric"     bsdfs/dielectric.cpp:105 (smooth interface: two delta lobes) */
 #define MSK_BSDF_CONDUCTOR      4  /* "conductor"      bsdfs/conductor.cpp (smooth metal: one delta reflection lobe; semantics at msk_bsdf_desc) */
+#define MSK_BSDF_PLASTIC        6  /* "plastic": a smooth dielectric coat (one delta reflection lobe) over a diffuse base; semantics at
+                                      msk_bsdf_desc.  Type 5 is unassigned and refused */
 #define MSK_EMITTER_AREA       0   /* "area"     emitters/area.cpp:61          */
 #define MSK_TEXTURE_CHECKERBOARD 1 /* "checkerboard" textures/checkerboard.cpp:52 */
 #define MSK_TEXTURE_BITMAP       2 /* "bitmap", bilinear filter (ABI v8; semantics below, at msk_texture_desc) */
@@ -164,6 +166,28 @@ typedef struct msk_spectrum_desc {
  * = its own index) it mirrors on both faces; one-sided (back_bsdf = -1) it is black from behind.  The reference's defaults,
  * which the flatteners write when a parameter is absent, are eta = 0, k = 1, specular_reflectance = 1 (uniform spectra): for them
  * fresnel_conductor is exactly 1.0f for every cos_i in (0, 1], a perfect mirror.
+ * MSK_BSDF_PLASTIC (bsdfs/roughplastic.cpp with a delta coat in the GGX coat's place; Mitsuba's `plastic`): a delta reflection lobe
+ * and a diffuse lobe, one of them picked per sample.  It reads the diffuse reflectance rho(l) exactly as MSK_BSDF_DIFFUSE does
+ * (reflectance, reflectance_scale, reflectance_texture, reflectance_regular), specular_reflectance = a constant spectrum s(l),
+ * ior_eta = int_ior / ext_ior and ior_inv_eta, sample_visible read as `nonlinear` (0, or anything else = 1) and back_bsdf; alpha_*,
+ * eta, k and specular_transmittance are ignored.  An ior_eta that is not finite or is below 1 is refused.  Two constants per entry
+ * are computed at scene creation, in double, and rounded to fp32 (msk_gpu_plastic_constants returns them):
+ *   fdr_int = 1 - (1 - fdr_ext) / ior_eta^2, fdr_ext = 2 * integral over mu in [0, 1] of F(mu; ior_eta) mu (Gauss-Legendre), F the
+ *             exact unpolarised dielectric Fresnel reflectance: the hemispherical reflectance seen from inside;
+ *   ssw     = s_mean / (d_mean + s_mean), the means of s(l) and of rho(l) over the 95 CIE sample wavelengths (a bitmap: over its
+ *             texels too; a checkerboard: over its two colours); 1 when both means are 0.  It moves variance only.
+ * fp32, one operation at a time, with wi on the front side: cos_i = wi.z, F_i = fresnel_dielectric(cos_i, ior_eta) (render/fresnel.h:37-63
+ * as msk_device.h has it), ps = F_i * ssw, pd = (1 - F_i) * (1 - ssw).  cos_i <= 0 or ps + pd == 0: the sample fails, eval and
+ * pdf are 0.  Otherwise ps = ps / (ps + pd), pd = 1 - ps, and D(l) = rho(l) / (1 - fdr_int * rho(l)) when nonlinear, else
+ * rho(l) / (1 - fdr_int).  sample: sample1 < ps takes the delta lobe, wo = (-wi.x, -wi.y, wi.z), pdf = ps, value(l) = s(l) * F_i / ps,
+ * eta = 1.  Otherwise the diffuse lobe: wo = square_to_cosine_hemisphere(u), F_o = fresnel_dielectric(wo.z, ior_eta), pdf =
+ * pd * wo.z / pi (as pd * (1 / pi * wo.z)), value(l) = D(l) * ior_inv_eta^2 * (1 - F_i) * (1 - F_o) / pd, and 0 when pdf <= 0; eta = 1.
+ * eval and pdf are the diffuse lobe's alone, for cos_i > 0 and cos_o > 0: eval(l) = D(l) * ior_inv_eta^2 * (1 - F_i) * (1 - F_o) *
+ * (1 / pi) * cos_o, pdf = pd * (1 / pi * cos_o).  The products run left to right as written, with f = ior_inv_eta * ior_inv_eta *
+ * (1 - F_i) * (1 - F_o) one scalar.  Integrator: a plastic hit always takes its next-event sample; when the sampled lobe is the
+ * delta one the emitter the ray reaches counts with emitter density 0, MIS weight 1 (path.cpp:104-106), as after a mask's null lobe.
+ * A scene that holds one runs the kernels a `mask` scene runs (every entry then has a mask record, the constant opacity 1 unless the
+ * scene gives it a mask), `mask` over it is allowed, and the "direct" integrator refuses it (MSK_ERR_UNSUPPORTED).
  * back_bsdf implements the "twosided" adapter (bsdfs/twosided.cpp:38-101): the BSDF evaluated with
  * flipped wi/wo when cos(theta_i) < 0; the entry's own index for twosided(A), -1 for a one-sided BSDF.
  * reflectance_texture: 0 = the diffuse reflectance is the constant `reflectance`; k > 0 = it is
@@ -710,6 +734,20 @@ int  msk_gpu_mask_sample(msk_scene *scene, uint32_t bsdf, uint64_t n, const floa
                          float *out_wo_pdf, float *out_value, float *out_flags);
 int  msk_gpu_mask_eval(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *wo, const float *wavelengths,
                        float *out_a_pdf, float *out_value);
+
+/*
+ * The same two probes on a MSK_BSDF_PLASTIC entry, in a scene with or without a mask (without one every entry has the constant opacity
+ * 1): arguments and outputs as msk_gpu_mask_sample / msk_gpu_mask_eval.  out_flags n * 4 = {eta, the sampled lobe was delta (1 / 0:
+ * the coat, or a mask's null lobe), null lobe (1 / 0), a direction was produced (1 / 0)}.  MSK_ERR_INVALID_ARG for an entry out of
+ * range or one that is not a plastic.
+ * msk_gpu_plastic_constants: out = {fdr_int, ssw}, the two constants the packer computed for the entry (msk_bsdf_desc), as the
+ * kernels read them.  No device work.
+ */
+int  msk_gpu_plastic_sample(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *sample1_u, const float *wavelengths,
+                            float *out_wo_pdf, float *out_value, float *out_flags);
+int  msk_gpu_plastic_eval(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *wo, const float *wavelengths,
+                          float *out_a_pdf, float *out_value);
+int  msk_gpu_plastic_constants(msk_scene *scene, uint32_t bsdf, float out[2]);
 
 /* ---- the "direct" integrator ----------------------------------------------- */
 /*

@@ -18,6 +18,7 @@ MSK_ERR_INVALID_ARG, MSK_ERR_NO_DEVICE, MSK_ERR_HIP, MSK_ERR_OOM, MSK_ERR_UNSUPP
 MSK_BSDF_DIFFUSE, MSK_BSDF_ROUGHCONDUCTOR, MSK_BSDF_ROUGHDIELECTRIC = 0, 1, 2
 MSK_BSDF_DIELECTRIC = 3       # "dielectric" (bsdfs/dielectric.cpp): smooth interface, two delta lobes
 MSK_BSDF_CONDUCTOR = 4        # "conductor": smooth metal, one delta reflection lobe
+MSK_BSDF_PLASTIC = 6          # "plastic": a delta dielectric coat over a diffuse base (type 5 is unassigned)
 MSK_EMITTER_AREA, MSK_EMITTER_CONSTANT = 0, 1
 MSK_EMITTER_ENVMAP = 2        # "envmap": a lat-long radiance image, importance-sampled (EnvmapDesc, msk_gpu_scene_create_env)
 MSK_EMITTER_POINT = 3         # "point": an isotropic delta light (PointDesc + SceneExt, msk_gpu_scene_create_ext)
@@ -184,6 +185,7 @@ EXPORTS = ["msk_gpu_init", "msk_gpu_shutdown", "msk_gpu_last_error", "msk_gpu_sc
            "msk_gpu_scene_create_masks", "msk_gpu_mask_sample", "msk_gpu_mask_eval",
            "msk_gpu_scene_create_lights", "msk_gpu_light_sample",
            "msk_gpu_scene_create_lens", "msk_gpu_camera_sample",
+           "msk_gpu_plastic_sample", "msk_gpu_plastic_eval", "msk_gpu_plastic_constants",
            "msk_gpu_render_direct", "msk_gpu_render_direct_device", "msk_gpu_sample_pixels_direct"]
 
 # integrators/aov.cpp:21-28
@@ -261,6 +263,12 @@ def load_library(path=None):
     lib.msk_gpu_mask_sample.restype = C.c_int
     lib.msk_gpu_mask_eval.argtypes = [vp, C.c_uint32, u64, vp, vp, vp, vp, vp, vp]
     lib.msk_gpu_mask_eval.restype = C.c_int
+    lib.msk_gpu_plastic_sample.argtypes = [vp, C.c_uint32, u64, vp, vp, vp, vp, vp, vp, vp]
+    lib.msk_gpu_plastic_sample.restype = C.c_int
+    lib.msk_gpu_plastic_eval.argtypes = [vp, C.c_uint32, u64, vp, vp, vp, vp, vp, vp]
+    lib.msk_gpu_plastic_eval.restype = C.c_int
+    lib.msk_gpu_plastic_constants.argtypes = [vp, C.c_uint32, C.POINTER(C.c_float * 2)]
+    lib.msk_gpu_plastic_constants.restype = C.c_int
     lib.msk_gpu_render_direct.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(DirectParams), vp, C.POINTER(Stats)]
     lib.msk_gpu_render_direct.restype = C.c_int
     lib.msk_gpu_render_direct_device.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(DirectParams), vp, vp, C.POINTER(Stats)]
@@ -530,7 +538,7 @@ class Scene:
         self.ctx.check(self.ctx.lib.msk_gpu_conductor_sample(self.handle, int(bsdf), len(c), _ptr(c), _ptr(wl), _ptr(val)))
         return val
 
-    def mask_sample(self, bsdf, uv, wi, sample1_u, wavelengths):
+    def mask_sample(self, bsdf, uv, wi, sample1_u, wavelengths, _entry="msk_gpu_mask_sample"):
         """sample() of the decorated BSDF entry `bsdf` of a scene that holds a mask: uv float32[n, 2], wi float32[n, 3] (local),
         sample1_u float32[n, 3] = {sample1, u.x, u.y}, wavelengths float32[n, 4] -> ({wo, pdf} float32[n, 4], value float32[n, 4],
         {eta, delta, null lobe, ok} float32[n, 4])."""
@@ -541,10 +549,10 @@ class Scene:
         if not (len(uv) == len(wi) == len(su) == len(wl)):
             raise ValueError("uv, wi, sample1_u and wavelengths must name the same number of points")
         a, b, c = (np.empty((len(uv), 4), np.float32) for _ in range(3))
-        self.ctx.check(self.ctx.lib.msk_gpu_mask_sample(self.handle, int(bsdf), len(uv), _ptr(uv), _ptr(wi), _ptr(su), _ptr(wl), _ptr(a), _ptr(b), _ptr(c)))
+        self.ctx.check(getattr(self.ctx.lib, _entry)(self.handle, int(bsdf), len(uv), _ptr(uv), _ptr(wi), _ptr(su), _ptr(wl), _ptr(a), _ptr(b), _ptr(c)))
         return a, b, c
 
-    def mask_eval(self, bsdf, uv, wi, wo, wavelengths):
+    def mask_eval(self, bsdf, uv, wi, wo, wavelengths, _entry="msk_gpu_mask_eval"):
         """The opacity, eval() and pdf() of the decorated BSDF entry `bsdf`: uv float32[n, 2], wi / wo float32[n, 3] (local),
         wavelengths float32[n, 4] -> ({a, pdf} float32[n, 2], eval float32[n, 4])."""
         uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
@@ -554,8 +562,23 @@ class Scene:
         if not (len(uv) == len(wi) == len(wo) == len(wl)):
             raise ValueError("uv, wi, wo and wavelengths must name the same number of points")
         a, v = np.empty((len(uv), 2), np.float32), np.empty((len(uv), 4), np.float32)
-        self.ctx.check(self.ctx.lib.msk_gpu_mask_eval(self.handle, int(bsdf), len(uv), _ptr(uv), _ptr(wi), _ptr(wo), _ptr(wl), _ptr(a), _ptr(v)))
+        self.ctx.check(getattr(self.ctx.lib, _entry)(self.handle, int(bsdf), len(uv), _ptr(uv), _ptr(wi), _ptr(wo), _ptr(wl), _ptr(a), _ptr(v)))
         return a, v
+
+    def plastic_sample(self, bsdf, uv, wi, sample1_u, wavelengths):
+        """mask_sample on a `plastic` entry, in a scene with or without a mask; the flags' second word says that the sampled lobe was
+        delta (the coat, or a mask's null lobe)."""
+        return self.mask_sample(bsdf, uv, wi, sample1_u, wavelengths, _entry="msk_gpu_plastic_sample")
+
+    def plastic_eval(self, bsdf, uv, wi, wo, wavelengths):
+        """mask_eval on a `plastic` entry, in a scene with or without a mask."""
+        return self.mask_eval(bsdf, uv, wi, wo, wavelengths, _entry="msk_gpu_plastic_eval")
+
+    def plastic_constants(self, bsdf):
+        """(fdr_int, ssw) of the `plastic` entry `bsdf` as the packer computed them, float32."""
+        out = (C.c_float * 2)()
+        self.ctx.check(self.ctx.lib.msk_gpu_plastic_constants(self.handle, int(bsdf), C.byref(out)))
+        return np.float32(out[0]), np.float32(out[1])
 
     def close(self):
         if self.handle:

@@ -118,6 +118,7 @@ struct msk_scene {
     mskplan::SceneFacts facts;         // what the scene holds, which tree the traversal kernels walk and where tree and tables live: decided once, at
                                        // creation (msk_scene_tables.h, msk_plan.h), and all a render's launch plan needs to know of the scene
     std::vector<int32_t> emitter_types, bsdf_types;      // msk_gpu_point_sample / msk_gpu_conductor_sample check their index against these
+    std::vector<float> plastic_constants;                // {fdr_int, ssw} per BSDF entry of a scene that holds a plastic (msk_gpu_plastic_constants)
     uint32_t n_textures = 0, tex_base = 0;      // msk_gpu_eval_texture: texture k's record sits at float4 tex_base + 3 k of `bsdfs`
     int bvh_depth = 0;
     uint32_t n_tris = 0;
@@ -391,6 +392,10 @@ extern "C" int msk_gpu_scene_create_lens(msk_ctx *ctx, const msk_scene_desc *d, 
     std::unique_ptr<msk_scene> s(new msk_scene());
     s->ctx = ctx; s->n_tris = d->n_faces;
     s->emitter_types = std::move(t.emitter_types); s->bsdf_types = std::move(t.bsdf_types);
+    if (t.has_plastic) {                                   // msk_gpu_plastic_constants: words 5 and 6 of every BSDF record
+        s->plastic_constants.resize((size_t) d->n_bsdfs * 2);
+        for (uint32_t b = 0; b < d->n_bsdfs; ++b) { s->plastic_constants[b * 2] = t.bsdfs[(size_t) b * 4 * MSK_BSDF_F4 + 5]; s->plastic_constants[b * 2 + 1] = t.bsdfs[(size_t) b * 4 * MSK_BSDF_F4 + 6]; }
+    }
     s->n_textures = t.n_textures; s->tex_base = t.tex_base;
     if (int rc = upload_tables(s.get(), t, gpu_build ? nullptr : &bvh, d->n_faces)) return rc;
     if (gpu_build) if (int rc = device_build_tree(s.get(), t, d, knobs, &bvh)) return rc;
@@ -419,7 +424,7 @@ extern "C" int msk_gpu_scene_create_lens(msk_ctx *ctx, const msk_scene_desc *d, 
     f.trace_mode = tree.trace_mode; f.lds_scene = tree.lds_scene; f.trace_lds_bytes = tree.trace_lds_bytes;
     f.lds_tables = tables.lds_tables; f.shade_lds_bytes = tables.shade_lds_bytes;
     f.all_diffuse = t.all_diffuse; f.has_regular = t.has_regular; f.has_dielectric = t.has_dielectric; f.has_bitmap = t.has_bitmap;
-    f.has_envmap = t.has_envmap; f.has_delta = t.has_delta; f.has_mask = t.has_mask; f.has_lens = lens != nullptr;
+    f.has_envmap = t.has_envmap; f.has_delta = t.has_delta; f.has_mask = t.has_mask; f.has_plastic = t.has_plastic; f.has_lens = lens != nullptr;
     f.cull_ok = cb.on && t.env_emitter < 0;
     if (f.trace_lds_bytes > ctx->prop.sharedMemPerBlock)
         return fail(ctx, MSK_ERR_UNSUPPORTED, "BVH depth %d needs %zu B of traversal stack per block", bvh.max_depth, tree.binary_stack_bytes);
@@ -1556,6 +1561,9 @@ static int check_direct(msk_scene *scene, const msk_render_params *prm, const ms
     if (scene->facts.has_mask)
         return fail(ctx, MSK_ERR_UNSUPPORTED, "%s: the scene holds a `mask` BSDF, which the \"direct\" integrator does not support "
                     "(a cutout would be a black hole in a one-bounce integrator; use \"path\")", who);
+    if (scene->facts.has_plastic)
+        return fail(ctx, MSK_ERR_UNSUPPORTED, "%s: the scene holds a `plastic` BSDF, which the \"direct\" integrator does not support "
+                    "(its kernel carries neither the coat's delta lobe nor the diffuse base under it; use \"path\")", who);
     if (prm->rng_mode == MSK_RNG_PCG_BLOCK)
         return fail(ctx, MSK_ERR_UNSUPPORTED, "%s: MSK_RNG_PCG_BLOCK is not supported by the \"direct\" integrator (it uses MSK_RNG_COUNTER)", who);
     if (d->light_samples > mskplan::kDirectMaxSamples)
@@ -1765,13 +1773,15 @@ extern "C" int msk_gpu_camera_sample(msk_scene *scene, uint64_t n, const float *
     return on_first_part(scene, [&](msk_scene *s) { return camera_probe(s, n, film_pos, aperture_u, out_rays); });
 }
 
-// msk_gpu_mask_sample (eval == 0: in_b = {sample1, u.x, u.y}, three outputs) / msk_gpu_mask_eval (in_b = wo; out_a = n * 2 {a, pdf}, no out_c)
+// msk_gpu_mask_sample (eval == 0: in_b = {sample1, u.x, u.y}, three outputs) / msk_gpu_mask_eval (in_b = wo; out_a = n * 2 {a, pdf}, no out_c);
+// msk_gpu_plastic_sample / msk_gpu_plastic_eval (plastic: the same kernel on an entry that must be a plastic, in a scene with or without a mask)
 static int mask_probe(msk_scene *scene, const char *who, uint32_t eval, uint32_t bsdf, uint64_t n, const float *uv, const float *in_a, const float *in_b,
-                      const float *wavelengths, float *out_a, float *out_b, float *out_c) {
+                      const float *wavelengths, float *out_a, float *out_b, float *out_c, bool plastic = false) {
     msk_ctx *ctx = scene->ctx;
     MSK_REFUSE_LOST(ctx);
-    if (!scene->facts.has_mask) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: the scene holds no mask", who);
+    if (!plastic && !scene->facts.has_mask) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: the scene holds no mask", who);
     if (bsdf >= scene->bsdf_types.size()) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: bsdf %u out of range (the scene has %zu)", who, bsdf, scene->bsdf_types.size());
+    if (plastic && scene->bsdf_types[bsdf] != MSK_BSDF_PLASTIC) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: bsdf %u is not a plastic of this scene", who, bsdf);
     std::vector<float> tmp(eval ? n * 4 : 0);           // eval: the kernel's float4 {a, pdf, 0, 0}, of which the caller gets two floats
     const int rc = run_probe(scene, "k_mask_probe", n, {{uv, n * 8}, {in_a, n * 12}, {in_b, n * 12}, {wavelengths, n * 16}},
                              {{eval ? tmp.data() : out_a, n * 16}, {out_b, n * 16}, {out_c, n * 16}}, [&](void *const *in, void *const *o, uint32_t grid) {
@@ -1793,4 +1803,26 @@ extern "C" int msk_gpu_mask_eval(msk_scene *scene, uint32_t bsdf, uint64_t n, co
     if (!scene || (n && (!uv || !wi || !wo || !wavelengths || !out_a_pdf || !out_value)))
         return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_mask_eval: NULL argument");
     return on_first_part(scene, [&](msk_scene *s) { return mask_probe(s, "msk_gpu_mask_eval", 1, bsdf, n, uv, wi, wo, wavelengths, out_a_pdf, out_value, nullptr); });
+}
+extern "C" int msk_gpu_plastic_sample(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *sample1_u, const float *wavelengths,
+                                      float *out_wo_pdf, float *out_value, float *out_flags) {
+    if (!scene || (n && (!uv || !wi || !sample1_u || !wavelengths || !out_wo_pdf || !out_value || !out_flags)))
+        return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_plastic_sample: NULL argument");
+    return on_first_part(scene, [&](msk_scene *s) { return mask_probe(s, "msk_gpu_plastic_sample", 0, bsdf, n, uv, wi, sample1_u, wavelengths, out_wo_pdf, out_value, out_flags, true); });
+}
+extern "C" int msk_gpu_plastic_eval(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *wo, const float *wavelengths,
+                                    float *out_a_pdf, float *out_value) {
+    if (!scene || (n && (!uv || !wi || !wo || !wavelengths || !out_a_pdf || !out_value)))
+        return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_plastic_eval: NULL argument");
+    return on_first_part(scene, [&](msk_scene *s) { return mask_probe(s, "msk_gpu_plastic_eval", 1, bsdf, n, uv, wi, wo, wavelengths, out_a_pdf, out_value, nullptr, true); });
+}
+// the packed {fdr_int, ssw} of a plastic entry: host memory, no device work
+extern "C" int msk_gpu_plastic_constants(msk_scene *scene, uint32_t bsdf, float out[2]) {
+    if (!scene || !out) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_plastic_constants: NULL argument");
+    return on_first_part(scene, [&](msk_scene *s) {
+        if (bsdf >= s->bsdf_types.size() || s->bsdf_types[bsdf] != MSK_BSDF_PLASTIC)
+            return fail(s->ctx, MSK_ERR_INVALID_ARG, "msk_gpu_plastic_constants: bsdf %u is not a plastic of this scene", bsdf);
+        out[0] = s->plastic_constants[(size_t) bsdf * 2]; out[1] = s->plastic_constants[(size_t) bsdf * 2 + 1];
+        return (int) MSK_OK;
+    });
 }

@@ -1952,6 +1952,54 @@ MSK_DEV spec conductor_sample(const TB &tb, const BsdfRec &b, f3 wi, spec wl, f3
     for (int i = 0; i < 4; ++i) F.v[i] = fresnel_conductor(cos_i, eta.v[i], kk.v[i]);
     return spectrum_eval(tb, b.spec, wl) * F;
 }
+// The smooth `plastic` (msk_gpu.h: MSK_BSDF_PLASTIC — the text these two functions follow, operation by operation): a delta coat over
+// a diffuse base, wi on the front side.  b.b.y = fdr_int, b.b.z = ssw (the packer's constants, msk_plastic_tables.h), b.b.w =
+// nonlinear; `refl` = rho at wl, evaluated by the caller as for the diffuse BSDF.  Only the SceneTablesM instantiations call them.
+// The two lobe probabilities; false: cos_i <= 0 or ps + pd == 0 (the sample fails, eval and pdf are 0)
+MSK_DEV bool plastic_lobes(const BsdfRec &b, float cos_i, float *F_i, float *ps, float *pd) {
+    if (cos_i <= 0.f) return false;
+    float ct, e_it, e_ti;
+    fresnel_dielectric(cos_i, b.ior.x, F_i, &ct, &e_it, &e_ti);
+    const float a = *F_i * b.b.z, d = (1.f - *F_i) * (1.f - b.b.z);
+    const float sum = a + d;
+    if (sum == 0.f) return false;
+    *ps = a / sum; *pd = 1.f - *ps;
+    return true;
+}
+// D(l) f with f = ior_inv_eta^2 (1 - F_i) (1 - F_o): the diffuse lobe's value before its cosine or its density
+MSK_DEV spec plastic_diffuse(const BsdfRec &b, spec refl, float F_i, float cos_o) {
+    float F_o, ct, e_it, e_ti;
+    fresnel_dielectric(cos_o, b.ior.x, &F_o, &ct, &e_it, &e_ti);
+    spec D;
+    if (__float_as_int(b.b.w)) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) D.v[i] = refl.v[i] / (1.f - b.b.y * refl.v[i]);
+    } else D = refl / (1.f - b.b.y);
+    const float f = b.ior.y * b.ior.y * (1.f - F_i) * (1.f - F_o);
+    return D * f;
+}
+MSK_DEV void plastic_eval_pdf(const BsdfRec &b, f3 wi, f3 wo, spec refl, spec *val, float *pdf) {
+    float F_i, ps, pd;
+    if (!(wo.z > 0.f) || !plastic_lobes(b, wi.z, &F_i, &ps, &pd)) return;
+    *val = plastic_diffuse(b, refl, F_i, wo.z) * MSK_INV_PI_F * wo.z;
+    *pdf = pd * (MSK_INV_PI_F * wo.z);
+}
+// *delta_lobe: the sampled lobe was the coat's (BSDFFlags::Delta of the sample, path.cpp:104-106)
+template <class TB>
+MSK_DEV spec plastic_sample(const TB &tb, const BsdfRec &b, f3 wi, float sample1, f2 sample, spec wl, spec refl, f3 *wo, float *pdf, bool *ok, bool *delta_lobe) {
+    float F_i, ps, pd;
+    if (!plastic_lobes(b, wi.z, &F_i, &ps, &pd)) return splat(0.f);
+    *ok = true;
+    if (sample1 < ps) {
+        *delta_lobe = true;
+        *wo = mk3(-wi.x, -wi.y, wi.z);
+        *pdf = ps;
+        return spectrum_eval(tb, b.spec, wl) * F_i / ps;
+    }
+    *wo = square_to_cosine_hemisphere(sample);
+    *pdf = pd * (MSK_INV_PI_F * wo->z);
+    return *pdf > 0.f ? plastic_diffuse(b, refl, F_i, wo->z) / pd : splat(0.f);
+}
 // BSDFFlags::Smooth (path.cpp:56): every lobe but the delta ones of `dielectric` and `conductor` takes a next-event sample
 template <class TB>
 MSK_DEV bool bsdf_is_delta(const BsdfRec &b) {
@@ -1971,6 +2019,7 @@ MSK_DEV void bsdf_eval_pdf(const TB &tb, const BsdfRec &b, f3 wi, f3 wo, spec wl
         }
         return;
     }
+    if (tb_traits<TB>::mask && __float_as_int(b.a.x) == MSK_BSDF_PLASTIC) { plastic_eval_pdf(b, wi, wo, refl, val, pdf); return; }
     if (__float_as_int(b.a.x) == MSK_BSDF_ROUGHDIELECTRIC) { roughdielectric_eval_pdf(tb, b, wi, wo, wl, val, pdf); return; }
     if (tb_traits<TB>::dielectric && __float_as_int(b.a.x) == MSK_BSDF_DIELECTRIC) return;      // dielectric.cpp:74-82: zero
     if (tb_traits<TB>::delta && __float_as_int(b.a.x) == MSK_BSDF_CONDUCTOR) return;            // the mirror likewise
@@ -2028,6 +2077,20 @@ MSK_DEV spec bsdf_sample(const TB &tb, const BsdfRec &b, f3 wi, float sample1, f
 #pragma unroll
     for (int i = 0; i < 4; ++i) F.v[i] = fresnel_conductor(c, eta.v[i], kk.v[i]);
     return F * weight;
+}
+
+// The same from the mask level up, where a BSDF with a smooth lobe can sample a delta one (the plastic's coat): *delta_lobe says
+// that it did (BSDFFlags::Delta of the sample, path.cpp:104-106).  An overload, which only the mask level's code calls (behind
+// `if constexpr`), so that the levels below compile from the text above and to the instructions they had.
+template <bool DIFFUSE_ONLY, class TB>
+MSK_DEV spec bsdf_sample(const TB &tb, const BsdfRec &b, f3 wi, float sample1, f2 sample, spec wl, spec refl, f3 *wo, float *pdf, float *eta_out,
+                         bool *ok, bool *delta_lobe) {
+    *delta_lobe = false;
+    if (__float_as_int(b.a.x) == MSK_BSDF_PLASTIC) {
+        *wo = mk3(0.f, 0.f, 0.f); *pdf = 0.f; *ok = false; *eta_out = 1.f;
+        return plastic_sample(tb, b, wi, sample1, sample, wl, refl, wo, pdf, ok, delta_lobe);
+    }
+    return bsdf_sample<DIFFUSE_ONLY>(tb, b, wi, sample1, sample, wl, refl, wo, pdf, eta_out, ok);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2406,7 +2469,7 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
                 const uint32_t pb = 3 + 3 * (depth - 1);
                 spec refl = splat(0.f);                  // SmoothDiffuse::m_reflectance->eval(si) (diffuse.cpp:31,44): once per bounce
                 if (DIFFUSE_ONLY) refl = srgb_model_eval(bs.a.z, bs.a.w, bs.b.x, wl) * bs.ior.w;      // * reflectance_scale
-                else if (__float_as_int(bs.a.x) == 0) {
+                else if (__float_as_int(bs.a.x) == 0 || (tb_traits<TB>::mask && __float_as_int(bs.a.x) == MSK_BSDF_PLASTIC)) {      // (the plastic's base as the diffuse BSDF)
                     const uint32_t tex = __float_as_uint(bs.ior.z);
                     refl = reflectance_eval(tb, mk3(bs.a.z, bs.a.w, bs.b.x), bs.ior.w, tex, [&]() { return hit_uv(tb, hit); }, wl);
                 }
@@ -2521,8 +2584,13 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
                         bsdf_val = splat(1.f); bs_pdf = 1.f - opacity; bs_eta = 1.f; ok = true; wo_l = mk3(0.f, 0.f, 0.f);
                         delta_out = true;                                  // "the last bounce was delta"
                     } else {
+                        if constexpr (tb_traits<TB>::mask) {
+                            bool coat;                                     // a plastic sampled its delta coat: the two marks are combined with OR
+                            bsdf_val = bsdf_sample<DIFFUSE_ONLY>(tb, bs, wi_s, sample1, u2, wl, refl, &wo_l, &bs_pdf, &bs_eta, &ok, &coat);
+                            if (coat) delta_out = true;
+                            bs_pdf = opacity * bs_pdf; scattered = true;
+                        } else
                         bsdf_val = bsdf_sample<DIFFUSE_ONLY>(tb, bs, wi_s, sample1, u2, wl, refl, &wo_l, &bs_pdf, &bs_eta, &ok);
-                        if (tb_traits<TB>::mask) { bs_pdf = opacity * bs_pdf; scattered = true; }
                     }
                     if (!ok) {
                         // failed sample: zero direction, the reference's ray misses and the loop ends (path.cpp:89-97) — but the
@@ -3075,7 +3143,7 @@ k_mask_probe(DeviceScene sc, uint32_t eval, uint32_t bsdf, uint64_t n, const flo
         const int back = __float_as_int(bs.a.y);
         if (back >= 0 && wi.z < 0.f) { wi.z = -wi.z; flipped = true; if (back != (int) bsdf) bs = load_bsdf(tb, back); }
         spec refl = splat(0.f);
-        if (__float_as_int(bs.a.x) == 0) refl = reflectance_eval(tb, mk3(bs.a.z, bs.a.w, bs.b.x), bs.ior.w, __float_as_uint(bs.ior.z), [&]() { return t; }, w);
+        if (__float_as_int(bs.a.x) == 0 || __float_as_int(bs.a.x) == MSK_BSDF_PLASTIC) refl = reflectance_eval(tb, mk3(bs.a.z, bs.a.w, bs.b.x), bs.ior.w, __float_as_uint(bs.ior.z), [&]() { return t; }, w);
         if (eval) {
             f3 wo = mk3(in_b[i * 3], in_b[i * 3 + 1], in_b[i * 3 + 2]);
             if (flipped) wo.z = -wo.z;
@@ -3092,7 +3160,9 @@ k_mask_probe(DeviceScene sc, uint32_t eval, uint32_t bsdf, uint64_t n, const flo
                 v = splat(1.f); pdf = 1.f - a; eta = 1.f; ok = true; delta = true;
                 wo = mk3(-in_a[i * 3], -in_a[i * 3 + 1], -in_a[i * 3 + 2]);
             } else {
-                v = bsdf_sample<false>(tb, bs, wi, in_b[i * 3], u, w, refl, &wo, &pdf, &eta, &ok);
+                bool coat;
+                v = bsdf_sample<false>(tb, bs, wi, in_b[i * 3], u, w, refl, &wo, &pdf, &eta, &ok, &coat);
+                if (coat) delta = true;
                 pdf = a * pdf;
                 if (flipped) wo.z = -wo.z;
             }

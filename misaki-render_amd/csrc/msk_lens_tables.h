@@ -24,11 +24,8 @@ inline int check_lens(const msk_lens_desc *lens, std::string *msg) {
 // the tables of a scene with a lens, from those pack() made for the same scene without one
 inline void add_lens_tables(const msk_scene_desc *d, HostTables *t) {
     t->all_diffuse = false;          // the lens kernels are instantiations of the general shading variant
-    if (t->has_mask) return;         // the records are there
-    t->mask_base = t->n_bsdf_f4;
-    t->n_bsdf_f4 += 3u * d->n_bsdfs;
-    t->bsdfs.resize((size_t) t->n_bsdf_f4 * 4, 0.f);
-    for (uint32_t b = 0; b < d->n_bsdfs; ++b) t->bsdfs[((size_t) t->mask_base + 3u * b + 1u) * 4 + 1] = 1.f;      // {filter 0 = constant, opacity 1}
+    if (t->has_mask || t->has_plastic) return;         // the records are there
+    add_unit_mask_records(d->n_bsdfs, t->bsdfs, t->n_bsdf_f4, t->mask_base);      // {filter 0 = constant, opacity 1} (msk_plastic_tables.h)
 }
 
 }  // namespace mskscene

@@ -159,6 +159,8 @@ struct SceneFacts {
                                   // delta light, the mirror lobe and the `constant` sky's own density run, whatever else the scene holds
     bool has_mask = false;        // a `mask` (msk_mask_desc): the instantiations with the opacity lookup, the null lobe and the `scattered` bit run,
                                   // whatever else the scene holds
+    bool has_plastic = false;     // a `plastic` (MSK_BSDF_PLASTIC): the same instantiations run (they carry its two lobes and the per-sample delta mark);
+                                  // the scene has mask records of opacity 1 where it holds no mask
     bool has_lens = false;        // a `thinlens` sensor (msk_lens_desc): the instantiations whose new camera samples start on the lens run, whatever
                                   // else the scene holds
     size_t trace_lds_bytes = 0, shade_lds_bytes = 0;
@@ -299,11 +301,11 @@ struct LaunchPlan {
     uint32_t sync_group = 8, timing_every = 1;
 };
 
-// The shading family a scene runs, whatever the call: the first feature it holds in the order lens, mask, delta, envmap, bitmap,
-// dielectric — each family's kernels carry everything the later ones' do.  SHADE_GENERAL: none of them; the wavefront path then
+// The shading family a scene runs, whatever the call: the first feature it holds in the order lens, mask (or plastic, which lives in
+// the mask family), delta, envmap, bitmap, dielectric — each family's kernels carry everything the later ones' do.  SHADE_GENERAL: none of them; the wavefront path then
 // picks among the three base kinds per call (make_launch_plan), MSK_RNG_PCG_BLOCK runs k_path_serial.
 inline ShadeKind shade_family(const SceneFacts &sc) {
-    return sc.has_lens ? SHADE_LENS : sc.has_mask ? SHADE_MASK : sc.has_delta ? SHADE_DELTA : sc.has_envmap ? SHADE_ENVMAP : sc.has_bitmap ? SHADE_BITMAP :
+    return sc.has_lens ? SHADE_LENS : (sc.has_mask || sc.has_plastic) ? SHADE_MASK : sc.has_delta ? SHADE_DELTA : sc.has_envmap ? SHADE_ENVMAP : sc.has_bitmap ? SHADE_BITMAP :
            sc.has_dielectric ? SHADE_DIELECTRIC : SHADE_GENERAL;
 }
 

@@ -21,6 +21,7 @@
 
 #include "msk_mask_tables.h"
 #include "msk_light_tables.h"
+#include "msk_plastic_tables.h"
 
 namespace mskscene {
 
@@ -45,6 +46,9 @@ struct HostTables {
     // has_mask_image: an opacity is an image, whose values lie behind everything else in `texels`.  Set by pack_masks()
     bool has_mask = false, has_mask_image = false;
     uint32_t mask_base = 0;
+    // a `plastic` (MSK_BSDF_PLASTIC, msk_plastic_tables.h): the scene runs the kernels a mask scene runs, and has the mask records whether
+    // it holds a mask or not (has_mask says whether it holds one)
+    bool has_plastic = false;
 };
 
 static inline float h_dot(const float *a, const float *b) { return a[0] * b[0] + (a[1] * b[1] + a[2] * b[2]); }
@@ -97,11 +101,17 @@ struct Packer : HostTables {
         pack_env_radius();
         if (has_delta) all_diffuse = false;  // the delta light and the mirror live in instantiations of the general shading variant
         if (has_mask) all_diffuse = false;   // ... and the null lobe
+        if (has_plastic) all_diffuse = false;
         return MSK_OK;
     }
 
     // the mask records, behind the texture records in `bsdfs` (msk_mask_tables.h).  A scene without masks gets none: its tables are what they were.
-    int pack_masks() { return pack_mask_records(d, n_masks, masks, bsdfs, n_bsdf_f4, has_mask, has_mask_image, mask_base, mask_values, msg); }
+    // A scene with a plastic and no mask gets records of the constant opacity 1 (msk_plastic_tables.h).
+    int pack_masks() {
+        if (int rc = pack_mask_records(d, n_masks, masks, bsdfs, n_bsdf_f4, has_mask, has_mask_image, mask_base, mask_values, msg)) return rc;
+        if (has_plastic && !has_mask) add_unit_mask_records(d->n_bsdfs, bsdfs, n_bsdf_f4, mask_base);
+        return MSK_OK;
+    }
 
     int check_header() {
         if (d->abi_version != MSK_ABI_VERSION)
@@ -278,12 +288,13 @@ struct Packer : HostTables {
         for (uint32_t b = 0; b < d->n_bsdfs; ++b) {
             const msk_bsdf_desc &bd = d->bsdfs[b];
             if (bd.type != MSK_BSDF_DIFFUSE && bd.type != MSK_BSDF_ROUGHCONDUCTOR && bd.type != MSK_BSDF_ROUGHDIELECTRIC && bd.type != MSK_BSDF_DIELECTRIC &&
-                bd.type != MSK_BSDF_CONDUCTOR)
+                bd.type != MSK_BSDF_CONDUCTOR && bd.type != MSK_BSDF_PLASTIC)
                 return refuse(msg, MSK_ERR_UNSUPPORTED,
                               "bsdf %u: type %d is not supported by this back end (diffuse, roughconductor, roughdielectric, dielectric, conductor)", b, bd.type);
             if (bd.back_bsdf >= (int32_t) d->n_bsdfs || bd.back_bsdf < -1)
                 return refuse(msg, MSK_ERR_INVALID_ARG, "bsdf %u: back_bsdf %d out of range", b, bd.back_bsdf);
-            if (bd.type != MSK_BSDF_DIFFUSE && !(bd.alpha_u >= 0.f && bd.alpha_v >= 0.f))
+            const bool plastic = bd.type == MSK_BSDF_PLASTIC, has_rho = bd.type == MSK_BSDF_DIFFUSE || plastic;      // a plastic's base is the diffuse BSDF's reflectance
+            if (!has_rho && !(bd.alpha_u >= 0.f && bd.alpha_v >= 0.f))
                 return refuse(msg, MSK_ERR_INVALID_ARG, "bsdf %u: negative roughness", b);
             if ((bd.type == MSK_BSDF_ROUGHDIELECTRIC || bd.type == MSK_BSDF_DIELECTRIC) && !(bd.ior_eta > 0.f && bd.ior_inv_eta > 0.f))
                 return refuse(msg, MSK_ERR_INVALID_ARG, "bsdf %u: the relative index of refraction must be positive", b);
@@ -299,13 +310,14 @@ struct Packer : HostTables {
                 return refuse(msg, MSK_ERR_INVALID_ARG, "bsdf %u: type %d is not supported for a descriptor with a relative index of refraction (ior_eta %g, ior_inv_eta %g): "
                               "a conductor has none (1 / 1, or 0 / 0 = unset); its eta and k are spectra", b, bd.type, (double) bd.ior_eta, (double) bd.ior_inv_eta);
             if (bd.type == MSK_BSDF_CONDUCTOR) has_delta = true;
+            if (plastic) { if (int rc = check_plastic(bd, b, msg)) return rc; has_plastic = true; }
             if (bd.reflectance_texture > d->n_textures)
                 return refuse(msg, MSK_ERR_INVALID_ARG, "bsdf %u: reflectance_texture %u out of range", b, bd.reflectance_texture);
-            if (bd.type == MSK_BSDF_DIFFUSE && !bd.reflectance_regular && !(bd.reflectance_scale >= 0.f && bd.reflectance_scale < INFINITY))
+            if (has_rho && !bd.reflectance_regular && !(bd.reflectance_scale >= 0.f && bd.reflectance_scale < INFINITY))
                 return refuse(msg, MSK_ERR_INVALID_ARG, "bsdf %u: reflectance_scale must be finite and non-negative (1 for an srgb reflectance)", b);
-            if (bd.reflectance_texture && bd.type != MSK_BSDF_DIFFUSE)
+            if (bd.reflectance_texture && !has_rho)
                 return refuse(msg, MSK_ERR_UNSUPPORTED, "bsdf %u: only the diffuse reflectance can be textured", b);
-            if (bd.reflectance_regular && (bd.type != MSK_BSDF_DIFFUSE || bd.reflectance_texture))
+            if (bd.reflectance_regular && (!has_rho || bd.reflectance_texture))
                 return refuse(msg, MSK_ERR_INVALID_ARG, "bsdf %u: reflectance_regular names the reflectance of an untextured diffuse BSDF", b);
             if (bd.type != MSK_BSDF_DIFFUSE || bd.back_bsdf >= 0 || bd.reflectance_texture || bd.reflectance_regular) all_diffuse = false;
             // the device record, MSK_BSDF_F4 float4 (msk_kernels.h: BsdfRec): {type, back, r0, r1} {r2, au, av, sample_visible} eta k
@@ -314,7 +326,7 @@ struct Packer : HostTables {
             std::memcpy(&o[0], &bd.type, 4); std::memcpy(&o[1], &bd.back_bsdf, 4);
             msk_spectrum_desc refl;
             refl.coeff[0] = bd.reflectance[0]; refl.coeff[1] = bd.reflectance[1]; refl.coeff[2] = bd.reflectance[2];
-            refl.scale = bd.type == MSK_BSDF_DIFFUSE ? bd.reflectance_scale : 0.f; refl.regular = bd.reflectance_regular;
+            refl.scale = has_rho ? bd.reflectance_scale : 0.f; refl.regular = bd.reflectance_regular;
             float r4[4] = {};
             if ((rc_spec = spectrum_record(refl, r4, "reflectance", b))) return rc_spec;
             o[2] = r4[0]; o[3] = r4[1]; o[4] = r4[2];
@@ -326,6 +338,11 @@ struct Packer : HostTables {
             const uint32_t tex_off = bd.reflectance_texture ? std::max(1u, d->n_bsdfs) * MSK_BSDF_F4 + (bd.reflectance_texture - 1) * 3 : 0u;
             std::memcpy(&o[26], &tex_off, 4);
             o[27] = r4[3];                                             // reflectance_scale, or -1 for a tabulated reflectance
+            if (plastic) {                                             // {fdr_int, ssw} where the rough types keep alpha_u, alpha_v; `nonlinear` as 0 / 1
+                plastic_constants(d, bd, &o[5]);
+                const int32_t nonlinear = bd.sample_visible != 0 ? 1 : 0;
+                std::memcpy(&o[7], &nonlinear, 4);
+            }
         }
         return MSK_OK;
     }
@@ -517,7 +534,7 @@ inline void tag_classes(mskbvh::Built &bvh, const HostTables &t, const msk_scene
         std::memcpy(&w, &bvh.tris[k * 16 + 3], 4);
         std::memcpy(&mesh, &t.tv[(size_t) w * 12 + 3], 4);
         const int32_t b = t.mesh_info[(size_t) mesh * 4];
-        const uint32_t cls = (b >= 0 && (uint32_t) b < d->n_bsdfs) ? (uint32_t) d->bsdfs[b].type : 0u;      // MSK_BSDF_* = 0, 1, 2, 3 (and 4, the smooth conductor, with class 0)
+        const uint32_t cls = (b >= 0 && (uint32_t) b < d->n_bsdfs) ? (uint32_t) d->bsdfs[b].type : 0u;      // MSK_BSDF_* = 0, 1, 2, 3 (and 4, the smooth conductor, with class 0; 6, the plastic, with class 2: the classes only order the sort)
         w |= (cls & (MSK_N_CLASSES - 1u)) << MSK_CLASS_SHIFT;
         std::memcpy(&bvh.tris[k * 16 + 3], &w, 4);
     }

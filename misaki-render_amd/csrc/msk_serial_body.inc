@@ -81,7 +81,7 @@
                         res = res + thr * emitter_radiance(tb, si.emitter_id, wl);
                     if (depth >= prm.max_depth && prm.max_depth > 0) break;             // path.cpp:48-49
                     spec refl = splat(0.f);
-                    if (__float_as_int(bs.a.x) == 0) {
+                    if (__float_as_int(bs.a.x) == 0 || (tb_traits<TB>::mask && __float_as_int(bs.a.x) == MSK_BSDF_PLASTIC)) {      // (the plastic's base as the diffuse BSDF)
                         const uint32_t tex = __float_as_uint(bs.ior.z);
                         refl = reflectance_eval(tb, mk3(bs.a.z, bs.a.w, bs.b.x), bs.ior.w, tex, [&]() { return hit_uv(tb, hit); }, wl);
                     }
@@ -187,10 +187,13 @@
                     // a mask picks its lobe by u.x (mask.cpp:43-44): the nested BSDF with u.x / a, or the null lobe along the ray's own direction
                     const bool null_lobe = tb_traits<TB>::mask && !mask_pick_nested(opacity, &u2);
                     spec bsdf_val;
+                    bool coat = false;                                                 // a plastic sampled its delta coat (set only where tb_traits<TB>::mask)
                     if (tb_traits<TB>::mask && null_lobe) { bsdf_val = splat(1.f); bs_pdf = 1.f - opacity; bs_eta = 1.f; ok = true; wo_l = mk3(0.f, 0.f, 0.f); }
-                    else {
+                    else if constexpr (tb_traits<TB>::mask) {
+                        bsdf_val = bsdf_sample<false>(tb, bs, wi_s, sample1, u2, wl, refl, &wo_l, &bs_pdf, &bs_eta, &ok, &coat);
+                        bs_pdf = opacity * bs_pdf; scattered = true;
+                    } else {
                         bsdf_val = bsdf_sample<false>(tb, bs, wi_s, sample1, u2, wl, refl, &wo_l, &bs_pdf, &bs_eta, &ok);
-                        if (tb_traits<TB>::mask) { bs_pdf = opacity * bs_pdf; scattered = true; }
                     }
                     const bool hidden = tb_traits<TB>::mask && prm.hide_emitters && !scattered;      // path.cpp:92-93; DESIGN.md section 9, departure 8
                     f3 wo = mk3(0.f, 0.f, 0.f);
@@ -234,7 +237,7 @@
                     }
                     thr = thr * bsdf_val;                                              // path.cpp:99 (a failed sample: weight 0, pdf 0, eta 1)
                     eta *= bs_eta;                                                     // path.cpp:100
-                    if (delta || (tb_traits<TB>::mask && null_lobe)) emitter_pdf = 0.f;                                      // path.cpp:104-106: BSDFFlags::Delta
+                    if (delta || (tb_traits<TB>::mask && (null_lobe || coat))) emitter_pdf = 0.f;                                      // path.cpp:104-106: BSDFFlags::Delta
                     if (hit_emitter && !hidden) res = res + thr * value * mis_weight(bs_pdf, emitter_pdf);
                     hit = hit_b;
                     if (depth + 1 >= prm.rr_depth) {                                   // path.cpp:116-122

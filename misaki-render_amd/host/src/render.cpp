@@ -693,6 +693,68 @@ private:
 MSK_IMPLEMENT_CLASS(SmoothConductor, BSDF)
 MSK_REGISTER_INSTANCE(SmoothConductor, "conductor")
 
+// The smooth `plastic`: a delta dielectric coat over a diffuse base (include/msk_gpu.h at MSK_BSDF_PLASTIC; the reference's
+// bsdfs/roughplastic.cpp with the GGX coat made smooth).  diffuse_reflectance: an rgb, a spectrum or a texture that varies over
+// the surface, default 0.5; specular_reflectance: a constant spectrum or an rgb, default 1; int_ior 1.49, ext_ior 1.00028;
+// nonlinear false.  An absent or float-valued spectrum is a `uniform` one, so that the defaults are exact on the device.
+class SmoothPlastic final : public BSDF {
+public:
+    SmoothPlastic(const Properties &props) : BSDF(props) {
+        const float int_ior = props.float_("int_ior", 1.49f), ext_ior = props.float_("ext_ior", 1.00028f);
+        m_eta = int_ior / ext_ior; m_inv_eta = ext_ior / int_ior;
+        m_nonlinear = props.bool_("nonlinear", false);
+        m_diffuse_reflectance = spectrum(props, "diffuse_reflectance", 0.5f, false);
+        m_specular_reflectance = spectrum(props, "specular_reflectance", 1.f, true);
+    }
+    static ref<Texture> spectrum(const Properties &props, const std::string &name, float def, bool constant) {
+        if (props.has_property(name) && props.type(name) == Properties::Type::Object) {
+            ref<Texture> t = props.texture(name);
+            Texture::Flat f;
+            if (constant && (!t->flatten(f) || f.uses_d65))
+                Throw("plastic: \"{}\" must be a constant spectrum or an rgb (a texture that varies over the surface is not supported)", name);
+            return t;
+        }
+        if (props.has_property(name) && props.type(name) == Properties::Type::Color) {
+            Properties p(constant ? "srgb_unbounded" : "srgb");
+            p.set_color("color", props.color(name));
+            return InstanceManager::get()->create_instance<Texture>(p);
+        }
+        Properties p("uniform");
+        p.set_float("value", props.float_(name, def));
+        return InstanceManager::get()->create_instance<Texture>(p);
+    }
+    bool flatten(msk_bsdf_desc &out, FlatTables &tables) const override {
+        Texture::Flat f, s;
+        msk_texture_desc td;
+        if (!m_specular_reflectance->flatten(s) || s.uses_d65) return false;
+        init_bsdf_desc(out);
+        out.type = MSK_BSDF_PLASTIC;
+        out.ior_eta = m_eta; out.ior_inv_eta = m_inv_eta;
+        out.sample_visible = m_nonlinear ? 1 : 0;
+        if (m_diffuse_reflectance->flatten(f) && f.regular) {
+            out.reflectance_regular = tables.add_regular(f);
+        } else if (m_diffuse_reflectance->flatten(f) && !f.uses_d65) {
+            std::memcpy(out.reflectance, f.coeff, sizeof f.coeff);
+            out.reflectance_scale = f.scale;
+        } else if (m_diffuse_reflectance->flatten_texture(td, tables)) {
+            out.reflectance[0] = 0.f; out.reflectance[1] = 0.f; out.reflectance[2] = INFINITY;      // unused under a texture: the default's words
+            out.reflectance_scale = 0.5f;
+            tables.textures.push_back(td);
+            out.reflectance_texture = (uint32_t) tables.textures.size();
+        } else {
+            return false;
+        }
+        return tables.put(out.specular_reflectance, s);
+    }
+    MSK_DECLARE_CLASS()
+private:
+    ref<Texture> m_diffuse_reflectance, m_specular_reflectance;
+    float m_eta, m_inv_eta;
+    bool m_nonlinear;
+};
+MSK_IMPLEMENT_CLASS(SmoothPlastic, BSDF)
+MSK_REGISTER_INSTANCE(SmoothPlastic, "plastic")
+
 // bsdfs/twosided.cpp:12-36
 class TwoSidedBRDF final : public BSDF {
 public:

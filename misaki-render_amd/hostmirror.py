@@ -183,6 +183,9 @@ class MeshSpec:
         (the smooth interface; a scalar c = the `uniform` spectrum <spectrum value="c"/>), or
         {"type": "conductor", "eta": rgb | c (default 0), "k": rgb | c (default 1), "specular_reflectance": rgb | c (default 1),
          "twosided": bool} (the smooth conductor: a mirror), or
+        {"type": "plastic", "diffuse_reflectance": rgb | c (default 0.5) | a Regular | a checkerboard or bitmap texture as below,
+         "specular_reflectance": rgb | c (default 1), "int_ior": 1.49, "ext_ior": 1.00028, "nonlinear": bool (default False),
+         "twosided": bool} (a smooth dielectric coat over a diffuse base; the mesh's `reflectance` is not read), or
         {"type": "diffuse", "twosided": bool, "texture": {"type": "checkerboard", "color0": rgb, "color1": rgb,
          "scale": (sx, sy) | "matrix": 16 floats (the to_uv 4x4, row-major)}} (texture absent = `reflectance`), or the texture
         {"type": "bitmap", "pixels": float32 [H, W, 3] linear RGB (row 0 = texel row 0 = the image's top row),
@@ -359,6 +362,8 @@ def _bsdf_xml(m, v3, directory=None):
         if spec.get("twosided"):
             inner = ['<bsdf type="twosided">'] + ['    ' + b for b in inner] + ['</bsdf>']
         return ['        ' + b for b in inner]
+    if spec["type"] == "plastic":
+        return _plastic_xml(m, spec, v3, directory)
     body = []
     if spec["type"] not in ("dielectric", "conductor"):          # (the smooth BSDFs read no microfacet parameters)
         a = spec.get("alpha", 0.1)
@@ -382,6 +387,51 @@ def _bsdf_xml(m, v3, directory=None):
         if k in spec:
             body.append('<float name="%s" value="%r"/>' % (k, float(spec[k])))
     inner = ['<bsdf type="%s">' % spec["type"]] + ['    ' + b for b in body] + ['</bsdf>']
+    if spec.get("twosided"):
+        inner = ['<bsdf type="twosided">'] + ['    ' + b for b in inner] + ['</bsdf>']
+    return ['        ' + b for b in inner]
+
+
+def _texture_xml(name, tex, shape, v3, directory):
+    """A <texture name=...> element: a bitmap (its pixels go to <directory>/textures/<shape>.pfm) or a checkerboard"""
+    if tex["type"] == "bitmap":
+        os.makedirs(os.path.join(directory, "textures"), exist_ok=True)
+        write_pfm(os.path.join(directory, "textures", shape + ".pfm"), tex["pixels"])
+        return ['<texture name="%s" type="bitmap">' % name, '    <string name="filename" value="textures/%s.pfm"/>' % shape] + \
+               (['    <string name="filter_type" value="%s"/>' % tex["filter"]] if "filter" in tex else []) + _to_uv_xml(tex) + ['</texture>']
+    xf = '<scale x="%.9g" y="%.9g"/>' % tuple(tex["scale"]) if "scale" in tex else \
+         '<matrix value="%s"/>' % " ".join("%.9g" % float(np.float32(x)) for x in tex["matrix"])
+    return ['<texture name="%s" type="%s">' % (name, tex["type"]), '    <rgb name="color0" value="%s"/>' % v3(tex["color0"]),
+            '    <rgb name="color1" value="%s"/>' % v3(tex["color1"]), '    <transform name="to_uv">', '        ' + xf, '    </transform>', '</texture>']
+
+
+PLASTIC_SPECULAR = 'plastic: "specular_reflectance" must be a constant spectrum or an rgb (a texture that varies over the surface is not supported)'
+
+
+def _plastic_xml(m, spec, v3, directory):
+    """<bsdf type="plastic"> with the properties the spec names (an absent one takes the plugin's default)"""
+    body = []
+    if "diffuse_reflectance" in spec:
+        d = spec["diffuse_reflectance"]
+        if isinstance(d, dict):
+            body += _texture_xml("diffuse_reflectance", d, m.name, v3, directory)
+        else:
+            body.append('<spectrum name="diffuse_reflectance" value="%s"/>' % d.text if isinstance(d, Regular) else
+                        '<spectrum name="diffuse_reflectance" value="%.9g"/>' % float(d) if np.isscalar(d) else
+                        '<rgb name="diffuse_reflectance" value="%s"/>' % v3(d))
+    if "specular_reflectance" in spec:
+        sr = spec["specular_reflectance"]
+        if isinstance(sr, dict):
+            body += _texture_xml("specular_reflectance", sr, m.name + "_specular", v3, directory)
+        else:
+            body.append('<spectrum name="specular_reflectance" value="%.9g"/>' % float(sr) if np.isscalar(sr) else
+                        '<rgb name="specular_reflectance" value="%s"/>' % v3(sr))
+    for k in ("int_ior", "ext_ior"):
+        if k in spec:
+            body.append('<float name="%s" value="%r"/>' % (k, float(spec[k])))
+    if "nonlinear" in spec:
+        body.append('<boolean name="nonlinear" value="%s"/>' % ("true" if spec["nonlinear"] else "false"))
+    inner = ['<bsdf type="plastic">'] + ['    ' + b for b in body] + ['</bsdf>']
     if spec.get("twosided"):
         inner = ['<bsdf type="twosided">'] + ['    ' + b for b in inner] + ['</bsdf>']
     return ['        ' + b for b in inner]
@@ -742,6 +792,29 @@ def _bsdf_desc(m, fetch, index, textures=None, pool=None, texels=None):
             if isinstance(v, dict):
                 raise ValueError('conductor: "%s" must be a constant spectrum or an rgb (a texture that varies over the surface is not supported)' % key)
             setattr(b, key, spectrum_desc(v, fetch, pool))
+    elif spec["type"] == "plastic":
+        # msk_gpu.h, MSK_BSDF_PLASTIC: the base's reflectance where the diffuse BSDF keeps its own; defaults 0.5 and 1 as `uniform` spectra
+        b.type = abi.MSK_BSDF_PLASTIC
+        sr = spec.get("specular_reflectance", 1.0)
+        if isinstance(sr, dict):
+            raise ValueError(PLASTIC_SPECULAR)
+        d = spec.get("diffuse_reflectance", 0.5)
+        if isinstance(d, dict):
+            b.reflectance[:] = (0.0, 0.0, float("inf"))
+            b.reflectance_scale = 0.5
+            textures.append(_texture_desc(d, fetch, texels))
+            b.reflectance_texture = len(textures)
+        elif isinstance(d, Regular):
+            b.reflectance_regular = pool.add(d)
+        elif np.isscalar(d):
+            b.reflectance[:] = (0.0, 0.0, float("inf"))
+            b.reflectance_scale = float(np.float32(d))
+        else:
+            b.reflectance[:] = fetch(tuple(d))
+        b.specular_reflectance = spectrum_desc(sr, fetch, pool)
+        int_ior, ext_ior = np.float32(spec.get("int_ior", 1.49)), np.float32(spec.get("ext_ior", 1.00028))
+        b.ior_eta, b.ior_inv_eta = float(int_ior / ext_ior), float(ext_ior / int_ior)
+        b.sample_visible = int(bool(spec.get("nonlinear", False)))
     elif spec["type"] == "dielectric":
         # bsdfs/dielectric.cpp:14-20: m_eta = int_ior / ext_ior in fp32, defaults 1.49 / 1.00028; no microfacet parameters
         if spec.get("twosided"):
