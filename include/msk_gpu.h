@@ -60,6 +60,7 @@ extern "C" {
 #define MSK_BSDF_CONDUCTOR      4  /* "conductor"      bsdfs/conductor.cpp (smooth metal: one delta reflection lobe; semantics at msk_bsdf_desc) */
 #define MSK_BSDF_PLASTIC        6  /* "plastic": a smooth dielectric coat (one delta reflection lobe) over a diffuse base; semantics at
                                       msk_bsdf_desc.  Type 5 is unassigned and refused */
+#define MSK_BSDF_ROUGHPLASTIC   7  /* "roughplastic": the plastic with a rough (GGX) coat in the delta one's place; semantics at msk_bsdf_desc */
 #define MSK_EMITTER_AREA       0   /* "area"     emitters/area.cpp:61          */
 #define MSK_TEXTURE_CHECKERBOARD 1 /* "checkerboard" textures/checkerboard.cpp:52 */
 #define MSK_TEXTURE_BITMAP       2 /* "bitmap", bilinear filter (ABI v8; semantics below, at msk_texture_desc) */
@@ -188,6 +189,24 @@ typedef struct msk_spectrum_desc {
  * delta one the emitter the ray reaches counts with emitter density 0, MIS weight 1 (path.cpp:104-106), as after a mask's null lobe.
  * A scene that holds one runs the kernels a `mask` scene runs (every entry then has a mask record, the constant opacity 1 unless the
  * scene gives it a mask), `mask` over it is allowed, and the "direct" integrator refuses it (MSK_ERR_UNSUPPORTED).
+ * MSK_BSDF_ROUGHPLASTIC (bsdfs/roughplastic.cpp, which is RGB-typed and not built: this text is the specification): the plastic with
+ * a GGX coat in the delta one's place, two smooth lobes.  It reads what MSK_BSDF_PLASTIC reads, with the same refusals and the same
+ * two constants fdr_int and ssw, and alpha_u: alpha_v must equal it ("anisotropic" coats are refused, MSK_ERR_INVALID_ARG, as
+ * roughplastic.cpp:23-25 does), a negative or non-finite alpha is refused, and a = max(alpha_u, 1e-4) is applied at use, as for the
+ * rough types.  sample_visible is read as `nonlinear`, as for the plastic.  Departure: there is no visible-normal variant.  The
+ * reference's MicrofacetDistribution::sample (render/microfacet.h:131-143) draws the normal from D(m) cos(theta_m) whatever the flag,
+ * while roughplastic.cpp:144-146 returns the visible-normal density under it, so that sample = eval / pdf is biased there; the
+ * reference's default is false (microfacet.h:53,90), for which the file is consistent, and that is what is built.
+ * fp32, one operation at a time, wi on the front side: cos_i = wi.z; F_i, ps, pd and their failure conditions exactly as for the
+ * plastic.  eval / pdf for cos_i > 0 and cos_o > 0 (0 otherwise, and where the plastic's lobes fail): H = normalized(wo + wi), D =
+ * distr_eval(H, a, a), G = smith_g1(wi, H, a, a) * smith_g1(wo, H, a, a), F_h = fresnel_dielectric(dot(wi, H), ior_eta), c =
+ * ((F_h * D) * G) / (4 * cos_i), base(l) = the plastic's eval(l), value(l) = s(l) * c + base(l); p_s = (D * H.z) / (4 * dot(wo, H)),
+ * 0 when D == 0; pdf = ps * p_s + pd * ((1 / pi) * cos_o).  sample: sample1 < ps draws m = sample_ggx(u, a, a, &pm) (the function
+ * the roughconductor calls) and wo = m * 2 * dot(wi, m) - wi; pm == 0 or wo.z <= 0: a direction was produced, value 0, pdf 0.
+ * Otherwise wo = square_to_cosine_hemisphere(u).  Then pdf = pdf(wi, wo), value = pdf > 0 ? eval(wi, wo) / pdf : 0
+ * (roughplastic.cpp:71-75); eta = 1; the sample is never delta.  Integrator: an ordinary smooth BSDF — every hit takes its next-event
+ * sample with this eval / pdf, an emitter the sampled ray reaches is weighted with the mixture pdf.  A scene that holds one runs
+ * the kernels a plastic scene runs, `mask` over it is allowed, and the "direct" integrator refuses it (MSK_ERR_UNSUPPORTED).
  * back_bsdf implements the "twosided" adapter (bsdfs/twosided.cpp:38-101): the BSDF evaluated with
  * flipped wi/wo when cos(theta_i) < 0; the entry's own index for twosided(A), -1 for a one-sided BSDF.
  * reflectance_texture: 0 = the diffuse reflectance is the constant `reflectance`; k > 0 = it is
@@ -748,6 +767,15 @@ int  msk_gpu_plastic_sample(msk_scene *scene, uint32_t bsdf, uint64_t n, const f
 int  msk_gpu_plastic_eval(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *wo, const float *wavelengths,
                           float *out_a_pdf, float *out_value);
 int  msk_gpu_plastic_constants(msk_scene *scene, uint32_t bsdf, float out[2]);
+/*
+ * The two probes on a MSK_BSDF_ROUGHPLASTIC entry: arguments and outputs as msk_gpu_plastic_sample / msk_gpu_plastic_eval (the delta
+ * flag is 0 unless a mask's null lobe was sampled).  MSK_ERR_INVALID_ARG for an entry out of range or one that is not a roughplastic.
+ * msk_gpu_plastic_constants answers for a roughplastic entry too.
+ */
+int  msk_gpu_roughplastic_sample(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *sample1_u, const float *wavelengths,
+                                 float *out_wo_pdf, float *out_value, float *out_flags);
+int  msk_gpu_roughplastic_eval(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *wo, const float *wavelengths,
+                               float *out_a_pdf, float *out_value);
 
 /* ---- the "direct" integrator ----------------------------------------------- */
 /*

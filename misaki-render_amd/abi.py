@@ -19,6 +19,7 @@ MSK_BSDF_DIFFUSE, MSK_BSDF_ROUGHCONDUCTOR, MSK_BSDF_ROUGHDIELECTRIC = 0, 1, 2
 MSK_BSDF_DIELECTRIC = 3       # "dielectric" (bsdfs/dielectric.cpp): smooth interface, two delta lobes
 MSK_BSDF_CONDUCTOR = 4        # "conductor": smooth metal, one delta reflection lobe
 MSK_BSDF_PLASTIC = 6          # "plastic": a delta dielectric coat over a diffuse base (type 5 is unassigned)
+MSK_BSDF_ROUGHPLASTIC = 7     # "roughplastic": the plastic with a GGX coat in the delta one's place
 MSK_EMITTER_AREA, MSK_EMITTER_CONSTANT = 0, 1
 MSK_EMITTER_ENVMAP = 2        # "envmap": a lat-long radiance image, importance-sampled (EnvmapDesc, msk_gpu_scene_create_env)
 MSK_EMITTER_POINT = 3         # "point": an isotropic delta light (PointDesc + SceneExt, msk_gpu_scene_create_ext)
@@ -186,6 +187,7 @@ EXPORTS = ["msk_gpu_init", "msk_gpu_shutdown", "msk_gpu_last_error", "msk_gpu_sc
            "msk_gpu_scene_create_lights", "msk_gpu_light_sample",
            "msk_gpu_scene_create_lens", "msk_gpu_camera_sample",
            "msk_gpu_plastic_sample", "msk_gpu_plastic_eval", "msk_gpu_plastic_constants",
+           "msk_gpu_roughplastic_sample", "msk_gpu_roughplastic_eval",
            "msk_gpu_render_direct", "msk_gpu_render_direct_device", "msk_gpu_sample_pixels_direct"]
 
 # integrators/aov.cpp:21-28
@@ -267,6 +269,10 @@ def load_library(path=None):
     lib.msk_gpu_plastic_sample.restype = C.c_int
     lib.msk_gpu_plastic_eval.argtypes = [vp, C.c_uint32, u64, vp, vp, vp, vp, vp, vp]
     lib.msk_gpu_plastic_eval.restype = C.c_int
+    lib.msk_gpu_roughplastic_sample.argtypes = [vp, C.c_uint32, u64, vp, vp, vp, vp, vp, vp, vp]
+    lib.msk_gpu_roughplastic_sample.restype = C.c_int
+    lib.msk_gpu_roughplastic_eval.argtypes = [vp, C.c_uint32, u64, vp, vp, vp, vp, vp, vp]
+    lib.msk_gpu_roughplastic_eval.restype = C.c_int
     lib.msk_gpu_plastic_constants.argtypes = [vp, C.c_uint32, C.POINTER(C.c_float * 2)]
     lib.msk_gpu_plastic_constants.restype = C.c_int
     lib.msk_gpu_render_direct.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(DirectParams), vp, C.POINTER(Stats)]
@@ -574,8 +580,16 @@ class Scene:
         """mask_eval on a `plastic` entry, in a scene with or without a mask."""
         return self.mask_eval(bsdf, uv, wi, wo, wavelengths, _entry="msk_gpu_plastic_eval")
 
+    def roughplastic_sample(self, bsdf, uv, wi, sample1_u, wavelengths):
+        """mask_sample on a `roughplastic` entry, in a scene with or without a mask."""
+        return self.mask_sample(bsdf, uv, wi, sample1_u, wavelengths, _entry="msk_gpu_roughplastic_sample")
+
+    def roughplastic_eval(self, bsdf, uv, wi, wo, wavelengths):
+        """mask_eval on a `roughplastic` entry, in a scene with or without a mask."""
+        return self.mask_eval(bsdf, uv, wi, wo, wavelengths, _entry="msk_gpu_roughplastic_eval")
+
     def plastic_constants(self, bsdf):
-        """(fdr_int, ssw) of the `plastic` entry `bsdf` as the packer computed them, float32."""
+        """(fdr_int, ssw) of the `plastic` or `roughplastic` entry `bsdf` as the packer computed them, float32."""
         out = (C.c_float * 2)()
         self.ctx.check(self.ctx.lib.msk_gpu_plastic_constants(self.handle, int(bsdf), C.byref(out)))
         return np.float32(out[0]), np.float32(out[1])

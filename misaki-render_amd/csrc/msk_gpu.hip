@@ -392,9 +392,12 @@ extern "C" int msk_gpu_scene_create_lens(msk_ctx *ctx, const msk_scene_desc *d, 
     std::unique_ptr<msk_scene> s(new msk_scene());
     s->ctx = ctx; s->n_tris = d->n_faces;
     s->emitter_types = std::move(t.emitter_types); s->bsdf_types = std::move(t.bsdf_types);
-    if (t.has_plastic) {                                   // msk_gpu_plastic_constants: words 5 and 6 of every BSDF record
+    if (t.has_plastic) {                                   // msk_gpu_plastic_constants: words 5 and 6 of every BSDF record (a roughplastic's: 20 and 21)
         s->plastic_constants.resize((size_t) d->n_bsdfs * 2);
-        for (uint32_t b = 0; b < d->n_bsdfs; ++b) { s->plastic_constants[b * 2] = t.bsdfs[(size_t) b * 4 * MSK_BSDF_F4 + 5]; s->plastic_constants[b * 2 + 1] = t.bsdfs[(size_t) b * 4 * MSK_BSDF_F4 + 6]; }
+        for (uint32_t b = 0; b < d->n_bsdfs; ++b) {
+            const float *o = &t.bsdfs[(size_t) b * 4 * MSK_BSDF_F4 + mskscene::plastic_constants_word(s->bsdf_types[b])];
+            s->plastic_constants[b * 2] = o[0]; s->plastic_constants[b * 2 + 1] = o[1];
+        }
     }
     s->n_textures = t.n_textures; s->tex_base = t.tex_base;
     if (int rc = upload_tables(s.get(), t, gpu_build ? nullptr : &bvh, d->n_faces)) return rc;
@@ -1561,9 +1564,14 @@ static int check_direct(msk_scene *scene, const msk_render_params *prm, const ms
     if (scene->facts.has_mask)
         return fail(ctx, MSK_ERR_UNSUPPORTED, "%s: the scene holds a `mask` BSDF, which the \"direct\" integrator does not support "
                     "(a cutout would be a black hole in a one-bounce integrator; use \"path\")", who);
-    if (scene->facts.has_plastic)
+    if (scene->facts.has_plastic) {
+        for (int32_t type : scene->bsdf_types)
+            if (type == MSK_BSDF_ROUGHPLASTIC)
+                return fail(ctx, MSK_ERR_UNSUPPORTED, "%s: the scene holds a `roughplastic` BSDF, which the \"direct\" integrator does not support "
+                            "(its kernel carries neither the GGX coat nor the diffuse base under it; use \"path\")", who);
         return fail(ctx, MSK_ERR_UNSUPPORTED, "%s: the scene holds a `plastic` BSDF, which the \"direct\" integrator does not support "
                     "(its kernel carries neither the coat's delta lobe nor the diffuse base under it; use \"path\")", who);
+    }
     if (prm->rng_mode == MSK_RNG_PCG_BLOCK)
         return fail(ctx, MSK_ERR_UNSUPPORTED, "%s: MSK_RNG_PCG_BLOCK is not supported by the \"direct\" integrator (it uses MSK_RNG_COUNTER)", who);
     if (d->light_samples > mskplan::kDirectMaxSamples)
@@ -1774,14 +1782,16 @@ extern "C" int msk_gpu_camera_sample(msk_scene *scene, uint64_t n, const float *
 }
 
 // msk_gpu_mask_sample (eval == 0: in_b = {sample1, u.x, u.y}, three outputs) / msk_gpu_mask_eval (in_b = wo; out_a = n * 2 {a, pdf}, no out_c);
-// msk_gpu_plastic_sample / msk_gpu_plastic_eval (plastic: the same kernel on an entry that must be a plastic, in a scene with or without a mask)
+// msk_gpu_plastic_sample / msk_gpu_plastic_eval and the roughplastic pair (plastic = MSK_BSDF_PLASTIC / MSK_BSDF_ROUGHPLASTIC: the same kernel on an entry that
+// must be of that type, in a scene with or without a mask)
 static int mask_probe(msk_scene *scene, const char *who, uint32_t eval, uint32_t bsdf, uint64_t n, const float *uv, const float *in_a, const float *in_b,
-                      const float *wavelengths, float *out_a, float *out_b, float *out_c, bool plastic = false) {
+                      const float *wavelengths, float *out_a, float *out_b, float *out_c, int plastic = 0) {
     msk_ctx *ctx = scene->ctx;
     MSK_REFUSE_LOST(ctx);
     if (!plastic && !scene->facts.has_mask) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: the scene holds no mask", who);
     if (bsdf >= scene->bsdf_types.size()) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: bsdf %u out of range (the scene has %zu)", who, bsdf, scene->bsdf_types.size());
-    if (plastic && scene->bsdf_types[bsdf] != MSK_BSDF_PLASTIC) return fail(ctx, MSK_ERR_INVALID_ARG, "%s: bsdf %u is not a plastic of this scene", who, bsdf);
+    if (plastic && scene->bsdf_types[bsdf] != plastic)
+        return fail(ctx, MSK_ERR_INVALID_ARG, "%s: bsdf %u is not a %s of this scene", who, bsdf, plastic == MSK_BSDF_ROUGHPLASTIC ? "roughplastic" : "plastic");
     std::vector<float> tmp(eval ? n * 4 : 0);           // eval: the kernel's float4 {a, pdf, 0, 0}, of which the caller gets two floats
     const int rc = run_probe(scene, "k_mask_probe", n, {{uv, n * 8}, {in_a, n * 12}, {in_b, n * 12}, {wavelengths, n * 16}},
                              {{eval ? tmp.data() : out_a, n * 16}, {out_b, n * 16}, {out_c, n * 16}}, [&](void *const *in, void *const *o, uint32_t grid) {
@@ -1808,19 +1818,31 @@ extern "C" int msk_gpu_plastic_sample(msk_scene *scene, uint32_t bsdf, uint64_t 
                                       float *out_wo_pdf, float *out_value, float *out_flags) {
     if (!scene || (n && (!uv || !wi || !sample1_u || !wavelengths || !out_wo_pdf || !out_value || !out_flags)))
         return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_plastic_sample: NULL argument");
-    return on_first_part(scene, [&](msk_scene *s) { return mask_probe(s, "msk_gpu_plastic_sample", 0, bsdf, n, uv, wi, sample1_u, wavelengths, out_wo_pdf, out_value, out_flags, true); });
+    return on_first_part(scene, [&](msk_scene *s) { return mask_probe(s, "msk_gpu_plastic_sample", 0, bsdf, n, uv, wi, sample1_u, wavelengths, out_wo_pdf, out_value, out_flags, MSK_BSDF_PLASTIC); });
 }
 extern "C" int msk_gpu_plastic_eval(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *wo, const float *wavelengths,
                                     float *out_a_pdf, float *out_value) {
     if (!scene || (n && (!uv || !wi || !wo || !wavelengths || !out_a_pdf || !out_value)))
         return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_plastic_eval: NULL argument");
-    return on_first_part(scene, [&](msk_scene *s) { return mask_probe(s, "msk_gpu_plastic_eval", 1, bsdf, n, uv, wi, wo, wavelengths, out_a_pdf, out_value, nullptr, true); });
+    return on_first_part(scene, [&](msk_scene *s) { return mask_probe(s, "msk_gpu_plastic_eval", 1, bsdf, n, uv, wi, wo, wavelengths, out_a_pdf, out_value, nullptr, MSK_BSDF_PLASTIC); });
 }
-// the packed {fdr_int, ssw} of a plastic entry: host memory, no device work
+extern "C" int msk_gpu_roughplastic_sample(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *sample1_u, const float *wavelengths,
+                                           float *out_wo_pdf, float *out_value, float *out_flags) {
+    if (!scene || (n && (!uv || !wi || !sample1_u || !wavelengths || !out_wo_pdf || !out_value || !out_flags)))
+        return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_roughplastic_sample: NULL argument");
+    return on_first_part(scene, [&](msk_scene *s) { return mask_probe(s, "msk_gpu_roughplastic_sample", 0, bsdf, n, uv, wi, sample1_u, wavelengths, out_wo_pdf, out_value, out_flags, MSK_BSDF_ROUGHPLASTIC); });
+}
+extern "C" int msk_gpu_roughplastic_eval(msk_scene *scene, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *wo, const float *wavelengths,
+                                         float *out_a_pdf, float *out_value) {
+    if (!scene || (n && (!uv || !wi || !wo || !wavelengths || !out_a_pdf || !out_value)))
+        return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_roughplastic_eval: NULL argument");
+    return on_first_part(scene, [&](msk_scene *s) { return mask_probe(s, "msk_gpu_roughplastic_eval", 1, bsdf, n, uv, wi, wo, wavelengths, out_a_pdf, out_value, nullptr, MSK_BSDF_ROUGHPLASTIC); });
+}
+// the packed {fdr_int, ssw} of a plastic or roughplastic entry: host memory, no device work
 extern "C" int msk_gpu_plastic_constants(msk_scene *scene, uint32_t bsdf, float out[2]) {
     if (!scene || !out) return fail(scene ? scene->ctx : nullptr, MSK_ERR_INVALID_ARG, "msk_gpu_plastic_constants: NULL argument");
     return on_first_part(scene, [&](msk_scene *s) {
-        if (bsdf >= s->bsdf_types.size() || s->bsdf_types[bsdf] != MSK_BSDF_PLASTIC)
+        if (bsdf >= s->bsdf_types.size() || (s->bsdf_types[bsdf] != MSK_BSDF_PLASTIC && s->bsdf_types[bsdf] != MSK_BSDF_ROUGHPLASTIC))
             return fail(s->ctx, MSK_ERR_INVALID_ARG, "msk_gpu_plastic_constants: bsdf %u is not a plastic of this scene", bsdf);
         out[0] = s->plastic_constants[(size_t) bsdf * 2]; out[1] = s->plastic_constants[(size_t) bsdf * 2 + 1];
         return (int) MSK_OK;

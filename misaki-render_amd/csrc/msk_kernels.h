@@ -2000,6 +2000,50 @@ MSK_DEV spec plastic_sample(const TB &tb, const BsdfRec &b, f3 wi, float sample1
     *pdf = pd * (MSK_INV_PI_F * wo->z);
     return *pdf > 0.f ? plastic_diffuse(b, refl, F_i, wo->z) / pd : splat(0.f);
 }
+// The `roughplastic` (msk_gpu.h: MSK_BSDF_ROUGHPLASTIC — the text these functions follow, operation by operation): the plastic with a
+// GGX coat in the delta one's place, two smooth lobes.  b.b.y = alpha, b.trans.x = fdr_int, b.trans.y = ssw (msk_plastic_tables.h), b.b.w =
+// nonlinear.  plastic_lobes and plastic_diffuse read the record as a plastic's: this is the record with the two constants where
+// those expect them.
+MSK_DEV BsdfRec roughplastic_as_plastic(const BsdfRec &b) {
+    BsdfRec p = b;
+    p.b.y = b.trans.x; p.b.z = b.trans.y;
+    return p;
+}
+template <class TB>
+MSK_DEV void roughplastic_eval_pdf(const TB &tb, const BsdfRec &b, f3 wi, f3 wo, spec wl, spec refl, spec *val, float *pdf) {
+    const float cos_i = wi.z, cos_o = wo.z;
+    const BsdfRec p = roughplastic_as_plastic(b);
+    float F_i, ps, pd;
+    if (!(cos_o > 0.f) || !plastic_lobes(p, cos_i, &F_i, &ps, &pd)) return;
+    const float a = clamp_alpha(b.b.y);
+    const f3 H = normalized(wo + wi);
+    const float D = distr_eval(H, a, a);
+    const float G = smith_g1(wi, H, a, a) * smith_g1(wo, H, a, a);
+    float F_h, ct, e_it, e_ti;
+    fresnel_dielectric(dot(wi, H), b.ior.x, &F_h, &ct, &e_it, &e_ti);
+    const float c = ((F_h * D) * G) / (4.f * cos_i);
+    const spec base = plastic_diffuse(p, refl, F_i, cos_o) * MSK_INV_PI_F * cos_o;
+    *val = spectrum_eval(tb, b.spec, wl) * c + base;
+    const float p_s = D == 0.f ? 0.f : (D * H.z) / (4.f * dot(wo, H));
+    *pdf = ps * p_s + pd * (MSK_INV_PI_F * cos_o);
+}
+// sample = eval / pdf of the two-lobe mixture (roughplastic.cpp:44-76); never delta, eta = 1
+template <class TB>
+MSK_DEV spec roughplastic_sample(const TB &tb, const BsdfRec &b, f3 wi, float sample1, f2 sample, spec wl, spec refl, f3 *wo, float *pdf, bool *ok) {
+    float F_i, ps, pd;
+    if (!plastic_lobes(roughplastic_as_plastic(b), wi.z, &F_i, &ps, &pd)) return splat(0.f);
+    *ok = true;
+    if (sample1 < ps) {
+        const float a = clamp_alpha(b.b.y);
+        float pm;
+        const f3 m = sample_ggx(sample, a, a, &pm);
+        *wo = m * 2.f * dot(wi, m) - wi;
+        if (pm == 0.f || wo->z <= 0.f) return splat(0.f);
+    } else *wo = square_to_cosine_hemisphere(sample);
+    spec val = splat(0.f);
+    roughplastic_eval_pdf(tb, b, wi, *wo, wl, refl, &val, pdf);
+    return *pdf > 0.f ? val / *pdf : splat(0.f);
+}
 // BSDFFlags::Smooth (path.cpp:56): every lobe but the delta ones of `dielectric` and `conductor` takes a next-event sample
 template <class TB>
 MSK_DEV bool bsdf_is_delta(const BsdfRec &b) {
@@ -2020,6 +2064,7 @@ MSK_DEV void bsdf_eval_pdf(const TB &tb, const BsdfRec &b, f3 wi, f3 wo, spec wl
         return;
     }
     if (tb_traits<TB>::mask && __float_as_int(b.a.x) == MSK_BSDF_PLASTIC) { plastic_eval_pdf(b, wi, wo, refl, val, pdf); return; }
+    if (tb_traits<TB>::mask && __float_as_int(b.a.x) == MSK_BSDF_ROUGHPLASTIC) { roughplastic_eval_pdf(tb, b, wi, wo, wl, refl, val, pdf); return; }
     if (__float_as_int(b.a.x) == MSK_BSDF_ROUGHDIELECTRIC) { roughdielectric_eval_pdf(tb, b, wi, wo, wl, val, pdf); return; }
     if (tb_traits<TB>::dielectric && __float_as_int(b.a.x) == MSK_BSDF_DIELECTRIC) return;      // dielectric.cpp:74-82: zero
     if (tb_traits<TB>::delta && __float_as_int(b.a.x) == MSK_BSDF_CONDUCTOR) return;            // the mirror likewise
@@ -2089,6 +2134,10 @@ MSK_DEV spec bsdf_sample(const TB &tb, const BsdfRec &b, f3 wi, float sample1, f
     if (__float_as_int(b.a.x) == MSK_BSDF_PLASTIC) {
         *wo = mk3(0.f, 0.f, 0.f); *pdf = 0.f; *ok = false; *eta_out = 1.f;
         return plastic_sample(tb, b, wi, sample1, sample, wl, refl, wo, pdf, ok, delta_lobe);
+    }
+    if (__float_as_int(b.a.x) == MSK_BSDF_ROUGHPLASTIC) {
+        *wo = mk3(0.f, 0.f, 0.f); *pdf = 0.f; *ok = false; *eta_out = 1.f;
+        return roughplastic_sample(tb, b, wi, sample1, sample, wl, refl, wo, pdf, ok);
     }
     return bsdf_sample<DIFFUSE_ONLY>(tb, b, wi, sample1, sample, wl, refl, wo, pdf, eta_out, ok);
 }
@@ -2469,7 +2518,7 @@ MSK_DEV RegionView shade_region(const DeviceScene &sc, const TB &tb, const DoneQ
                 const uint32_t pb = 3 + 3 * (depth - 1);
                 spec refl = splat(0.f);                  // SmoothDiffuse::m_reflectance->eval(si) (diffuse.cpp:31,44): once per bounce
                 if (DIFFUSE_ONLY) refl = srgb_model_eval(bs.a.z, bs.a.w, bs.b.x, wl) * bs.ior.w;      // * reflectance_scale
-                else if (__float_as_int(bs.a.x) == 0 || (tb_traits<TB>::mask && __float_as_int(bs.a.x) == MSK_BSDF_PLASTIC)) {      // (the plastic's base as the diffuse BSDF)
+                else if (__float_as_int(bs.a.x) == 0 || (tb_traits<TB>::mask && (__float_as_int(bs.a.x) == MSK_BSDF_PLASTIC || __float_as_int(bs.a.x) == MSK_BSDF_ROUGHPLASTIC))) {      // (a plastic's base as the diffuse BSDF)
                     const uint32_t tex = __float_as_uint(bs.ior.z);
                     refl = reflectance_eval(tb, mk3(bs.a.z, bs.a.w, bs.b.x), bs.ior.w, tex, [&]() { return hit_uv(tb, hit); }, wl);
                 }
@@ -3143,7 +3192,7 @@ k_mask_probe(DeviceScene sc, uint32_t eval, uint32_t bsdf, uint64_t n, const flo
         const int back = __float_as_int(bs.a.y);
         if (back >= 0 && wi.z < 0.f) { wi.z = -wi.z; flipped = true; if (back != (int) bsdf) bs = load_bsdf(tb, back); }
         spec refl = splat(0.f);
-        if (__float_as_int(bs.a.x) == 0 || __float_as_int(bs.a.x) == MSK_BSDF_PLASTIC) refl = reflectance_eval(tb, mk3(bs.a.z, bs.a.w, bs.b.x), bs.ior.w, __float_as_uint(bs.ior.z), [&]() { return t; }, w);
+        if (__float_as_int(bs.a.x) == 0 || __float_as_int(bs.a.x) == MSK_BSDF_PLASTIC || __float_as_int(bs.a.x) == MSK_BSDF_ROUGHPLASTIC) refl = reflectance_eval(tb, mk3(bs.a.z, bs.a.w, bs.b.x), bs.ior.w, __float_as_uint(bs.ior.z), [&]() { return t; }, w);
         if (eval) {
             f3 wo = mk3(in_b[i * 3], in_b[i * 3 + 1], in_b[i * 3 + 2]);
             if (flipped) wo.z = -wo.z;

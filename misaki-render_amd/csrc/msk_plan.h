@@ -159,7 +159,7 @@ struct SceneFacts {
                                   // delta light, the mirror lobe and the `constant` sky's own density run, whatever else the scene holds
     bool has_mask = false;        // a `mask` (msk_mask_desc): the instantiations with the opacity lookup, the null lobe and the `scattered` bit run,
                                   // whatever else the scene holds
-    bool has_plastic = false;     // a `plastic` (MSK_BSDF_PLASTIC): the same instantiations run (they carry its two lobes and the per-sample delta mark);
+    bool has_plastic = false;     // a `plastic` or a `roughplastic` (MSK_BSDF_PLASTIC, MSK_BSDF_ROUGHPLASTIC): the same instantiations run (they carry its two lobes and the per-sample delta mark);
                                   // the scene has mask records of opacity 1 where it holds no mask
     bool has_lens = false;        // a `thinlens` sensor (msk_lens_desc): the instantiations whose new camera samples start on the lens run, whatever
                                   // else the scene holds

@@ -6,6 +6,9 @@
 // A scene with a plastic runs the SceneTablesM instantiations, which carry the mask code: such a scene must have the mask records at the
 // end of `bsdfs`.  One that holds no mask gets them here, every entry the constant opacity 1, as a scene with a lens does
 // (msk_lens_tables.h).
+// A type-7 entry (MSK_BSDF_ROUGHPLASTIC) keeps alpha where the rough types keep alpha_u (word 5; word 6 = alpha_v, equal to it) and
+// `nonlinear` where type 6 keeps it (word 7); its two constants stand in the first two words of the specular_transmittance float4,
+// which the type does not read: word 20 = fdr_int, word 21 = ssw (msk_kernels.h: roughplastic_sample).  It sets has_plastic too.
 #pragma once
 #include "../../include/msk_gpu.h"
 
@@ -26,15 +29,30 @@ inline int refuse_plastic(std::string *msg, int code, const char *fmt, ...) {
     return code;
 }
 
-// what pack_bsdfs asks of a type-6 descriptor beyond what it asks of every type
-inline int check_plastic(const msk_bsdf_desc &bd, uint32_t b, std::string *msg) {
+// the words of the 28-float BSDF record that hold {fdr_int, ssw} (ssw follows fdr_int)
+constexpr uint32_t kPlasticConstantsWord = 5, kRoughPlasticConstantsWord = 20;
+inline uint32_t plastic_constants_word(int32_t type) { return type == MSK_BSDF_ROUGHPLASTIC ? kRoughPlasticConstantsWord : kPlasticConstantsWord; }
+
+// what pack_bsdfs asks of a type-6 descriptor beyond what it asks of every type (who: the type's name in the text)
+inline int check_plastic(const msk_bsdf_desc &bd, uint32_t b, std::string *msg, const char *who = "plastic") {
     if (!(std::isfinite(bd.ior_eta) && bd.ior_eta >= 1.f))
-        return refuse_plastic(msg, MSK_ERR_INVALID_ARG, "bsdf %u: plastic: the relative index of refraction ior_eta %g must be finite and at least 1 "
-                              "(int_ior / ext_ior of a coat denser than what surrounds it)", b, (double) bd.ior_eta);
+        return refuse_plastic(msg, MSK_ERR_INVALID_ARG, "bsdf %u: %s: the relative index of refraction ior_eta %g must be finite and at least 1 "
+                              "(int_ior / ext_ior of a coat denser than what surrounds it)", b, who, (double) bd.ior_eta);
     if (!(std::isfinite(bd.ior_inv_eta) && bd.ior_inv_eta > 0.f))
-        return refuse_plastic(msg, MSK_ERR_INVALID_ARG, "bsdf %u: plastic: ior_inv_eta %g must be finite and positive", b, (double) bd.ior_inv_eta);
+        return refuse_plastic(msg, MSK_ERR_INVALID_ARG, "bsdf %u: %s: ior_inv_eta %g must be finite and positive", b, who, (double) bd.ior_inv_eta);
     if (bd.specular_reflectance.regular == 0 && !std::isfinite(bd.specular_reflectance.scale))
-        return refuse_plastic(msg, MSK_ERR_INVALID_ARG, "bsdf %u: plastic: the scale of specular_reflectance must be finite", b);
+        return refuse_plastic(msg, MSK_ERR_INVALID_ARG, "bsdf %u: %s: the scale of specular_reflectance must be finite", b, who);
+    return MSK_OK;
+}
+// ... and of a type-7 one: type 6's checks, and one finite, non-negative roughness (roughplastic.cpp:23-25 refuses an anisotropic coat)
+inline int check_roughplastic(const msk_bsdf_desc &bd, uint32_t b, std::string *msg) {
+    if (int rc = check_plastic(bd, b, msg, "roughplastic")) return rc;
+    if (!(std::isfinite(bd.alpha_u) && std::isfinite(bd.alpha_v) && bd.alpha_u >= 0.f && bd.alpha_v >= 0.f))
+        return refuse_plastic(msg, MSK_ERR_INVALID_ARG, "bsdf %u: roughplastic: the roughness alpha (%g, %g) must be finite and non-negative", b,
+                              (double) bd.alpha_u, (double) bd.alpha_v);
+    if (bd.alpha_u != bd.alpha_v)
+        return refuse_plastic(msg, MSK_ERR_INVALID_ARG, "bsdf %u: roughplastic: alpha_u %g and alpha_v %g differ: anisotropic coats are not supported", b,
+                              (double) bd.alpha_u, (double) bd.alpha_v);
     return MSK_OK;
 }
 
@@ -130,7 +148,7 @@ inline double plastic_mean_reflectance(const msk_scene_desc *d, const msk_bsdf_d
     return s / (double) n;
 }
 
-// {fdr_int, ssw} of a type-6 entry, rounded to fp32
+// {fdr_int, ssw} of a type-6 or type-7 entry, rounded to fp32
 inline void plastic_constants(const msk_scene_desc *d, const msk_bsdf_desc &bd, float out[2]) {
     out[0] = (float) plastic_fdr_int((double) bd.ior_eta);
     const double s_mean = plastic_mean_spectrum(d, bd.specular_reflectance), d_mean = plastic_mean_reflectance(d, bd);

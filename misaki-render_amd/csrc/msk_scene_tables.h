@@ -46,7 +46,7 @@ struct HostTables {
     // has_mask_image: an opacity is an image, whose values lie behind everything else in `texels`.  Set by pack_masks()
     bool has_mask = false, has_mask_image = false;
     uint32_t mask_base = 0;
-    // a `plastic` (MSK_BSDF_PLASTIC, msk_plastic_tables.h): the scene runs the kernels a mask scene runs, and has the mask records whether
+    // a `plastic` or a `roughplastic` (MSK_BSDF_PLASTIC, MSK_BSDF_ROUGHPLASTIC, msk_plastic_tables.h): the scene runs the kernels a mask scene runs, and has the mask records whether
     // it holds a mask or not (has_mask says whether it holds one)
     bool has_plastic = false;
 };
@@ -288,12 +288,13 @@ struct Packer : HostTables {
         for (uint32_t b = 0; b < d->n_bsdfs; ++b) {
             const msk_bsdf_desc &bd = d->bsdfs[b];
             if (bd.type != MSK_BSDF_DIFFUSE && bd.type != MSK_BSDF_ROUGHCONDUCTOR && bd.type != MSK_BSDF_ROUGHDIELECTRIC && bd.type != MSK_BSDF_DIELECTRIC &&
-                bd.type != MSK_BSDF_CONDUCTOR && bd.type != MSK_BSDF_PLASTIC)
+                bd.type != MSK_BSDF_CONDUCTOR && bd.type != MSK_BSDF_PLASTIC && bd.type != MSK_BSDF_ROUGHPLASTIC)
                 return refuse(msg, MSK_ERR_UNSUPPORTED,
                               "bsdf %u: type %d is not supported by this back end (diffuse, roughconductor, roughdielectric, dielectric, conductor)", b, bd.type);
             if (bd.back_bsdf >= (int32_t) d->n_bsdfs || bd.back_bsdf < -1)
                 return refuse(msg, MSK_ERR_INVALID_ARG, "bsdf %u: back_bsdf %d out of range", b, bd.back_bsdf);
-            const bool plastic = bd.type == MSK_BSDF_PLASTIC, has_rho = bd.type == MSK_BSDF_DIFFUSE || plastic;      // a plastic's base is the diffuse BSDF's reflectance
+            const bool rough_coat = bd.type == MSK_BSDF_ROUGHPLASTIC, plastic = bd.type == MSK_BSDF_PLASTIC || rough_coat;
+            const bool has_rho = bd.type == MSK_BSDF_DIFFUSE || plastic;      // a plastic's base is the diffuse BSDF's reflectance
             if (!has_rho && !(bd.alpha_u >= 0.f && bd.alpha_v >= 0.f))
                 return refuse(msg, MSK_ERR_INVALID_ARG, "bsdf %u: negative roughness", b);
             if ((bd.type == MSK_BSDF_ROUGHDIELECTRIC || bd.type == MSK_BSDF_DIELECTRIC) && !(bd.ior_eta > 0.f && bd.ior_inv_eta > 0.f))
@@ -310,7 +311,7 @@ struct Packer : HostTables {
                 return refuse(msg, MSK_ERR_INVALID_ARG, "bsdf %u: type %d is not supported for a descriptor with a relative index of refraction (ior_eta %g, ior_inv_eta %g): "
                               "a conductor has none (1 / 1, or 0 / 0 = unset); its eta and k are spectra", b, bd.type, (double) bd.ior_eta, (double) bd.ior_inv_eta);
             if (bd.type == MSK_BSDF_CONDUCTOR) has_delta = true;
-            if (plastic) { if (int rc = check_plastic(bd, b, msg)) return rc; has_plastic = true; }
+            if (plastic) { if (int rc = rough_coat ? check_roughplastic(bd, b, msg) : check_plastic(bd, b, msg)) return rc; has_plastic = true; }
             if (bd.reflectance_texture > d->n_textures)
                 return refuse(msg, MSK_ERR_INVALID_ARG, "bsdf %u: reflectance_texture %u out of range", b, bd.reflectance_texture);
             if (has_rho && !bd.reflectance_regular && !(bd.reflectance_scale >= 0.f && bd.reflectance_scale < INFINITY))
@@ -338,8 +339,8 @@ struct Packer : HostTables {
             const uint32_t tex_off = bd.reflectance_texture ? std::max(1u, d->n_bsdfs) * MSK_BSDF_F4 + (bd.reflectance_texture - 1) * 3 : 0u;
             std::memcpy(&o[26], &tex_off, 4);
             o[27] = r4[3];                                             // reflectance_scale, or -1 for a tabulated reflectance
-            if (plastic) {                                             // {fdr_int, ssw} where the rough types keep alpha_u, alpha_v; `nonlinear` as 0 / 1
-                plastic_constants(d, bd, &o[5]);
+            if (plastic) {                                             // {fdr_int, ssw} where the rough types keep alpha_u, alpha_v (the roughplastic, which
+                plastic_constants(d, bd, &o[plastic_constants_word(bd.type)]);      // keeps its alpha there: in two words of `trans`); `nonlinear` as 0 / 1
                 const int32_t nonlinear = bd.sample_visible != 0 ? 1 : 0;
                 std::memcpy(&o[7], &nonlinear, 4);
             }
@@ -534,7 +535,7 @@ inline void tag_classes(mskbvh::Built &bvh, const HostTables &t, const msk_scene
         std::memcpy(&w, &bvh.tris[k * 16 + 3], 4);
         std::memcpy(&mesh, &t.tv[(size_t) w * 12 + 3], 4);
         const int32_t b = t.mesh_info[(size_t) mesh * 4];
-        const uint32_t cls = (b >= 0 && (uint32_t) b < d->n_bsdfs) ? (uint32_t) d->bsdfs[b].type : 0u;      // MSK_BSDF_* = 0, 1, 2, 3 (and 4, the smooth conductor, with class 0; 6, the plastic, with class 2: the classes only order the sort)
+        const uint32_t cls = (b >= 0 && (uint32_t) b < d->n_bsdfs) ? (uint32_t) d->bsdfs[b].type : 0u;      // MSK_BSDF_* = 0, 1, 2, 3 (and 4, the smooth conductor, with class 0; 6, the plastic, with class 2; 7, the roughplastic, with class 3: the classes only order the sort)
         w |= (cls & (MSK_N_CLASSES - 1u)) << MSK_CLASS_SHIFT;
         std::memcpy(&bvh.tris[k * 16 + 3], &w, 4);
     }

@@ -81,7 +81,7 @@
                         res = res + thr * emitter_radiance(tb, si.emitter_id, wl);
                     if (depth >= prm.max_depth && prm.max_depth > 0) break;             // path.cpp:48-49
                     spec refl = splat(0.f);
-                    if (__float_as_int(bs.a.x) == 0 || (tb_traits<TB>::mask && __float_as_int(bs.a.x) == MSK_BSDF_PLASTIC)) {      // (the plastic's base as the diffuse BSDF)
+                    if (__float_as_int(bs.a.x) == 0 || (tb_traits<TB>::mask && (__float_as_int(bs.a.x) == MSK_BSDF_PLASTIC || __float_as_int(bs.a.x) == MSK_BSDF_ROUGHPLASTIC))) {      // (a plastic's base as the diffuse BSDF)
                         const uint32_t tex = __float_as_uint(bs.ior.z);
                         refl = reflectance_eval(tb, mk3(bs.a.z, bs.a.w, bs.b.x), bs.ior.w, tex, [&]() { return hit_uv(tb, hit); }, wl);
                     }

@@ -697,21 +697,21 @@ MSK_REGISTER_INSTANCE(SmoothConductor, "conductor")
 // bsdfs/roughplastic.cpp with the GGX coat made smooth).  diffuse_reflectance: an rgb, a spectrum or a texture that varies over
 // the surface, default 0.5; specular_reflectance: a constant spectrum or an rgb, default 1; int_ior 1.49, ext_ior 1.00028;
 // nonlinear false.  An absent or float-valued spectrum is a `uniform` one, so that the defaults are exact on the device.
-class SmoothPlastic final : public BSDF {
+class SmoothPlastic : public BSDF {
 public:
-    SmoothPlastic(const Properties &props) : BSDF(props) {
+    SmoothPlastic(const Properties &props, const char *who = "plastic") : BSDF(props) {
         const float int_ior = props.float_("int_ior", 1.49f), ext_ior = props.float_("ext_ior", 1.00028f);
         m_eta = int_ior / ext_ior; m_inv_eta = ext_ior / int_ior;
         m_nonlinear = props.bool_("nonlinear", false);
-        m_diffuse_reflectance = spectrum(props, "diffuse_reflectance", 0.5f, false);
-        m_specular_reflectance = spectrum(props, "specular_reflectance", 1.f, true);
+        m_diffuse_reflectance = spectrum(props, "diffuse_reflectance", 0.5f, false, who);
+        m_specular_reflectance = spectrum(props, "specular_reflectance", 1.f, true, who);
     }
-    static ref<Texture> spectrum(const Properties &props, const std::string &name, float def, bool constant) {
+    static ref<Texture> spectrum(const Properties &props, const std::string &name, float def, bool constant, const char *who) {
         if (props.has_property(name) && props.type(name) == Properties::Type::Object) {
             ref<Texture> t = props.texture(name);
             Texture::Flat f;
             if (constant && (!t->flatten(f) || f.uses_d65))
-                Throw("plastic: \"{}\" must be a constant spectrum or an rgb (a texture that varies over the surface is not supported)", name);
+                Throw("{}: \"{}\" must be a constant spectrum or an rgb (a texture that varies over the surface is not supported)", who, name);
             return t;
         }
         if (props.has_property(name) && props.type(name) == Properties::Type::Color) {
@@ -754,6 +754,44 @@ private:
 };
 MSK_IMPLEMENT_CLASS(SmoothPlastic, BSDF)
 MSK_REGISTER_INSTANCE(SmoothPlastic, "plastic")
+
+// `roughplastic`: the plastic with a GGX coat (include/msk_gpu.h at MSK_BSDF_ROUGHPLASTIC; bsdfs/roughplastic.cpp:12-42).  The plastic's
+// properties, and alpha (default 0.1; alpha_u / alpha_v only when equal: roughplastic.cpp:23-25) and distribution (default "ggx",
+// the only one built).  sample_visible = true is refused: the header's departure.
+class RoughPlastic final : public SmoothPlastic {
+public:
+    RoughPlastic(const Properties &props) : SmoothPlastic(props, "roughplastic") {
+        const std::string distr = props.string("distribution", "ggx");
+        if (distr != "ggx") {
+            if (distr == "beckmann") Throw("roughplastic: the \"beckmann\" distribution is not implemented (use \"ggx\")");
+            Throw("Specified an invalid distribution \"{}\", must be \"beckmann\" or \"ggx\"!", distr);
+        }
+        if (props.bool_("sample_visible", false))
+            Throw("roughplastic: \"sample_visible\" = true is not supported: the reference draws the coat's normal from D(m) cos(theta_m) whatever the "
+                  "flag and returns the visible-normal density under it, which biases sample = eval / pdf");
+        if (props.has_property("alpha_u") || props.has_property("alpha_v")) {
+            if (!props.has_property("alpha_u") || !props.has_property("alpha_v"))
+                Throw("Microfacet model: both 'alpha_u' and 'alpha_v' must be specified.");
+            if (props.has_property("alpha")) Throw("Microfacet model: please specifyeither 'alpha' or 'alpha_u'/'alpha_v'.");
+            m_alpha = props.float_("alpha_u");
+            if (m_alpha != props.float_("alpha_v"))
+                Throw("roughplastic: \"alpha_u\" and \"alpha_v\" differ: anisotropic coats are not supported (give \"alpha\", or two equal values)");
+        } else {
+            m_alpha = props.float_("alpha", 0.1f);
+        }
+    }
+    bool flatten(msk_bsdf_desc &out, FlatTables &tables) const override {
+        if (!SmoothPlastic::flatten(out, tables)) return false;
+        out.type = MSK_BSDF_ROUGHPLASTIC;
+        out.alpha_u = out.alpha_v = m_alpha;
+        return true;
+    }
+    MSK_DECLARE_CLASS()
+private:
+    float m_alpha;
+};
+MSK_IMPLEMENT_CLASS(RoughPlastic, SmoothPlastic)
+MSK_REGISTER_INSTANCE(RoughPlastic, "roughplastic")
 
 // bsdfs/twosided.cpp:12-36
 class TwoSidedBRDF final : public BSDF {

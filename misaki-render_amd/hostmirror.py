@@ -186,6 +186,8 @@ class MeshSpec:
         {"type": "plastic", "diffuse_reflectance": rgb | c (default 0.5) | a Regular | a checkerboard or bitmap texture as below,
          "specular_reflectance": rgb | c (default 1), "int_ior": 1.49, "ext_ior": 1.00028, "nonlinear": bool (default False),
          "twosided": bool} (a smooth dielectric coat over a diffuse base; the mesh's `reflectance` is not read), or
+        {"type": "roughplastic", the plastic's keys, "alpha": a (default 0.1) | (au, av) with au == av, "distribution": "ggx"}
+         (the plastic with a GGX coat; "beckmann", unequal alphas and "sample_visible": True are refused), or
         {"type": "diffuse", "twosided": bool, "texture": {"type": "checkerboard", "color0": rgb, "color1": rgb,
          "scale": (sx, sy) | "matrix": 16 floats (the to_uv 4x4, row-major)}} (texture absent = `reflectance`), or the texture
         {"type": "bitmap", "pixels": float32 [H, W, 3] linear RGB (row 0 = texel row 0 = the image's top row),
@@ -362,7 +364,7 @@ def _bsdf_xml(m, v3, directory=None):
         if spec.get("twosided"):
             inner = ['<bsdf type="twosided">'] + ['    ' + b for b in inner] + ['</bsdf>']
         return ['        ' + b for b in inner]
-    if spec["type"] == "plastic":
+    if spec["type"] in ("plastic", "roughplastic"):
         return _plastic_xml(m, spec, v3, directory)
     body = []
     if spec["type"] not in ("dielectric", "conductor"):          # (the smooth BSDFs read no microfacet parameters)
@@ -406,10 +408,17 @@ def _texture_xml(name, tex, shape, v3, directory):
 
 
 PLASTIC_SPECULAR = 'plastic: "specular_reflectance" must be a constant spectrum or an rgb (a texture that varies over the surface is not supported)'
+# the `roughplastic` plugin's refusals, in the C++ host's words (host/src/render.cpp: RoughPlastic)
+ROUGHPLASTIC_SPECULAR = "rough" + PLASTIC_SPECULAR
+ROUGHPLASTIC_BECKMANN = 'roughplastic: the "beckmann" distribution is not implemented (use "ggx")'
+ROUGHPLASTIC_DISTRIBUTION = 'Specified an invalid distribution "%s", must be "beckmann" or "ggx"!'
+ROUGHPLASTIC_ANISOTROPIC = 'roughplastic: "alpha_u" and "alpha_v" differ: anisotropic coats are not supported (give "alpha", or two equal values)'
+ROUGHPLASTIC_VISIBLE = ('roughplastic: "sample_visible" = true is not supported: the reference draws the coat\'s normal from D(m) cos(theta_m) whatever the '
+                        'flag and returns the visible-normal density under it, which biases sample = eval / pdf')
 
 
 def _plastic_xml(m, spec, v3, directory):
-    """<bsdf type="plastic"> with the properties the spec names (an absent one takes the plugin's default)"""
+    """<bsdf type="plastic"> or <bsdf type="roughplastic"> with the properties the spec names (an absent one takes the plugin's default)"""
     body = []
     if "diffuse_reflectance" in spec:
         d = spec["diffuse_reflectance"]
@@ -431,7 +440,16 @@ def _plastic_xml(m, spec, v3, directory):
             body.append('<float name="%s" value="%r"/>' % (k, float(spec[k])))
     if "nonlinear" in spec:
         body.append('<boolean name="nonlinear" value="%s"/>' % ("true" if spec["nonlinear"] else "false"))
-    inner = ['<bsdf type="plastic">'] + ['    ' + b for b in body] + ['</bsdf>']
+    if spec["type"] == "roughplastic":
+        if "alpha" in spec:
+            a = spec["alpha"]
+            body += ['<float name="alpha" value="%r"/>' % float(a)] if np.isscalar(a) else \
+                    ['<float name="alpha_u" value="%r"/>' % float(a[0]), '<float name="alpha_v" value="%r"/>' % float(a[1])]
+        if "distribution" in spec:
+            body.append('<string name="distribution" value="%s"/>' % spec["distribution"])
+        if "sample_visible" in spec:
+            body.append('<boolean name="sample_visible" value="%s"/>' % ("true" if spec["sample_visible"] else "false"))
+    inner = ['<bsdf type="%s">' % spec["type"]] + ['    ' + b for b in body] + ['</bsdf>']
     if spec.get("twosided"):
         inner = ['<bsdf type="twosided">'] + ['    ' + b for b in inner] + ['</bsdf>']
     return ['        ' + b for b in inner]
@@ -792,12 +810,25 @@ def _bsdf_desc(m, fetch, index, textures=None, pool=None, texels=None):
             if isinstance(v, dict):
                 raise ValueError('conductor: "%s" must be a constant spectrum or an rgb (a texture that varies over the surface is not supported)' % key)
             setattr(b, key, spectrum_desc(v, fetch, pool))
-    elif spec["type"] == "plastic":
+    elif spec["type"] in ("plastic", "roughplastic"):
         # msk_gpu.h, MSK_BSDF_PLASTIC: the base's reflectance where the diffuse BSDF keeps its own; defaults 0.5 and 1 as `uniform` spectra
-        b.type = abi.MSK_BSDF_PLASTIC
+        # MSK_BSDF_ROUGHPLASTIC: the same and one alpha; the checks in the order of the C++ plugin's constructor
+        rough = spec["type"] == "roughplastic"
+        b.type = abi.MSK_BSDF_ROUGHPLASTIC if rough else abi.MSK_BSDF_PLASTIC
         sr = spec.get("specular_reflectance", 1.0)
         if isinstance(sr, dict):
-            raise ValueError(PLASTIC_SPECULAR)
+            raise ValueError(ROUGHPLASTIC_SPECULAR if rough else PLASTIC_SPECULAR)
+        if rough:
+            distr = spec.get("distribution", "ggx")
+            if distr != "ggx":
+                raise ValueError(ROUGHPLASTIC_BECKMANN if distr == "beckmann" else ROUGHPLASTIC_DISTRIBUTION % distr)
+            if spec.get("sample_visible", False):
+                raise ValueError(ROUGHPLASTIC_VISIBLE)
+            a = spec.get("alpha", 0.1)
+            au, av = (a, a) if np.isscalar(a) else a
+            if np.float32(au) != np.float32(av):
+                raise ValueError(ROUGHPLASTIC_ANISOTROPIC)
+            b.alpha_u = b.alpha_v = float(np.float32(au))
         d = spec.get("diffuse_reflectance", 0.5)
         if isinstance(d, dict):
             b.reflectance[:] = (0.0, 0.0, float("inf"))
