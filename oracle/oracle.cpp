@@ -88,6 +88,25 @@
  *   D16 (6)  mask: the nested lobe has X's value and the density a pdf_X (mask.cpp multiplies the value AND keeps the pdf).
  *   D17 (7)  mask: the opacity is a scalar.
  *   D18 (8)  mask: under hide_emitters an AREA emitter reached while `scattered` is false adds nothing.
+ *   `plastic` and `roughplastic` (types 6 and 7) are restated from the text of include/msk_gpu.h at msk_bsdf_desc (MSK_BSDF_PLASTIC,
+ *   MSK_BSDF_ROUGHPLASTIC) and from the tests' fp32 restatements (plastic_ref.py, roughplastic_ref.py), not from the device's code; the
+ *   reference's bsdfs/roughplastic.cpp is RGB-typed and not built, so the header's text is the specification:
+ *   D19      plastic: the coat is a delta lobe that sets kDelta per SAMPLE while the entry keeps its smooth lobe: every hit takes its
+ *            next-event sample (the diffuse lobe's eval / pdf alone), and an emitter or sky the mirrored ray reaches counts with
+ *            emitter density 0, weight exactly 1.
+ *   D20      the two constants fdr_int and ssw are computed here per entry, in double, by a rule of this file's own (plastic_fdr_int:
+ *            24-point Gauss-Legendre on dyadic panels towards mu = 0, where the integrand's nearest singularity lies for eta near 1;
+ *            the packer's is 64 points on four equal panels) and rounded once to fp32; csrc/msk_plastic_tables.h is not included.
+ *   D21      roughplastic: no visible-normal variant.  The sample_visible word is read as `nonlinear` for both types; the normal is
+ *            drawn from D(m) cos(theta_m) (sample_ggx) and the coat's density is (D H.z) / (4 dot(wo, H)), where roughplastic.cpp:144-146
+ *            returns the visible-normal density under the flag (biased there: tests/test_roughplastic_bsdf.py).
+ *   D22      a scene that holds a plastic of either type counts a `constant` sky with its own density (D15): it runs the kernels a
+ *            mask scene runs.  The `direct` integrator refuses such a scene.
+ *   D23      the next-event sample of the `spot` and `directional` emitters (msk_gpu.h at msk_light_desc; tests/light_ref.py), no more:
+ *            two closed forms of each plastic are lit by a sun, and the twin has to render them.  Delta lights like the point light
+ *            (D14: weight 1; D15: such a scene counts a `constant` sky with its own density); the refusals of msk_light_desc; a
+ *            scene whose spot or sun comes without its descriptor, or an emitter type this file does not know, is refused where it
+ *            ran the area light's code before.  Their parity scenes, tallies and the lens are a later step.
  */
 #include "oracle_math.h"
 #include "msk_gpu.h"
@@ -147,11 +166,19 @@ struct Scene {
     Envmap envmap;
     bool env_is_image = false;
     std::vector<V3> point_pos;             // msk_point_desc.position per emitter (MSK_EMITTER_POINT entries only)
+    // msk_light_desc per emitter (MSK_EMITTER_SPOT / MSK_EMITTER_DIRECTIONAL entries only; D23)
+    struct Light { V3 position, direction; float cos_cutoff = 0.f, cos_beam = 0.f; };
+    std::vector<Light> lights;
+    bool any_sun = false;
     // msk_mask_desc per BSDF entry (filter < 0: the entry has no mask)
     struct Mask { int filter = -1; float opacity = 1.f; float to_uv[6]; uint32_t W = 0, H = 0; std::vector<float> values; };
     std::vector<Mask> masks;
     bool any_mask = false;
-    bool own_density_sky = false;          // D15: a point emitter, a `conductor` entry or a mask is in the scene
+    bool own_density_sky = false;          // D15: a point emitter, a `conductor` entry, a mask or a plastic (D22) is in the scene
+    // D20: {fdr_int, ssw} per BSDF entry ({0, 0} for an entry that is no plastic)
+    struct PlasticK { float fdr_int = 0.f, ssw = 0.f; };
+    std::vector<PlasticK> plastic_k;
+    bool any_plastic = false;
 
     std::vector<BVHNode> nodes;
     std::vector<uint32_t> tri_order;
@@ -267,16 +294,134 @@ static bool is_rotation(const float *r) {
                        (double) r[2] * ((double) r[3] * r[7] - (double) r[4] * r[6]);
     return det > 0.0;
 }
+// ---------------------------------------------------------------------------
+// D20: the two constants of a `plastic` / `roughplastic` entry (msk_gpu.h at msk_bsdf_desc), in double, rounded once by the caller
+// ---------------------------------------------------------------------------
+// the exact unpolarised Fresnel reflectance of a dielectric boundary met from the thin side at cosine mu, relative index eta >= 1
+static double plastic_fresnel_exact(double mu, double eta) {
+    if (eta == 1.0) return 0.0;
+    const double sin2_t = (1.0 - mu * mu) / (eta * eta);              // Snell
+    const double cos_t = std::sqrt(1.0 - sin2_t);                      // eta >= 1: no total reflection from this side
+    const double rs = (mu - eta * cos_t) / (mu + eta * cos_t), rp = (eta * mu - cos_t) / (eta * mu + cos_t);
+    return 0.5 * (rs * rs + rp * rp);
+}
+// fdr_int = 1 - (1 - fdr_ext) / eta^2 with fdr_ext = 2 int_0^1 F(mu) mu dmu.  F is analytic on (0, 1] with branch points at
+// mu = +- i sqrt(eta^2 - 1), which approach mu = 0 as eta -> 1: the panels are [2^-(k+1), 2^-k], k = 0 .. 59, so that every panel
+// keeps the branch points at least its own length away (a 24-point rule then converges past 1e-16 per panel); what is left,
+// [0, 2^-60], holds less than 2^-120.
+static double plastic_fdr_int(double eta) {
+    if (eta == 1.0) return 0.0;
+    constexpr int N = 24;
+    static double node[N], weight[N];
+    static std::once_flag once;
+    std::call_once(once, [] {
+        const double pi = 3.14159265358979323846;
+        for (int i = 0; i < N; ++i) {                                  // the roots of the Legendre polynomial P_24 by Newton's iteration
+            double x = std::cos(pi * (i + 0.75) / (N + 0.5)), d = 1.0;
+            for (int it = 0; it < 64; ++it) {
+                double a = 1.0, b = x;
+                for (int k = 2; k <= N; ++k) { const double c = ((2 * k - 1) * x * b - (k - 1) * a) / k; a = b; b = c; }
+                d = N * (a - x * b) / (1.0 - x * x);
+                const double step = b / d;
+                x -= step;
+                if (std::fabs(step) < 1e-17) break;
+            }
+            double a = 1.0, b = x;
+            for (int k = 2; k <= N; ++k) { const double c = ((2 * k - 1) * x * b - (k - 1) * a) / k; a = b; b = c; }
+            d = N * (a - x * b) / (1.0 - x * x);
+            node[i] = x; weight[i] = 2.0 / ((1.0 - x * x) * d * d);
+        }
+    });
+    double total = 0.0;
+    for (int k = 59; k >= 0; --k) {                                    // the small panels first
+        const double lo = std::ldexp(1.0, -(k + 1)), half = 0.5 * lo;  // [lo, 2 lo]
+        double panel = 0.0;
+        for (int i = 0; i < N; ++i) {
+            const double mu = lo + half * (node[i] + 1.0);
+            panel += weight[i] * plastic_fresnel_exact(mu, eta) * mu;
+        }
+        total += half * panel;
+    }
+    return 1.0 - (1.0 - 2.0 * total) / (eta * eta);
+}
+// the sigmoid polynomial S(coeff, l) of render/srgb.h:8-19 in double ({0, 0, +-inf}: the constants 1 and 0)
+static double plastic_sigmoid(const float *c, double l) {
+    if (std::isinf(c[2])) return c[2] > 0.f ? 1.0 : 0.0;
+    const double x = ((double) c[0] * l + (double) c[1]) * l + (double) c[2];
+    return std::max(0.5 + x / (2.0 * std::sqrt(1.0 + x * x)), 0.0);
+}
+static double plastic_mean_sigmoid(const float *c) {
+    double s = 0.0;
+    for (int i = 0; i < MSK_CIE_SAMPLES; ++i) s += plastic_sigmoid(c, 360.0 + 5.0 * i);
+    return s / MSK_CIE_SAMPLES;
+}
+// the mean over the 95 CIE wavelengths of the tabulated spectrum k (1-based; msk_regular_spectrum_desc: lerp, the end segments continued)
+static double plastic_mean_regular(const msk_scene_desc *d, uint32_t k) {
+    const msk_regular_spectrum_desc &r = d->regular_spectra[k - 1];
+    const double step = ((double) r.lambda_max - (double) r.lambda_min) / (double) (r.size - 1);
+    const float *v = d->regular_values + r.first_value;
+    double s = 0.0;
+    for (int i = 0; i < MSK_CIE_SAMPLES; ++i) {
+        const double x = (360.0 + 5.0 * i - (double) r.lambda_min) / step;
+        const long seg = std::min(std::max((long) std::floor(x), 0l), (long) r.size - 2);
+        const double t = x - (double) seg;
+        s += (1.0 - t) * (double) v[seg] + t * (double) v[seg + 1];
+    }
+    return s / MSK_CIE_SAMPLES;
+}
+static void plastic_constants(const msk_scene_desc *d, const msk_bsdf_desc &b, double *fdr_int, double *ssw) {
+    *fdr_int = plastic_fdr_int((double) b.ior_eta);
+    const msk_spectrum_desc &sp = b.specular_reflectance;
+    const double s_mean = sp.regular ? plastic_mean_regular(d, sp.regular) : (double) sp.scale * plastic_mean_sigmoid(sp.coeff);
+    double d_mean;
+    if (b.reflectance_regular) d_mean = plastic_mean_regular(d, b.reflectance_regular);
+    else if (!b.reflectance_texture) d_mean = (double) b.reflectance_scale * plastic_mean_sigmoid(b.reflectance);
+    else {
+        const msk_texture_desc &t = d->textures[b.reflectance_texture - 1];
+        if (t.type == MSK_TEXTURE_CHECKERBOARD) d_mean = 0.5 * (plastic_mean_sigmoid(t.color0) + plastic_mean_sigmoid(t.color1));
+        else {
+            const size_t n = (size_t) t.width * t.height;
+            d_mean = 0.0;
+            for (size_t k = 0; k < n; ++k) d_mean += plastic_mean_sigmoid(d->texels + ((size_t) t.first_texel + k) * 3);
+            d_mean /= (double) n;
+        }
+    }
+    *ssw = (d_mean + s_mean) > 0.0 ? s_mean / (d_mean + s_mean) : 1.0;
+}
+// What the library refuses of the BSDF entries at scene creation that this file would otherwise misread (msk_gpu.h at msk_bsdf_desc):
+// an unassigned type, a back_bsdf out of range, and a plastic's ior_eta below 1, specular scale or roughness
+static bool bsdfs_acceptable(const msk_scene_desc *d) {
+    for (uint32_t i = 0; i < d->n_bsdfs; ++i) {
+        const msk_bsdf_desc &b = d->bsdfs[i];
+        const bool known = b.type == MSK_BSDF_DIFFUSE || b.type == MSK_BSDF_ROUGHCONDUCTOR || b.type == MSK_BSDF_ROUGHDIELECTRIC || b.type == MSK_BSDF_DIELECTRIC ||
+                           b.type == MSK_BSDF_CONDUCTOR || b.type == MSK_BSDF_PLASTIC || b.type == MSK_BSDF_ROUGHPLASTIC;
+        if (!known) return false;                                      // type 5, and 8 or more
+        if (b.back_bsdf < -1 || b.back_bsdf >= (int32_t) d->n_bsdfs) return false;
+        if (b.type == MSK_BSDF_PLASTIC || b.type == MSK_BSDF_ROUGHPLASTIC) {
+            if (!(std::isfinite(b.ior_eta) && b.ior_eta >= 1.f)) return false;
+            if (!(std::isfinite(b.ior_inv_eta) && b.ior_inv_eta > 0.f)) return false;
+            if (b.specular_reflectance.regular == 0 && !std::isfinite(b.specular_reflectance.scale)) return false;
+            if (b.specular_reflectance.regular > d->n_regular_spectra || b.reflectance_regular > d->n_regular_spectra || b.reflectance_texture > d->n_textures) return false;
+        }
+        if (b.type == MSK_BSDF_ROUGHPLASTIC) {
+            if (!(std::isfinite(b.alpha_u) && std::isfinite(b.alpha_v) && b.alpha_u >= 0.f && b.alpha_v >= 0.f)) return false;
+            if (b.alpha_u != b.alpha_v) return false;                  // roughplastic.cpp:23-25: no anisotropic coat
+        }
+    }
+    return true;
+}
+
 // What a scene holds beyond msk_scene_desc; false = something the library refuses at scene creation (msk_gpu.h at
 // msk_gpu_scene_create_env / _ext / _masks)
-static bool scene_extensions(Scene *sc, const msk_scene_desc *d, const msk_scene_masks *em) {
+static bool scene_extensions(Scene *sc, const msk_scene_desc *d, const msk_scene_masks *em, uint32_t n_lights, const msk_light_desc *lights) {
     const msk_envmap_desc *env = em ? em->ext.envmap : nullptr;
     uint32_t n_env = 0, n_image = 0;
     for (uint32_t e = 0; e < d->n_emitters; ++e) {
         const int32_t t = d->emitters[e].type;
         if (t == MSK_EMITTER_CONSTANT || t == MSK_EMITTER_ENVMAP) ++n_env;
         if (t == MSK_EMITTER_ENVMAP) ++n_image;
-        if (t == MSK_EMITTER_POINT && d->emitters[e].mesh_id != -1) return false;
+        if ((t == MSK_EMITTER_POINT || t == MSK_EMITTER_SPOT || t == MSK_EMITTER_DIRECTIONAL) && d->emitters[e].mesh_id != -1) return false;
+        if (t < MSK_EMITTER_AREA || t > MSK_EMITTER_DIRECTIONAL) return false;      // no unknown emitter type reaches the area light's code
     }
     if (n_env > 1 || (n_image != 0) != (env != nullptr)) return false;
     if (env) {
@@ -316,6 +461,31 @@ static bool scene_extensions(Scene *sc, const msk_scene_desc *d, const msk_scene
     bool any_point = false;
     for (uint32_t e = 0; e < d->n_emitters; ++e)
         if (d->emitters[e].type == MSK_EMITTER_POINT) { any_point = true; if (!seen[e]) return false; }
+    // D23: exactly one msk_light_desc per MSK_EMITTER_SPOT / MSK_EMITTER_DIRECTIONAL emitter, in any order (the refusals listed at msk_light_desc)
+    sc->lights.assign(d->n_emitters, Scene::Light());
+    std::vector<int> lit(d->n_emitters, 0);
+    if (n_lights && !lights) return false;
+    bool any_light = false;
+    for (uint32_t k = 0; k < n_lights; ++k) {
+        const msk_light_desc &l = lights[k];
+        if (l.emitter >= d->n_emitters || lit[l.emitter]++) return false;
+        const int32_t t = d->emitters[l.emitter].type;
+        if (t != MSK_EMITTER_SPOT && t != MSK_EMITTER_DIRECTIONAL) return false;
+        const double n2 = (double) l.direction[0] * l.direction[0] + (double) l.direction[1] * l.direction[1] + (double) l.direction[2] * l.direction[2];
+        if (!(std::isfinite(l.direction[0]) && std::isfinite(l.direction[1]) && std::isfinite(l.direction[2])) || !(std::fabs(n2 - 1.0) <= 1e-5)) return false;
+        if (t == MSK_EMITTER_SPOT) {
+            if (!(std::isfinite(l.position[0]) && std::isfinite(l.position[1]) && std::isfinite(l.position[2]))) return false;
+            if (!(l.cos_cutoff >= -1.f && l.cos_cutoff < 1.f) || !(l.cos_beam >= l.cos_cutoff && l.cos_beam <= 1.f)) return false;
+        }
+        Scene::Light &o = sc->lights[l.emitter];
+        o.position = mk3(l.position[0], l.position[1], l.position[2]); o.direction = mk3(l.direction[0], l.direction[1], l.direction[2]);
+        o.cos_cutoff = l.cos_cutoff; o.cos_beam = l.cos_beam;
+    }
+    for (uint32_t e = 0; e < d->n_emitters; ++e) {
+        const int32_t t = d->emitters[e].type;
+        if (t == MSK_EMITTER_SPOT || t == MSK_EMITTER_DIRECTIONAL) { any_light = true; if (!lit[e]) return false; }
+        if (t == MSK_EMITTER_DIRECTIONAL) sc->any_sun = true;
+    }
     // at most one msk_mask_desc per entry
     sc->masks.assign(d->n_bsdfs, Scene::Mask());
     const uint32_t n_masks = em ? em->n_masks : 0u;
@@ -337,13 +507,23 @@ static bool scene_extensions(Scene *sc, const msk_scene_desc *d, const msk_scene
     }
     bool any_conductor = false;
     for (uint32_t b = 0; b < d->n_bsdfs; ++b) any_conductor |= d->bsdfs[b].type == MSK_BSDF_CONDUCTOR;
-    sc->own_density_sky = any_point || any_conductor || sc->any_mask;                    // D15
+    // D20: the constants of the plastics, each rounded once
+    sc->plastic_k.assign(d->n_bsdfs, Scene::PlasticK());
+    for (uint32_t b = 0; b < d->n_bsdfs; ++b)
+        if (d->bsdfs[b].type == MSK_BSDF_PLASTIC || d->bsdfs[b].type == MSK_BSDF_ROUGHPLASTIC) {
+            double fdr_int, ssw;
+            plastic_constants(d, d->bsdfs[b], &fdr_int, &ssw);
+            sc->plastic_k[b].fdr_int = (float) fdr_int; sc->plastic_k[b].ssw = (float) ssw;
+            sc->any_plastic = true;
+        }
+    sc->own_density_sky = any_point || any_light || any_conductor || sc->any_mask || sc->any_plastic;      // D15, D22, D23
     return true;
 }
 
-static Scene *scene_from_desc(const msk_scene_desc *d, const msk_scene_masks *em = nullptr) {
+static Scene *scene_from_desc(const msk_scene_desc *d, const msk_scene_masks *em = nullptr, uint32_t n_lights = 0, const msk_light_desc *lights = nullptr) {
+    if (!bsdfs_acceptable(d)) return nullptr;
     Scene *sc = new Scene();
-    if (!scene_extensions(sc, d, em)) { delete sc; return nullptr; }
+    if (!scene_extensions(sc, d, em, n_lights, lights)) { delete sc; return nullptr; }
     if (d->n_texels) sc->texels.assign(d->texels, d->texels + (size_t) d->n_texels * 3);
     sc->meshes.assign(d->meshes, d->meshes + d->n_meshes);
     sc->bsdfs.assign(d->bsdfs, d->bsdfs + d->n_bsdfs);
@@ -394,7 +574,7 @@ static Scene *scene_from_desc(const msk_scene_desc *d, const msk_scene_masks *em
     // scene.cpp:35-41 m_environment; constant.cpp:21-28 set_scene: sphere around Scene::bbox() (bbox.h:105-112)
     for (uint32_t e = 0; e < d->n_emitters; ++e)
         if (sc->emitters[e].type == MSK_EMITTER_CONSTANT || sc->emitters[e].type == MSK_EMITTER_ENVMAP) sc->env = (int) e;
-    if (sc->env >= 0) {
+    if (sc->env >= 0 || sc->any_sun) {                             // (msk_light_desc: a scene with a sun computes it whether it holds an environment emitter or not)
         V3 pmin = mk3(kInf, kInf, kInf), pmax = mk3(-kInf, -kInf, -kInf);
         for (uint32_t v = 0; v < d->n_vertices; ++v) {
             const float *q = &sc->vertices[(size_t) v * 8];
@@ -454,6 +634,15 @@ enum PathTally { kTallyNullLobe, kTallyEmitterAfterNull, kTallyEmitterAfterDelta
                  kTallyDeadSample,         // BSDF samples that failed or left a zero throughput: where the device's segment count may differ by one
                  kTallySegmentDropped,     // a sample with a lobe whose throughput is zero and no shadow ray pending: the wavefront kernels end the path, no ray
                  kTallySegmentExtra,       // a failed sample with a shadow ray pending: the wavefront kernels keep the slot one more sweep, one (zero) ray
+                 // the plastics' branches (D19-D22), appended so that the eleven named events and the four counter tallies above keep their places
+                 kTallyPlasticCoat, kTallyPlasticBase,       // a type-6 sample took the delta coat / the diffuse base
+                 kTallyEmitterAfterCoat,                      // an emitter or sky reached after a sampled type-6 coat: emitter density 0, weight 1
+                 kTallyRoughPlasticCoat, kTallyRoughPlasticBase,      // a type-7 sample took the GGX coat (and lived) / the base
+                 kTallyRoughPlasticFailed,                    // a type-7 coat sample with pm == 0 or wo.z <= 0: a direction with value 0
+                 kTallyPlasticFromBehind,                     // cos_i <= 0 at a one-sided entry of either type: the sample fails
+                 kTallyPlasticBackFace,                       // a twosided entry of either type met from the back
+                 kTallyNullOverPlastic,                       // a mask's null lobe at an entry whose nested BSDF is a plastic of either type
+                 kTallyRRAfterCoat,                           // Russian roulette ended the path after a coat sample of either type
                  kTallyCount };
 static std::atomic<uint64_t> g_path[kTallyCount];
 struct PathTallies { uint64_t v[kTallyCount] = {}; };
@@ -844,6 +1033,34 @@ static DirectSample emitter_sample_direct(const Scene &sc, int e, const Interact
         ds.p = sc.point_pos[e]; ds.n = -ds.d; ds.emitter = e; ds.point = true;
         return ds;
     }
+    if (em.type == MSK_EMITTER_SPOT) {
+        // msk_gpu.h at msk_light_desc: the point light's d, dist, inv; c = -(d . a); the falloff tested in this order: c >= cos_beam gives
+        // 1, c <= cos_cutoff gives 0, otherwise t = (c - cos_cutoff) / (cos_beam - cos_cutoff), f = (t * t) * (3 - 2 * t); f == 0: pdf = 0
+        const Scene::Light &l = sc.lights[e];
+        DirectSample ds;
+        *spec = point_sample(l.position, ref.p, emitter_radiance(sc, e, wl), &ds.d, &ds.dist, &ds.pdf);
+        ds.p = l.position; ds.n = -ds.d; ds.emitter = e; ds.point = true;
+        if (ds.pdf != 0.f) {
+            const float c = -(ds.d.x * l.direction.x + (ds.d.y * l.direction.y + ds.d.z * l.direction.z));
+            float f;
+            if (c >= l.cos_beam) f = 1.f;
+            else if (c <= l.cos_cutoff) f = 0.f;
+            else { const float t = (c - l.cos_cutoff) / (l.cos_beam - l.cos_cutoff); f = (t * t) * (3.f - 2.f * t); }
+            *spec = *spec * f;
+            if (f == 0.f) { ds.pdf = 0.f; *spec = s4(0.f); }
+        }
+        return ds;
+    }
+    if (em.type == MSK_EMITTER_DIRECTIONAL) {
+        // msk_gpu.h at msk_light_desc: d = -w, dist = 2 * env_radius, pdf = 1, value(l) = E(l)
+        const Scene::Light &l = sc.lights[e];
+        DirectSample ds;
+        ds.d = mk3(-l.direction.x, -l.direction.y, -l.direction.z);
+        ds.dist = 2.f * sc.env_radius;
+        ds.p = ref.p + ds.d * ds.dist; ds.n = -ds.d; ds.pdf = 1.f; ds.emitter = e; ds.point = true;
+        *spec = emitter_radiance(sc, e, wl);
+        return ds;
+    }
     if (em.type == MSK_EMITTER_ENVMAP) {
         // msk_gpu.h at msk_envmap_desc: next-event value = L(uv) / pdf_omega, dist = 2 * env_radius; pdf 0 gives no contribution
         DirectSample ds;
@@ -1128,6 +1345,7 @@ static S4 dielectric_sample(const Scene &sc, const msk_bsdf_desc &b, V3 wi, V2 s
 }
 // BSDFFlags::Smooth of bsdf->flags() (path.cpp:56): every BSDF here but `dielectric`, whose two components are delta (dielectric.cpp:21-23)
 // and `conductor`, one delta reflection lobe (msk_gpu.h at MSK_BSDF_CONDUCTOR: "no next-event sample is taken at such a hit")
+// (true for `plastic` too, D19: its diffuse lobe is smooth, the coat's delta mark belongs to the sample)
 static bool bsdf_has_smooth_lobe(const msk_bsdf_desc &b) { return b.type != MSK_BSDF_DIELECTRIC && b.type != MSK_BSDF_CONDUCTOR; }
 // msk_gpu.h at MSK_BSDF_CONDUCTOR: cos_i <= 0 fails (no direction); otherwise wo = (-wi.x, -wi.y, wi.z), pdf = 1, eta = 1,
 // value(l) = specular_reflectance(l) * fresnel_conductor(cos_i, eta(l), k(l)), one product
@@ -1211,6 +1429,109 @@ static S4 reflectance_eval(const Scene &sc, Reflectance r, S4 wl) {
     return srgb_model_eval(r.coeff, wl) * r.scale;
 }
 
+// ---------------------------------------------------------------------------
+// `plastic` and `roughplastic` (msk_gpu.h at msk_bsdf_desc; D19-D21), fp32, one operation at a time, wi on the front side
+// ---------------------------------------------------------------------------
+static inline bool is_plastic(const msk_bsdf_desc &b) { return b.type == MSK_BSDF_PLASTIC || b.type == MSK_BSDF_ROUGHPLASTIC; }
+// {fdr_int, ssw} of entry b of the scene; false for a descriptor that is not an entry of `sc` (the bare descriptors of the BSDF KAT hooks)
+static bool plastic_k_of(const Scene &sc, const msk_bsdf_desc &b, Scene::PlasticK *k) {
+    if (sc.bsdfs.empty() || &b < sc.bsdfs.data() || &b >= sc.bsdfs.data() + sc.bsdfs.size()) return false;
+    const size_t i = (size_t) (&b - sc.bsdfs.data());
+    if (i >= sc.plastic_k.size()) return false;
+    *k = sc.plastic_k[i];
+    return true;
+}
+static float fresnel_F(float cos_i, float eta) {
+    float F, ct, e_it, e_ti;
+    fresnel_dielectric(cos_i, eta, &F, &ct, &e_it, &e_ti);
+    return F;
+}
+// F_i = fresnel_dielectric(cos_i, ior_eta), ps = F_i * ssw, pd = (1 - F_i) * (1 - ssw); cos_i <= 0 or ps + pd == 0 fails; otherwise
+// ps = ps / (ps + pd), pd = 1 - ps
+static bool plastic_lobes(const msk_bsdf_desc &b, float ssw, float cos_i, float *F_i, float *ps, float *pd) {
+    if (!(cos_i > 0.f)) return false;
+    *F_i = fresnel_F(cos_i, b.ior_eta);
+    const float a = *F_i * ssw;
+    const float d = (1.f - *F_i) * (1.f - ssw);
+    const float s = a + d;
+    if (s == 0.f) return false;
+    *ps = a / s;
+    *pd = 1.f - *ps;
+    return true;
+}
+// D(l) * f with D(l) = rho(l) / (1 - fdr_int * rho(l)) when nonlinear, else rho(l) / (1 - fdr_int), and the one scalar
+// f = ior_inv_eta * ior_inv_eta * (1 - F_i) * (1 - F_o), the products left to right
+static S4 plastic_diffuse(const msk_bsdf_desc &b, float fdr_int, S4 rho, float F_i, float cos_o) {
+    const float F_o = fresnel_F(cos_o, b.ior_eta);
+    S4 D;
+    if (b.sample_visible != 0) { for (int i = 0; i < 4; ++i) D.v[i] = rho.v[i] / (1.f - fdr_int * rho.v[i]); }      // the word is read as `nonlinear`
+    else D = rho / (1.f - fdr_int);
+    const float f = ((b.ior_inv_eta * b.ior_inv_eta) * (1.f - F_i)) * (1.f - F_o);
+    return D * f;
+}
+// eval and pdf of type 6: the diffuse lobe's alone, for cos_i > 0 and cos_o > 0
+static void plastic_eval_pdf(const Scene &sc, const msk_bsdf_desc &b, Scene::PlasticK k, Reflectance refl, V3 wi, V3 wo, S4 wl, S4 *val, float *pdf) {
+    *val = s4(0.f); *pdf = 0.f;
+    float F_i, ps, pd;
+    if (!plastic_lobes(b, k.ssw, wi.z, &F_i, &ps, &pd) || !(wo.z > 0.f)) return;
+    *val = (plastic_diffuse(b, k.fdr_int, reflectance_eval(sc, refl, wl), F_i, wo.z) * kInvPi) * wo.z;
+    *pdf = pd * (kInvPi * wo.z);
+}
+// sample of type 6: sample1 < ps takes the delta coat, otherwise the diffuse base
+static S4 plastic_sample(const Scene &sc, const msk_bsdf_desc &b, Scene::PlasticK k, Reflectance refl, V3 wi, float sample1, V2 sample, S4 wl, BSDFSampleRec *bs) {
+    float F_i, ps, pd;
+    if (!plastic_lobes(b, k.ssw, wi.z, &F_i, &ps, &pd)) return s4(0.f);
+    bs->eta = 1.f;
+    if (sample1 < ps) {
+        bs->wo = mk3(-wi.x, -wi.y, wi.z);
+        bs->pdf = ps;
+        bs->sampled_type = kDeltaReflection;                          // D19: the mark of this sample, not of the entry
+        return (spectrum_eval(sc, b.specular_reflectance, wl) * F_i) / ps;
+    }
+    bs->wo = square_to_cosine_hemisphere(sample);
+    bs->pdf = pd * (kInvPi * bs->wo.z);
+    bs->sampled_type = kDiffuseReflection;
+    if (!(bs->pdf > 0.f)) return s4(0.f);
+    return plastic_diffuse(b, k.fdr_int, reflectance_eval(sc, refl, wl), F_i, bs->wo.z) / pd;
+}
+// eval and pdf of type 7, the mixture: value(l) = s(l) * c + base(l), pdf = ps * p_s + pd * ((1 / pi) * cos_o)
+static void roughplastic_eval_pdf(const Scene &sc, const msk_bsdf_desc &b, Scene::PlasticK k, Reflectance refl, V3 wi, V3 wo, S4 wl, S4 *val, float *pdf) {
+    *val = s4(0.f); *pdf = 0.f;
+    float F_i, ps, pd;
+    if (!plastic_lobes(b, k.ssw, wi.z, &F_i, &ps, &pd) || !(wo.z > 0.f)) return;
+    const float a = clamp_alpha(b.alpha_u);
+    const S4 base = (plastic_diffuse(b, k.fdr_int, reflectance_eval(sc, refl, wl), F_i, wo.z) * kInvPi) * wo.z;
+    const float pdf_d = pd * (kInvPi * wo.z);
+    const V3 H = normalized(wo + wi);
+    const float D = distr_eval(H, a, a);
+    const float G = smith_g1(wi, H, a, a) * smith_g1(wo, H, a, a);
+    const float F_h = fresnel_F(dot(wi, H), b.ior_eta);
+    const float c = ((F_h * D) * G) / (4.f * wi.z);
+    *val = spectrum_eval(sc, b.specular_reflectance, wl) * c + base;
+    const float p_s = D == 0.f ? 0.f : (D * H.z) / (4.f * dot(wo, H));
+    *pdf = ps * p_s + pdf_d;
+}
+// sample of type 7: a direction from the coat (sample_ggx, mirrored) or from the base, then eval / pdf of the mixture; never delta
+static S4 roughplastic_sample(const Scene &sc, const msk_bsdf_desc &b, Scene::PlasticK k, Reflectance refl, V3 wi, float sample1, V2 sample, S4 wl, BSDFSampleRec *bs) {
+    float F_i, ps, pd;
+    if (!plastic_lobes(b, k.ssw, wi.z, &F_i, &ps, &pd)) return s4(0.f);
+    bs->eta = 1.f;
+    if (sample1 < ps) {
+        const float a = clamp_alpha(b.alpha_u);
+        float pm;
+        const V3 m = sample_ggx(sample, a, a, &pm);
+        bs->wo = m * 2.f * dot(wi, m) - wi;
+        bs->sampled_type = kGlossyReflection;
+        if (pm == 0.f || !(bs->wo.z > 0.f)) { bs->pdf = 0.f; return s4(0.f); }      // a direction was produced: value 0, pdf 0
+    } else {
+        bs->wo = square_to_cosine_hemisphere(sample);
+        bs->sampled_type = kDiffuseReflection;
+    }
+    S4 val;
+    roughplastic_eval_pdf(sc, b, k, refl, wi, bs->wo, wl, &val, &bs->pdf);
+    return bs->pdf > 0.f ? val / bs->pdf : s4(0.f);
+}
+
 // one-sided evaluation (wi already on the front side for twosided); refl = reflectance_at() of the hit
 static void bsdf_eval_pdf(const Scene &sc, const msk_bsdf_desc &b, Reflectance refl, V3 wi, V3 wo, S4 wl, S4 *val, float *pdf) {
     *val = s4(0.f); *pdf = 0.f;
@@ -1225,6 +1546,14 @@ static void bsdf_eval_pdf(const Scene &sc, const msk_bsdf_desc &b, Reflectance r
     if (b.type == MSK_BSDF_ROUGHDIELECTRIC) { roughdielectric_eval_pdf(sc, b, wi, wo, wl, val, pdf); return; }
     if (b.type == MSK_BSDF_DIELECTRIC) return;                         // dielectric.cpp:74-82: eval and pdf are zero
     if (b.type == MSK_BSDF_CONDUCTOR) return;                          // msk_gpu.h at MSK_BSDF_CONDUCTOR: eval and pdf are zero
+    if (is_plastic(b)) {
+        Scene::PlasticK k;
+        if (!plastic_k_of(sc, b, &k)) return;                          // a bare descriptor has no constants: zero, never another type's code
+        if (b.type == MSK_BSDF_PLASTIC) plastic_eval_pdf(sc, b, k, refl, wi, wo, wl, val, pdf);
+        else roughplastic_eval_pdf(sc, b, k, refl, wi, wo, wl, val, pdf);
+        return;
+    }
+    if (b.type != MSK_BSDF_ROUGHCONDUCTOR) return;                     // no unknown type reaches the conductor's code (scene creation refuses them)
     const float au = clamp_alpha(b.alpha_u), av = clamp_alpha(b.alpha_v);
     // roughconductor.cpp:82-98 eval
     if (cos_i > 0.f && cos_o > 0.f) {
@@ -1249,6 +1578,12 @@ static S4 bsdf_sample(const Scene &sc, const msk_bsdf_desc &b, Reflectance refl,
     if (b.type == MSK_BSDF_ROUGHDIELECTRIC) return roughdielectric_sample(sc, b, wi, sample1, sample, wl, bs);
     if (b.type == MSK_BSDF_DIELECTRIC) return dielectric_sample(sc, b, wi, sample, wl, bs);
     if (b.type == MSK_BSDF_CONDUCTOR) return conductor_sample(sc, b, wi, wl, bs);
+    if (is_plastic(b)) {
+        Scene::PlasticK k;
+        if (!plastic_k_of(sc, b, &k)) return s4(0.f);
+        return b.type == MSK_BSDF_PLASTIC ? plastic_sample(sc, b, k, refl, wi, sample1, sample, wl, bs) : roughplastic_sample(sc, b, k, refl, wi, sample1, sample, wl, bs);
+    }
+    if (b.type != MSK_BSDF_DIFFUSE && b.type != MSK_BSDF_ROUGHCONDUCTOR) return s4(0.f);      // no unknown type reaches the conductor's code
     float cos_i = wi.z;
     if (cos_i <= 0.f) return s4(0.f);
     if (b.type == MSK_BSDF_DIFFUSE) {                                  // diffuse.cpp:18-33
@@ -1364,7 +1699,16 @@ static S4 path_sample(const Scene &sc, Sampler &sampler, Ray ray, S4 wl, const m
             bsdf_val = bsdf_sample(sc, *bb, reflectance_at(sc, *bb, si.uv), wi_s, sample1, u2, wl, &bs);
             if (flipped) bs.wo.z *= -1.f;
             if (masked) bs.pdf = opacity * bs.pdf;                 // D16: pdf = a pdf_X, the value stays X's
+            if (is_plastic(*bb)) {                                 // (tallies only)
+                if (flipped) tally(kTallyPlasticBackFace);
+                if (bb->back_bsdf < 0 && !(wi_s.z > 0.f)) tally(kTallyPlasticFromBehind);
+                if (bb->type == MSK_BSDF_PLASTIC) { if (bs.sampled_type == kDeltaReflection) tally(kTallyPlasticCoat); else if (bs.sampled_type) tally(kTallyPlasticBase); }
+                else if (bs.sampled_type == kGlossyReflection) tally(bs.pdf == 0.f ? kTallyRoughPlasticFailed : kTallyRoughPlasticCoat);
+                else if (bs.sampled_type) tally(kTallyRoughPlasticBase);
+            }
         }
+        if (null_lobe && is_plastic(bsdf)) tally(kTallyNullOverPlastic);
+        const bool coat_sample = !null_lobe && is_plastic(bsdf) && (bs.sampled_type == kDeltaReflection || bs.sampled_type == kGlossyReflection);
         const V3 bs_wo = bs.wo; const float bs_pdf = bs.pdf, bs_eta = bs.eta;
         const uint32_t sampled_type = bs.sampled_type;
         {   // (tallies only) where the device's segment count parts from `if (sampled_type) ++cnt.segments` below
@@ -1427,6 +1771,7 @@ static S4 path_sample(const Scene &sc, Sampler &sampler, Ray ray, S4 wl, const m
             const float weight = mis_weight(bs_pdf, emitter_pdf);
             if (null_lobe) tally(kTallyEmitterAfterNull);
             if (sampled_type & kDelta) tally(kTallyEmitterAfterDelta);
+            if ((sampled_type & kDelta) && bsdf.type == MSK_BSDF_PLASTIC) tally(kTallyEmitterAfterCoat);
             if (env_hit && sc.env_is_image && !delta && weight > 0.f && weight < 1.f) tally(kTallyEnvmapMissSmooth);
             if (hidden) { if (!env_hit) tally(kTallyAreaHidden); }
             else result = result + throughput * value * weight;
@@ -1434,7 +1779,7 @@ static S4 path_sample(const Scene &sc, Sampler &sampler, Ray ray, S4 wl, const m
         si = si_bsdf;
         if (depth + 1 >= rr_depth) {                               // path.cpp:116-122
             float q = std::min(max4(throughput) * eta * eta, 0.95f);
-            if (sampler.single(base + 1, 1) >= q) { if (null_lobe) tally(kTallyRRAfterNull); break; }
+            if (sampler.single(base + 1, 1) >= q) { if (null_lobe) tally(kTallyRRAfterNull); if (coat_sample) tally(kTallyRRAfterCoat); break; }
             throughput = throughput / q;
         }
     }
@@ -1597,6 +1942,7 @@ static S4 direct_sample(const Scene &sc, Sampler &sampler, Ray ray, S4 wl, const
 // what the library refuses of a `direct` call (msk_gpu.h): 0 when it is taken
 static int direct_refusal(const Scene &sc, const msk_render_params &prm, const msk_direct_params &dp) {
     if (sc.any_mask) return MSK_ERR_UNSUPPORTED;
+    if (sc.any_plastic) return MSK_ERR_UNSUPPORTED;                    // D22: as msk_gpu_render_direct does
     if (prm.rng_mode != MSK_RNG_COUNTER) return MSK_ERR_UNSUPPORTED;
     if (dp.light_samples > 4096u || dp.bsdf_samples > 4096u || (dp.light_samples == 0u && dp.bsdf_samples == 0u)) return MSK_ERR_INVALID_ARG;
     return 0;
@@ -1837,9 +2183,16 @@ extern "C" {
 // the ABI's own structs; NULL for what the library refuses at scene creation (scene_extensions)
 void *msk_oracle_scene_create_masks(const msk_scene_desc *d, const msk_scene_masks *em) { return scene_from_desc(d, em); }
 void *msk_oracle_scene_create(const msk_scene_desc *d) { return msk_oracle_scene_create_masks(d, nullptr); }
+void *msk_oracle_scene_create_lights(const msk_scene_desc *d, const msk_scene_lights *el) {
+    return el ? scene_from_desc(d, &el->masks, el->n_lights, el->lights) : scene_from_desc(d, nullptr);
+}
 // reads and clears the path tallies (see PathTally): out receives msk_oracle_path_tally_count() values
-int msk_oracle_path_tally_count() { return (int) kTallyCount; }
-void msk_oracle_path_tallies(uint64_t *out) { path_flush(); for (int i = 0; i < kTallyCount; ++i) out[i] = g_path[i].exchange(0); }
+// (these two keep answering for the fifteen tallies they always had, so that a caller written for them reads what it expects)
+int msk_oracle_path_tally_count() { return (int) kTallyPlasticCoat; }
+void msk_oracle_path_tallies(uint64_t *out) { path_flush(); for (int i = 0; i < kTallyPlasticCoat; ++i) out[i] = g_path[i].exchange(0); }
+// ... and these two for all of them, the plastics' ten behind the fifteen
+int msk_oracle_path_tally_count_all() { return (int) kTallyCount; }
+void msk_oracle_path_tallies_all(uint64_t *out) { path_flush(); for (int i = 0; i < kTallyCount; ++i) out[i] = g_path[i].exchange(0); }
 
 // ---- known-answer hooks of the features restated from include/msk_gpu.h (shaped like msk_oracle_bsdf_sample2) ----
 static S4 load4(const float *p) { S4 r; for (int i = 0; i < 4; ++i) r.v[i] = p[i]; return r; }
@@ -1877,6 +2230,18 @@ int msk_oracle_point_sample(void *s, uint32_t emitter, const float *p3, const fl
     store4(out_value4, v);
     return 0;
 }
+// the next-event sample of the spot or directional emitter `emitter`, as msk_gpu_light_sample gives it: out_d_dist4 = {d, dist}, out_value4
+// (the value zeros where f == 0, everything zeros where dist == 0)
+int msk_oracle_light_sample(void *s, uint32_t emitter, const float *p3, const float *wl4, float *out_d_dist4, float *out_value4) {
+    const Scene &sc = *(Scene *) s;
+    if (emitter >= sc.emitters.size() || (sc.emitters[emitter].type != MSK_EMITTER_SPOT && sc.emitters[emitter].type != MSK_EMITTER_DIRECTIONAL)) return -1;
+    Interaction ref; ref.p = mk3(p3[0], p3[1], p3[2]);
+    S4 v;
+    const DirectSample ds = emitter_sample_direct(sc, (int) emitter, ref, V2{0.f, 0.f}, load4(wl4), &v);
+    out_d_dist4[0] = ds.d.x; out_d_dist4[1] = ds.d.y; out_d_dist4[2] = ds.d.z; out_d_dist4[3] = ds.dist;
+    store4(out_value4, v);
+    return 0;
+}
 // the delta lobe's value of conductor `bsdf` for cos_theta_i (zeros for cos_i <= 0)
 int msk_oracle_conductor_sample(void *s, uint32_t bsdf, float cos_theta_i, const float *wl4, float *out_value4) {
     const Scene &sc = *(Scene *) s;
@@ -1910,7 +2275,7 @@ int msk_oracle_mask_sample(void *s, uint32_t bsdf, const float *uv2, const float
     }
     out_wo_pdf4[0] = bs.wo.x; out_wo_pdf4[1] = bs.wo.y; out_wo_pdf4[2] = bs.wo.z; out_wo_pdf4[3] = bs.pdf;
     store4(out_value4, value);
-    out_flags4[0] = bs.eta; out_flags4[1] = (null_lobe || !bsdf_has_smooth_lobe(sc.bsdfs[bsdf])) ? 1.f : 0.f;
+    out_flags4[0] = bs.eta; out_flags4[1] = (null_lobe || (bs.sampled_type & kDelta) != 0u || !bsdf_has_smooth_lobe(sc.bsdfs[bsdf])) ? 1.f : 0.f;
     out_flags4[2] = null_lobe ? 1.f : 0.f; out_flags4[3] = bs.sampled_type ? 1.f : 0.f;
     return 0;
 }
@@ -1926,6 +2291,45 @@ int msk_oracle_mask_eval(void *s, uint32_t bsdf, const float *uv2, const float *
     bsdf_eval_pdf(sc, *bb, reflectance_at(sc, *bb, uv), wi, wo, load4(wl4), &v, &pdf);
     out_a_pdf2[0] = a; out_a_pdf2[1] = a * pdf;
     store4(out_value4, v * a);
+    return 0;
+}
+// The probes of a `plastic` / `roughplastic` entry, arguments and outputs as msk_gpu_plastic_sample / _plastic_eval /
+// _roughplastic_sample / _roughplastic_eval take and give them (n points; the mask hooks' layout: a scene without a mask has opacity 1
+// on every entry).  Non-zero for an entry out of range or of another type.
+static int plastic_probe_sample(void *s, int32_t type, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *sample1_u, const float *wl,
+                                float *out_wo_pdf, float *out_value, float *out_flags) {
+    const Scene &sc = *(Scene *) s;
+    if (bsdf >= sc.bsdfs.size() || sc.bsdfs[bsdf].type != type) return MSK_ERR_INVALID_ARG;
+    for (uint64_t i = 0; i < n; ++i)
+        msk_oracle_mask_sample(s, bsdf, uv + 2 * i, wi + 3 * i, sample1_u + 3 * i, wl + 4 * i, out_wo_pdf + 4 * i, out_value + 4 * i, out_flags + 4 * i);
+    return 0;
+}
+static int plastic_probe_eval(void *s, int32_t type, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *wo, const float *wl,
+                              float *out_a_pdf, float *out_value) {
+    const Scene &sc = *(Scene *) s;
+    if (bsdf >= sc.bsdfs.size() || sc.bsdfs[bsdf].type != type) return MSK_ERR_INVALID_ARG;
+    for (uint64_t i = 0; i < n; ++i) msk_oracle_mask_eval(s, bsdf, uv + 2 * i, wi + 3 * i, wo + 3 * i, wl + 4 * i, out_a_pdf + 2 * i, out_value + 4 * i);
+    return 0;
+}
+int msk_oracle_plastic_sample(void *s, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *sample1_u, const float *wavelengths,
+                              float *out_wo_pdf, float *out_value, float *out_flags) {
+    return plastic_probe_sample(s, MSK_BSDF_PLASTIC, bsdf, n, uv, wi, sample1_u, wavelengths, out_wo_pdf, out_value, out_flags);
+}
+int msk_oracle_plastic_eval(void *s, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *wo, const float *wavelengths, float *out_a_pdf, float *out_value) {
+    return plastic_probe_eval(s, MSK_BSDF_PLASTIC, bsdf, n, uv, wi, wo, wavelengths, out_a_pdf, out_value);
+}
+int msk_oracle_roughplastic_sample(void *s, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *sample1_u, const float *wavelengths,
+                                   float *out_wo_pdf, float *out_value, float *out_flags) {
+    return plastic_probe_sample(s, MSK_BSDF_ROUGHPLASTIC, bsdf, n, uv, wi, sample1_u, wavelengths, out_wo_pdf, out_value, out_flags);
+}
+int msk_oracle_roughplastic_eval(void *s, uint32_t bsdf, uint64_t n, const float *uv, const float *wi, const float *wo, const float *wavelengths, float *out_a_pdf, float *out_value) {
+    return plastic_probe_eval(s, MSK_BSDF_ROUGHPLASTIC, bsdf, n, uv, wi, wo, wavelengths, out_a_pdf, out_value);
+}
+// out2 = {fdr_int, ssw} of a plastic entry of either type, as this file computed them (D20)
+int msk_oracle_plastic_constants(void *s, uint32_t bsdf, float *out2) {
+    const Scene &sc = *(Scene *) s;
+    if (bsdf >= sc.bsdfs.size() || !is_plastic(sc.bsdfs[bsdf])) return MSK_ERR_INVALID_ARG;
+    out2[0] = sc.plastic_k[bsdf].fdr_int; out2[1] = sc.plastic_k[bsdf].ssw;
     return 0;
 }
 void msk_oracle_scene_destroy(void *s) { delete (Scene *) s; }

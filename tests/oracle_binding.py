@@ -22,9 +22,14 @@ class Oracle:
         lib.msk_oracle_scene_create.argtypes = [C.POINTER(abi.SceneDesc)]
         lib.msk_oracle_scene_create_masks.restype = vp
         lib.msk_oracle_scene_create_masks.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(abi.SceneMasks)]
+        lib.msk_oracle_scene_create_lights.restype = vp
+        lib.msk_oracle_scene_create_lights.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(abi.SceneLights)]
+        lib.msk_oracle_light_sample.argtypes = [vp, C.c_uint32, vp, vp, vp, vp]
         lib.msk_oracle_scene_destroy.argtypes = [vp]
         lib.msk_oracle_path_tally_count.restype = C.c_int
         lib.msk_oracle_path_tallies.argtypes = [vp]
+        lib.msk_oracle_path_tally_count_all.restype = C.c_int
+        lib.msk_oracle_path_tallies_all.argtypes = [vp]
         lib.msk_oracle_eval_texture.argtypes = [vp, C.c_uint32, vp, vp, vp]
         lib.msk_oracle_env_eval.argtypes = [vp, vp, vp, vp, vp]
         lib.msk_oracle_env_sample.argtypes = [vp, vp, vp, vp, vp]
@@ -32,6 +37,11 @@ class Oracle:
         lib.msk_oracle_conductor_sample.argtypes = [vp, C.c_uint32, C.c_float, vp, vp]
         lib.msk_oracle_mask_sample.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
         lib.msk_oracle_mask_eval.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
+        for name in ("msk_oracle_plastic_sample", "msk_oracle_roughplastic_sample"):
+            getattr(lib, name).argtypes = [vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
+        for name in ("msk_oracle_plastic_eval", "msk_oracle_roughplastic_eval"):
+            getattr(lib, name).argtypes = [vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp, vp, vp]
+        lib.msk_oracle_plastic_constants.argtypes = [vp, C.c_uint32, vp]
         lib.msk_oracle_set_bvh.argtypes = [vp, C.c_int]
         lib.msk_oracle_render.argtypes = [vp, C.POINTER(abi.RenderParams), vp, C.POINTER(abi.Stats), C.c_int]
         lib.msk_oracle_render_aov.argtypes = [vp, C.POINTER(abi.RenderParams), vp, C.c_uint32, vp, C.POINTER(abi.Stats), C.c_int]
@@ -167,7 +177,10 @@ class Oracle:
 
     PATH_TALLIES = ("null_lobe", "emitter_after_null", "emitter_after_delta", "envmap_miss_after_smooth", "point_unoccluded", "point_occluded",
                     "sky_own_density", "area_emitter_hidden", "rr_after_null", "texel_wrap", "envmap_pole_clamp", "shadow_rays_nonzero", "dead_samples",
-                    "segments_dropped", "segments_extra")
+                    "segments_dropped", "segments_extra",
+                    # the plastics' branches, appended: the first eleven names and the four counter tallies keep their places
+                    "plastic_coat", "plastic_base", "emitter_after_coat", "roughplastic_coat", "roughplastic_base", "roughplastic_failed",
+                    "plastic_from_behind", "plastic_back_face", "null_over_plastic", "rr_after_coat")
 
     def path_tallies(self):
         """Reads and clears the oracle's path tallies (oracle.cpp: PathTally) -> dict.  Beside the named path events: the next-event
@@ -175,10 +188,10 @@ class Oracle:
         zero throughput (where the device's segment count may differ from the oracle's by one each); of those, the samples with a lobe,
         a zero throughput and no shadow ray pending (`segments_dropped`: the wavefront kernels end the path without a ray the oracle
         counts) and the failed samples with one pending (`segments_extra`: they keep the slot for one more, zero, ray)."""
-        n = self.lib.msk_oracle_path_tally_count()
-        assert n == len(self.PATH_TALLIES)
+        n = self.lib.msk_oracle_path_tally_count_all()       # (msk_oracle_path_tally_count / _path_tallies keep to the first fifteen)
+        assert n == len(self.PATH_TALLIES) and self.lib.msk_oracle_path_tally_count() == 15
         a = (C.c_uint64 * n)()
-        self.lib.msk_oracle_path_tallies(a)
+        self.lib.msk_oracle_path_tallies_all(a)
         return dict(zip(self.PATH_TALLIES, [int(x) for x in a]))
 
     DIRECT_TALLIES = ("primary_miss_env", "primary_emitter_seen", "primary_emitter_hidden", "twosided_flipped", "light_skipped_delta",
@@ -240,9 +253,9 @@ def _row(a, k):
 
 
 class OracleScene:
-    def __init__(self, orc, flat, envmap=None, points=None, masks=None):
-        """flat's envmap, points and masks are passed exactly as abi.Scene passes them (msk_scene_masks); a scene the library
-        refuses at creation raises ValueError"""
+    def __init__(self, orc, flat, envmap=None, points=None, masks=None, lights=None):
+        """flat's envmap, points, masks and lights are passed exactly as abi.Scene passes them (msk_scene_masks, and msk_scene_lights
+        for a scene with a spot or a directional emitter); a scene the library refuses at creation raises ValueError"""
         self.orc, self.flat, self.abi = orc, flat, orc.abi
         abi = orc.abi
         self.envmap = envmap if envmap is not None else getattr(flat, "envmap", None)
@@ -256,7 +269,15 @@ class OracleScene:
         self.masks = mk if (mk is not None and len(mk)) else None
         ext = abi.SceneExt(C.pointer(self.envmap) if self.envmap is not None else None, len(self.points) if self.points is not None else 0, self.points)
         self.em = abi.SceneMasks(ext, len(self.masks) if self.masks is not None else 0, self.masks)
-        self.h = orc.lib.msk_oracle_scene_create_masks(C.byref(flat.desc), C.byref(self.em))
+        lt = lights if lights is not None else getattr(flat, "lights", None)
+        if lt is not None and not isinstance(lt, C.Array):
+            lt = (abi.LightDesc * max(1, len(lt)))(*lt) if len(lt) else None
+        self.lights = lt if (lt is not None and len(lt)) else None
+        if self.lights is not None:
+            self.el = abi.SceneLights(self.em, len(self.lights), self.lights)
+            self.h = orc.lib.msk_oracle_scene_create_lights(C.byref(flat.desc), C.byref(self.el))
+        else:
+            self.h = orc.lib.msk_oracle_scene_create_masks(C.byref(flat.desc), C.byref(self.em))
         if not self.h:
             raise ValueError("the oracle refuses this scene (as the library does at scene creation)")
 
@@ -285,6 +306,15 @@ class OracleScene:
         _rows(lambda k: self.orc.lib.msk_oracle_point_sample(self.h, int(emitter), _row(p, k), _row(wl, k), _row(dd, k), _row(val, k)), p)
         return dd, val
 
+    def light_sample(self, emitter, ref_points, wavelengths):
+        """as abi.Scene.light_sample, of a spot or directional emitter: -> ({d, dist} float32[n, 4], value float32[n, 4])"""
+        p, wl = np.ascontiguousarray(ref_points, np.float32).reshape(-1, 3), np.ascontiguousarray(wavelengths, np.float32).reshape(-1, 4)
+        dd, val = np.empty((len(p), 4), np.float32), np.empty((len(p), 4), np.float32)
+        for k in range(len(p)):
+            if self.orc.lib.msk_oracle_light_sample(self.h, int(emitter), _row(p, k), _row(wl, k), _row(dd, k), _row(val, k)) != 0:
+                raise ValueError("emitter %d is neither a spot nor a directional emitter" % emitter)
+        return dd, val
+
     def conductor_sample(self, bsdf, cos_theta_i, wavelengths):
         c, wl = np.ascontiguousarray(cos_theta_i, np.float32).reshape(-1), np.ascontiguousarray(wavelengths, np.float32).reshape(-1, 4)
         val = np.empty((len(c), 4), np.float32)
@@ -304,6 +334,45 @@ class OracleScene:
         a, v = np.empty((len(uv), 2), np.float32), np.empty((len(uv), 4), np.float32)
         _rows(lambda k: self.orc.lib.msk_oracle_mask_eval(self.h, int(bsdf), _row(uv, k), _row(wi, k), _row(wo, k), _row(wl, k), _row(a, k), _row(v, k)), uv)
         return a, v
+
+    def _plastic_sample(self, entry, bsdf, uv, wi, sample1_u, wavelengths):
+        uv, wi = np.ascontiguousarray(uv, np.float32).reshape(-1, 2), np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
+        su, wl = np.ascontiguousarray(sample1_u, np.float32).reshape(-1, 3), np.ascontiguousarray(wavelengths, np.float32).reshape(-1, 4)
+        assert len(uv) == len(wi) == len(su) == len(wl)
+        a, b, c = (np.empty((len(uv), 4), np.float32) for _ in range(3))
+        if getattr(self.orc.lib, entry)(self.h, int(bsdf), len(uv), _p(uv), _p(wi), _p(su), _p(wl), _p(a), _p(b), _p(c)) != 0:
+            raise ValueError("%s: entry %d is out of range or of another type" % (entry, bsdf))
+        return a, b, c
+
+    def _plastic_eval(self, entry, bsdf, uv, wi, wo, wavelengths):
+        uv, wi = np.ascontiguousarray(uv, np.float32).reshape(-1, 2), np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
+        wo, wl = np.ascontiguousarray(wo, np.float32).reshape(-1, 3), np.ascontiguousarray(wavelengths, np.float32).reshape(-1, 4)
+        assert len(uv) == len(wi) == len(wo) == len(wl)
+        a, v = np.empty((len(uv), 2), np.float32), np.empty((len(uv), 4), np.float32)
+        if getattr(self.orc.lib, entry)(self.h, int(bsdf), len(uv), _p(uv), _p(wi), _p(wo), _p(wl), _p(a), _p(v)) != 0:
+            raise ValueError("%s: entry %d is out of range or of another type" % (entry, bsdf))
+        return a, v
+
+    def plastic_sample(self, bsdf, uv, wi, sample1_u, wavelengths):
+        """as abi.Scene.plastic_sample: -> ({wo, pdf}, value, {eta, delta, null lobe, a direction was produced}), float32[n, 4] each"""
+        return self._plastic_sample("msk_oracle_plastic_sample", bsdf, uv, wi, sample1_u, wavelengths)
+
+    def plastic_eval(self, bsdf, uv, wi, wo, wavelengths):
+        """as abi.Scene.plastic_eval: -> ({a, pdf} float32[n, 2], eval float32[n, 4])"""
+        return self._plastic_eval("msk_oracle_plastic_eval", bsdf, uv, wi, wo, wavelengths)
+
+    def roughplastic_sample(self, bsdf, uv, wi, sample1_u, wavelengths):
+        return self._plastic_sample("msk_oracle_roughplastic_sample", bsdf, uv, wi, sample1_u, wavelengths)
+
+    def roughplastic_eval(self, bsdf, uv, wi, wo, wavelengths):
+        return self._plastic_eval("msk_oracle_roughplastic_eval", bsdf, uv, wi, wo, wavelengths)
+
+    def plastic_constants(self, bsdf):
+        """(fdr_int, ssw) of the `plastic` or `roughplastic` entry `bsdf` as the oracle computed them itself, float32"""
+        out = np.zeros(2, np.float32)
+        if self.orc.lib.msk_oracle_plastic_constants(self.h, int(bsdf), _p(out)) != 0:
+            raise ValueError("entry %d is out of range or not a plastic" % bsdf)
+        return np.float32(out[0]), np.float32(out[1])
 
     def set_bvh(self, on):
         self.orc.lib.msk_oracle_set_bvh(self.h, int(on))

@@ -43,6 +43,25 @@ def test_random_scenes_are_valid_oracle_inputs(oracle, abi):
         b, _ = sc.render(abi.render_params(spp=2, seed=s), threads=3)
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32)) and np.isfinite(a).all() and a[..., 4].min() > 0 and st.invalid_samples == 0
         sc.close()
+    # with `plastic` / `roughplastic` on some meshes (plastic=True): the same three properties, and both types occur over the seeds
+    seen = set()
+    for s in (11001, 11002, 11005, 11006):                              # (11007 draws an extrapolated table that goes negative, with or without plastics)
+        flat = fz.random_scene(np.random.RandomState(s), plastic=True, seed=s)
+        plain, again = fz.random_scene(np.random.RandomState(s)), fz.random_scene(np.random.RandomState(s), plastic=False, seed=s)
+        d = flat.desc
+        types = {d.bsdfs[i].type for i in range(d.n_bsdfs)}
+        assert types & {abi.MSK_BSDF_PLASTIC, abi.MSK_BSDF_ROUGHPLASTIC}
+        seen |= types
+        assert not any(plain.desc.bsdfs[i].type in (abi.MSK_BSDF_PLASTIC, abi.MSK_BSDF_ROUGHPLASTIC) for i in range(plain.desc.n_bsdfs))
+        assert np.array_equal(flat.vertices.view(np.uint32), plain.vertices.view(np.uint32)) and np.array_equal(flat.faces, plain.faces)
+        assert np.array_equal(again.vertices.view(np.uint32), plain.vertices.view(np.uint32))
+        assert all(bytes(again.desc.bsdfs[i]) == bytes(plain.desc.bsdfs[i]) for i in range(plain.desc.n_bsdfs))
+        sc = oracle.scene(flat)
+        a, st = sc.render(abi.render_params(spp=2, seed=s), threads=2)
+        b, _ = sc.render(abi.render_params(spp=2, seed=s), threads=3)
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)) and np.isfinite(a).all() and a[..., 4].min() > 0 and st.invalid_samples == 0
+        sc.close()
+    assert {abi.MSK_BSDF_PLASTIC, abi.MSK_BSDF_ROUGHPLASTIC} <= seen
 
 
 def test_the_seeds_of_the_regression_sweeps_still_make_their_scenes():
@@ -110,6 +129,19 @@ def test_gpu_equals_oracle_on_random_scenes_with_glass(gpu_ctx, oracle):
 @pytest.mark.gpu
 def test_gpu_equals_oracle_on_random_scenes_with_glass_and_many_samples(gpu_ctx, oracle):
     assert _fuzz().sweep(gpu_ctx, oracle, list(range(9100, 9104)), verbose=False, spp=400, glass=True) == []
+
+
+@pytest.mark.gpu
+def test_gpu_equals_oracle_on_random_scenes_with_plastic(gpu_ctx, oracle):
+    """The sweep with some meshes of every scene turned into `plastic` or `roughplastic` (any relative index from 1 up, either base
+    formula, coats from alpha 1e-4 to 0.5, textured and tabulated spectra, one- and twosided, some under a mask, some of them
+    emitters), next to whatever else the generator makes"""
+    assert _fuzz().sweep(gpu_ctx, oracle, list(range(11000, 11040)), plastic=True) == []
+
+
+@pytest.mark.gpu
+def test_gpu_equals_oracle_on_random_scenes_with_plastic_and_many_samples(gpu_ctx, oracle):
+    assert _fuzz().sweep(gpu_ctx, oracle, list(range(11100, 11104)), verbose=False, spp=400, plastic=True) == []
 
 
 def _fuzz_rays():

@@ -1,7 +1,7 @@
 """Randomised parity sweep: random triangle soups (including slivers and near-degenerate triangles), random BSDFs of
 every type, one to three area emitters, optional environment, random integrator properties — the GPU film must equal
-the oracle's bit for bit on every one.  usage: fuzz_parity.py n_scenes [first_seed [spp [glass]]]  (glass: any fourth argument
-turns some meshes of every scene into smooth `dielectric`)"""
+the oracle's bit for bit on every one.  usage: fuzz_parity.py n_scenes [first_seed [spp [glass [plastic]]]]  (glass: a fourth argument
+other than 0 turns some meshes of every scene into smooth `dielectric`; plastic: a fifth one turns some into `plastic` / `roughplastic`)"""
 import importlib, sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import numpy as np
@@ -9,10 +9,13 @@ abi = importlib.import_module("misaki-render_amd.abi"); hm = importlib.import_mo
 import oracle_binding
 
 
-def random_scene(rng, glass=False, seed=0):
+def random_scene(rng, glass=False, seed=0, plastic=False):
     """glass=True turns some meshes into the smooth `dielectric` (emitters included: glass that emits); what becomes glass is drawn
     from a generator of its own, made from `seed`, so that `rng` is consumed exactly as without it: a seed's scene with
-    glass=False is the scene it always was, and with glass=True it is that scene with some BSDFs exchanged."""
+    glass=False is the scene it always was, and with glass=True it is that scene with some BSDFs exchanged.
+    plastic=True does the same for `plastic` and `roughplastic`, from another generator of its own: a relative index in [1, 2.6]
+    (sometimes exactly 1), `nonlinear`, alpha 10**U(-4, -0.3), an rgb / uniform / checkerboard base, a specular_reflectance that is 0,
+    a constant, an rgb or a table, `twosided`, and sometimes a constant-opacity `mask` over it."""
     meshes = []
     n_mesh = rng.randint(3, 9)
     n_light = rng.randint(1, 4)
@@ -137,6 +140,41 @@ def random_scene(rng, glass=False, seed=0):
                       "specular_reflectance": tint(), "specular_transmittance": tint()}
             if isinstance(m.reflectance, hm.Regular) or np.isscalar(m.reflectance):
                 m.reflectance = (0.5, 0.5, 0.5)                                        # (unused by the BSDF)
+    if plastic:
+        prng = np.random.RandomState((int(seed) * 2246822519 + 0x91a571c) % (2 ** 32))
+        n_plastic = 0
+        for k, m in enumerate(meshes):
+            # every third mesh on average, and at least one per scene (the last one, if none was drawn before it)
+            if prng.randint(0, 3) and not (n_plastic == 0 and k == len(meshes) - 1):
+                continue
+            n_plastic += 1
+            kind = prng.randint(0, 4)
+            if kind == 0:
+                base = float(prng.choice([0.0, 1.0, prng.uniform(0.05, 0.95)]))          # `uniform`
+            elif kind == 1:
+                mat = np.zeros(16)
+                mat[[0, 1, 2, 4, 5, 6]] = prng.uniform(-12, 12, 6) * (prng.uniform(size=6) < 0.8)
+                mat[15] = 1
+                base = {"type": "checkerboard", "color0": tuple(float(x) for x in prng.uniform(0.02, 0.98, 3)), "color1": tuple(float(x) for x in prng.uniform(0.02, 0.98, 3)),
+                        "matrix": [float(np.float32(x)) for x in mat]}
+            else:
+                base = tuple(float(x) for x in prng.uniform(0.05, 0.95, 3))               # rgb
+            kind = prng.randint(0, 5)
+            if kind == 0:
+                coat = 0.0                                                                # no coat at all: ssw = 0
+            elif kind == 1:
+                coat = float(prng.uniform(0.2, 1.0))
+            elif kind == 2:
+                coat = hm.Regular(360.0, 830.0, prng.uniform(0.2, 1.0, int(prng.choice([2, 7, 31]))).astype(np.float32))
+            else:
+                coat = tuple(float(x) for x in prng.uniform(0.05, 1.0, 3))
+            spec = {"type": "plastic", "diffuse_reflectance": base, "specular_reflectance": coat, "int_ior": 1.0 if prng.randint(0, 10) == 0 else float(prng.uniform(1.0, 2.6)),
+                    "ext_ior": 1.0, "nonlinear": bool(prng.randint(0, 2)), "twosided": bool(prng.randint(0, 2))}
+            if prng.randint(0, 2):
+                spec.update(type="roughplastic", alpha=float(10 ** prng.uniform(-4, -0.3)))
+            m.bsdf = {"type": "mask", "opacity": float(prng.choice([0.25, 0.5, 0.9, 1.0])), "bsdf": spec} if prng.randint(0, 4) == 0 else spec
+            if isinstance(m.reflectance, hm.Regular) or np.isscalar(m.reflectance):
+                m.reflectance = (0.5, 0.5, 0.5)                                        # (unused by the BSDF)
     flat = hm.flatten(meshes, fw, fh, env=env, camera=camera, filter_stddev=stddev, crop=crop)
     # vertex normals (perturbed face normals) and texture coordinates on some meshes: mesh.cpp:68-96
     verts, faces = flat.vertices, flat.faces
@@ -188,11 +226,11 @@ def random_params(rng):
     return kw
 
 
-def sweep(ctx, orc, seeds, verbose=True, spp=None, glass=False):
+def sweep(ctx, orc, seeds, verbose=True, spp=None, glass=False, plastic=False):
     bad = []
     for s in seeds:
         rng = np.random.RandomState(s)
-        flat = random_scene(rng, glass=glass, seed=s)
+        flat = random_scene(rng, glass=glass, seed=s, plastic=plastic)
         kw = random_params(rng)
         if spp:
             kw["spp"] = spp
@@ -219,6 +257,6 @@ if __name__ == "__main__":
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 50
     seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     spp = int(sys.argv[3]) if len(sys.argv) > 3 else None        # optional: samples per pixel for every scene
-    bad = sweep(abi.Context(0), oracle_binding.load(), range(seed0, seed0 + n), spp=spp or None, glass=len(sys.argv) > 4)
+    bad = sweep(abi.Context(0), oracle_binding.load(), range(seed0, seed0 + n), spp=spp or None, glass=len(sys.argv) > 4 and sys.argv[4] != "0", plastic=len(sys.argv) > 5)
     print("fuzz: %d scenes, %d with a film different from the oracle's" % (n, len(bad)))
     sys.exit(1 if bad else 0)
