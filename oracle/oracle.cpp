@@ -106,7 +106,19 @@
  *            two closed forms of each plastic are lit by a sun, and the twin has to render them.  Delta lights like the point light
  *            (D14: weight 1; D15: such a scene counts a `constant` sky with its own density); the refusals of msk_light_desc; a
  *            scene whose spot or sun comes without its descriptor, or an emitter type this file does not know, is refused where it
- *            ran the area light's code before.  Their parity scenes, tallies and the lens are a later step.
+ *            ran the area light's code before.  Their tallies (spot_beam / _ramp / _dark, spot_ / sun_occluded / _unoccluded, and the
+ *            direct integrator's light_spot_* / light_sun_*) tell the falloff's three branches and the three delta lights apart.
+ *   D24      the `thinlens` sensor, written from the six steps at msk_lens_desc in msk_gpu.h (tests/lens_ref.py is the second witness),
+ *            not from the device's code: near_p as the pinhole computes it; the lens point from this file's own
+ *            square_to_uniform_disk_concentric times R; the focus point near_p (f / near_p.z); the direction normalized in camera
+ *            space, tnear / tfar from its z; origin and direction through apply_point / apply_vector.  The aperture sample is pair 2 of
+ *            the sample's key under MSK_RNG_COUNTER and no other draw moves; R = 0 goes through this code; a scene without a lens keeps
+ *            camera_ray as it was.  Every render entry point refuses a lens scene under MSK_RNG_PCG_BLOCK (the library:
+ *            MSK_ERR_UNSUPPORTED); scene creation refuses what msk_lens_desc lists.  A scene with a lens counts a `constant` sky
+ *            with its own density (D15), whatever else it holds: msk_lens_desc gives it kernels of its own that carry the mask code,
+ *            and msk_mask_desc says "A `constant` sky counts with the density of the ray's own direction, as in every scene that
+ *            runs the kernels of msk_point_desc" (D22 reads the plastics the same way).  Found by the randomised sweep: the twin
+ *            kept D9's stale record for a lens over a `constant` sky and nothing else, and every such scene's film differed.
  */
 #include "oracle_math.h"
 #include "msk_gpu.h"
@@ -174,11 +186,14 @@ struct Scene {
     struct Mask { int filter = -1; float opacity = 1.f; float to_uv[6]; uint32_t W = 0, H = 0; std::vector<float> values; };
     std::vector<Mask> masks;
     bool any_mask = false;
-    bool own_density_sky = false;          // D15: a point emitter, a `conductor` entry, a mask or a plastic (D22) is in the scene
+    bool own_density_sky = false;          // D15: a point emitter, a `conductor` entry, a mask or a plastic (D22) is in the scene, or it has a lens (D24)
     // D20: {fdr_int, ssw} per BSDF entry ({0, 0} for an entry that is no plastic)
     struct PlasticK { float fdr_int = 0.f, ssw = 0.f; };
     std::vector<PlasticK> plastic_k;
     bool any_plastic = false;
+    // msk_lens_desc (D24); has_lens false: the pinhole camera of msk_camera_desc alone
+    bool has_lens = false;
+    float lens_radius = 0.f, lens_focus = 0.f;
 
     std::vector<BVHNode> nodes;
     std::vector<uint32_t> tri_order;
@@ -520,10 +535,15 @@ static bool scene_extensions(Scene *sc, const msk_scene_desc *d, const msk_scene
     return true;
 }
 
-static Scene *scene_from_desc(const msk_scene_desc *d, const msk_scene_masks *em = nullptr, uint32_t n_lights = 0, const msk_light_desc *lights = nullptr) {
+static Scene *scene_from_desc(const msk_scene_desc *d, const msk_scene_masks *em = nullptr, uint32_t n_lights = 0, const msk_light_desc *lights = nullptr,
+                              const msk_lens_desc *lens = nullptr) {
     if (!bsdfs_acceptable(d)) return nullptr;
+    // msk_lens_desc: "aperture_radius negative, NaN or infinite; focus_distance not finite or not greater than 0"
+    if (lens && (!(std::isfinite(lens->aperture_radius) && lens->aperture_radius >= 0.f) || !(std::isfinite(lens->focus_distance) && lens->focus_distance > 0.f))) return nullptr;
     Scene *sc = new Scene();
+    if (lens) { sc->has_lens = true; sc->lens_radius = lens->aperture_radius; sc->lens_focus = lens->focus_distance; }
     if (!scene_extensions(sc, d, em, n_lights, lights)) { delete sc; return nullptr; }
+    if (sc->has_lens) sc->own_density_sky = true;                  // D24: the lens' kernels carry the mask code and its sky rule
     if (d->n_texels) sc->texels.assign(d->texels, d->texels + (size_t) d->n_texels * 3);
     sc->meshes.assign(d->meshes, d->meshes + d->n_meshes);
     sc->bsdfs.assign(d->bsdfs, d->bsdfs + d->n_bsdfs);
@@ -643,7 +663,14 @@ enum PathTally { kTallyNullLobe, kTallyEmitterAfterNull, kTallyEmitterAfterDelta
                  kTallyPlasticBackFace,                       // a twosided entry of either type met from the back
                  kTallyNullOverPlastic,                       // a mask's null lobe at an entry whose nested BSDF is a plastic of either type
                  kTallyRRAfterCoat,                           // Russian roulette ended the path after a coat sample of either type
+                 // the spot's falloff, the three delta lights told apart and the lens (D23, D24), appended; kTallyPointOccluded / Unoccluded
+                 // keep counting every delta light
+                 kTallySpotBeam, kTallySpotRamp,              // a spot's next-event sample with c >= cos_beam / strictly inside the ramp with f != 0
+                 kTallySpotDark,                              // ... with f == 0: pdf 0, no shadow ray
+                 kTallySpotOccluded, kTallySpotUnoccluded, kTallySunOccluded, kTallySunUnoccluded,
+                 kTallyLensDiskFirst, kTallyLensDiskSecond,   // the concentric map's x x > y y branch / the other one, per camera ray of a render
                  kTallyCount };
+static const int kTallyCountPlastics = (int) kTallySpotBeam;     // what msk_oracle_path_tally_count_all answered when it was introduced
 static std::atomic<uint64_t> g_path[kTallyCount];
 struct PathTallies { uint64_t v[kTallyCount] = {}; };
 static thread_local PathTallies tl_path;
@@ -659,7 +686,11 @@ enum DirectTally { kDirPrimaryMissEnv, kDirPrimaryEmitterSeen, kDirPrimaryEmitte
                    kDirBsdfEmitterFrontMis,   // an area emitter's front with 0 < w_b < 1
                    kDirBsdfEmitterBack, kDirBsdfNonEmitter, kDirBsdfMissImage, kDirBsdfMissConstant, kDirBsdfMissNothing,
                    kDirBsdfEmitterAfterDelta, // an emitter or environment after a delta lobe: p_e = 0, weight exactly 1
+                   // appended: the light loop tells spot from sun from point (kDirLightPointVisible / Occluded keep counting every delta light)
+                   kDirLightSpotVisible, kDirLightSpotOccluded, kDirLightSpotDark,      // Dark: f == 0, the sample is skipped
+                   kDirLightSunVisible, kDirLightSunOccluded, kDirLightPointOnlyVisible, kDirLightPointOnlyOccluded,
                    kDirTallyCount };
+static const int kDirTallyCountFirst = (int) kDirLightSpotVisible;      // the twenty-one msk_oracle_direct_tally_count keeps answering for
 static std::atomic<uint64_t> g_direct[kDirTallyCount];
 struct DirectTallies { uint64_t v[kDirTallyCount] = {}; };
 static thread_local DirectTallies tl_direct;
@@ -913,8 +944,28 @@ static V3 apply_vector(const float m[16], V3 v) {  // transform.h:123-125, 3x3 b
     return mk3(m[0] * v.x + (m[1] * v.y + m[2] * v.z), m[4] * v.x + (m[5] * v.y + m[6] * v.z),
                m[8] * v.x + (m[9] * v.y + m[10] * v.z));
 }
-static Ray camera_ray(const Scene &sc, float wavelength_sample, V2 pos, S4 *wl, S4 *weight) {
+// msk_gpu.h at msk_lens_desc (D24), steps 1 to 6, each fp32 operation on its own.  `counted`: a render's ray (the disk map's branch is tallied)
+static Ray lens_ray(const Scene &sc, V2 pos, V2 aperture, bool counted) {
+    const V3 near_p = apply_point(sc.camera.sample_to_camera, mk3(pos.x, pos.y, 0.f));                 // 1
+    int branch = 0;
+    const V2 disk = square_to_uniform_disk_concentric(aperture, &branch);                                // 2
+    if (counted && branch) tally(branch == 1 ? kTallyLensDiskFirst : kTallyLensDiskSecond);              // (the branch the map itself reports)
+    const float lx = disk.x * sc.lens_radius, ly = disk.y * sc.lens_radius;
+    const float ft = sc.lens_focus / near_p.z;                                                            // 3
+    const V3 fp = mk3(near_p.x * ft, near_p.y * ft, near_p.z * ft);
+    const V3 dl = normalized(mk3(fp.x - lx, fp.y - ly, fp.z));                                            // 4
+    const float inv_z = 1.f / dl.z;
+    Ray ray;
+    ray.mint = sc.camera.near_clip * inv_z;
+    ray.maxt = sc.camera.far_clip * inv_z;
+    ray.o = apply_point(sc.camera.to_world, mk3(lx, ly, 0.f));                                            // 5
+    ray.d = apply_vector(sc.camera.to_world, dl);                                                         // 6
+    return ray;
+}
+// aperture: read by a scene with a lens only
+static Ray camera_ray(const Scene &sc, float wavelength_sample, V2 pos, S4 *wl, S4 *weight, V2 aperture = V2{0.5f, 0.5f}, bool counted = false) {
     sample_wavelength(wavelength_sample, wl, weight);              // perspective.cpp:26-28
+    if (sc.has_lens) return lens_ray(sc, pos, aperture, counted);
     V3 near_p = apply_point(sc.camera.sample_to_camera, mk3(pos.x, pos.y, 0.f));
     V3 d = normalized(near_p);
     float inv_z = 1.f / d.z;
@@ -1004,7 +1055,7 @@ static V3 env_sample(const Scene::Envmap &m, V2 u2, V2 *uv, float *pdf) {
     return mk3(r[0] * lx + (r[1] * ly + r[2] * lz), r[3] * lx + (r[4] * ly + r[5] * lz), r[6] * lx + (r[7] * ly + r[8] * lz));
 }
 
-struct DirectSample { V3 p, n, d; float dist, pdf; int emitter; bool point = false; };
+struct DirectSample { V3 p, n, d; float dist, pdf; int emitter; bool point = false; int falloff = 0; };      // falloff (tallies only): a spot's branch, 1 beam, 2 ramp, 3 dark
 
 // core/distribution.h:106-116 Distribution1D::sample / sample_reuse
 static uint32_t distr_sample(const std::vector<float> &cdf, float u) {
@@ -1043,11 +1094,11 @@ static DirectSample emitter_sample_direct(const Scene &sc, int e, const Interact
         if (ds.pdf != 0.f) {
             const float c = -(ds.d.x * l.direction.x + (ds.d.y * l.direction.y + ds.d.z * l.direction.z));
             float f;
-            if (c >= l.cos_beam) f = 1.f;
+            if (c >= l.cos_beam) { f = 1.f; ds.falloff = 1; }
             else if (c <= l.cos_cutoff) f = 0.f;
-            else { const float t = (c - l.cos_cutoff) / (l.cos_beam - l.cos_cutoff); f = (t * t) * (3.f - 2.f * t); }
+            else { const float t = (c - l.cos_cutoff) / (l.cos_beam - l.cos_cutoff); f = (t * t) * (3.f - 2.f * t); ds.falloff = 2; }
             *spec = *spec * f;
-            if (f == 0.f) { ds.pdf = 0.f; *spec = s4(0.f); }
+            if (f == 0.f) { ds.pdf = 0.f; *spec = s4(0.f); ds.falloff = 3; }
         }
         return ds;
     }
@@ -1660,6 +1711,7 @@ static S4 path_sample(const Scene &sc, Sampler &sampler, Ray ray, S4 wl, const m
             S4 emitter_val, unoccluded = s4(0.f);
             bool occluded = false;
             ds = sample_emitter_direct(sc, si, u, wl, &emitter_val, &cnt.shadow_rays, &unoccluded, &occluded);
+            if (ds.falloff) tally(ds.falloff == 1 ? kTallySpotBeam : ds.falloff == 2 ? kTallySpotRamp : kTallySpotDark);
             if (ds.pdf != 0.f) {
                 V3 wo = si.sh.to_local(ds.d), wi_s = si.wi;
                 bool flipped;
@@ -1674,6 +1726,9 @@ static S4 path_sample(const Scene &sc, Sampler &sampler, Ray ray, S4 wl, const m
                     const S4 term = throughput * unoccluded * bsdf_val * weight;
                     if (term.v[0] != 0.f || term.v[1] != 0.f || term.v[2] != 0.f || term.v[3] != 0.f) { has_shadow = true; tally(kTallyShadowNonzero); }
                     if (ds.point) tally(occluded ? kTallyPointOccluded : kTallyPointUnoccluded);
+                    const int32_t etype = sc.emitters[ds.emitter].type;
+                    if (etype == MSK_EMITTER_SPOT) tally(occluded ? kTallySpotOccluded : kTallySpotUnoccluded);
+                    if (etype == MSK_EMITTER_DIRECTIONAL) tally(occluded ? kTallySunOccluded : kTallySunUnoccluded);
                 }
                 if (g_trace_path)
                     std::printf("  d%d NEE: ds.pdf %.9g bsdf_pdf %.9g w %.9g emitter_val %.9g bsdf_val %.9g %.9g %.9g %.9g thr %.9g wo_local %.9g %.9g %.9g wi %.9g %.9g %.9g\n", depth, ds.pdf,
@@ -1854,6 +1909,7 @@ static S4 direct_sample(const Scene &sc, Sampler &sampler, Ray ray, S4 wl, const
             if (etype == MSK_EMITTER_CONSTANT) tally(kDirLightConstantSky);
             if (etype == MSK_EMITTER_ENVMAP) tally(kDirLightImage);
             if (etype == MSK_EMITTER_AREA && ds.pdf == 0.f) tally(kDirLightAreaBack);
+            if (ds.falloff == 3) tally(kDirLightSpotDark);
             if (ds.pdf != 0.f) {
                 V3 wo = si.sh.to_local(ds.d);
                 if (flipped) wo.z *= -1.f;
@@ -1867,6 +1923,9 @@ static S4 direct_sample(const Scene &sc, Sampler &sampler, Ray ray, S4 wl, const
                     ++cnt.shadow_rays;
                     lt.shadow = true; lt.occluded = occluded;
                     if (ds.point) tally(occluded ? kDirLightPointOccluded : kDirLightPointVisible);
+                    if (etype == MSK_EMITTER_SPOT) tally(occluded ? kDirLightSpotOccluded : kDirLightSpotVisible);
+                    if (etype == MSK_EMITTER_DIRECTIONAL) tally(occluded ? kDirLightSunOccluded : kDirLightSunVisible);
+                    if (etype == MSK_EMITTER_POINT) tally(occluded ? kDirLightPointOnlyOccluded : kDirLightPointOnlyVisible);
                     if (etype == MSK_EMITTER_AREA) tally(occluded ? kDirLightAreaOccluded : kDirLightAreaVisible);
                     if (!occluded) {
                         term = term / fN;
@@ -1940,6 +1999,10 @@ static S4 direct_sample(const Scene &sc, Sampler &sampler, Ray ray, S4 wl, const
     return result;
 }
 // what the library refuses of a `direct` call (msk_gpu.h): 0 when it is taken
+// D24: a lens scene under MSK_RNG_PCG_BLOCK (the reference's sampler draws no aperture sample that could pin that mode)
+static int lens_refusal(const Scene &sc, const msk_render_params &prm) {
+    return sc.has_lens && prm.rng_mode != MSK_RNG_COUNTER ? MSK_ERR_UNSUPPORTED : 0;
+}
 static int direct_refusal(const Scene &sc, const msk_render_params &prm, const msk_direct_params &dp) {
     if (sc.any_mask) return MSK_ERR_UNSUPPORTED;
     if (sc.any_plastic) return MSK_ERR_UNSUPPORTED;                    // D22: as msk_gpu_render_direct does
@@ -2057,9 +2120,11 @@ static void render_sample(const Scene &sc, Sampler &sampler, V2 pos, const msk_r
     float jx, jy; sampler.pair(0, &jx, &jy);
     *position_sample = V2{pos.x + jx, pos.y + jy};
     float wavelength_sample = sampler.single(1, 0);
-    if (sampler.mode == MSK_RNG_PCG_BLOCK) { float a, b; sampler.pair(2, &a, &b); }   // aperture sample, unused
+    V2 aperture{0.5f, 0.5f};
+    if (sampler.mode == MSK_RNG_PCG_BLOCK) { float a, b; sampler.pair(2, &a, &b); }   // aperture sample, unused (a lens scene is refused in this mode)
+    else if (sc.has_lens) sampler.pair(2, &aperture.x, &aperture.y);                  // D24: pair 2 of the sample's key
     S4 wl, ray_weight;
-    Ray ray = camera_ray(sc, wavelength_sample, *position_sample, &wl, &ray_weight);
+    Ray ray = camera_ray(sc, wavelength_sample, *position_sample, &wl, &ray_weight, aperture, true);
     ++cnt.samples;
     S4 result;
     if (out_wl) *out_wl = wl;
@@ -2183,6 +2248,10 @@ extern "C" {
 // the ABI's own structs; NULL for what the library refuses at scene creation (scene_extensions)
 void *msk_oracle_scene_create_masks(const msk_scene_desc *d, const msk_scene_masks *em) { return scene_from_desc(d, em); }
 void *msk_oracle_scene_create(const msk_scene_desc *d) { return msk_oracle_scene_create_masks(d, nullptr); }
+// everything msk_scene_lens holds; the entry points above and below are this one with lens = NULL
+void *msk_oracle_scene_create_lens(const msk_scene_desc *d, const msk_scene_lens *el) {
+    return el ? scene_from_desc(d, &el->lights.masks, el->lights.n_lights, el->lights.lights, el->lens) : scene_from_desc(d, nullptr);
+}
 void *msk_oracle_scene_create_lights(const msk_scene_desc *d, const msk_scene_lights *el) {
     return el ? scene_from_desc(d, &el->masks, el->n_lights, el->lights) : scene_from_desc(d, nullptr);
 }
@@ -2190,9 +2259,20 @@ void *msk_oracle_scene_create_lights(const msk_scene_desc *d, const msk_scene_li
 // (these two keep answering for the fifteen tallies they always had, so that a caller written for them reads what it expects)
 int msk_oracle_path_tally_count() { return (int) kTallyPlasticCoat; }
 void msk_oracle_path_tallies(uint64_t *out) { path_flush(); for (int i = 0; i < kTallyPlasticCoat; ++i) out[i] = g_path[i].exchange(0); }
-// ... and these two for all of them, the plastics' ten behind the fifteen
-int msk_oracle_path_tally_count_all() { return (int) kTallyCount; }
-void msk_oracle_path_tallies_all(uint64_t *out) { path_flush(); for (int i = 0; i < kTallyCount; ++i) out[i] = g_path[i].exchange(0); }
+// ... and these two for twenty-five, the plastics' ten behind the fifteen.  The name is historical: they were all there were when the
+// pair was introduced, and a binding written then asserts the count; msk_oracle_path_tally_total / _tallies_first below read all of them
+int msk_oracle_path_tally_count_all() { return kTallyCountPlastics; }
+void msk_oracle_path_tallies_all(uint64_t *out) { path_flush(); for (int i = 0; i < kTallyCountPlastics; ++i) out[i] = g_path[i].exchange(0); }
+// ... and these two for every tally there is, however many are appended later: the caller says how many it knows (n <= total) and
+// reads and clears those; what it does not know stays untouched.  The two pairs above are this with n = 15 and n = 25, and keep
+// those answers so that a caller written for them reads what it expects.
+int msk_oracle_path_tally_total() { return (int) kTallyCount; }
+int msk_oracle_path_tallies_first(uint64_t *out, int n) {
+    if (n < 0 || n > (int) kTallyCount) return -1;
+    path_flush();
+    for (int i = 0; i < n; ++i) out[i] = g_path[i].exchange(0);
+    return 0;
+}
 
 // ---- known-answer hooks of the features restated from include/msk_gpu.h (shaped like msk_oracle_bsdf_sample2) ----
 static S4 load4(const float *p) { S4 r; for (int i = 0; i < 4; ++i) r.v[i] = p[i]; return r; }
@@ -2340,6 +2420,7 @@ void msk_oracle_set_trace(int on) { g_trace_path = on; }
 void msk_oracle_isect_counters(uint64_t *out8) { isect_flush(); for (int i = 0; i < 8; ++i) out8[i] = g_isect[i].exchange(0); }
 
 int msk_oracle_render(void *s, const msk_render_params *prm, float *film, msk_stats *stats, int n_threads) {
+    if (int rc = lens_refusal(*(Scene *) s, *prm)) return rc;
     Counters c;
     auto t0 = std::chrono::steady_clock::now();
     render(*(Scene *) s, *prm, film, &c, n_threads);
@@ -2360,6 +2441,7 @@ int msk_oracle_render_aov(void *s, const msk_render_params *prm, const int32_t *
         if (w < 0) return -1;
         spec.types.push_back(aov_types[i]); spec.channels += w;
     }
+    if (int rc = lens_refusal(*(Scene *) s, *prm)) return rc;
     Counters c;
     render(*(Scene *) s, *prm, film, &c, n_threads, &spec);
     if (stats) { std::memset(stats, 0, sizeof(*stats)); stats->samples = c.samples; stats->segments = c.segments; stats->shadow_rays = c.shadow_rays; stats->invalid_samples = c.invalid; }
@@ -2369,7 +2451,7 @@ int msk_oracle_render_aov(void *s, const msk_render_params *prm, const int32_t *
 int msk_oracle_sample_pixels(void *s, const msk_render_params *prm, uint64_t n_pixels, const int32_t *pixels,
                              float *out_xyz, float *out_pos) {
     const Scene &sc = *(Scene *) s;
-    if (prm->rng_mode != MSK_RNG_COUNTER) return -1;
+    if (prm->rng_mode != MSK_RNG_COUNTER) return MSK_ERR_UNSUPPORTED;      // counter RNG only, as msk_gpu_sample_pixels
     Counters cnt;
     for (uint64_t i = 0; i < n_pixels; ++i) {
         int x = pixels[2 * i], y = pixels[2 * i + 1];
@@ -2390,6 +2472,7 @@ int msk_oracle_sample_pixels(void *s, const msk_render_params *prm, uint64_t n_p
 // MSK_RNG_PCG_BLOCK, a count above 4096, both counts 0
 int msk_oracle_render_direct(void *s, const msk_render_params *prm, const msk_direct_params *direct, float *film, msk_stats *stats, int n_threads) {
     const Scene &sc = *(Scene *) s;
+    if (int rc = lens_refusal(sc, *prm)) return rc;
     if (int rc = direct_refusal(sc, *prm, *direct)) return rc;
     Counters c;
     auto t0 = std::chrono::steady_clock::now();
@@ -2406,6 +2489,7 @@ int msk_oracle_render_direct(void *s, const msk_render_params *prm, const msk_di
 int msk_oracle_sample_pixels_direct(void *s, const msk_render_params *prm, const msk_direct_params *direct, uint64_t n_pixels, const int32_t *pixels,
                                     float *out_xyz, float *out_pos) {
     const Scene &sc = *(Scene *) s;
+    if (int rc = lens_refusal(sc, *prm)) return rc;
     if (int rc = direct_refusal(sc, *prm, *direct)) return rc;
     const uint32_t stride = prm->sample_stride ? prm->sample_stride : 1;
     Counters cnt;
@@ -2434,6 +2518,7 @@ int msk_oracle_direct_terms(void *s, const msk_render_params *prm, const msk_dir
                             float *out_head, int32_t *out_counts, int32_t *out_light_i, float *out_light_f, int32_t *out_bsdf_i, float *out_bsdf_f,
                             int32_t *out_draws) {
     const Scene &sc = *(Scene *) s;
+    if (int rc = lens_refusal(sc, *prm)) return rc;
     if (int rc = direct_refusal(sc, *prm, *direct)) return rc;
     std::vector<uint32_t> log;
     Sampler sampler; sampler.mode = MSK_RNG_COUNTER; sampler.log = &log;
@@ -2462,8 +2547,12 @@ int msk_oracle_direct_terms(void *s, const msk_render_params *prm, const msk_dir
     return 0;
 }
 // reads and clears the direct tallies (see DirectTally): out receives msk_oracle_direct_tally_count() values
-int msk_oracle_direct_tally_count() { return (int) kDirTallyCount; }
-void msk_oracle_direct_tallies(uint64_t *out) { direct_flush(); for (int i = 0; i < kDirTallyCount; ++i) out[i] = g_direct[i].exchange(0); }
+// (these two keep answering for their twenty-one)
+int msk_oracle_direct_tally_count() { return kDirTallyCountFirst; }
+void msk_oracle_direct_tallies(uint64_t *out) { direct_flush(); for (int i = 0; i < kDirTallyCountFirst; ++i) out[i] = g_direct[i].exchange(0); }
+// ... and these two for all of them, the delta lights' seven behind the twenty-one
+int msk_oracle_direct_tally_count_all() { return (int) kDirTallyCount; }
+void msk_oracle_direct_tallies_all(uint64_t *out) { direct_flush(); for (int i = 0; i < kDirTallyCount; ++i) out[i] = g_direct[i].exchange(0); }
 
 int msk_oracle_trace_closest(void *s, uint64_t n, const float *rays, float *out_hit) {
     const Scene &sc = *(Scene *) s;
@@ -2624,11 +2713,26 @@ void msk_oracle_perspective_camera(float fov, float near_, float far_, int width
     }
     to_world16[12] = 0; to_world16[13] = 0; to_world16[14] = 0; to_world16[15] = 1;
 }
+// (a scene with a lens: the ray through the lens' centre, u = (0.5, 0.5); msk_oracle_camera_sample takes the aperture sample)
 void msk_oracle_camera_ray(void *s, float wavelength_sample, float px, float py, float *out_ray8, float *wl4, float *w4) {
     S4 a, b; Ray r = camera_ray(*(Scene *) s, wavelength_sample, V2{px, py}, &a, &b);
     out_ray8[0] = r.o.x; out_ray8[1] = r.o.y; out_ray8[2] = r.o.z; out_ray8[3] = r.mint;
     out_ray8[4] = r.d.x; out_ray8[5] = r.d.y; out_ray8[6] = r.d.z; out_ray8[7] = r.maxt;
     for (int i = 0; i < 4; ++i) { wl4[i] = a.v[i]; w4[i] = b.v[i]; }
+}
+// the camera ray of n film positions, shaped like msk_gpu_camera_sample: film_pos n * 2, aperture_u n * 2 (read only by a scene with a
+// lens, may be NULL otherwise), out n * 8 = {o, tnear} {d, tfar}.  No tally moves.
+int msk_oracle_camera_sample(void *s, uint64_t n, const float *film_pos2, const float *aperture_u2, float *out8) {
+    const Scene &sc = *(Scene *) s;
+    if (sc.has_lens && !aperture_u2) return -1;
+    for (uint64_t i = 0; i < n; ++i) {
+        S4 a, b;
+        const V2 u = sc.has_lens ? V2{aperture_u2[2 * i], aperture_u2[2 * i + 1]} : V2{0.5f, 0.5f};
+        const Ray r = camera_ray(sc, 0.5f, V2{film_pos2[2 * i], film_pos2[2 * i + 1]}, &a, &b, u, false);
+        float *o = out8 + 8 * i;
+        o[0] = r.o.x; o[1] = r.o.y; o[2] = r.o.z; o[3] = r.mint; o[4] = r.d.x; o[5] = r.d.y; o[6] = r.d.z; o[7] = r.maxt;
+    }
+    return 0;
 }
 int msk_oracle_spiral_blocks(int w, int h, int block_size, int max_out, int32_t *out4) {
     auto b = spiral_blocks(w, h, block_size);

@@ -327,17 +327,21 @@ static inline V3 square_to_uniform_sphere(V2 sample) {
 }
 static const float kInvFourPi = float(0.07957747154594766788);
 // core/warp.h:17-32
-static inline V2 square_to_uniform_disk_concentric(V2 sample) {
+// branch (may be NULL; tallies only): which of the three the pair took, 0 the centre, 1 x x > y y, 2 the other
+static inline V2 square_to_uniform_disk_concentric(V2 sample, int *branch = nullptr) {
     float x = 2.f * sample.x - 1.f;
     float y = 2.f * sample.y - 1.f;
     float phi, r;
     if (x == 0 && y == 0) {
         r = phi = 0;
+        if (branch) *branch = 0;
     } else if (x * x > y * y) {
         r = x;
+        if (branch) *branch = 1;
         phi = (kPi / 4.f) * (y / x);
     } else {
         r = y;
+        if (branch) *branch = 2;
         phi = (kPi / 2.f) - (x / y) * (kPi / 4.f);
     }
     float s, c;

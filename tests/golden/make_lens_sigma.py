@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Writes tests/golden/lens_sigma.json: the per-sample standard deviation of X, Y, Z of the furnace of
 tests/test_thinlens.py::test_a_lens_does_not_change_radiance under the "direct" integrator at (1, 1), measured on the CPU oracle's
-`direct` with 2^20 samples, as make_radiometry_sigma.py measures the "path" scenarios.  The oracle has no lens: the furnace's
-radiance is the same from every point and in every direction, so the pinhole's samples have the distribution the lens' have.  The
+`direct` with 2^20 samples, as make_radiometry_sigma.py measures the "path" scenarios.  It is measured through the
+pinhole: the furnace's radiance is the same from every point and in every direction, so the pinhole's samples have the distribution
+the lens' have.  The
 mean is recorded for orientation only; no test reads it.  Seeds differ from the tests' own."""
 import importlib
 import json

@@ -14,6 +14,17 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+class OracleRefusal(ValueError):
+    """a render call the oracle refuses as the library does (MSK_ERR_UNSUPPORTED: a lens scene under MSK_RNG_PCG_BLOCK, sample_pixels
+    under MSK_RNG_PCG_BLOCK).  Any other non-zero return of those calls is a failure, not a refusal"""
+
+
+def _taken(rc):
+    if rc == -5:                                                             # MSK_ERR_UNSUPPORTED
+        raise OracleRefusal("the oracle refuses this call (MSK_ERR_UNSUPPORTED), as the library does")
+    assert rc == 0, rc
+
+
 class Oracle:
     def __init__(self, lib, abi):
         self.lib, self.abi = lib, abi
@@ -24,12 +35,17 @@ class Oracle:
         lib.msk_oracle_scene_create_masks.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(abi.SceneMasks)]
         lib.msk_oracle_scene_create_lights.restype = vp
         lib.msk_oracle_scene_create_lights.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(abi.SceneLights)]
+        lib.msk_oracle_scene_create_lens.restype = vp
+        lib.msk_oracle_scene_create_lens.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(abi.SceneLens)]
+        lib.msk_oracle_camera_sample.argtypes = [vp, C.c_uint64, vp, vp, vp]
         lib.msk_oracle_light_sample.argtypes = [vp, C.c_uint32, vp, vp, vp, vp]
         lib.msk_oracle_scene_destroy.argtypes = [vp]
         lib.msk_oracle_path_tally_count.restype = C.c_int
         lib.msk_oracle_path_tallies.argtypes = [vp]
         lib.msk_oracle_path_tally_count_all.restype = C.c_int
         lib.msk_oracle_path_tallies_all.argtypes = [vp]
+        lib.msk_oracle_path_tally_total.restype = C.c_int
+        lib.msk_oracle_path_tallies_first.argtypes = [vp, C.c_int]
         lib.msk_oracle_eval_texture.argtypes = [vp, C.c_uint32, vp, vp, vp]
         lib.msk_oracle_env_eval.argtypes = [vp, vp, vp, vp, vp]
         lib.msk_oracle_env_sample.argtypes = [vp, vp, vp, vp, vp]
@@ -52,6 +68,8 @@ class Oracle:
                                                 vp, vp, vp, vp, vp, vp, vp]
         lib.msk_oracle_direct_tally_count.restype = C.c_int
         lib.msk_oracle_direct_tallies.argtypes = [vp]
+        lib.msk_oracle_direct_tally_count_all.restype = C.c_int
+        lib.msk_oracle_direct_tallies_all.argtypes = [vp]
         lib.msk_oracle_trace_closest.argtypes = [vp, C.c_uint64, vp, vp]
         lib.msk_oracle_trace_any.argtypes = [vp, C.c_uint64, vp, vp]
         lib.msk_oracle_camera_ray.argtypes = [vp, C.c_float, C.c_float, C.c_float, vp, vp, vp]
@@ -180,7 +198,11 @@ class Oracle:
                     "segments_dropped", "segments_extra",
                     # the plastics' branches, appended: the first eleven names and the four counter tallies keep their places
                     "plastic_coat", "plastic_base", "emitter_after_coat", "roughplastic_coat", "roughplastic_base", "roughplastic_failed",
-                    "plastic_from_behind", "plastic_back_face", "null_over_plastic", "rr_after_coat")
+                    "plastic_from_behind", "plastic_back_face", "null_over_plastic", "rr_after_coat",
+                    # the spot's falloff, the delta lights told apart (point_unoccluded / point_occluded above keep counting every delta
+                    # light) and the lens' disk map, appended
+                    "spot_beam", "spot_ramp", "spot_dark", "spot_occluded", "spot_unoccluded", "sun_occluded", "sun_unoccluded",
+                    "lens_disk_first", "lens_disk_second")
 
     def path_tallies(self):
         """Reads and clears the oracle's path tallies (oracle.cpp: PathTally) -> dict.  Beside the named path events: the next-event
@@ -188,24 +210,28 @@ class Oracle:
         zero throughput (where the device's segment count may differ from the oracle's by one each); of those, the samples with a lobe,
         a zero throughput and no shadow ray pending (`segments_dropped`: the wavefront kernels end the path without a ray the oracle
         counts) and the failed samples with one pending (`segments_extra`: they keep the slot for one more, zero, ray)."""
-        n = self.lib.msk_oracle_path_tally_count_all()       # (msk_oracle_path_tally_count / _path_tallies keep to the first fifteen)
-        assert n == len(self.PATH_TALLIES) and self.lib.msk_oracle_path_tally_count() == 15
+        n = self.lib.msk_oracle_path_tally_total()           # (msk_oracle_path_tally_count / _count_all keep to the first fifteen / twenty-five)
+        assert n == len(self.PATH_TALLIES) and self.lib.msk_oracle_path_tally_count() == 15 and self.lib.msk_oracle_path_tally_count_all() == 25
         a = (C.c_uint64 * n)()
-        self.lib.msk_oracle_path_tallies_all(a)
+        assert self.lib.msk_oracle_path_tallies_first(a, n) == 0
         return dict(zip(self.PATH_TALLIES, [int(x) for x in a]))
 
     DIRECT_TALLIES = ("primary_miss_env", "primary_emitter_seen", "primary_emitter_hidden", "twosided_flipped", "light_skipped_delta",
                       "light_area_visible", "light_area_occluded", "light_area_back", "light_constant_sky", "light_image", "light_point_visible",
                       "light_point_occluded", "light_last_emitter", "bsdf_not_traced", "bsdf_emitter_front_mis", "bsdf_emitter_back",
-                      "bsdf_non_emitter", "bsdf_miss_image", "bsdf_miss_constant", "bsdf_miss_nothing", "bsdf_emitter_after_delta")
+                      "bsdf_non_emitter", "bsdf_miss_image", "bsdf_miss_constant", "bsdf_miss_nothing", "bsdf_emitter_after_delta",
+                      # appended: the light loop tells spot from sun from point (light_point_visible / _occluded above keep counting every
+                      # delta light); light_spot_dark: f == 0, the sample is skipped
+                      "light_spot_visible", "light_spot_occluded", "light_spot_dark", "light_sun_visible", "light_sun_occluded",
+                      "light_point_only_visible", "light_point_only_occluded")
 
     def direct_tallies(self):
         """Reads and clears the oracle's tallies of the `direct` integrator (oracle.cpp: DirectTally) -> dict: which branches of
         direct_sample the renders since the last call reached"""
-        n = self.lib.msk_oracle_direct_tally_count()
-        assert n == len(self.DIRECT_TALLIES)
+        n = self.lib.msk_oracle_direct_tally_count_all()     # (msk_oracle_direct_tally_count / _direct_tallies keep to the first twenty-one)
+        assert n == len(self.DIRECT_TALLIES) and self.lib.msk_oracle_direct_tally_count() == 21
         a = (C.c_uint64 * n)()
-        self.lib.msk_oracle_direct_tallies(a)
+        self.lib.msk_oracle_direct_tallies_all(a)
         return dict(zip(self.DIRECT_TALLIES, [int(x) for x in a]))
 
     def gaussian_filter(self, stddev):
@@ -253,9 +279,10 @@ def _row(a, k):
 
 
 class OracleScene:
-    def __init__(self, orc, flat, envmap=None, points=None, masks=None, lights=None):
-        """flat's envmap, points, masks and lights are passed exactly as abi.Scene passes them (msk_scene_masks, and msk_scene_lights
-        for a scene with a spot or a directional emitter); a scene the library refuses at creation raises ValueError"""
+    def __init__(self, orc, flat, envmap=None, points=None, masks=None, lights=None, lens=None):
+        """flat's envmap, points, masks, lights and lens are passed exactly as abi.Scene passes them (msk_scene_masks, msk_scene_lights
+        for a scene with a spot or a directional emitter, msk_scene_lens for one with a `thinlens` sensor: a flat with a lens never
+        reaches the oracle as a pinhole); a scene the library refuses at creation raises ValueError"""
         self.orc, self.flat, self.abi = orc, flat, orc.abi
         abi = orc.abi
         self.envmap = envmap if envmap is not None else getattr(flat, "envmap", None)
@@ -273,7 +300,12 @@ class OracleScene:
         if lt is not None and not isinstance(lt, C.Array):
             lt = (abi.LightDesc * max(1, len(lt)))(*lt) if len(lt) else None
         self.lights = lt if (lt is not None and len(lt)) else None
-        if self.lights is not None:
+        self.lens = lens if lens is not None else getattr(flat, "lens", None)
+        if self.lens is not None:
+            el = abi.SceneLights(self.em, len(self.lights) if self.lights is not None else 0, self.lights)
+            self.eln = abi.SceneLens(el, C.pointer(self.lens))
+            self.h = orc.lib.msk_oracle_scene_create_lens(C.byref(flat.desc), C.byref(self.eln))
+        elif self.lights is not None:
             self.el = abi.SceneLights(self.em, len(self.lights), self.lights)
             self.h = orc.lib.msk_oracle_scene_create_lights(C.byref(flat.desc), C.byref(self.el))
         else:
@@ -314,6 +346,17 @@ class OracleScene:
             if self.orc.lib.msk_oracle_light_sample(self.h, int(emitter), _row(p, k), _row(wl, k), _row(dd, k), _row(val, k)) != 0:
                 raise ValueError("emitter %d is neither a spot nor a directional emitter" % emitter)
         return dd, val
+
+    def camera_sample(self, film_pos, aperture_u=None):
+        """as abi.Scene.camera_sample: film positions (n, 2) and, for a scene with a lens, aperture samples (n, 2) -> float32[n, 8] =
+        {o, tnear, d, tfar}; a pinhole scene ignores aperture_u"""
+        p = np.ascontiguousarray(film_pos, np.float32).reshape(-1, 2)
+        u = None if aperture_u is None else np.ascontiguousarray(aperture_u, np.float32).reshape(-1, 2)
+        assert u is None or len(u) == len(p)
+        out = np.empty((len(p), 8), np.float32)
+        if self.orc.lib.msk_oracle_camera_sample(self.h, len(p), _p(p), None if u is None else _p(u), _p(out)) != 0:
+            raise ValueError("a scene with a lens needs aperture_u")
+        return out
 
     def conductor_sample(self, bsdf, cos_theta_i, wavelengths):
         c, wl = np.ascontiguousarray(cos_theta_i, np.float32).reshape(-1), np.ascontiguousarray(wavelengths, np.float32).reshape(-1, 4)
@@ -385,8 +428,7 @@ class OracleScene:
         h, w = self._film_shape()
         film = np.zeros((h, w, 5), np.float32)
         st = self.abi.Stats()
-        rc = self.orc.lib.msk_oracle_render(self.h, C.byref(params), _p(film), C.byref(st), threads)
-        assert rc == 0
+        _taken(self.orc.lib.msk_oracle_render(self.h, C.byref(params), _p(film), C.byref(st), threads))
         return film, st
 
     def render_aov(self, params, aov_types, threads=8):
@@ -396,8 +438,7 @@ class OracleScene:
         h, w = self._film_shape()
         film = np.zeros((h, w, 5 + n_ch), np.float32)
         st = self.abi.Stats()
-        rc = self.orc.lib.msk_oracle_render_aov(self.h, C.byref(params), _p(types), len(types), _p(film), C.byref(st), threads)
-        assert rc == 0
+        _taken(self.orc.lib.msk_oracle_render_aov(self.h, C.byref(params), _p(types), len(types), _p(film), C.byref(st), threads))
         return film, st
 
     def sample_pixels(self, params, pixels):
@@ -405,8 +446,7 @@ class OracleScene:
         n = pixels.shape[0]
         xyz = np.zeros((n, params.spp, 3), np.float32)
         pos = np.zeros((n, params.spp, 2), np.float32)
-        rc = self.orc.lib.msk_oracle_sample_pixels(self.h, C.byref(params), n, _p(pixels), _p(xyz), _p(pos))
-        assert rc == 0
+        _taken(self.orc.lib.msk_oracle_sample_pixels(self.h, C.byref(params), n, _p(pixels), _p(xyz), _p(pos)))
         return xyz, pos
 
     # ---- the "direct" integrator, shaped like abi.Scene's calls; a call the library refuses raises ValueError

@@ -62,6 +62,38 @@ def test_random_scenes_are_valid_oracle_inputs(oracle, abi):
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32)) and np.isfinite(a).all() and a[..., 4].min() > 0 and st.invalid_samples == 0
         sc.close()
     assert {abi.MSK_BSDF_PLASTIC, abi.MSK_BSDF_ROUGHPLASTIC} <= seen
+    # with a `thinlens` sensor (lens=True) and with `spot` / `directional` emitters (lights=True): valid inputs, the option is in the
+    # scene, and nothing else of the scene moved: the lens leaves every byte of the flat as it was, the lights append emitters behind
+    # the scene's own.  A lens scene is refused under MSK_RNG_PCG_BLOCK.  Apertures of 0 and above, spots and suns occur over the seeds
+    radii, kinds = set(), set()
+    for s in (13001, 13003, 13004, 13005):                              # (13002 draws a table whose extrapolation goes negative: its film's minimum is
+                                                                        # below 0 with or without a lens, and through the lens three samples in 2^18 pass -1e-5)
+        plain = fz.random_scene(np.random.RandomState(s))
+        for opt in (dict(lens=True), dict(lights=True), dict(lens=True, lights=True)):
+            flat = fz.random_scene(np.random.RandomState(s), seed=s, **opt)
+            d, pd = flat.desc, plain.desc
+            assert (flat.lens is not None) == ("lens" in opt) and (flat.lights is not None) == ("lights" in opt) and plain.lens is None and plain.lights is None
+            assert np.array_equal(flat.vertices.view(np.uint32), plain.vertices.view(np.uint32)) and np.array_equal(flat.faces, plain.faces)
+            assert bytes(d.camera) == bytes(pd.camera) and bytes(d.film) == bytes(pd.film) and d.n_bsdfs == pd.n_bsdfs
+            assert all(bytes(d.bsdfs[i]) == bytes(pd.bsdfs[i]) for i in range(pd.n_bsdfs)) and all(bytes(d.emitters[i]) == bytes(pd.emitters[i]) for i in range(pd.n_emitters))
+            if "lights" in opt:
+                extra = [d.emitters[i].type for i in range(pd.n_emitters, d.n_emitters)]
+                assert 1 <= len(extra) <= 3 and set(extra) <= {abi.MSK_EMITTER_SPOT, abi.MSK_EMITTER_DIRECTIONAL} and len(flat.lights) == len(extra)
+                kinds |= set(extra)
+            else:
+                assert fz.scene_digest(flat) == fz.scene_digest(plain)
+            if "lens" in opt:
+                radii.add(flat.lens.aperture_radius > 0)
+            sc = oracle.scene(flat)
+            assert (sc.lens is not None) == ("lens" in opt)
+            a, st = sc.render(abi.render_params(spp=2, seed=s), threads=2)
+            b, _ = sc.render(abi.render_params(spp=2, seed=s), threads=3)
+            assert np.array_equal(a.view(np.uint32), b.view(np.uint32)) and np.isfinite(a).all() and a[..., 4].min() > 0 and st.invalid_samples == 0
+            if "lens" in opt:
+                with pytest.raises(ValueError):
+                    sc.render(abi.render_params(spp=2, seed=s, rng_mode=abi.MSK_RNG_PCG_BLOCK), threads=2)
+            sc.close()
+    assert radii == {False, True} and kinds == {abi.MSK_EMITTER_SPOT, abi.MSK_EMITTER_DIRECTIONAL}
 
 
 def test_the_seeds_of_the_regression_sweeps_still_make_their_scenes():
@@ -73,6 +105,11 @@ def test_the_seeds_of_the_regression_sweeps_still_make_their_scenes():
     assert sorted(int(k) for k in want) == list(range(5000, 5061)) + list(range(7000, 7008)) + [20657]
     moved = [int(k) for k, v in want.items() if fz.scene_digest(fz.random_scene(np.random.RandomState(int(k)))) != v]
     assert moved == []
+    # ... nor the lens and the spot / sun options: switched off by name, and the lens switched on (it is no part of the flat's
+    # bytes), three kept seeds still make the recorded bytes
+    for k in (5000, 7003, 20657):
+        for opt in (dict(lens=False, lights=False), dict(lens=True)):
+            assert fz.scene_digest(fz.random_scene(np.random.RandomState(k), seed=k, **opt)) == want[str(k)], (k, opt)
 
 
 def test_hit_acceptance_does_not_depend_on_the_tree(oracle):
@@ -142,6 +179,22 @@ def test_gpu_equals_oracle_on_random_scenes_with_plastic(gpu_ctx, oracle):
 @pytest.mark.gpu
 def test_gpu_equals_oracle_on_random_scenes_with_plastic_and_many_samples(gpu_ctx, oracle):
     assert _fuzz().sweep(gpu_ctx, oracle, list(range(11100, 11104)), verbose=False, spp=400, plastic=True) == []
+
+
+@pytest.mark.gpu
+def test_gpu_equals_oracle_on_random_scenes_with_a_lens(gpu_ctx, oracle):
+    """The sweep through a `thinlens` sensor (an aperture that is 0, small or as wide as the scene, focused before, inside or behind
+    it): the `_l` kernels with whatever else the generator makes, ragged films, crop windows and shards included"""
+    assert _fuzz().sweep(gpu_ctx, oracle, list(range(13000, 13040)), lens=True) == []
+
+
+@pytest.mark.gpu
+def test_gpu_equals_oracle_on_random_scenes_with_spots_and_suns(gpu_ctx, oracle):
+    """The sweep with one to three `spot` / `directional` emitters behind the scene's own; the second half of the seeds through a
+    lens as well, with plastics on some meshes: everything the `_l` kernels carry"""
+    fz = _fuzz()
+    assert fz.sweep(gpu_ctx, oracle, list(range(15000, 15020)), lights=True) == []
+    assert fz.sweep(gpu_ctx, oracle, list(range(15020, 15040)), lights=True, lens=True, plastic=True) == []
 
 
 def _fuzz_rays():

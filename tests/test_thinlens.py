@@ -1,8 +1,11 @@
 """The `thinlens` sensor (include/msk_gpu.h at msk_lens_desc): depth of field from the aperture sample.
 
-The oracle has no lens, so nothing here is a film of the oracle's.  Correctness rests on three things: the contract restated in
-numpy fp32 (lens_ref.py), which the probe must equal bit for bit; per-sample float64 expectations (an in-focus edge is sharp, an
-out-of-focus edge blurs by the circular segment of the lens that sees past it); and identities between kernels.
+Correctness rests on three things here: the contract restated in numpy fp32 (lens_ref.py), which the probe must equal bit for bit;
+per-sample float64 expectations (an in-focus edge is sharp, an out-of-focus edge blurs by the circular segment of the lens that sees
+past it); and identities between kernels.  The oracle restates the lens too (oracle.cpp, D24): test_lens_light_oracle_parity.py holds
+its twin to this file's restatement and float64 expectations (check_sharp, check_blur, run_lens_radiance and mix_expected take either
+side) and the device to the twin bit for bit, on the very scenes and parameters of `variant_reference` below, so the anchor of
+test_every_execution_variant is a film of the oracle's.
 
 CPU: the restatement against float64; validation, layout and exports as a stand-alone native program, plain and sanitized; the two
 flatteners; the launch plan.  GPU: probe = restatement; the sharp edge; the blurred edge; closed-form radiance through a lens under
@@ -288,8 +291,7 @@ def test_probe_equals_the_restatement(gpu_ctx, hostmirror, oracle, abi, cam):
 
 
 # ===================================================================================================== GPU 6: in focus it is sharp
-@pytest.mark.gpu
-def test_in_focus_it_is_sharp(gpu_ctx, hostmirror, abi):
+def check_sharp(make_scene, hostmirror, abi):
     """(6) An emitting screen fills the side x > x0 of the focus plane z = f; x0 projects to column 32.7.  max_depth = 1: emission
     only.  The same seed on a screen that fills the view gives every sample's lit value W_i (the radiance is uniform, the value is a
     function of the sample's wavelengths alone).  Every sample is all zeros or W_i, bit for bit, and it is lit exactly when the focus
@@ -301,7 +303,7 @@ def test_in_focus_it_is_sharp(gpu_ctx, hostmirror, abi):
     asserted first, from the film positions alone (m is 7e-4 of a pixel's width: 0.03 % of four columns)."""
     edge, full, x0, side = edge_setup(hostmirror, abi, FOCUS)
     prm = abi.render_params(spp=64, seed=21, max_depth=1)
-    ge, gf = abi.Scene(gpu_ctx, edge), abi.Scene(gpu_ctx, full)
+    ge, gf = make_scene(edge), make_scene(full)
     try:
         xyz, pos = ge.sample_pixels(prm, EDGE_PIXELS)
         w, wpos = gf.sample_pixels(prm, EDGE_PIXELS)
@@ -321,17 +323,24 @@ def test_in_focus_it_is_sharp(gpu_ctx, hostmirror, abi):
     assert 0.3 < lit.mean() < 0.7                                  # the edge runs through the four columns
 
 
-# ===================================================================================================== GPU 7: out of focus it blurs
 @pytest.mark.gpu
-@pytest.mark.parametrize("depth", [0.6, 1.6])
-def test_out_of_focus_it_blurs_by_the_right_amount(gpu_ctx, hostmirror, abi, depth):
+def test_in_focus_it_is_sharp(gpu_ctx, hostmirror, abi):
+    """(6) check_sharp on the device"""
+    check_sharp(lambda flat: abi.Scene(gpu_ctx, flat), hostmirror, abi)
+
+
+# ===================================================================================================== GPU 7: out of focus it blurs
+BLUR_DEPTHS = [0.6, 1.6]
+
+
+def check_blur(make_scene, hostmirror, abi, depth):
     """(7) the screen at z_e = 0.6 f and 1.6 f.  Sample i is lit with probability p_i, the share of the lens disk whose ray towards the
     focus point F passes the edge: a.x (1 - z_e / f) + F.x z_e / f > x0, a circular segment (lens_ref.lit_fraction, float64).
     |sum(lit_i) - sum(p_i)| <= 5 sqrt(sum p_i (1 - p_i)) + the change of sum(p_i) when x0 moves by +- m (test 6's m).  2^16 samples."""
     z_e = depth * FOCUS
     edge, full, x0, side = edge_setup(hostmirror, abi, z_e)
     prm = abi.render_params(spp=256, seed=23, max_depth=1)
-    ge, gf = abi.Scene(gpu_ctx, edge), abi.Scene(gpu_ctx, full)
+    ge, gf = make_scene(edge), make_scene(full)
     try:
         xyz, pos = ge.sample_pixels(prm, EDGE_PIXELS)
         w, _ = gf.sample_pixels(prm, EDGE_PIXELS)
@@ -355,6 +364,13 @@ def test_out_of_focus_it_blurs_by_the_right_amount(gpu_ctx, hostmirror, abi, dep
     share = lit.reshape(64, 4, -1).mean((0, 2))
     want = p0.reshape(64, 4, -1).mean((0, 2))
     assert np.all(np.abs(share - want) < 0.02) and np.all((want > 0.02) & (want < 0.98)), (share, want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("depth", BLUR_DEPTHS)
+def test_out_of_focus_it_blurs_by_the_right_amount(gpu_ctx, hostmirror, abi, depth):
+    """(7) check_blur on the device"""
+    check_blur(lambda flat: abi.Scene(gpu_ctx, flat), hostmirror, abi, depth)
 
 
 # ===================================================================================================== GPU 8: radiance
@@ -397,7 +413,9 @@ def run_lens_radiance(name, side, hm, abi, direct):
             x = R.hit_plane(o, d / np.linalg.norm(d, axis=-1, keepdims=True), (0, 0, 0), (0, 1, 0))
             assert np.abs(x).max() < 1.0
     per_pixel = max(-(-RC.samples_needed(sigma[g], e[g], q[g], side.caps) // len(idx)) for g, idx in enumerate(case.groups))
-    spp = min(side.max_spp, 1 << int(np.log2(side.max_records // len(case.pixels))))
+    spp = side.max_spp
+    if side.max_records:                                                 # (as run_sampled: the CPU side has no such limit)
+        spp = min(spp, 1 << int(np.log2(side.max_records // len(case.pixels))))
     spp = min(spp, 1 << int(np.ceil(np.log2(per_pixel))))
     n_seeds = -(-per_pixel // spp)
     seed0 = zlib.crc32((name + ("direct" if direct else "lens")).encode()) << 8

@@ -1,7 +1,8 @@
 """Randomised parity sweep: random triangle soups (including slivers and near-degenerate triangles), random BSDFs of
 every type, one to three area emitters, optional environment, random integrator properties — the GPU film must equal
-the oracle's bit for bit on every one.  usage: fuzz_parity.py n_scenes [first_seed [spp [glass [plastic]]]]  (glass: a fourth argument
-other than 0 turns some meshes of every scene into smooth `dielectric`; plastic: a fifth one turns some into `plastic` / `roughplastic`)"""
+the oracle's bit for bit on every one.  usage: fuzz_parity.py n_scenes [first_seed [spp [glass [plastic [lens [lights]]]]]]  (glass is
+on when its argument is other than 0, plastic when it is given at all, lens and lights when given and other than 0.  glass turns some meshes of every scene into smooth `dielectric`; plastic turns some
+into `plastic` / `roughplastic`; lens gives every scene a `thinlens` sensor; lights adds `spot` and `directional` emitters)"""
 import importlib, sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import numpy as np
@@ -9,13 +10,17 @@ abi = importlib.import_module("misaki-render_amd.abi"); hm = importlib.import_mo
 import oracle_binding
 
 
-def random_scene(rng, glass=False, seed=0, plastic=False):
+def random_scene(rng, glass=False, seed=0, plastic=False, lens=False, lights=False):
     """glass=True turns some meshes into the smooth `dielectric` (emitters included: glass that emits); what becomes glass is drawn
     from a generator of its own, made from `seed`, so that `rng` is consumed exactly as without it: a seed's scene with
     glass=False is the scene it always was, and with glass=True it is that scene with some BSDFs exchanged.
     plastic=True does the same for `plastic` and `roughplastic`, from another generator of its own: a relative index in [1, 2.6]
     (sometimes exactly 1), `nonlinear`, alpha 10**U(-4, -0.3), an rgb / uniform / checkerboard base, a specular_reflectance that is 0,
-    a constant, an rgb or a table, `twosided`, and sometimes a constant-opacity `mask` over it."""
+    a constant, an rgb or a table, `twosided`, and sometimes a constant-opacity `mask` over it.
+    lights=True adds one to three `spot` / `directional` emitters behind the scene's own (a spot anywhere around the scene, aimed into
+    it, half-angles from 5 to 120 degrees, sometimes a hard edge; a sun from any direction), lens=True a `thinlens` sensor (an aperture
+    that is 0, small or as wide as the scene, focused before, inside or behind it): each from a generator of its own, drawn after
+    everything else, so that a seed's scene without the option is the scene it always was."""
     meshes = []
     n_mesh = rng.randint(3, 9)
     n_light = rng.randint(1, 4)
@@ -175,7 +180,29 @@ def random_scene(rng, glass=False, seed=0, plastic=False):
             m.bsdf = {"type": "mask", "opacity": float(prng.choice([0.25, 0.5, 0.9, 1.0])), "bsdf": spec} if prng.randint(0, 4) == 0 else spec
             if isinstance(m.reflectance, hm.Regular) or np.isscalar(m.reflectance):
                 m.reflectance = (0.5, 0.5, 0.5)                                        # (unused by the BSDF)
-    flat = hm.flatten(meshes, fw, fh, env=env, camera=camera, filter_stddev=stddev, crop=crop)
+    unit = (camera["near"] / hm.CBOX_CAMERA["near"]) if camera else 1.0      # the scene's scale against the Cornell box's
+    light_specs = []
+    if lights:
+        lrng = np.random.RandomState((int(seed) * 3266489917 + 0x5907) % (2 ** 32))
+        for _ in range(lrng.randint(1, 4)):
+            if lrng.randint(0, 3) == 0:
+                light_specs.append({"type": "directional", "irradiance": tuple(float(x) for x in lrng.uniform(0.5, 8.0, 3)), "direction": tuple(float(x) for x in lrng.normal(size=3))})
+                continue
+            origin = (lrng.uniform(-1, 1, 3) * 450 + np.array([278, 273, 280])) * unit
+            target = (lrng.uniform(-1, 1, 3) * 150 + np.array([278, 273, 280])) * unit
+            cutoff = float(lrng.uniform(5.0, 120.0))
+            beam = cutoff if lrng.randint(0, 5) == 0 else float(cutoff * lrng.uniform(0.1, 1.0))
+            k = lrng.randint(0, 3)
+            inten = float(lrng.uniform(1e4, 1e6)) if k == 0 else tuple(float(x) for x in lrng.uniform(1e4, 1e6, 3))
+            inten = tuple(v * unit * unit for v in inten) if isinstance(inten, tuple) else inten * unit * unit
+            light_specs.append({"type": "spot", "intensity": inten, "cutoff_angle": cutoff, "beam_width": beam,
+                                "lookat": {"origin": tuple(float(v) for v in origin), "target": tuple(float(v) for v in target), "up": (0.0, 1.0, 0.0) if lrng.randint(0, 2) else (0.3, 0.2, 1.0)}})
+    flat = hm.flatten(meshes, fw, fh, env=env, camera=camera, filter_stddev=stddev, crop=crop, lights=light_specs)
+    if lens:
+        arng = np.random.RandomState((int(seed) * 668265263 + 0x1e45) % (2 ** 32))
+        radius = float(arng.choice([0.0, 2.0, 25.0, 300.0]) * arng.uniform(0.5, 1.5) * unit)
+        focus = float(arng.choice([200.0, 800.0, 1100.0, 4000.0]) * arng.uniform(0.7, 1.3) * unit)
+        flat.lens = abi.LensDesc(float(np.float32(radius)), float(np.float32(focus)))
     # vertex normals (perturbed face normals) and texture coordinates on some meshes: mesh.cpp:68-96
     verts, faces = flat.vertices, flat.faces
     for i in range(flat.desc.n_meshes):
@@ -226,11 +253,11 @@ def random_params(rng):
     return kw
 
 
-def sweep(ctx, orc, seeds, verbose=True, spp=None, glass=False, plastic=False):
+def sweep(ctx, orc, seeds, verbose=True, spp=None, glass=False, plastic=False, lens=False, lights=False):
     bad = []
     for s in seeds:
         rng = np.random.RandomState(s)
-        flat = random_scene(rng, glass=glass, seed=s, plastic=plastic)
+        flat = random_scene(rng, glass=glass, seed=s, plastic=plastic, lens=lens, lights=lights)
         kw = random_params(rng)
         if spp:
             kw["spp"] = spp
@@ -257,6 +284,7 @@ if __name__ == "__main__":
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 50
     seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     spp = int(sys.argv[3]) if len(sys.argv) > 3 else None        # optional: samples per pixel for every scene
-    bad = sweep(abi.Context(0), oracle_binding.load(), range(seed0, seed0 + n), spp=spp or None, glass=len(sys.argv) > 4 and sys.argv[4] != "0", plastic=len(sys.argv) > 5)
+    on = lambda k: len(sys.argv) > k and sys.argv[k] != "0"
+    bad = sweep(abi.Context(0), oracle_binding.load(), range(seed0, seed0 + n), spp=spp or None, glass=on(4), plastic=len(sys.argv) > 5, lens=on(6), lights=on(7))
     print("fuzz: %d scenes, %d with a film different from the oracle's" % (n, len(bad)))
     sys.exit(1 if bad else 0)
